@@ -12,7 +12,10 @@ hidden 128, batch 128, node_num 7 -> ~57 nodes / graph).  Batches shard across
 ranks (independent mini-batches per GPU, weak scaling) with one RCCL all-reduce
 of the flat gradient bucket per step.
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "measurement").
+Prints ONE JSON line on rank 0 (see DESIGN.md "measurement").  A plain run sets up, warms up, times ONE region of
+exactly --steps steps and prints the line (value, ms_per_step); --full adds what takes runs of its own: the median of
+--repeats (default 5) regions, the roofline, end-to-end and CPU-baseline figures, the N > 1 exchange diagnostics.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (same arguments -> same inputs).
 """
 from __future__ import annotations
 
@@ -55,15 +58,25 @@ def parse():
     ap.add_argument("--workload", default="spmotif_b0.9_causalgcn_h128_l3_bs128", choices=list(WORKLOADS))
     ap.add_argument("--mode", default="graph", choices=["graph", "eager"])
     ap.add_argument("--batches", type=int, default=8, help="distinct resident mini-batches per rank")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: --repeats 5 timed regions by default, the roofline, end-to-end and "
+                         "CPU-baseline figures (each still switched off by its --no-* option) and the N > 1 exchange diagnostics")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end (batch assembly included) figure")
     ap.add_argument("--no-sequence", action="store_true", help="one hipGraph launch per step instead of one per pass over the resident batches")
     ap.add_argument("--no-engine", action="store_true", help="operator-level autograd path instead of the native step engine")
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; value = median (BASELINE.md section 3)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; value = median (BASELINE.md section 3); default 1, with --full 5")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed (stats, log-probs, gradients, parameters and "
+                         "BatchNorm running statistics after its update) as DIR/<name>.npy")
     ap.add_argument("--dry", action="store_true", help="launch plumbing only: rendezvous, one collective, the JSON line's shape with value null (no model, no timed region; runs without a GPU over CAL_BENCH_BACKEND=gloo)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.repeats is None:
+        a.repeats = 5 if a.full else 1
+    return a
 
 
 def _free_port() -> int:
@@ -74,9 +87,9 @@ def _free_port() -> int:
 
 
 def self_launch(a) -> None:
-    """`python bench.py --gpus N` (N > 1) without a launcher: re-exec the same command line under torch.distributed.run, one
-    rank per GPU, rendezvous on 127.0.0.1 -- the form the driver uses for N = 1 then works for N = 2/4/8 unmodified.  Never
-    returns.  Fewer than N visible devices is an error here, before any rank starts (ranks would otherwise share a device
+    """`python bench.py --gpus N` (N > 1) without a launcher: run the same command line under torch.distributed.run, one
+    rank per GPU, rendezvous on 127.0.0.1, in a child process -- the form the driver uses for N = 1 then works for N = 2/4/8
+    unmodified.  Never returns: exits with the launcher's status.  Fewer than N visible devices is an error here, before any rank starts (ranks would otherwise share a device
     and RCCL would hang or fail late); CAL_BENCH_BACKEND=gloo lifts the check (test aid: ranks may share devices)."""
     backend = os.environ.get("CAL_BENCH_BACKEND", "nccl")
     if backend == "nccl" and not a.dry:
@@ -90,7 +103,8 @@ def self_launch(a) -> None:
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(a.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush(); sys.stderr.flush()
-    os.execve(sys.executable, cmd, env)
+    import subprocess
+    sys.exit(subprocess.run(cmd, env=env).returncode)
 
 
 def model_args(wl):
@@ -121,6 +135,7 @@ def cpu_baseline(wl, batches_cpu, seconds):
     unfused op sequence on ~7k-row tensors does not scale to hundreds of threads, and the best
     setting is what a user of the reference would run."""
     from oracle import cal_oracle as O
+    O.BN_STATS = "kernel"                      # BatchNorm1d's own CPU kernel, as the reference runs it on a CPU
     cores = os.cpu_count() or 1
     torch.manual_seed(666)
     sd = O.init_state(wl["model"], wl["nfeat"], wl["ncls"], hidden=wl["hidden"], layers=wl["layers"], heads=4)
@@ -504,6 +519,39 @@ def reference_loop(wl, margs, gs, steps=60):
     return out
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(path, trainer, model, stats, batch_size):
+    """--dump-outputs DIR: what the timed path's LAST step hands its caller, one float32 DIR/<name>.npy each -- ``stats``
+    (loss, c / o / co losses, correct count), ``logp`` (the three heads' [B, C] log-probs; native engine only), ``grad.<p>``
+    (the step's gradients), ``param.<p>`` and ``buffer.<b>`` (parameters and BatchNorm running statistics after its update).
+    Over DUMP_CAP_BYTES in all, every array above its share keeps a fixed sample of its elements (seeded by its name, sorted
+    flat indices), so two builds are compared element for element."""
+    import zlib
+    out = {"stats": stats}
+    if trainer.engine is not None:
+        C = trainer.engine.C
+        out["logp"] = trainer.engine.buffer("logp", 3 * batch_size * C).view(3, batch_size, C)
+    for name, p in model.named_parameters():
+        out["param." + name] = p
+        if p.grad is not None:
+            out["grad." + name] = p.grad
+    for name, b in model.named_buffers():
+        if b.is_floating_point():
+            out["buffer." + name] = b
+    out = {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+    if sum(v.nbytes for v in out.values()) > DUMP_CAP_BYTES:
+        share = DUMP_CAP_BYTES // 4 // len(out)
+        for k, v in out.items():
+            if v.size > share:
+                rng = np.random.default_rng(zlib.crc32(k.encode()))
+                out[k] = v.reshape(-1)[np.sort(rng.choice(v.size, share, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def dry_run(a, wl, world, rank, local_rank):
     """--dry: everything the launch needs and nothing the measurement does -- process group up (RCCL when GPUs are there, else
     CAL_BENCH_BACKEND=gloo), one all-reduce so that every rank is seen, rank 0 prints the line with value null."""
@@ -579,7 +627,7 @@ def main():
         for bname, buf in model.named_buffers():
             if buf.dtype.is_floating_point:
                 dist.broadcast(buf, 0)
-    batches_cpu = make_batches(wl, a.batches, seed=seed + 1000 * rank)
+    batches_cpu = make_batches(wl, a.batches, seed=seed + 1000 * rank) if a.full and not a.no_cpu_baseline else None
     batches = [b.to("cuda") for b in make_batches(wl, a.batches, seed=seed + 1000 * rank)]
     mode = a.mode
     use_engine = False if a.no_engine else None
@@ -647,10 +695,17 @@ def main():
             dt = float(t.item())
         regions.append(dt)
     dt = float(np.median(regions))
+    if a.dump_outputs and rank == 0:            # before anything below steps the model or touches the gradient bucket
+        dump_outputs(a.dump_outputs, trainer, model, stats, wl["batch"])
     # N > 1 diagnostics (the driver's 8-GPU run is the only multi-GPU measurement there is): per-rank step time of the
-    # median region's policy, and the gradient exchange alone -- 20 eager all-reduces of the flat bucket between events
+    # median region's policy, and (--full) the gradient exchange alone -- 20 eager all-reduces of the flat bucket between events
     dp_diag = None
     if world > 1:
+        dp_diag = {"exchange": "one-shot peer-memory kernel (CAL_AMD_P2P_EXCHANGE=1)" if getattr(trainer, "p2p", None) is not None else "all-reduce (%s)" % dist.get_backend(),
+                   "exchange_in_graph": bool(trainer.exchange_in_graph), "fused_opt": bool(trainer.fused_opt),
+                   "sequence_graph": bool(seq), "backend": dist.get_backend(), "rccl_ranks_seen": dist.get_world_size(),
+                   "bucket_bytes": int(trainer.flat_g.numel() * 4)}
+    if world > 1 and a.full:
         local = torch.tensor([float(np.median(local_regions))], dtype=torch.float64, device="cuda")
         allr = [torch.zeros_like(local) for _ in range(world)]
         dist.all_gather(allr, local)
@@ -665,12 +720,8 @@ def main():
         e1.record()
         torch.cuda.synchronize()
         trainer.flat_g.copy_(saved)
-        dp_diag = {"exchange": "one-shot peer-memory kernel (CAL_AMD_P2P_EXCHANGE=1)" if getattr(trainer, "p2p", None) is not None else "all-reduce (%s)" % dist.get_backend(),
-                   "exchange_in_graph": bool(trainer.exchange_in_graph), "fused_opt": bool(trainer.fused_opt),
-                   "sequence_graph": bool(seq), "backend": dist.get_backend(), "rccl_ranks_seen": dist.get_world_size(),
-                   "bucket_bytes": int(trainer.flat_g.numel() * 4),
-                   "allreduce_us_eager": 1e3 * e0.elapsed_time(e1) / 20,
-                   "ms_per_step_by_rank": [round(1e3 * float(t.item()) / a.steps, 5) for t in allr]}
+        dp_diag.update(allreduce_us_eager=1e3 * e0.elapsed_time(e1) / 20,
+                       ms_per_step_by_rank=[round(1e3 * float(t.item()) / a.steps, 5) for t in allr])
     trainer.check_status()
     final = stats.tolist()
     graphs = wl["batch"] * a.steps * world
@@ -695,7 +746,7 @@ def main():
         out["data_parallel"] = dp_diag
     # rank 0 also at N > 1 (after the timed regions; the other ranks wait at the barrier below): a SCALE line then carries
     # the same roofline / cpu_baseline blocks as the N = 1 line and can be cross-checked against it (round-4 review)
-    if rank == 0:
+    if rank == 0 and a.full:
         if not a.no_roofline:
             try:
                 if trainer.engine is not None:

@@ -1,12 +1,13 @@
 #!/bin/bash
-# usage (GPU box): scripts/trace_step.sh <workload> <tag>  -> gpurun_out/<tag>/trace_<workload>.txt
+# usage (GPU box): scripts/trace_step.sh <workload> <tag>  -> $OUT/<tag>/trace_<workload>.txt
 # the launches of ONE eager step in issue order with their durations (rocprofv3 --kernel-trace, last of 6 steps)
 w=$1; tag=$2
+OUT=${OUT:-results}         # output root: $OUT/<tag>/
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out/$tag
+mkdir -p $OUT/$tag
 rocprofv3 --kernel-trace --output-format csv -d /tmp/trace_$tag/$w -o t -- \
     python bench.py --workload $w --steps 4 --warmup 2 --batches 1 --repeats 1 --mode eager --no-cpu-baseline --no-e2e --no-roofline > /tmp/trace_$w.log 2>&1
-python - <<PY > gpurun_out/$tag/trace_$w.txt
+python - <<PY > $OUT/$tag/trace_$w.txt
 import csv, glob
 f = glob.glob("/tmp/trace_$tag/$w/**/*kernel_trace.csv", recursive=True)[0]
 rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r["Start_Timestamp"]))
@@ -23,4 +24,4 @@ for r in rows[lo:hi]:
     prev_end = e
 print("launches %d, sum of durations %.1f us, span %.1f us" % (hi - lo, tot / 1e3, (prev_end - t0) / 1e3))
 PY
-tail -3 gpurun_out/$tag/trace_$w.txt
+tail -3 $OUT/$tag/trace_$w.txt

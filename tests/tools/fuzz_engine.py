@@ -76,6 +76,13 @@ def one_variant(rng, hidden):
 
 
 def run(case, seed, name="CausalGCN", kw=None, autograd=False, want_ctx=False):
+    """One case of the sweep (``_run``).  The oracle's BatchNorm statistics come from torch's CPU kernel (oracle BN_STATS =
+    "kernel"): the bound scales with the fp32 oracle's own error, and ``resolve`` re-runs that kernel in its variants."""
+    with O.bn_stats("kernel"):
+        return _run(case, seed, name, kw, autograd, want_ctx)
+
+
+def _run(case, seed, name="CausalGCN", kw=None, autograd=False, want_ctx=False):
     """autograd: through the nn.Module surface (forward by the engine, the loss by torch, cal_engine_backward_from) instead
     of the one-call training step."""
     from cal_amd import model as M
@@ -248,7 +255,8 @@ def _step64(ctx, force=None, x=None, dtype=torch.float64, sd=None, bn32=False):
     keep = O.F
     O.F = shim
     try:
-        out = tr.step((b.x if x is None else x).to(dtype), b.edge_index, b.batch, b.y, perm=ctx["perm"])
+        with O.bn_stats("kernel"):
+            out = tr.step((b.x if x is None else x).to(dtype), b.edge_index, b.batch, b.y, perm=ctx["perm"])
     finally:
         O.F = keep
     return shim, tr, out

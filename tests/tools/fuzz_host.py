@@ -21,6 +21,13 @@ from oracle import cal_oracle as O               # noqa: E402
 
 
 def run(case, seed, name, kw):
+    """One case against the oracle with torch's CPU BatchNorm kernel (BN_STATS = "kernel"): the host path's BatchNorm1d runs
+    that kernel, and the bound scales with the fp32 oracle's own error."""
+    with O.bn_stats("kernel"):
+        return _run(case, seed, name, kw)
+
+
+def _run(case, seed, name, kw):
     from cal_amd import model as M
     hidden, layers, nfeat, ncls, sizes = case
     torch.manual_seed(seed)
