@@ -205,11 +205,8 @@ struct Engine {
     int ro_rows;             // 1: ... also for 129 .. 512 graphs, in row blocks (k_ro_step<true>); CAL_AMD_RO_ROWS=0: the GEMM chain there
     int striped;             // 1: the per-graph kernels exchange their BatchNorm sums through NSTRIPE accumulator planes (engine.hpp: stripe_sum)
                              // instead of partial rows + k_stats_final; CAL_AMD_STRIPED=0 keeps the finishing launches
-    int attwide;             // 1: the attention block of 129-256-node graphs per graph (engine_attwide.hpp); CAL_AMD_ATTWIDE=0: the node-level kernels
-    int rpb_div;             // rows per workgroup of the node-level row kernels = max(32, N / rpb_div); CAL_AMD_RPB_DIV (experiment); 0 = by size
     int fold_zero;           // 1: forward + backward steps on the per-graph plan have no k_zero_f64 launch (PlanFold); CAL_AMD_FOLD_ZERO=0: always the launch
     int bn0_dirty_host;      // host twin of the device word status[3]: a training forward has been enqueued since the last k_finish
-    int gw_cols;             // CAL_AMD_GW_COLS (experiment): 32 / 64 forces the wide forward kernels' slice width, 0 = by occupancy
     int gwide;               // 1: graphs of 129 .. 256 nodes run the wide per-graph convolutions (engine_gwide.hpp); CAL_AMD_GWIDE=0: the node-level chain
     int ro_step;             // 1: training steps run the readout as one launch (k_ro_step); CAL_AMD_RO_STEP=0 keeps the four kernels
     float *dzl, *dyh1, *dy1, *dxh, *dpool, *dZco, *gn, *gself, *ddeg, *dl, *dzco, *dXhco, *dZ, *dzi, *dXh, *slabs;
@@ -277,11 +274,8 @@ CAL_EXPORT void* cal_engine_create(int64_t F, int64_t H, int64_t C, int64_t L) {
     { const char* v = getenv("CAL_AMD_RO_ROWS"); e->ro_rows = !(v && v[0] == '0'); }
     { const char* v = getenv("CAL_AMD_STRIPED"); e->striped = !(v && v[0] == '0'); }
     { const char* v = getenv("CAL_AMD_GWIDE"); e->gwide = !(v && v[0] == '0'); }
-    { const char* v = getenv("CAL_AMD_GW_COLS"); e->gw_cols = v ? atoi(v) : 0; }
     { const char* v = getenv("CAL_AMD_FOLD_ZERO"); e->fold_zero = !(v && v[0] == '0'); }
-    { const char* v = getenv("CAL_AMD_ATTWIDE"); e->attwide = !(v && v[0] == '0'); }
-    { const char* v = getenv("CAL_AMD_RPB_DIV"); e->rpb_div = v ? std::max(1, atoi(v)) : 0; }
-    e->bn0_dirty_host = 1;                            // 32 / 64 (experiment): forward slice width forced
+    e->bn0_dirty_host = 1;
     {
         // k_ro_step's 3 * H / 16 workgroups (133 KB of LDS each: one per CU) meet at spin barriers: they must all be
         // resident.  A device (or CU mask / partition) with fewer compute units than that takes the four-kernel readout.
@@ -495,6 +489,54 @@ CAL_EXPORT int64_t cal_engine_buffer_offset(void* h, const char* name) {
 
 namespace {
 
+// How a step runs, block by block: chosen once per step (make_route) from the engine, the batch's shape and the mode, and read
+// by every phase of engine_forward / engine_backward.  Conv: node-level chain, per-graph kernels for graphs of <= 64 / <= 128 nodes
+// (engine_gconv*.hpp; the GAT / GIN ones are the 64-node form), wide per-graph kernels for 129 .. 256 nodes (engine_gwide.hpp).
+enum class Plan { Node, Graph256, Graph1024, Big };
+enum class Conv { Node, Graph64, Graph128, Wide };
+enum class Att { Node, Graph, Wide };
+enum class FeatFwd { Gemm, Rows };
+enum class FeatBwd { Gemm, Rows, Units };
+enum class Readout { Gemm, FourKernel, OneLaunch, Rows };
+struct Route {
+    Plan plan;          // GraphPlan: k_plan_graph<256 | 1024 threads> per graph, k_plan_big + plan_rank, or the node-level plan_build
+    bool plan_stats;    // bn_feat's statistics ride in the plan kernel
+    bool plan_coef;     // k_plan_graph writes the unit coefficients for the wide convolutions (coef in slot order, coef_src by source)
+    FeatFwd feat_fwd;   // feature layer: tiled GEMM, or row kernels (engine_feat.hpp)
+    // Units: k_feat_bwd* fed by the first backbone layer's partial input gradients, per graph or (feat_chunks, behind the wide
+    // convolutions) per FB_T-row chunk; Rows: k_bn_bwd_feat, only behind a node-level GCN / GAT layer 1 (the forward's row kernels
+    // do not imply the backward's); Gemm: the GEMM chain
+    FeatBwd feat_bwd;
+    bool feat_chunks;
+    // backbone: the forward may run per graph where the backward is node-level (128-node graphs, > 512 units, a GAT layer's
+    // per-graph bounds GG_E against GGB_E); a GIN forward in training mode runs per graph only where its backward does (it
+    // leaves gt1 alone, and the node-level backward reads gagg / gy)
+    Conv bb_fwd, bb_bwd;
+    int gw_cols_bb, gw_cols_co;   // wide forward slice width: 32 (two workgroups per CU) when 64-column slices would leave CUs idle
+    int nsplit_bb, nsplit_co;     // wide backward: workgroups per (graph, slice) of k_gw_bwd
+    bool lean_bb, lean_co;        // per-graph backward: the 80 KB k_gconv_bwd (two workgroups per CU) when there are more workgroups than CUs
+    // attention block between the backbone and the causal convolutions: the wide forward needs 3 T >= CUs (fewer workgroups lose
+    // to the node-parallel pair), its backward does not; the per-graph forward and backward have bounds of their own
+    Att att_fwd, att_bwd;
+    int ag_split;                 // workgroups per graph of k_att_bwd_graph / k_att_bwd_wide
+    // causal convolutions: forward per graph up to 128 nodes, backward only for 64-node graphs of <= 512 units; where the
+    // forward pooled per graph and the backward is node-level, the backward counts the positive rows itself (launch_pool_cnt)
+    Conv co_fwd, co_bwd;
+    // readout: the backward of OneLaunch is done by the forward's launch; Rows leaves slabs for k_finish; FourKernel runs
+    // k_ro_bwd_a / _b.  Only training steps with a backward take OneLaunch / Rows.
+    Readout ro;
+    // BatchNorm sites whose sums go through the accumulator planes (engine.hpp: stripe_sum): those whose producers are per-graph
+    // kernels and whose EVERY reader is a striped reader (k_gconv_fwd, k_gconv_bwd, k_att_bwd_graph, k_feat_bwd*, the final commit)
+    bool st_feat;       // BatchNorm_1 from the feature layer's GEMM: read by the first backbone layer both ways and k_feat_bwd*
+    bool st_bb;         // the backbone's: forward statistics, backward sums of layers L..2 (layers that run per graph both ways)
+    bool st_bb1;        // backward sums of layer 1: read by k_feat_bwd*, or by a striped k_bn_bwd (wide), or inside the GIN layer
+    bool st_co;         // bnc / bno: statistics from the attention forward, backward sums from the two-branch convolution backward
+    // the node-level GCNConv chain of a SMALL batch (graphs beyond the per-graph kernels): the sums that leave a GEMM epilogue
+    // go into the planes; their readers are the small-batch GEMMs' prologues, k_bn_bwd<.., ST> and k_att_bwd<.., ST>.  The
+    // aggregation / attention kernels' statistics keep their partial rows (thousands of short workgroups).
+    bool st_node;
+};
+
 struct Ctx {
     Engine* e;
     hipStream_t st;
@@ -508,10 +550,19 @@ struct Ctx {
     const int64_t* y; const int64_t* perm; float wc, wo, wco; int want_grad;
     int draw_perm;      // the step draws its own intervention permutation (first kernel) into Engine::perm_dev
     int tick_in_finish; // the step ends with the Adam update: k_finish advances the step counter
-    int ro_done;        // the forward's k_ro_step already ran the readout backward
     int adam_in_finish; // k_finish applies Adam to every gradient it completes (no k_adam launch)
     size_t parts_off;   // bump allocator over Engine::parts
     FinalArgs fin;      // pending k_stats_final tasks
+    Route r;
+};
+
+// what the backward's phases share: the final commit's task list (k_finish), the bump allocator over Engine::slabs, and the
+// column sums kept as partial rows until that commit (no finalise launch)
+struct Deferred { double* p; int P; int stride; };
+struct Bwd {
+    FinishArgs fa;
+    size_t slab_off;
+    Deferred d_convb[MAX_LAYERS], d_gin_b1[MAX_LAYERS], d_cb, d_ob, d_dwn, d_dwe, d_bn0;
 };
 
 BNRef bnref(const Ctx& c, int k, int rows, int update) {
@@ -630,22 +681,34 @@ int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 // k_espmm launch: lanes per row from the width, per-edge weights / output statistics from the branch (both branches alike)
 int launch_espmm(hipStream_t st, const CSR& csr, const SpmmBranch2& bb, int nbranch, int relu, float loop_w, int N, int H, int rpb);
 
-#define RC0(x) do { int rc0_ = (x); if (rc0_) return rc0_; } while (0)
-// weight-gradient GEMM (TN) with split-K slabs when the reduction axis is long
-int grad_gemm(Ctx& c, GemmArgs& a, int nbatch, float** dst, FinishArgs& fa, size_t& slab_off) {
-    int S = splitk_for(a.M, a.N, a.K, nbatch);
-    gemm_set_split(a, S);
-    if (a.nsplit > 1) {
-        for (int b = 0; b < nbatch; ++b) {
-            size_t need = (size_t)a.nsplit * a.M * a.N;
-            if (slab_off + need > c.e->slab_floats || fa.nst >= MAX_SLABS) { set_error("engine: slab workspace exhausted"); return 2; }
-            a.p[b].C = c.e->slabs + slab_off;
-            fa.st[fa.nst++] = SlabTask{c.e->slabs + slab_off, dst[b], a.M * a.N, a.nsplit};
-            slab_off += need;
-        }
-    } else {
-        for (int b = 0; b < nbatch; ++b) a.p[b].C = dst[b];
+#define RC(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
+int no_parts() { set_error("engine: partial-row workspace exhausted"); return 2; }
+int no_slabs() { set_error("engine: slab workspace exhausted"); return 2; }
+// `need` floats of the slab workspace whose S blocks of n k_finish sums into dst; null when exhausted
+float* slab_take(Ctx& c, Bwd& b, size_t need, float* dst, int n, int S) {
+    if (b.slab_off + need > c.e->slab_floats || b.fa.nst >= MAX_SLABS) return nullptr;
+    float* p = c.e->slabs + b.slab_off;
+    b.fa.st[b.fa.nst++] = SlabTask{p, dst, n, S};
+    b.slab_off += need;
+    return p;
+}
+// deferred column sums: P partial rows of `cols`, summed by the final commit
+Acc defer(Ctx& c, Deferred& d, int P, int cols) {
+    d.p = parts_alloc(c, (size_t)P * cols); d.P = P; d.stride = cols;
+    return d.p ? Acc(nullptr, d.p, cols) : Acc();
+}
+// split-K slabs of a weight-gradient GEMM (TN) when the reduction axis is long
+int grad_slabs(Ctx& c, Bwd& b, GemmArgs& a, int nbatch, float** dst) {
+    gemm_set_split(a, splitk_for(a.M, a.N, a.K, nbatch));
+    for (int q = 0; q < nbatch; ++q) {
+        a.p[q].C = a.nsplit > 1 ? slab_take(c, b, (size_t)a.nsplit * a.M * a.N, dst[q], a.M * a.N, a.nsplit) : dst[q];
+        if (!a.p[q].C) return no_slabs();
     }
+    return 0;
+}
+// weight-gradient GEMM (TN) with split-K slabs when the reduction axis is long
+int grad_gemm(Ctx& c, Bwd& b, GemmArgs& a, int nbatch, float** dst) {
+    RC(grad_slabs(c, b, a, nbatch, dst));
     // fork: everything enqueued on the main stream so far (the producers of A and B) precedes it
     hipStream_t s = c.st;
     // Measured on MI355X / ROCm 7.2: forking the 9 dW GEMMs costs more than it hides (graph replay
@@ -669,24 +732,12 @@ void join_side(Ctx& c) {
 
 // dX (NT, `ax`) and dW (TN, `aw`, split-K slabs like grad_gemm) of one layer in a single launch when both
 // go to the tiled kernel; otherwise the two launches of before.
-int dual_gemm(Ctx& c, GemmArgs& ax, int nbx, GemmArgs& aw, int nbw, float** dst, FinishArgs& fa, size_t& slab_off) {
+int dual_gemm(Ctx& c, Bwd& b, GemmArgs& ax, int nbx, GemmArgs& aw, int nbw, float** dst) {
     if (use_ks(ax.M)) {
-        RC0(grad_gemm(c, aw, nbw, dst, fa, slab_off));
+        RC(grad_gemm(c, b, aw, nbw, dst));
         return fwd_gemm(c, true, ax, nbx);
     }
-    int S = splitk_for(aw.M, aw.N, aw.K, nbw);
-    gemm_set_split(aw, S);
-    if (aw.nsplit > 1) {
-        for (int b = 0; b < nbw; ++b) {
-            size_t need = (size_t)aw.nsplit * aw.M * aw.N;
-            if (slab_off + need > c.e->slab_floats || fa.nst >= MAX_SLABS) { set_error("engine: slab workspace exhausted"); return 2; }
-            aw.p[b].C = c.e->slabs + slab_off;
-            fa.st[fa.nst++] = SlabTask{c.e->slabs + slab_off, dst[b], aw.M * aw.N, aw.nsplit};
-            slab_off += need;
-        }
-    } else {
-        for (int b = 0; b < nbw; ++b) aw.p[b].C = dst[b];
-    }
+    RC(grad_slabs(c, b, aw, nbw, dst));
     return launch_gemm_dual(ax, nbx, aw, nbw, c.st);
 }
 
@@ -749,60 +800,6 @@ int launch_espmm(hipStream_t st, const CSR& csr, const SpmmBranch2& bb, int nbra
     });
 }
 
-// per-graph fused convolution (engine_gconv.hpp): needs the batch's per-graph bounds from the host
-bool use_gc(const Ctx& c) {
-    const Engine* e = c.e;
-    return e->max_nodes > 0 && e->max_nodes <= GC_T && e->max_edges <= GC_E && e->H % GC_N == 0 && e->H <= GC_K && c.B > 0;
-}
-bool gc_small(const Ctx& c) { return c.e->max_nodes <= 64 && c.e->max_edges <= gc_edge_cap(64); }
-// wide per-graph convolutions, both ways (engine_gwide.hpp): graphs of 129 .. 256 nodes (the reference's default SPMotif shape)
-bool use_gw(const Ctx& c) {
-    const Engine* e = c.e;
-    return e->gwide && e->max_nodes > GC_T && e->max_nodes <= GW_T && e->max_edges <= GW_E && e->H % GC_N == 0 && e->H <= GW_K && c.B > 0 &&
-           e->ntiles == 0 && e->K == 0 && !e->gin;
-}
-// the attention block between the backbone and the causal convolutions per graph for the wide shapes (engine_attwide.hpp): needs the
-// per-graph plan's facts (a graph's edges are one run of edge_index columns, no self loops: slot ranges = edge ranges)
-bool use_aw(const Ctx& c) {
-    const Engine* e = c.e;
-    return use_gw(c) && e->attwide && e->node_ptr && e->edge_ptr && e->max_nodes <= AW_T && e->max_edges <= AW_E && e->H <= 256 && c.T <= 512;
-}
-// per-graph fused backward (engine_gconv_bwd.hpp): 64-node graphs only
-bool use_gcb(const Ctx& c) { return use_gc(c) && gc_small(c) && c.T <= 128 * 4; }
-// Which BatchNorm sites of a step go through the accumulator planes (engine.hpp: stripe_sum): those whose producers are per-graph
-// kernels and whose EVERY reader is a striped reader (k_gconv_fwd, k_gconv_bwd, k_att_bwd_graph, k_feat_bwd*, the final commit).
-//   co: bnc / bno -- statistics from k_att_fwd_graph, backward sums from the two-branch k_gconv_bwd; read by the two-branch
-//       k_gconv_fwd / k_gconv_bwd and by k_att_bwd_graph (the node-level k_att_bwd of > 256 units is a plain reader)
-//   bb: the GCNConv backbone -- statistics of layers 2..L from k_gconv_fwd, backward sums of layers L..1 from k_gconv_bwd
-//       (a GAT / GIN backbone has its own per-graph kernels: plain readers)
-bool att_graph_fwd(const Ctx& c) {
-    const Engine* e = c.e;
-    return use_gc(c) && e->max_nodes <= 4 * (512 / group_for(e->H, 4)) && e->max_edges <= GP_E;
-}
-bool striped_co(const Ctx& c) { return c.e->striped && c.training && att_graph_fwd(c) && use_gcb(c) && c.T <= 256; }
-bool striped_bb(const Ctx& c) { return c.e->striped && c.training && use_gc(c) && use_gcb(c) && c.e->K == 0 && !c.e->gin; }
-//   gat: the same for a GATConv backbone whose layers run per graph both ways (k_ggat_fwd / k_ggat_bwd)
-bool striped_gat(const Ctx& c) {
-    const Engine* e = c.e;
-    if (!(e->striped && c.training && e->K > 0 && use_gc(c) && gc_small(c) && use_gcb(c))) return false;
-    const int D = e->H / e->K;
-    return (D == 32 || D == 64) && e->max_edges <= GG_E && e->max_edges <= GGB_E;
-}
-//   gin: a GINConv backbone whose layers run per graph both ways (k_ggin_fwd<1|2> / k_ggin_bwd<2|1>): the BatchNorm inside the layer
-bool striped_gin(const Ctx& c) {
-    const Engine* e = c.e;
-    return e->striped && c.training && e->gin && use_gc(c) && gc_small(c) && use_gcb(c) && e->max_edges <= GB_E && e->max_edges <= gc_edge_cap(64);
-}
-//   node: the node-level GCNConv chain of a SMALL batch (graphs beyond the per-graph kernels: configs[0], 230-250 nodes each) -- the
-//       sums that leave a GEMM epilogue (feature-layer statistics, every backward sum) go into the planes; their readers are the
-//       small-batch GEMMs' prologues (gemm.hip / gemm_ks.hip: striped readers), k_bn_bwd<.., ST> and k_att_bwd<.., ST>.  The
-//       aggregation / attention kernels' statistics keep their partial rows (thousands of short workgroups).
-bool striped_node(const Ctx& c) {
-    const Engine* e = c.e;
-    return e->striped && c.training && !use_gc(c) && e->K == 0 && !e->gin && c.N < 16384 && c.N > 0;
-}
-// the feature layer's output statistics (BatchNorm_1): read by the first backbone layer both ways and by k_feat_bwd*
-bool striped_feat(const Ctx& c) { return ((striped_bb(c) || striped_gat(c)) && c.e->F <= FM_F && c.e->H <= FB_H) || striped_node(c); }
 // partial-row statistics of a per-graph kernel: one row per graph; st: into the workgroup's accumulator plane, no finishing launch
 Acc graph_acc(Ctx& c, double* dst, int cols, bool st = false) {
     if (st) return Acc(dst, nullptr, c.e->bn_plane);
@@ -811,74 +808,67 @@ Acc graph_acc(Ctx& c, double* dst, int cols, bool st = false) {
     final_task(c, p, c.T, cols, cols, dst);
     return Acc(dst, p, cols);
 }
+CSR csr_dst(const Ctx& c) { return CSR{c.e->rowptr_dst, c.e->nbr_dst, c.e->eid_dst, (int)c.E}; }
+CSR csr_src(const Ctx& c) { return CSR{c.e->rowptr_src, c.e->nbr_src, c.e->eid_src, (int)c.E}; }
 
-// Launch the per-graph fused backward for nb branches: slabs (one per graph) and the BatchNorm-backward partial
-// rows are registered like those of the GEMM path.  gb[k].dot_parts / .slab are filled in here.
-int gconv_bwd(Ctx& c, const CSR& gd, GconvBwdBranch* gb, int nb, float** dst, double** dsum, double** dprod,
-              FinishArgs& fa, size_t& slab_off, bool rs, bool st, const CSR* gs_wide = nullptr) {
+// the BatchNorm-backward sums of a per-graph backward kernel: into the accumulator planes of the site (st: every reader adds
+// them), or P partial rows [sum | prod] finalised by k_stats_final
+template <typename Args>
+int bn_bwd_sums(Ctx& c, Args& a, int P, double* dsum, double* dprod, bool st) {
+    if (st) { a.dacc_sum = dsum; a.dacc_prod = dprod; a.dacc_ss = c.e->bn_plane; return 0; }
+    const int H = c.e->H;
+    double* p = parts_alloc(c, (size_t)P * 2 * H);
+    if (!p) return no_parts();
+    a.dot_parts = p;
+    final_task(c, p, P, 2 * H, H, dsum);
+    final_task(c, p + H, P, 2 * H, H, dprod);
+    return 0;
+}
+
+// Launch the per-graph fused backward for nb branches (2: the causal convolutions, 1: a backbone layer): slabs (one per graph)
+// and the BatchNorm-backward partial rows are registered like those of the GEMM path.  gb[k].dot_parts / .slab are filled in here.
+int gconv_bwd(Ctx& c, Bwd& b, GconvBwdBranch* gb, int nb, float** dst, double** dsum, double** dprod, bool st) {
     Engine* e = c.e;
+    const bool co = nb == 2;
+    const bool wide = (co ? c.r.co_bwd : c.r.bb_bwd) == Conv::Wide;
+    const int nsplit = co ? c.r.nsplit_co : c.r.nsplit_bb;
+    const bool lean = co ? c.r.lean_co : c.r.lean_bb;
     const int H = e->H, B = c.T, nsl = H / GC_N;         // (B: units of this launch -- tiles or graphs)
-    // wide kernels: the dX' and dW products of a (graph, slice) go to two or four workgroups when one each would leave CUs without one
-    const int nsplit = !gs_wide ? 1 : (int64_t)B * nsl * nb * 4 <= e->num_cus ? 4 : (int64_t)B * nsl * nb * 2 <= e->num_cus ? 2 : 1;
     const int np2 = nsplit == 4 ? 2 : 1;                 // workgroups per (graph, slice) that leave BatchNorm-backward partial rows
     for (int k = 0; k < nb; ++k) {
         gb[k].batch = c.batch; gb[k].tile_gptr = e->ntiles > 0 ? e->tile_gptr : nullptr;
-        const size_t need = (size_t)B * H * H;
-        if (slab_off + need > e->slab_floats || fa.nst >= MAX_SLABS) { set_error("engine: slab workspace exhausted"); return 2; }
-        gb[k].slab = e->slabs + slab_off;
-        fa.st[fa.nst++] = SlabTask{e->slabs + slab_off, dst[k], H * H, B};
-        slab_off += need;
-        if (st) {        // the BatchNorm-backward sums go into the accumulator planes of the site (every reader adds them)
-            gb[k].dacc_sum = dsum[k]; gb[k].dacc_prod = dprod[k]; gb[k].dacc_ss = e->bn_plane;
-            continue;
-        }
-        double* p = parts_alloc(c, (size_t)B * nsl * np2 * 2 * H);
-        if (!p) { set_error("engine: partial-row workspace exhausted"); return 2; }
-        gb[k].dot_parts = p;
-        final_task(c, p, B * nsl * np2, 2 * H, H, dsum[k]);
-        final_task(c, p + H, B * nsl * np2, 2 * H, H, dprod[k]);
+        gb[k].slab = slab_take(c, b, (size_t)B * H * H, dst[k], H * H, B);
+        if (!gb[k].slab) return no_slabs();
+        RC(bn_bwd_sums(c, gb[k], B * nsl * np2, dsum[k], dprod[k], st));
     }
-    if (gs_wide) {
-        // graphs of up to 256 nodes (engine_gwide.hpp): CSR by SOURCE
+    const GconvBwdBranch2 b2{{gb[0], gb[nb - 1]}};
+    if (wide) {
+        // graphs of up to 256 nodes (engine_gwide.hpp): CSR by SOURCE; the dX' and dW products of a (graph, slice) go to two or
+        // four workgroups when one each would leave CUs without one
+        const CSR gs = csr_src(c);
         const dim3 gridw(B, nsl * nsplit, nb);
-        const GconvBwdBranch2 b2{{gb[0], gb[nb - 1]}};
-        if (rs) PROF_LAUNCH((k_gw_bwd<true, 2>), gridw, dim3(GW_NT), 0, c.st, *gs_wide, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, nsplit, e->status);
-        else if (gb[0].dout) PROF_LAUNCH((k_gw_bwd<false, 0>), gridw, dim3(GW_NT), 0, c.st, *gs_wide, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, nsplit, e->status);
-        else PROF_LAUNCH((k_gw_bwd<false, 1>), gridw, dim3(GW_NT), 0, c.st, *gs_wide, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, nsplit, e->status);
+        if (co) PROF_LAUNCH((k_gw_bwd<true, 2>), gridw, dim3(GW_NT), 0, c.st, gs, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, nsplit, e->status);
+        else if (gb[0].dout) PROF_LAUNCH((k_gw_bwd<false, 0>), gridw, dim3(GW_NT), 0, c.st, gs, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, nsplit, e->status);
+        else PROF_LAUNCH((k_gw_bwd<false, 1>), gridw, dim3(GW_NT), 0, c.st, gs, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, nsplit, e->status);
         CAL_CHECK_LAUNCH("k_gw_bwd");
         return 0;
     }
+    const CSR gd = csr_dst(c);
     const dim3 grid(B, nsl, nb);
-    // the two-branch launch: 2 x B x H/64 workgroups -- at 128 graphs twice the CUs; the 80 KB instantiation runs them as ONE round
-    // (its gn goes out in slot order: only when the per-graph attention backward consumes it)
-    const bool lean2 = rs && (int64_t)B * nsl * nb > e->num_cus && gb[0].gn_slot && gb[nb - 1].gn_slot;
-    if (lean2 && e->ntiles > 0) PROF_LAUNCH((k_gconv_bwd<true, 2, true, true>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, GconvBwdBranch2{{gb[0], gb[nb - 1]}}, e->loop_w, c.N, H, H, e->status);
-    else if (lean2) PROF_LAUNCH((k_gconv_bwd<true, 2, false, true>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, GconvBwdBranch2{{gb[0], gb[nb - 1]}}, e->loop_w, c.N, H, H, e->status);
-    else if (rs && e->ntiles > 0) PROF_LAUNCH((k_gconv_bwd<true, 2, true>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, GconvBwdBranch2{{gb[0], gb[nb - 1]}}, e->loop_w, c.N, H, H, e->status);
-    else if (rs) PROF_LAUNCH((k_gconv_bwd<true, 2>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, GconvBwdBranch2{{gb[0], gb[nb - 1]}}, e->loop_w, c.N, H, H, e->status);
-    // more workgroups than CUs (packed batches, batches of > 128 graphs): the 80 KB instantiation, two workgroups per CU
-    else if (gb[0].dout && (int64_t)B * nsl * nb > e->num_cus) PROF_LAUNCH((k_gconv_bwd<false, 0, false, true>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, GconvBwdBranch2{{gb[0], gb[nb - 1]}}, e->loop_w, c.N, H, H, e->status);
-    else if (gb[0].dout) PROF_LAUNCH((k_gconv_bwd<false, 0>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, GconvBwdBranch2{{gb[0], gb[nb - 1]}}, e->loop_w, c.N, H, H, e->status);
-    else if ((int64_t)B * nsl * nb > e->num_cus) PROF_LAUNCH((k_gconv_bwd<false, 1, false, true>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, GconvBwdBranch2{{gb[0], gb[nb - 1]}}, e->loop_w, c.N, H, H, e->status);
-    else PROF_LAUNCH((k_gconv_bwd<false, 1>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, GconvBwdBranch2{{gb[0], gb[nb - 1]}}, e->loop_w, c.N, H, H, e->status);
+    // lean: the 80 KB instantiation, two workgroups per CU -- the two-branch launch at 128 graphs is twice the CUs, packed batches
+    // and batches of > 128 graphs more (its two-branch gn goes out in slot order: only when k_att_bwd_graph consumes it)
+    if (co && lean && e->ntiles > 0) PROF_LAUNCH((k_gconv_bwd<true, 2, true, true>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, e->status);
+    else if (co && lean) PROF_LAUNCH((k_gconv_bwd<true, 2, false, true>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, e->status);
+    else if (co && e->ntiles > 0) PROF_LAUNCH((k_gconv_bwd<true, 2, true>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, e->status);
+    else if (co) PROF_LAUNCH((k_gconv_bwd<true, 2>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, e->status);
+    else if (gb[0].dout && lean) PROF_LAUNCH((k_gconv_bwd<false, 0, false, true>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, e->status);
+    else if (gb[0].dout) PROF_LAUNCH((k_gconv_bwd<false, 0>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, e->status);
+    else if (lean) PROF_LAUNCH((k_gconv_bwd<false, 1, false, true>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, e->status);
+    else PROF_LAUNCH((k_gconv_bwd<false, 1>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, e->status);
     CAL_CHECK_LAUNCH("k_gconv_bwd");
     return 0;
 }
 
-// the one-launch readout in row blocks (k_ro_step<true>): training steps of 129 .. 512 graphs
-bool use_ro_rows(const Ctx& c) {
-    const Engine* e = c.e;
-    const int B = c.B, H = e->H, C = e->C;
-    return e->ro_rows && e->ro_step && c.training && !e->cat && B > RS_B && B <= RBK_MAXRB * RS_B && H <= RS_K && H % RO_CW == 0 &&
-           RS_B * C <= 2048 && C <= 64 && (size_t)3 * cdiv(B, RS_B) * ((size_t)H * H + (size_t)C * H) <= e->slab_floats;
-}
-bool use_ro(const Ctx& c) {
-    const int B = c.B, H = c.e->H, C = c.e->C;
-    const int B4 = (B + 15) & ~15;
-    if (c.e->cat) return false;                     // the 2H-wide co head takes the GEMM path
-    return (size_t)B4 * (H + 4) <= (size_t)RO_LDS && B * H <= 16384 && H % RO_CW == 0 && B4 <= 256 && H <= 256 &&
-           B * C <= 2048 && C <= 64;
-}
 RoArgs make_ro(const Ctx& c) {
     Engine* e = c.e;
     const int L = e->L, H = e->H, C = e->C, B = c.B;
@@ -904,7 +894,6 @@ RoArgs make_ro(const Ctx& c) {
     return a;
 }
 
-#define RC(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 // profiling aid: cal_engine_debug_stop(k) makes the step return after its k-th launch site (0 = run all)
 static int g_stop_after = 0;
 static int g_stage = 0;
@@ -928,11 +917,6 @@ int gin_rows(Ctx& c, int mode, const GinRowArgs& ga) {
     });
 }
 
-// narrow feature matrices of big batches: the feature layer as row kernels (engine_feat.hpp) instead of tiled GEMMs
-bool feat_rows(const Ctx& c) {
-    const Engine* e = c.e;
-    return e->F <= FEAT_FMAX && c.N > 16384 && e->H % 4 == 0 && e->H <= 256 && group_for(e->H, 4) >= FEAT_FMAX;
-}
 template <typename Fn>
 int with_g_fp(int H, int F, Fn f) {
     return with_g(H, [&](auto g) {
@@ -980,37 +964,104 @@ int launch_pool_cnt(Ctx& c) {
     });
 }
 
-int engine_forward(Ctx& c, const float* x0, const int64_t* edge_index, const int64_t* batch, const int64_t* y,
-                   const int64_t* perm, float wc, float wo, float wco, int want_grad) {
+// The route of a step of this shape and mode (want_grad: a backward follows the forward in the same step)
+Route make_route(const Ctx& c, bool want_grad) {
+    const Engine* e = c.e;
+    const int N = c.N, B = c.B, T = c.T, H = e->H, F = e->F, C = e->C, L = e->L, mn = e->max_nodes, me = e->max_edges;
+    const bool gin = e->gin, gat = e->K > 0, gcn = !gin && !gat;
+    Route r;
+    memset(&r, 0, sizeof(r));
+    // per-graph plan (engine_plan.hpp) when the host vouches for the batch layout; for graphs of up to 8192 nodes (config 5) one
+    // 1024-thread workgroup per graph, rows ranked from a global scratch
+    const bool layout = e->node_ptr && e->edge_ptr && B > 0 && mn > 0;
+    if (layout && mn <= GP_T2 && me <= GP_E2) r.plan = mn > GP_T || me > GP_E ? Plan::Graph1024 : Plan::Graph256;
+    else if (layout && e->ntiles == 0 && mn <= GPB_T) r.plan = Plan::Big;
+    else r.plan = Plan::Node;
+    const bool graph_plan = r.plan == Plan::Graph256 || r.plan == Plan::Graph1024;
+    r.plan_stats = r.plan != Plan::Node && c.training && F <= 64;
+    // per-graph fused convolutions (engine_gconv.hpp): need the batch's per-graph bounds from the host; backward: 64-node graphs
+    const bool gc = mn > 0 && mn <= GC_T && me <= GC_E && H % GC_N == 0 && H <= GC_K && B > 0;
+    const bool small = mn <= 64 && me <= gc_edge_cap(64);
+    const bool gcb = gc && small && T <= 128 * 4;
+    // wide per-graph convolutions, both ways (engine_gwide.hpp): graphs of 129 .. 256 nodes (the reference's default SPMotif shape)
+    const bool gw = e->gwide && mn > GC_T && mn <= GW_T && me <= GW_E && H % GC_N == 0 && H <= GW_K && B > 0 && e->ntiles == 0 && gcn;
+    r.plan_coef = graph_plan && gw;
+    if (gin) {
+        r.bb_fwd = gc && small && (!c.training || (gcb && me <= GB_E)) ? Conv::Graph64 : Conv::Node;
+        r.bb_bwd = gcb && me <= GB_E ? Conv::Graph64 : Conv::Node;
+    } else if (gat) {
+        const int D = H / e->K;
+        r.bb_fwd = gc && small && (D == 32 || D == 64) && me <= GG_E ? Conv::Graph64 : Conv::Node;
+        r.bb_bwd = gcb && (D == 32 || D == 64) && me <= GGB_E ? Conv::Graph64 : Conv::Node;
+    } else {
+        r.bb_fwd = gw ? Conv::Wide : !gc ? Conv::Node : small ? Conv::Graph64 : Conv::Graph128;
+        r.bb_bwd = gw ? Conv::Wide : gcb ? Conv::Graph64 : Conv::Node;
+    }
+    r.co_fwd = gw ? Conv::Wide : !gc ? Conv::Node : small ? Conv::Graph64 : Conv::Graph128;
+    r.co_bwd = gw ? Conv::Wide : gcb ? Conv::Graph64 : Conv::Node;
+    const int64_t w1 = (int64_t)T * (H / GC_N), w2 = 2 * w1;     // workgroups of a one- / two-branch per-graph launch
+    r.gw_cols_bb = w1 * 2 <= e->num_cus ? 32 : 64;
+    r.gw_cols_co = w2 * 2 <= e->num_cus ? 32 : 64;
+    auto nsplit = [&](int64_t w) { return !gw ? 1 : w * 4 <= e->num_cus ? 4 : w * 2 <= e->num_cus ? 2 : 1; };
+    r.nsplit_bb = nsplit(w1); r.nsplit_co = nsplit(w2);
+    // attention: per graph needs the per-graph plan's facts (a graph's edges are one run of edge_index columns, no self loops)
+    const bool aw = gw && e->node_ptr && e->edge_ptr && mn <= AW_T && me <= AW_E && H <= 256 && T <= 512;
+    const bool ag = gc && mn <= 4 * (512 / group_for(H, 4)) && me <= GP_E;
+    r.att_fwd = aw && 3 * T >= e->num_cus ? Att::Wide : ag ? Att::Graph : Att::Node;
+    r.att_bwd = aw ? Att::Wide : gcb && T <= 256 ? Att::Graph : Att::Node;
+    r.ag_split = aw ? std::max(1, std::min(8, e->num_cus / std::max(T, 1))) : 2;
+    r.lean_bb = w1 > e->num_cus;
+    r.lean_co = w2 > e->num_cus && r.att_bwd == Att::Graph;
+    // narrow feature matrices of big batches: the feature layer as row kernels (engine_feat.hpp) instead of tiled GEMMs
+    const bool feat_rows = F <= FEAT_FMAX && N > 16384 && H % 4 == 0 && H <= 256 && group_for(H, 4) >= FEAT_FMAX;
+    r.feat_fwd = feat_rows ? FeatFwd::Rows : FeatFwd::Gemm;
+    r.feat_chunks = r.bb_bwd == Conv::Wide;
+    const bool rides = H <= FB_H && (r.feat_chunks ? F <= FB_F : F <= FM_F);
+    if (L == 0) r.feat_bwd = FeatBwd::Gemm;
+    else if (r.bb_bwd != Conv::Node) r.feat_bwd = rides ? FeatBwd::Units : FeatBwd::Gemm;
+    else r.feat_bwd = feat_rows && !gin ? FeatBwd::Rows : FeatBwd::Gemm;
+    const bool st = e->striped && c.training;
+    r.st_bb = st && r.bb_fwd == r.bb_bwd && r.bb_bwd != Conv::Node;
+    r.st_bb1 = r.st_bb && (gin || gw || r.feat_bwd == FeatBwd::Units);
+    r.st_node = st && gcn && !gc && N > 0 && N < 16384;
+    r.st_feat = (r.st_bb && !gin && !gw && r.feat_bwd == FeatBwd::Units) || r.st_node;
+    r.st_co = gw ? st : st && ag && gcb && T <= 256;
+    // readout (the 2H-wide co head of cat takes the GEMM chain); row blocks: training steps of 129 .. 512 graphs
+    const int B4 = (B + 15) & ~15;
+    const bool ro = !e->cat && (size_t)B4 * (H + 4) <= (size_t)RO_LDS && B * H <= 16384 && H % RO_CW == 0 && B4 <= 256 && H <= 256 &&
+                    B * C <= 2048 && C <= 64;
+    const bool ro_rows = e->ro_rows && e->ro_step && !e->cat && B > RS_B && B <= RBK_MAXRB * RS_B && H <= RS_K && H % RO_CW == 0 &&
+                         RS_B * C <= 2048 && C <= 64 && (size_t)3 * cdiv(B, RS_B) * ((size_t)H * H + (size_t)C * H) <= e->slab_floats;
+    const bool step = want_grad && c.training;
+    r.ro = ro && step && B <= RS_B && H <= RS_K && e->ro_step ? Readout::OneLaunch : ro_rows && step ? Readout::Rows
+         : ro ? Readout::FourKernel : Readout::Gemm;
+    return r;
+}
+
+// 0. zero the fp64 arena and the GraphPlan counters (one kernel, not memset nodes) -- or, for a forward + backward step on the
+//    per-graph plan, nothing: those duties ride in k_plan_graph (engine_plan.hpp: PlanFold) and bn_feat's statistics range was
+//    zeroed by the previous step's k_finish.  1. GraphPlan
+int fwd_plan(Ctx& c, const float* x0, const int64_t* edge_index) {
     Engine* e = c.e;
-    const int N = c.N, B = c.B, T = c.T, H = e->H, F = e->F, C = e->C, L = e->L;
+    const Route& r = c.r;
+    const int N = c.N, B = c.B, T = c.T, F = e->F;
     const int64_t E = c.E;
     hipStream_t st = c.st;
-    const size_t NH = (size_t)N * H;
-    const int64_t* tgp = e->ntiles > 0 ? e->tile_gptr : nullptr;
-    // per-graph plan (engine_plan.hpp) when the host vouches for the batch layout
-    const bool fast_plan = e->node_ptr && e->edge_ptr && B > 0 && e->max_nodes > 0 && e->max_nodes <= GP_T2 && e->max_edges <= GP_E2;
-    const bool wide_plan = fast_plan && (e->max_nodes > GP_T || e->max_edges > GP_E);
-    // ... and for graphs of up to 8192 nodes (config 5): one 1024-thread workgroup per graph, rows ranked from a global scratch
-    const bool big_plan = !fast_plan && e->node_ptr && e->edge_ptr && B > 0 && e->ntiles == 0 && e->max_nodes > 0 && e->max_nodes <= GPB_T;
-    const bool plan_stats = (fast_plan || big_plan) && c.training && F <= 64;      // bn_feat's statistics ride in the plan kernel
-    // 0. zero the fp64 arena and the GraphPlan counters (one kernel, not memset nodes) -- or, for a forward + backward step on
-    //    the per-graph plan, nothing: those duties ride in k_plan_graph (engine_plan.hpp: PlanFold) and bn_feat's statistics
-    //    range was zeroed by the previous step's k_finish
-    const bool fold = e->fold_zero && fast_plan && c.training && c.want_grad && !e->bn0_dirty_host && g_stop_after == 0;
+    const bool graph_plan = r.plan == Plan::Graph256 || r.plan == Plan::Graph1024;
+    const bool fold = e->fold_zero && graph_plan && c.training && c.want_grad && !e->bn0_dirty_host && g_stop_after == 0;
     if (c.training) e->bn0_dirty_host = 1;          // (cleared where k_finish is enqueued)
     if (!fold) {
-        const int64_t ni = (fast_plan || big_plan) ? 0 : 4 * ((int64_t)N + 1);
+        const int64_t ni = r.plan != Plan::Node ? 0 : 4 * ((int64_t)N + 1);
         hipLaunchKernelGGL(k_zero_f64, dim3(cdiv(std::max<int64_t>(e->arena_n, ni), 256) + (c.draw_perm ? cdiv(B, ZP_EPB) : 0)), dim3(256), 0, st,
                            e->arena, (int64_t)e->arena_n, e->work, ni, e->status, (e->K > 0 && c.training) ? e->gat_ctr : nullptr,
                            c.draw_perm ? e->perm_dev : nullptr, B, e->perm_seed, e->perm_ctr, c.adam_in_finish ? e->step : nullptr,
                            c.training ? e->status + 3 : nullptr);
         CAL_CHECK_LAUNCH("k_zero_f64"); STAGE();
     }
-    // 1. GraphPlan
-    if (fast_plan) {
-        auto kern = wide_plan ? k_plan_graph<GP_T2, GP_E2, 1024> : k_plan_graph<GP_T, GP_E, 256>;
-        const int nt = wide_plan ? 1024 : 256;
+    if (graph_plan) {
+        const bool wide = r.plan == Plan::Graph1024;
+        auto kern = wide ? k_plan_graph<GP_T2, GP_E2, 1024> : k_plan_graph<GP_T, GP_E, 256>;
+        const int nt = wide ? 1024 : 256;
         PlanFold pf;
         memset(&pf, 0, sizeof(pf));
         if (fold) {
@@ -1020,29 +1071,35 @@ int engine_forward(Ctx& c, const float* x0, const int64_t* edge_index, const int
             pf.perm = c.draw_perm ? e->perm_dev : nullptr; pf.permB = B; pf.seed = e->perm_seed; pf.perm_ctr = e->perm_ctr;
             pf.dirty = e->status + 3;
         }
-        hipLaunchKernelGGL(kern, dim3(T + ((fold && c.draw_perm) ? cdiv(B, nt / 4) : 0)), dim3(nt), 0, st, edge_index, E, N, T, e->node_ptr, e->edge_ptr, batch, tgp, B, e->loop_w,
+        hipLaunchKernelGGL(kern, dim3(T + ((fold && c.draw_perm) ? cdiv(B, nt / 4) : 0)), dim3(nt), 0, st, edge_index, E, N, T, e->node_ptr, e->edge_ptr,
+                           c.batch, e->ntiles > 0 ? e->tile_gptr : nullptr, B, e->loop_w,
                            e->rowptr_dst, e->nbr_dst, e->eid_dst, e->rowptr_src, e->nbr_src, e->eid_src, e->row32, e->col32,
-                           e->gptr, e->eptr, e->dis_unit, e->status, plan_stats ? x0 : nullptr, F, bn_stsum(c, 0), bn_stsq(c, 0),
-                           use_gw(c) ? e->coef : nullptr, use_gw(c) ? e->coef_src : nullptr, pf);
+                           e->gptr, e->eptr, e->dis_unit, e->status, r.plan_stats ? x0 : nullptr, F, bn_stsum(c, 0), bn_stsq(c, 0),
+                           r.plan_coef ? e->coef : nullptr, r.plan_coef ? e->coef_src : nullptr, pf);
         CAL_CHECK_LAUNCH("k_plan_graph"); STAGE();
-    } else if (big_plan) {
+    } else if (r.plan == Plan::Big) {
         int* scratch = e->work + 4 * ((size_t)e->capN + 1);
-        hipLaunchKernelGGL(k_plan_big, dim3(B, 2), dim3(1024), 0, st, edge_index, E, N, B, e->node_ptr, e->edge_ptr, batch, e->loop_w,
+        hipLaunchKernelGGL(k_plan_big, dim3(B, 2), dim3(1024), 0, st, edge_index, E, N, B, e->node_ptr, e->edge_ptr, c.batch, e->loop_w,
                            e->rowptr_dst, e->rowptr_src, e->row32, e->col32, e->gptr, e->eptr, e->dis_unit, e->status, scratch,
-                           plan_stats ? x0 : nullptr, F, bn_stsum(c, 0), bn_stsq(c, 0));
+                           r.plan_stats ? x0 : nullptr, F, bn_stsum(c, 0), bn_stsq(c, 0));
         CAL_CHECK_LAUNCH("k_plan_big"); STAGE();
         RC(plan_rank(E, N, e->rowptr_dst, e->nbr_dst, e->eid_dst, e->rowptr_src, e->nbr_src, e->eid_src, e->row32, e->col32, scratch, st)); STAGE();
     } else {
         RC(plan_build(edge_index, E, N, e->rowptr_dst, e->nbr_dst, e->eid_dst, e->rowptr_src, e->nbr_src, e->eid_src,
                       e->row32, e->col32, e->work, e->status, true, st)); STAGE();
-        hipLaunchKernelGGL(k_gptr_dis, dim3(cdiv(N + 1, 256)), dim3(256), 0, st, batch, N, B, e->gptr, e->rowptr_src, e->loop_w,
+        hipLaunchKernelGGL(k_gptr_dis, dim3(cdiv(N + 1, 256)), dim3(256), 0, st, c.batch, N, B, e->gptr, e->rowptr_src, e->loop_w,
                            e->dis_unit, e->status, e->rowptr_dst, e->eptr);
         CAL_CHECK_LAUNCH("k_gptr_dis"); STAGE();
     }
-    const CSR gd{e->rowptr_dst, e->nbr_dst, e->eid_dst, (int)c.E}, gs{e->rowptr_src, e->nbr_src, e->eid_src, (int)c.E};
-    (void)gs;
-    // 2. bn_feat statistics (model.py:90)
-    if (c.training && !plan_stats) {
+    return 0;
+}
+
+// 2. bn_feat statistics (model.py:90), unless they rode in the plan kernel; 3. h0 = relu(BN(x0) @ W_feat) (model.py:90-91, gcn_conv.py:75-77)
+int fwd_feat(Ctx& c, const float* x0) {
+    Engine* e = c.e;
+    const int N = c.N, H = e->H, F = e->F, L = e->L;
+    hipStream_t st = c.st;
+    if (c.training && !c.r.plan_stats) {
         // wide feature matrices (one-hot degrees: F = 139 at the NCI1-like shape): many short blocks whose column sums go to
         // partial rows (k_stats_final) -- F fp64 atomics per block on the same 2 F addresses cost more than the reads
         int tc = std::min(256, pow2ceil(F));
@@ -1054,8 +1111,7 @@ int engine_forward(Ctx& c, const float* x0, const int64_t* edge_index, const int
         CAL_CHECK_LAUNCH("k_colstats"); STAGE();
         if (wide) { RC(flush_finals(c)); STAGE(); }
     }
-    // 3. h0 = relu(BN(x0) @ W_feat)   (model.py:90-91, gcn_conv.py:75-77)
-    if (feat_rows(c)) {
+    if (c.r.feat_fwd == FeatFwd::Rows) {
         FeatFwdArgs fw;
         fw.x0 = x0; fw.W = e->P + e->o_feat_w; fw.out = e->h; fw.bn0 = bnref(c, 0, N, 1);
         if (c.training && L > 0 && !e->gin) { fw.st_sum = node_acc(c, bn_stsum(c, 1), H); fw.st_sq = node_acc(c, bn_stsq(c, 1), H); }
@@ -1064,49 +1120,49 @@ int engine_forward(Ctx& c, const float* x0, const int64_t* edge_index, const int
             return 0;
         }));
         CAL_CHECK_LAUNCH("k_feat_fwd_rows"); STAGE();
-        RC(flush_finals(c)); STAGE();
     } else {
         GemmArgs a = gemm_args(N, H, F, false, false, 1);
         a.p[0].A = x0; a.p[0].B = e->P + e->o_feat_w; a.p[0].C = e->h;
         a.p[0].xa.has_bn = 1; a.p[0].xa.bn = bnref(c, 0, N, 1);
-        // (a GIN layer starts with the aggregation, not a BatchNorm; striped: BatchNorm_1 is read by k_gconv_fwd / k_gconv_bwd / k_feat_bwd* only)
-        if (c.training && L > 0 && !e->gin) gemm_stats(c, a.p[0], N, H, bn_stsum(c, 1), bn_stsq(c, 1), false, F, striped_feat(c));
+        // (a GIN layer starts with the aggregation, not a BatchNorm)
+        if (c.training && L > 0 && !e->gin) gemm_stats(c, a.p[0], N, H, bn_stsum(c, 1), bn_stsq(c, 1), false, F, c.r.st_feat);
         RC(fwd_gemm(c, false, a, 1)); STAGE();
-        RC(flush_finals(c)); STAGE();
     }
-    // 4. backbone: h_i = relu(A_hat (BN_i(h_{i-1}) @ W_i) + b_i)   (model.py:93-95)
-    const bool gc = use_gc(c);
-    const bool gw = use_gw(c);
-    const bool gw_st = gw && e->striped && c.training;   // the wide kernels' BatchNorm sums go through the accumulator planes (every reader is a striped reader)
-    // 32-column slices (two workgroups per CU) when 64-column slices would leave half of the CUs without a workgroup
-    auto gw_narrow = [&](int nb) { return e->gw_cols ? e->gw_cols == 32 : (int64_t)T * (H / GC_N) * nb * 2 <= e->num_cus; };
-    const bool gat = e->K > 0;
+    RC(flush_finals(c)); STAGE();
+    return 0;
+}
+
+// 4. backbone: h_i = relu(A_hat (BN_i(h_{i-1}) @ W_i) + b_i)   (model.py:93-95)
+int fwd_backbone(Ctx& c) {
+    Engine* e = c.e;
+    const Route& r = c.r;
+    const int N = c.N, T = c.T, H = e->H, L = e->L;
+    const int64_t E = c.E;
+    hipStream_t st = c.st;
+    const size_t NH = (size_t)N * H;
+    const CSR gd = csr_dst(c);
     for (int i = 1; i <= L; ++i) {
-        // A training forward must leave what the backward of the SAME shape reads: the fused layer writes gt1 only, the
-        // node-level backward (T > 512 units, max_edges > GB_E) needs gagg / gy -> fused only where the backward is fused too.
-        if (e->gin && gc && gc_small(c) && e->max_edges <= gc_edge_cap(64) && (!c.training || (use_gcb(c) && e->max_edges <= GB_E))) {
+        const float* hin = e->h + (size_t)(i - 1) * NH;
+        float* hout = e->h + (size_t)i * NH;
+        if (e->gin && r.bb_fwd == Conv::Graph64) {
             // GINConv per graph (engine_ggin.hpp): (A + I)(h W1^T) + b1 with the BatchNorm statistics | BN, ReLU, Linear, ReLU
-            const float* hin = e->h + (size_t)(i - 1) * NH;
             float* t1 = e->gt1 + (size_t)(i - 1) * NH;
             GginFwdArgs ga;
             memset(&ga, 0, sizeof(ga));
             ga.x = hin; ga.W = e->P + e->o_conv_w[i - 1]; ga.bias = e->P + e->o_conv_b[i - 1]; ga.out = t1;
-            if (c.training) { ga.st_sum = graph_acc(c, bn_stsum(c, i), H, striped_gin(c)); ga.st_sq = graph_acc(c, bn_stsq(c, i), H, striped_gin(c)); }
+            if (c.training) { ga.st_sum = graph_acc(c, bn_stsum(c, i), H, r.st_bb); ga.st_sq = graph_acc(c, bn_stsq(c, i), H, r.st_bb); }
             {
-                ProfScope ps(st, 9, 2.0 * N * H * H + 2.0 * (double)(c.E + N) * H, true);
+                ProfScope ps(st, 9, 2.0 * N * H * H + 2.0 * (double)(E + N) * H, true);
                 PROF_LAUNCH((k_ggin_fwd<1>), dim3(T, H / GC_N), dim3(512), 0, st, gd, e->gptr, e->eptr, ga, H, H, e->status);
             }
             CAL_CHECK_LAUNCH("k_ggin_fwd<1>"); STAGE();
             RC(flush_finals(c)); STAGE();
             memset(&ga, 0, sizeof(ga));
-            ga.x = t1; ga.W = e->P + e->o_gin_w2[i - 1]; ga.bias = e->P + e->o_gin_b2[i - 1]; ga.out = e->h + (size_t)i * NH;
+            ga.x = t1; ga.W = e->P + e->o_gin_w2[i - 1]; ga.bias = e->P + e->o_gin_b2[i - 1]; ga.out = hout;
             ga.bn = bnref(c, i, N, 1);
             hipLaunchKernelGGL((k_ggin_fwd<2>), dim3(T, H / GC_N), dim3(512), 0, st, gd, e->gptr, e->eptr, ga, H, H, e->status);
             CAL_CHECK_LAUNCH("k_ggin_fwd<2>"); STAGE();
-            continue;
-        }
-        if (e->gin) {    // GINConv: unit-coefficient aggregation -> Linear -> BN -> ReLU -> Linear -> ReLU (model.py:188-194)
-            const float* hin = e->h + (size_t)(i - 1) * NH;
+        } else if (e->gin) {    // GINConv: unit-coefficient aggregation -> Linear -> BN -> ReLU -> Linear -> ReLU (model.py:188-194)
             float* agg = e->gagg + (size_t)(i - 1) * NH;
             float* t1 = e->gt1 + (size_t)(i - 1) * NH;
             float* yy = e->gy + (size_t)(i - 1) * NH;
@@ -1131,28 +1187,25 @@ int engine_forward(Ctx& c, const float* x0, const int64_t* edge_index, const int
             }
             {
                 GemmArgs a = gemm_args(N, H, H, false, true, 1);
-                a.p[0].A = yy; a.p[0].B = e->P + e->o_gin_w2[i - 1]; a.p[0].bias = e->P + e->o_gin_b2[i - 1];
-                a.p[0].C = e->h + (size_t)i * NH;
+                a.p[0].A = yy; a.p[0].B = e->P + e->o_gin_w2[i - 1]; a.p[0].bias = e->P + e->o_gin_b2[i - 1]; a.p[0].C = hout;
                 RC(fwd_gemm(c, true, a, 1)); STAGE();
             }
-            continue;
-        }
-        if (gat) {       // z = BN_i(h) W_i; attention scores, edge softmax (+dropout), aggregation, bias, ReLU (GATConv)
+        } else if (e->K > 0) {  // z = BN_i(h) W_i; attention scores, edge softmax (+dropout), aggregation, bias, ReLU (GATConv)
             const int K = e->K, D = H / K;
             float* zi = e->gz + (size_t)(i - 1) * NH;
-            float* sc = e->gsc + (size_t)(i - 1) * 4 * al((size_t)e->capN * K);
             const size_t nk = al((size_t)e->capN * K);
-            if (gc && gc_small(c) && (D == 32 || D == 64) && e->max_edges <= GG_E) {      // the whole layer per graph (engine_ggat.hpp)
+            float* sc = e->gsc + (size_t)(i - 1) * 4 * nk;
+            if (r.bb_fwd == Conv::Graph64) {      // the whole layer per graph (engine_ggat.hpp)
                 GgatArgs ga;
                 memset(&ga, 0, sizeof(ga));
-                ga.x = e->h + (size_t)(i - 1) * NH; ga.W = e->P + e->o_conv_w[i - 1]; ga.bias = e->P + e->o_conv_b[i - 1];
-                ga.att = e->P + e->o_conv_att[i - 1]; ga.bn = bnref(c, i, N, 1); ga.out = e->h + (size_t)i * NH; ga.z = zi;
+                ga.x = hin; ga.W = e->P + e->o_conv_w[i - 1]; ga.bias = e->P + e->o_conv_b[i - 1];
+                ga.att = e->P + e->o_conv_att[i - 1]; ga.bn = bnref(c, i, N, 1); ga.out = hout; ga.z = zi;
                 ga.adst = sc; ga.asrc = sc + nk; ga.mx = sc + 2 * nk; ga.den = sc + 3 * nk;
-                if (c.training && i < L) { ga.st_sum = graph_acc(c, bn_stsum(c, i + 1), H, striped_gat(c)); ga.st_sq = graph_acc(c, bn_stsq(c, i + 1), H, striped_gat(c)); }
+                if (c.training && i < L) { ga.st_sum = graph_acc(c, bn_stsum(c, i + 1), H, r.st_bb); ga.st_sq = graph_acc(c, bn_stsq(c, i + 1), H, r.st_bb); }
                 ga.heads = K; ga.D = D; ga.slope = e->gat_slope; ga.p = c.training ? e->gat_p : 0.f;
                 ga.seed = e->gat_seed[i - 1]; ga.ctr = (const uint64_t*)e->gat_ctr; ga.E = E;
                 {
-                    ProfScope ps(st, 7, 2.0 * N * H * H + 2.0 * (double)(c.E + N) * H, true);
+                    ProfScope ps(st, 7, 2.0 * N * H * H + 2.0 * (double)(E + N) * H, true);
                     PROF_LAUNCH(k_ggat_fwd, dim3(T, H / GC_N), dim3(256), 0, st, gd, e->gptr, e->eptr, ga, H, H, e->status);
                 }
                 CAL_CHECK_LAUNCH("k_ggat_fwd"); STAGE();
@@ -1160,132 +1213,125 @@ int engine_forward(Ctx& c, const float* x0, const int64_t* edge_index, const int
                 continue;
             }
             GemmArgs a = gemm_args(N, H, H, false, false, 0);
-            a.p[0].A = e->h + (size_t)(i - 1) * NH; a.p[0].B = e->P + e->o_conv_w[i - 1]; a.p[0].C = zi;
+            a.p[0].A = hin; a.p[0].B = e->P + e->o_conv_w[i - 1]; a.p[0].C = zi;
             a.p[0].xa.has_bn = 1; a.p[0].xa.bn = bnref(c, i, N, 1);
             { ProfScope ps(st, 0, 2.0 * N * H * H); RC(fwd_gemm(c, false, a, 1)); } STAGE();
-            float* hi = e->h + (size_t)i * NH;
             {
-                ProfScope ps(st, 5, 2.0 * N * H * 4 + (double)(c.E + N) * (8 + 12.0 * K) + (N + 1) * 4.0);
+                ProfScope ps(st, 5, 2.0 * N * H * 4 + (double)(E + N) * (8 + 12.0 * K) + (N + 1) * 4.0);
                 RC(gat_forward(e->rowptr_dst, e->nbr_dst, e->eid_dst, zi, e->P + e->o_conv_att[i - 1], e->P + e->o_conv_b[i - 1], 1,
-                               e->gat_slope, c.training ? e->gat_p : 0.f, e->gat_seed[i - 1], (const uint64_t*)e->gat_ctr, hi,
+                               e->gat_slope, c.training ? e->gat_p : 0.f, e->gat_seed[i - 1], (const uint64_t*)e->gat_ctr, hout,
                                sc, sc + nk, sc + 2 * nk, sc + 3 * nk, N, E, K, D, st));
             }
             STAGE();
             if (c.training && i < L) {
                 int tc = std::min(256, pow2ceil(H));
                 int rpb = std::max(32, cdiv(N, 1024));
-                if (H == 256 && aligned16(hi))
-                    hipLaunchKernelGGL(k_colstats4, dim3(cdiv(N, rpb)), dim3(256), 0, st, hi, N, rpb, Acc(bn_stsum(c, i + 1)), Acc(bn_stsq(c, i + 1)));
+                if (H == 256 && aligned16(hout))
+                    hipLaunchKernelGGL(k_colstats4, dim3(cdiv(N, rpb)), dim3(256), 0, st, hout, N, rpb, Acc(bn_stsum(c, i + 1)), Acc(bn_stsq(c, i + 1)));
                 else
-                    hipLaunchKernelGGL(k_colstats, dim3(cdiv(N, rpb)), dim3(256), 0, st, hi, N, H, tc, rpb, Acc(bn_stsum(c, i + 1)), Acc(bn_stsq(c, i + 1)));
+                    hipLaunchKernelGGL(k_colstats, dim3(cdiv(N, rpb)), dim3(256), 0, st, hout, N, H, tc, rpb, Acc(bn_stsum(c, i + 1)), Acc(bn_stsq(c, i + 1)));
                 CAL_CHECK_LAUNCH("k_colstats"); STAGE();
             }
-            continue;
-        }
-        if (gw) {        // GCNConv per graph of up to 256 nodes: MFMA product + sparse aggregation from LDS + statistics (engine_gwide.hpp)
+        } else if (r.bb_fwd != Conv::Node) {
+            // GCNConv per graph: MFMA product + aggregation + statistics in one kernel (engine_gconv.hpp); graphs of up to 256 nodes:
+            // the sparse aggregation from LDS (engine_gwide.hpp).  The first layer writes the unit coefficients in slot order
+            // unless k_plan_graph has.
             GconvBranch gb;
             memset(&gb, 0, sizeof(gb));
-            gb.x = e->h + (size_t)(i - 1) * NH; gb.W = e->P + e->o_conv_w[i - 1]; gb.bias = e->P + e->o_conv_b[i - 1];
-            gb.dis = e->dis_unit; gb.bn = bnref(c, i, N, 1); gb.out = e->h + (size_t)i * NH;
-            if (i == 1 && !fast_plan) gb.coef_out = e->coef; else gb.coef_in = e->coef;      // (k_plan_graph writes the unit coefficients in slot order)
-            if (c.training && i < L) { gb.st_sum = graph_acc(c, bn_stsum(c, i + 1), H, gw_st); gb.st_sq = graph_acc(c, bn_stsq(c, i + 1), H, gw_st); }
+            gb.x = hin; gb.W = e->P + e->o_conv_w[i - 1]; gb.bias = e->P + e->o_conv_b[i - 1];
+            gb.dis = e->dis_unit; gb.bn = bnref(c, i, N, 1); gb.out = hout;
+            if (i == 1 && !r.plan_coef) gb.coef_out = e->coef; else gb.coef_in = e->coef;
+            if (c.training && i < L) { gb.st_sum = graph_acc(c, bn_stsum(c, i + 1), H, r.st_bb); gb.st_sq = graph_acc(c, bn_stsq(c, i + 1), H, r.st_bb); }
+            const GconvBranch2 b2{{gb, gb}};
             {
-                ProfScope ps(st, 2, 2.0 * N * H * H + 2.0 * (double)(c.E + N) * H, true);
-                if (gw_narrow(1)) PROF_LAUNCH((k_gw_fwd<false, 32>), dim3(T, H / 32, 1), dim3(GW_NT), 0, st, gd, e->gptr, e->eptr, GconvBranch2{{gb, gb}}, 1, e->loop_w, H, H, e->status);
-                else PROF_LAUNCH((k_gw_fwd<false, 64>), dim3(T, H / GC_N, 1), dim3(GW_NT), 0, st, gd, e->gptr, e->eptr, GconvBranch2{{gb, gb}}, 1, e->loop_w, H, H, e->status);
+                ProfScope ps(st, 2, 2.0 * N * H * H + 2.0 * (double)(E + N) * H, true);
+                if (r.bb_fwd == Conv::Wide && r.gw_cols_bb == 32) PROF_LAUNCH((k_gw_fwd<false, 32>), dim3(T, H / 32, 1), dim3(GW_NT), 0, st, gd, e->gptr, e->eptr, b2, 1, e->loop_w, H, H, e->status);
+                else if (r.bb_fwd == Conv::Wide) PROF_LAUNCH((k_gw_fwd<false, 64>), dim3(T, H / GC_N, 1), dim3(GW_NT), 0, st, gd, e->gptr, e->eptr, b2, 1, e->loop_w, H, H, e->status);
+                else if (r.bb_fwd == Conv::Graph64) PROF_LAUNCH((k_gconv_fwd<false, 64, 512>), dim3(T, H / GC_N, 1), dim3(512), 0, st, gd, e->gptr, e->eptr, b2, 1, e->loop_w, H, H, e->status);
+                else PROF_LAUNCH((k_gconv_fwd<false, GC_T>), dim3(T, H / GC_N, 1), dim3(256), 0, st, gd, e->gptr, e->eptr, b2, 1, e->loop_w, H, H, e->status);
             }
-            CAL_CHECK_LAUNCH("k_gw_fwd"); STAGE();
+            CAL_CHECK_LAUNCH(r.bb_fwd == Conv::Wide ? "k_gw_fwd" : "k_gconv_fwd"); STAGE();
             RC(flush_finals(c)); STAGE();
-            continue;
-        }
-        if (gc) {        // GCNConv: GEMM + aggregation + statistics in one per-graph kernel
-            GconvBranch gb;
-            memset(&gb, 0, sizeof(gb));
-            gb.x = e->h + (size_t)(i - 1) * NH; gb.W = e->P + e->o_conv_w[i - 1]; gb.bias = e->P + e->o_conv_b[i - 1];
-            gb.dis = e->dis_unit; gb.bn = bnref(c, i, N, 1); gb.out = e->h + (size_t)i * NH;
-            if (i == 1) gb.coef_out = e->coef; else gb.coef_in = e->coef;
-            if (c.training && i < L) { gb.st_sum = graph_acc(c, bn_stsum(c, i + 1), H, striped_bb(c)); gb.st_sq = graph_acc(c, bn_stsq(c, i + 1), H, striped_bb(c)); }
+        } else {
+            GemmArgs a = gemm_args(N, H, H, false, false, 0);
+            a.p[0].A = hin; a.p[0].B = e->P + e->o_conv_w[i - 1]; a.p[0].C = e->z;
+            a.p[0].xa.has_bn = 1; a.p[0].xa.bn = bnref(c, i, N, 1);
+            { ProfScope ps(st, 0, 2.0 * N * H * H); RC(fwd_gemm(c, false, a, 1)); } STAGE();
+            SpmmBranch br{e->z, hout, e->P + e->o_conv_b[i - 1], nullptr, e->dis_unit, Acc(), Acc(), nullptr, nullptr, nullptr};
+            const bool wst = c.training && i < L;
+            const int rpb = spmm_rpb(H, wst, N);
+            if (wst) { br.st_sum = spmm_acc(c, bn_stsum(c, i + 1), H, rpb); br.st_sq = spmm_acc(c, bn_stsq(c, i + 1), H, rpb); }
             {
-                ProfScope ps(st, 2, 2.0 * N * H * H + 2.0 * (double)(c.E + N) * H, true);
-                if (gc_small(c)) PROF_LAUNCH((k_gconv_fwd<false, 64, 512>), dim3(T, H / GC_N, 1), dim3(512), 0, st, gd, e->gptr, e->eptr, GconvBranch2{{gb, gb}}, 1,
-                                                    e->loop_w, H, H, e->status);
-                else PROF_LAUNCH((k_gconv_fwd<false, GC_T>), dim3(T, H / GC_N, 1), dim3(256), 0, st, gd, e->gptr, e->eptr, GconvBranch2{{gb, gb}}, 1,
-                                        e->loop_w, H, H, e->status);
+                ProfScope ps(st, 1, 2.0 * N * H * 4 + (double)(E + N) * 8 + (N + 1) * 4.0, true);
+                RC(launch_espmm(st, gd, SpmmBranch2{{br, br}}, 1, 1, e->loop_w, N, H, rpb));
             }
-            CAL_CHECK_LAUNCH("k_gconv_fwd"); STAGE();
+            CAL_CHECK_LAUNCH("k_espmm"); STAGE();
             RC(flush_finals(c)); STAGE();
-            continue;
         }
-        GemmArgs a = gemm_args(N, H, H, false, false, 0);
-        a.p[0].A = e->h + (size_t)(i - 1) * NH; a.p[0].B = e->P + e->o_conv_w[i - 1]; a.p[0].C = e->z;
-        a.p[0].xa.has_bn = 1; a.p[0].xa.bn = bnref(c, i, N, 1);
-        { ProfScope ps(st, 0, 2.0 * N * H * H); RC(fwd_gemm(c, false, a, 1)); } STAGE();
-        SpmmBranch br{e->z, e->h + (size_t)i * NH, e->P + e->o_conv_b[i - 1], nullptr, e->dis_unit, Acc(), Acc(), nullptr, nullptr, nullptr};
-        const bool wst = c.training && i < L;
-        const int rpb = spmm_rpb(H, wst, N);
-        if (wst) { br.st_sum = spmm_acc(c, bn_stsum(c, i + 1), H, rpb); br.st_sq = spmm_acc(c, bn_stsq(c, i + 1), H, rpb); }
-        {
-            ProfScope ps(st, 1, 2.0 * N * H * 4 + (double)(c.E + N) * 8 + (N + 1) * 4.0, true);
-            RC(launch_espmm(st, gd, SpmmBranch2{{br, br}}, 1, 1, e->loop_w, N, H, rpb));
-        }
-        CAL_CHECK_LAUNCH("k_espmm"); STAGE();
-        RC(flush_finals(c)); STAGE();
     }
+    return 0;
+}
+
+// 5+6. node attention, edge projections, bnc / bno statistics, edge softmax + weighted degrees (model.py:97-111, gcn_conv.py:63-68)
+int fwd_att(Ctx& c) {
+    Engine* e = c.e;
+    const Route& r = c.r;
+    const int N = c.N, H = e->H, L = e->L;
+    const int64_t E = c.E;
+    hipStream_t st = c.st;
+    const float* x = e->h + (size_t)L * N * H;
+    const CSR gs = csr_src(c);
+    if (r.att_fwd != Att::Node) {
+        // per graph: all of it in one kernel (4 rows per lane group); graphs of 129-256 nodes: the same kernel in four row passes,
+        // four slots per lane (engine_attwide.hpp)
+        // (only when the launch has enough workgroups -- 32 graphs on 256 CUs lose to the node-parallel pair, 19.3 vs 12.6 us;
+        //  128 graphs win, 20.5 vs 24.0 us with their finishing launch.  The backward per graph wins at both: 22.8 vs 28.1, 30.8 vs 47.7 us)
+        const bool wide = r.att_fwd == Att::Wide;
+        const Acc a0 = graph_acc(c, bn_stsum(c, L + 1), H, r.st_co), a1 = graph_acc(c, bn_stsq(c, L + 1), H, r.st_co);
+        const Acc a2 = graph_acc(c, bn_stsum(c, L + 2), H, r.st_co), a3 = graph_acc(c, bn_stsq(c, L + 2), H, r.st_co);
+        auto launch = [&](auto kernel_of) {
+            return with_g(H, [&](auto g) {
+                hipLaunchKernelGGL(kernel_of(g), dim3(c.T), dim3(512), 0, st, e->gptr, gs, x, e->P + e->o_natt_w, e->P + e->o_natt_b,
+                                   e->P + e->o_eatt_w, e->P + e->o_eatt_b, e->anode, e->pq, e->att, e->dis_co, e->dis_co + N, a0, a1, a2, a3,
+                                   e->loop_w, H, E, e->status, e->no_node_att ? 0.f : 1.f, e->no_edge_att ? 0.f : 1.f, e->eptr);
+                return 0;
+            });
+        };
+        if (wide) RC(launch([](auto g) { return k_att_fwd_wide<4, decltype(g)::value>; }));
+        else RC(launch([](auto g) { return k_att_fwd_graph<4, decltype(g)::value>; }));
+        CAL_CHECK_LAUNCH(wide ? "k_att_fwd_wide" : "k_att_fwd_graph"); STAGE();
+        RC(flush_finals(c)); STAGE();
+        return 0;
+    }
+    const Acc a0 = node_acc(c, bn_stsum(c, L + 1), H), a1 = node_acc(c, bn_stsq(c, L + 1), H);
+    const Acc a2 = node_acc(c, bn_stsum(c, L + 2), H), a3 = node_acc(c, bn_stsq(c, L + 2), H);
+    RC(with_g(H, [&](auto g) {
+        constexpr int G = decltype(g)::value;
+        hipLaunchKernelGGL((k_node_att_fwd<4, G>), dim3(cdiv(N, c.rpb_n)), dim3(256), 0, st, x, e->P + e->o_natt_w,
+                           e->P + e->o_natt_b, e->P + e->o_eatt_w, e->anode, e->pq, a0, a1, a2, a3, N, H, c.rpb_n, e->no_node_att ? 0.f : 1.f);
+        return 0;
+    }));
+    CAL_CHECK_LAUNCH("k_node_att_fwd"); STAGE();
+    RC(flush_finals(c)); STAGE();
+    hipLaunchKernelGGL(k_edge_att_deg, dim3(cdiv(N, 32)), dim3(256), 0, st, gs, e->pq, e->P + e->o_eatt_b, e->att, e->dis_co,
+                       e->dis_co + N, e->loop_w, N, E, e->no_edge_att ? 0.f : 1.f);
+    CAL_CHECK_LAUNCH("k_edge_att_deg"); STAGE();
+    return 0;
+}
+
+// 7-9. z_k = BN_k(a_k * x) @ W_k, h_k = relu(A_hat_k z_k + b_k) for k in (context, objects), add-pool (model.py:112-116)
+int fwd_co(Ctx& c) {
+    Engine* e = c.e;
+    const Route& r = c.r;
+    const int N = c.N, B = c.B, T = c.T, H = e->H, L = e->L;
+    const int64_t E = c.E;
+    hipStream_t st = c.st;
+    const size_t NH = (size_t)N * H;
     const float* x = e->h + (size_t)L * NH;
-    // 5+6 per graph: node attention, edge softmax and weighted degrees in one kernel (4 rows per lane group)
-    // (forward: only when the launch has enough workgroups -- 32 graphs on 256 CUs lose to the node-parallel pair, 19.3 vs 12.6 us;
-    //  128 graphs win, 20.5 vs 24.0 us with their finishing launch.  The backward per graph wins at both: 22.8 vs 28.1, 30.8 vs 47.7 us)
-    const bool att_wide = use_aw(c) && 3 * T >= e->num_cus;
-    if (att_wide) {          // graphs of 129-256 nodes: the same kernel in four row passes, four slots per lane (engine_attwide.hpp)
-        const bool sw = gw_st;
-        const Acc a0 = graph_acc(c, bn_stsum(c, L + 1), H, sw), a1 = graph_acc(c, bn_stsq(c, L + 1), H, sw);
-        const Acc a2 = graph_acc(c, bn_stsum(c, L + 2), H, sw), a3 = graph_acc(c, bn_stsq(c, L + 2), H, sw);
-        RC(with_g(H, [&](auto g) {
-            constexpr int G = decltype(g)::value;
-            hipLaunchKernelGGL((k_att_fwd_wide<4, G>), dim3(T), dim3(512), 0, st, e->gptr, gs, x, e->P + e->o_natt_w, e->P + e->o_natt_b,
-                               e->P + e->o_eatt_w, e->P + e->o_eatt_b, e->anode, e->pq, e->att, e->dis_co, e->dis_co + N, a0, a1, a2, a3,
-                               e->loop_w, H, E, e->status, e->no_node_att ? 0.f : 1.f, e->no_edge_att ? 0.f : 1.f, e->eptr);
-            return 0;
-        }));
-        CAL_CHECK_LAUNCH("k_att_fwd_wide"); STAGE();
-        RC(flush_finals(c)); STAGE();
-    }
-    const bool att_graph = att_wide || att_graph_fwd(c);
-    if (att_graph && !att_wide) {
-        const bool sco = striped_co(c);
-        const Acc a0 = graph_acc(c, bn_stsum(c, L + 1), H, sco), a1 = graph_acc(c, bn_stsq(c, L + 1), H, sco);
-        const Acc a2 = graph_acc(c, bn_stsum(c, L + 2), H, sco), a3 = graph_acc(c, bn_stsq(c, L + 2), H, sco);
-        RC(with_g(H, [&](auto g) {
-            constexpr int G = decltype(g)::value;
-            hipLaunchKernelGGL((k_att_fwd_graph<4, G>), dim3(T), dim3(512), 0, st, e->gptr, gs, x, e->P + e->o_natt_w, e->P + e->o_natt_b,
-                               e->P + e->o_eatt_w, e->P + e->o_eatt_b, e->anode, e->pq, e->att, e->dis_co, e->dis_co + N, a0, a1, a2, a3,
-                               e->loop_w, H, E, e->status, e->no_node_att ? 0.f : 1.f, e->no_edge_att ? 0.f : 1.f, e->eptr);
-            return 0;
-        }));
-        CAL_CHECK_LAUNCH("k_att_fwd_graph"); STAGE();
-        RC(flush_finals(c)); STAGE();
-    }
-    // 5. node attention, edge projections, bnc/bno statistics (model.py:97-111)
-    if (!att_graph) {
-        const Acc a0 = node_acc(c, bn_stsum(c, L + 1), H), a1 = node_acc(c, bn_stsq(c, L + 1), H);
-        const Acc a2 = node_acc(c, bn_stsum(c, L + 2), H), a3 = node_acc(c, bn_stsq(c, L + 2), H);
-        RC(with_g(H, [&](auto g) {
-            constexpr int G = decltype(g)::value;
-            hipLaunchKernelGGL((k_node_att_fwd<4, G>), dim3(cdiv(N, c.rpb_n)), dim3(256), 0, st, x, e->P + e->o_natt_w,
-                               e->P + e->o_natt_b, e->P + e->o_eatt_w, e->anode, e->pq, a0, a1, a2, a3, N, H, c.rpb_n, e->no_node_att ? 0.f : 1.f);
-            return 0;
-        }));
-        CAL_CHECK_LAUNCH("k_node_att_fwd"); STAGE();
-        RC(flush_finals(c)); STAGE();
-    }
-    // 6. edge softmax + weighted degrees (model.py:102-104, gcn_conv.py:63-68)
-    if (!att_graph) {
-        hipLaunchKernelGGL(k_edge_att_deg, dim3(cdiv(N, 32)), dim3(256), 0, st, gs, e->pq, e->P + e->o_eatt_b, e->att, e->dis_co,
-                           e->dis_co + N, e->loop_w, N, E, e->no_edge_att ? 0.f : 1.f);
-        CAL_CHECK_LAUNCH("k_edge_att_deg"); STAGE();
-    }
-    // 7-9 fused: both weighted convolutions and the add-pool in one per-graph launch
-    if (gc) {
+    const CSR gd = csr_dst(c);
+    if (r.co_fwd != Conv::Node) {      // both weighted convolutions and the add-pool in one per-graph launch
+        const bool wide = r.co_fwd == Conv::Wide;
+        const int64_t* tgp = e->ntiles > 0 ? e->tile_gptr : nullptr;
         GconvBranch gb[2];
         memset(gb, 0, sizeof(gb));
         for (int k = 0; k < 2; ++k) {
@@ -1293,88 +1339,67 @@ int engine_forward(Ctx& c, const float* x0, const int64_t* edge_index, const int
             gb[k].ew = e->att + (size_t)k * E; gb[k].dis = e->dis_co + (size_t)k * N;
             gb[k].rs = e->anode + k; gb[k].rs_stride = 2; gb[k].bn = bnref(c, L + 1 + k, N, 1);
             gb[k].out = e->hco + (size_t)k * NH; gb[k].z = e->zco + (size_t)k * NH; gb[k].pooled = e->pooled + (size_t)k * B * H;
+            if (wide) continue;
             gb[k].coef_out = e->coef + (size_t)(1 + k) * E;
             gb[k].w_out = e->wslot + (size_t)k * E;
-            gb[k].batch = batch; gb[k].tile_gptr = tgp;          // packed batch: the add-pool is per GRAPH inside the tile
+            gb[k].batch = c.batch; gb[k].tile_gptr = tgp;          // packed batch: the add-pool is per GRAPH inside the tile
         }
-        if (tgp) hipLaunchKernelGGL((k_gconv_fwd<true, 64, 512, true>), dim3(T, H / GC_N, 2), dim3(512), 0, st, gd, e->gptr, e->eptr, GconvBranch2{{gb[0], gb[1]}}, 1,
-                                    e->loop_w, H, H, e->status);
-        else if (gc_small(c)) hipLaunchKernelGGL((k_gconv_fwd<true, 64, 512>), dim3(T, H / GC_N, 2), dim3(512), 0, st, gd, e->gptr, e->eptr, GconvBranch2{{gb[0], gb[1]}}, 1,
-                                            e->loop_w, H, H, e->status);
-        else hipLaunchKernelGGL((k_gconv_fwd<true, GC_T>), dim3(T, H / GC_N, 2), dim3(256), 0, st, gd, e->gptr, e->eptr, GconvBranch2{{gb[0], gb[1]}}, 1,
-                                e->loop_w, H, H, e->status);
-        CAL_CHECK_LAUNCH("k_gconv_fwd(co)"); STAGE();
+        const GconvBranch2 b2{{gb[0], gb[1]}};
+        if (tgp) hipLaunchKernelGGL((k_gconv_fwd<true, 64, 512, true>), dim3(T, H / GC_N, 2), dim3(512), 0, st, gd, e->gptr, e->eptr, b2, 1, e->loop_w, H, H, e->status);
+        else if (r.co_fwd == Conv::Graph64) hipLaunchKernelGGL((k_gconv_fwd<true, 64, 512>), dim3(T, H / GC_N, 2), dim3(512), 0, st, gd, e->gptr, e->eptr, b2, 1, e->loop_w, H, H, e->status);
+        else if (r.co_fwd == Conv::Graph128) hipLaunchKernelGGL((k_gconv_fwd<true, GC_T>), dim3(T, H / GC_N, 2), dim3(256), 0, st, gd, e->gptr, e->eptr, b2, 1, e->loop_w, H, H, e->status);
+        else if (r.gw_cols_co == 32) hipLaunchKernelGGL((k_gw_fwd<true, 32>), dim3(T, H / 32, 2), dim3(GW_NT), 0, st, gd, e->gptr, e->eptr, b2, 1, e->loop_w, H, H, e->status);
+        else hipLaunchKernelGGL((k_gw_fwd<true, 64>), dim3(T, H / GC_N, 2), dim3(GW_NT), 0, st, gd, e->gptr, e->eptr, b2, 1, e->loop_w, H, H, e->status);
+        CAL_CHECK_LAUNCH(wide ? "k_gw_fwd(co)" : "k_gconv_fwd(co)"); STAGE();
+        return 0;
     }
-    if (gw) {        // 7-9 for graphs of up to 256 nodes (engine_gwide.hpp)
-        GconvBranch gb[2];
-        memset(gb, 0, sizeof(gb));
-        for (int k = 0; k < 2; ++k) {
-            gb[k].x = x; gb[k].W = e->P + (k ? e->o_ow : e->o_cw); gb[k].bias = e->P + (k ? e->o_ob : e->o_cb);
-            gb[k].ew = e->att + (size_t)k * E; gb[k].dis = e->dis_co + (size_t)k * N;
-            gb[k].rs = e->anode + k; gb[k].rs_stride = 2; gb[k].bn = bnref(c, L + 1 + k, N, 1);
-            gb[k].out = e->hco + (size_t)k * NH; gb[k].z = e->zco + (size_t)k * NH; gb[k].pooled = e->pooled + (size_t)k * B * H;
-        }
-        if (gw_narrow(2)) hipLaunchKernelGGL((k_gw_fwd<true, 32>), dim3(T, H / 32, 2), dim3(GW_NT), 0, st, gd, e->gptr, e->eptr, GconvBranch2{{gb[0], gb[1]}}, 1, e->loop_w, H, H, e->status);
-        else hipLaunchKernelGGL((k_gw_fwd<true, 64>), dim3(T, H / GC_N, 2), dim3(GW_NT), 0, st, gd, e->gptr, e->eptr, GconvBranch2{{gb[0], gb[1]}}, 1, e->loop_w, H, H, e->status);
-        CAL_CHECK_LAUNCH("k_gw_fwd(co)"); STAGE();
+    GemmArgs a = gemm_args(N, H, H, false, false, 0);
+    for (int k = 0; k < 2; ++k) {
+        a.p[k].A = x; a.p[k].B = e->P + (k ? e->o_ow : e->o_cw); a.p[k].C = e->zco + (size_t)k * NH;
+        a.p[k].xa.rs = e->anode + k; a.p[k].xa.rs_stride = 2;
+        a.p[k].xa.has_bn = 1; a.p[k].xa.bn = bnref(c, L + 1 + k, N, 1);
     }
-    // 7. z_k = BN_k(a_k * x) @ W_k for k in (context, objects)   (model.py:112-113)
-    if (!gc && !gw) {
-        GemmArgs a = gemm_args(N, H, H, false, false, 0);
-        for (int k = 0; k < 2; ++k) {
-            a.p[k].A = x; a.p[k].B = e->P + (k ? e->o_ow : e->o_cw); a.p[k].C = e->zco + (size_t)k * NH;
-            a.p[k].xa.rs = e->anode + k; a.p[k].xa.rs_stride = 2;
-            a.p[k].xa.has_bn = 1; a.p[k].xa.bn = bnref(c, L + 1 + k, N, 1);
-        }
-        RC(fwd_gemm(c, false, a, 2)); STAGE();
-    }
-    // 8. h_k = relu(A_hat_k z_k + b_k)
-    if (!gc && !gw) {
-        SpmmBranch b0{e->zco, e->hco, e->P + e->o_cb, e->att, e->dis_co, Acc(), Acc(), nullptr, nullptr, nullptr};
-        SpmmBranch b1{e->zco + NH, e->hco + NH, e->P + e->o_ob, e->att + E, e->dis_co + N, Acc(), Acc(), nullptr, nullptr, nullptr};
-        RC(launch_espmm(st, gd, SpmmBranch2{{b0, b1}}, 2, 1, e->loop_w, N, H, spmm_rpb(H, false)));
-        CAL_CHECK_LAUNCH("k_espmm(co)"); STAGE();
-    }
-    // 9. add-pool (model.py:115-116)
-    if (!gc && !gw) {
-        RC(launch_pool2(c));
-        STAGE();
-    }
-    // 10. readouts (model.py:125-164)
-    if (use_ro(c) && want_grad && c.training && B <= RS_B && H <= RS_K && e->ro_step) {
-        // the whole readout, forward and backward, in one launch (engine_ro_step.hpp)
+    RC(fwd_gemm(c, false, a, 2)); STAGE();
+    SpmmBranch b0{e->zco, e->hco, e->P + e->o_cb, e->att, e->dis_co, Acc(), Acc(), nullptr, nullptr, nullptr};
+    SpmmBranch b1{e->zco + NH, e->hco + NH, e->P + e->o_ob, e->att + E, e->dis_co + N, Acc(), Acc(), nullptr, nullptr, nullptr};
+    RC(launch_espmm(st, gd, SpmmBranch2{{b0, b1}}, 2, 1, e->loop_w, N, H, spmm_rpb(H, false)));
+    CAL_CHECK_LAUNCH("k_espmm(co)"); STAGE();
+    RC(launch_pool2(c)); STAGE();
+    return 0;
+}
+
+// 10. readouts (model.py:125-164)
+int fwd_readout(Ctx& c) {
+    Engine* e = c.e;
+    const int B = c.B, H = e->H, C = e->C, L = e->L;
+    hipStream_t st = c.st;
+    if (c.r.ro == Readout::OneLaunch || c.r.ro == Readout::Rows) {
+        // the whole readout, forward and backward, in one launch (engine_ro_step.hpp); 128 < B <= 512: in row blocks of 128 graphs
+        // (k_ro_step<true>): the sums over all rows are exchanged between the row blocks inside the kernel, the weight gradients
+        // leave as one slab per row block (front of the slab workspace; engine_backward registers them with k_finish)
         RoStepArgs sa;
         memset(&sa, 0, sizeof(sa));
         sa.a = make_ro(c); sa.zpart = e->zpart; sa.sync = reinterpret_cast<int*>(e->arena + e->a_sync); sa.status = e->status;
-        hipLaunchKernelGGL(k_ro_step<false>, dim3(3, H / RO_CW), dim3(256), 0, st, sa);
+        if (c.r.ro == Readout::OneLaunch) {
+            hipLaunchKernelGGL(k_ro_step<false>, dim3(3, H / RO_CW), dim3(256), 0, st, sa);
+        } else {
+            const int nrb = cdiv(B, RS_B), nch = H / RO_CW;
+            sa.nrb = nrb;
+            sa.xch = parts_alloc(c, (size_t)3 * nch * RBK_XCH);
+            if (!sa.xch) return no_parts();
+            sa.gw1_slab = e->slabs; sa.gw2_slab = e->slabs + (size_t)3 * nrb * H * H;
+            hipLaunchKernelGGL(k_ro_step<true>, dim3(3, nch, nrb), dim3(256), 0, st, sa);
+        }
         CAL_CHECK_LAUNCH("k_ro_step"); STAGE();
-        c.ro_done = 1;
         return 0;
     }
-    if (use_ro_rows(c) && want_grad) {
-        // 128 < B <= 512: the same launch in row blocks of 128 graphs (k_ro_step<true>): the sums over all rows are exchanged
-        // between the row blocks inside the kernel, the weight gradients leave as one slab per row block (front of the slab
-        // workspace; engine_backward registers them with k_finish)
-        const int nrb = cdiv(B, RS_B), nch = H / RO_CW;
-        RoStepArgs sa;
-        memset(&sa, 0, sizeof(sa));
-        sa.a = make_ro(c); sa.zpart = e->zpart; sa.sync = reinterpret_cast<int*>(e->arena + e->a_sync); sa.status = e->status;
-        sa.nrb = nrb;
-        sa.xch = parts_alloc(c, (size_t)3 * nch * RBK_XCH);
-        if (!sa.xch) { set_error("engine: partial-row workspace exhausted"); return 2; }
-        sa.gw1_slab = e->slabs; sa.gw2_slab = e->slabs + (size_t)3 * nrb * H * H;
-        hipLaunchKernelGGL(k_ro_step<true>, dim3(3, nch, nrb), dim3(256), 0, st, sa);
-        CAL_CHECK_LAUNCH("k_ro_step"); STAGE();
-        c.ro_done = 2;
-        return 0;
-    }
-    if (use_ro(c)) {
+    if (c.r.ro == Readout::FourKernel) {
         const RoArgs ra = make_ro(c);
         hipLaunchKernelGGL(k_ro_fwd_a, dim3(3, H / RO_CW), dim3(256), 0, st, ra);
         CAL_CHECK_LAUNCH("k_ro_fwd_a"); STAGE();
         hipLaunchKernelGGL(k_ro_fwd_b, dim3(3, cdiv(B, RO_RB)), dim3(256), 0, st, ra);
         CAL_CHECK_LAUNCH("k_ro_fwd_b"); STAGE();
-        if (!want_grad) {                  // no backward to finish the loss sums
+        if (!c.want_grad) {                  // no backward to finish the loss sums
             hipLaunchKernelGGL(k_ro_loss, dim3(3), dim3(256), 0, st, ra);
             CAL_CHECK_LAUNCH("k_ro_loss");
         }
@@ -1383,7 +1408,7 @@ int engine_forward(Ctx& c, const float* x0, const int64_t* edge_index, const int
     const int bn_fc1 = L + 3, bn_fc2 = L + 4;   // + 2*head
     {
         int tc = std::min(256, pow2ceil(H));
-        hipLaunchKernelGGL(k_readout_prep, dim3(cdiv(B, c.rpb_b)), dim3(256), 0, st, e->pooled, perm, e->iperm, e->xco, B, H, tc,
+        hipLaunchKernelGGL(k_readout_prep, dim3(cdiv(B, c.rpb_b)), dim3(256), 0, st, e->pooled, c.perm, e->iperm, e->xco, B, H, tc,
                            c.rpb_b, bn_stsum(c, bn_fc1), bn_stsq(c, bn_fc1), bn_stsum(c, bn_fc1 + 2), bn_stsq(c, bn_fc1 + 2),
                            bn_stsum(c, bn_fc1 + 4), bn_stsq(c, bn_fc1 + 4), e->cat);
         CAL_CHECK_LAUNCH("k_readout_prep"); STAGE();
@@ -1416,66 +1441,41 @@ int engine_forward(Ctx& c, const float* x0, const int64_t* edge_index, const int
         }
         RC(fwd_gemm(c, true, a, 3)); STAGE();
     }
-    if (B > 256) hipLaunchKernelGGL(k_loss<1024>, dim3(1), dim3(1024), 0, st, e->zl, y, e->logp, e->dzl, e->stats, e->arena + e->a_db2, B, C, wc, wo,
-                                    wco, want_grad);
-    else hipLaunchKernelGGL(k_loss<256>, dim3(1), dim3(256), 0, st, e->zl, y, e->logp, e->dzl, e->stats, e->arena + e->a_db2, B, C, wc, wo,
-                            wco, want_grad);
+    if (B > 256) hipLaunchKernelGGL(k_loss<1024>, dim3(1), dim3(1024), 0, st, e->zl, c.y, e->logp, e->dzl, e->stats, e->arena + e->a_db2, B, C, c.wc, c.wo,
+                                    c.wco, c.want_grad);
+    else hipLaunchKernelGGL(k_loss<256>, dim3(1), dim3(256), 0, st, e->zl, c.y, e->logp, e->dzl, e->stats, e->arena + e->a_db2, B, C, c.wc, c.wo,
+                            c.wco, c.want_grad);
     CAL_CHECK_LAUNCH("k_loss"); STAGE();
     return 0;
 }
 
-int engine_backward(Ctx& c, const float* x0, const int64_t* batch) {
-    Engine* e = c.e;
-    const int N = c.N, B = c.B, T = c.T, H = e->H, F = e->F, C = e->C, L = e->L;
-    const int64_t E = c.E;
-    hipStream_t st = c.st;
-    const size_t NH = (size_t)N * H, BH = (size_t)B * H;
-    const CSR gd{e->rowptr_dst, e->nbr_dst, e->eid_dst, (int)c.E}, gs{e->rowptr_src, e->nbr_src, e->eid_src, (int)c.E};
-    const int bn_fc1 = L + 3, bn_fc2 = L + 4;
-    const float* xin[3] = {e->pooled, e->pooled + BH, e->xco};
-    FinishArgs fa;
-    memset(&fa, 0, sizeof(fa));
-    fa.tick = (c.tick_in_finish && !c.adam_in_finish) ? e->step : nullptr;      // (adam_in_finish: k_zero_f64 did it)
-    fa.ticked = c.adam_in_finish ? e->step : nullptr;
-    fa.perm_ctr = c.draw_perm ? e->perm_ctr : nullptr;
-    fa.status = e->status;
-    fa.host_status = e->host_status;
-    { const int wp0 = (e->bn[0].width + 3) / 4 * 4; fa.bn0z = e->arena + e->bn[0].arena; fa.bn0z_n = 2 * wp0; fa.dirty = e->status + 3; }
-    size_t slab_off = 0;
-    auto commit_p = [&](const double* src, int P, int stride, int dst, int n, float scale) {
-        if (fa.nct < MAX_COMMITS) fa.ct[fa.nct] = CommitTask{src, P, stride, dst, n, scale};
-        fa.nct++;
-    };
-    auto commit = [&](int src, int dst, int n, float scale) { commit_p(e->arena + src, 1, 0, dst, n, scale); };
-    // deferred column sums: partial rows kept until the final commit (no finalise launch needed)
-    const int PN = cdiv(N, c.rpb_n);
-    struct Deferred { double* p; int P; int stride; };
-    auto deferred = [&](int cols, Deferred& d) -> Acc {
-        d.p = parts_alloc(c, (size_t)PN * cols); d.P = PN; d.stride = cols;
-        return d.p ? Acc(nullptr, d.p, cols) : Acc();
-    };
-    const bool awb = use_aw(c);                                    // ... of k_att_bwd_wide (129-256-node graphs): two while 2 T workgroups fit the chip
-    const int ag_split = awb ? std::max(1, std::min(8, e->num_cus / std::max(T, 1))) : 2;       // workgroups per graph of k_att_bwd_graph
-    auto deferred_g = [&](int cols, Deferred& d) -> Acc {          // one partial row per workgroup of k_att_bwd_graph / k_att_bwd_wide
-        d.p = parts_alloc(c, (size_t)ag_split * T * cols); d.P = ag_split * T; d.stride = cols;
-        return d.p ? Acc(nullptr, d.p, cols) : Acc();
-    };
-    Deferred d_convb[MAX_LAYERS], d_cb, d_ob, d_dwn, d_dwe, d_bn0;
-    memset(d_convb, 0, sizeof(d_convb));
-    d_bn0.p = nullptr;
+int engine_forward(Ctx& c, const float* x0, const int64_t* edge_index) {
+    RC(fwd_plan(c, x0, edge_index));
+    RC(fwd_feat(c, x0));
+    RC(fwd_backbone(c));
+    RC(fwd_att(c));
+    RC(fwd_co(c));
+    return fwd_readout(c);
+}
 
-    const bool ro = use_ro(c) || c.ro_done == 2;
-    if (c.ro_done == 2) {                               // the row-blocked readout left one weight-gradient slab per row block
+// R. readout backward: nothing after the one-launch readout, the slabs of the row-blocked one, k_ro_bwd_a / _b, or the GEMM chain
+int bwd_readout(Ctx& c, Bwd& b) {
+    Engine* e = c.e;
+    const int B = c.B, H = e->H, C = e->C, L = e->L;
+    const size_t BH = (size_t)B * H;
+    hipStream_t st = c.st;
+    FinishArgs& fa = b.fa;
+    if (c.r.ro == Readout::Rows) {                     // the row-blocked readout left one weight-gradient slab per row block
         const int nrb = cdiv(B, RS_B);
         for (int hd = 0; hd < 3; ++hd) {
             fa.st[fa.nst++] = SlabTask{e->slabs + (size_t)hd * nrb * H * H, e->G + e->o_fc1_w[hd], H * H, nrb};
             fa.st[fa.nst++] = SlabTask{e->slabs + (size_t)3 * nrb * H * H + (size_t)hd * nrb * C * H, e->G + e->o_fc2_w[hd], C * H, nrb};
         }
-        slab_off = (size_t)3 * nrb * ((size_t)H * H + (size_t)C * H);
-        slab_off = (slab_off + 63) & ~(size_t)63;
+        b.slab_off = (size_t)3 * nrb * ((size_t)H * H + (size_t)C * H);
+        b.slab_off = (b.slab_off + 63) & ~(size_t)63;
     }
-    if (ro) {
-        if (!c.ro_done) {
+    if (c.r.ro != Readout::Gemm) {
+        if (c.r.ro == Readout::FourKernel) {
             const RoArgs ra = make_ro(c);
             hipLaunchKernelGGL(k_ro_bwd_a, dim3(3, H / RO_CW), dim3(256), 0, st, ra);
             CAL_CHECK_LAUNCH("k_ro_bwd_a"); STAGE();
@@ -1483,9 +1483,12 @@ int engine_backward(Ctx& c, const float* x0, const int64_t* batch) {
             CAL_CHECK_LAUNCH("k_ro_bwd_b"); STAGE();
         }
         fa.stats = e->stats; fa.wc = c.wc; fa.wo = c.wo; fa.wco = c.wco;
+        return 0;
     }
+    const int bn_fc1 = L + 3, bn_fc2 = L + 4;
+    const float* xin[3] = {e->pooled, e->pooled + BH, e->xco};
     // R1. dW2_h = dz_h^T @ BN2(y1_h)
-    if (!ro) {
+    {
         GemmArgs a = gemm_args(C, H, B, true, false, 0);
         float* dst[3];
         for (int hd = 0; hd < 3; ++hd) {
@@ -1493,10 +1496,10 @@ int engine_backward(Ctx& c, const float* x0, const int64_t* batch) {
             a.p[hd].xb.has_bn = 1; a.p[hd].xb.bn = bnref(c, bn_fc2 + 2 * hd, B, 0);
             dst[hd] = e->G + e->o_fc2_w[hd];
         }
-        RC(grad_gemm(c, a, 3, dst, fa, slab_off)); STAGE();
+        RC(grad_gemm(c, b, a, 3, dst)); STAGE();
     }
     // R2. d(BN2 out)_h = dz_h @ W2_h, with the BN2-backward sums
-    if (!ro) {
+    {
         GemmArgs a = gemm_args(B, H, C, false, false, 0);
         for (int hd = 0; hd < 3; ++hd) {
             a.p[hd].A = e->dzl + (size_t)hd * B * C; a.p[hd].B = e->P + e->o_fc2_w[hd]; a.p[hd].C = e->dyh1 + hd * BH;
@@ -1507,7 +1510,7 @@ int engine_backward(Ctx& c, const float* x0, const int64_t* batch) {
         RC(flush_finals(c)); STAGE();
     }
     // R3. BN2 backward + ReLU mask + fc1 bias gradients
-    if (!ro) {
+    {
         BnBwdProb p[3];
         for (int hd = 0; hd < 3; ++hd)
             p[hd] = BnBwdProb{e->dyh1 + hd * BH, e->y1 + hd * BH, e->dy1 + hd * BH, bnref(c, bn_fc2 + 2 * hd, B, 0),
@@ -1522,7 +1525,7 @@ int engine_backward(Ctx& c, const float* x0, const int64_t* batch) {
     const int Wco = e->cat ? 2 * H : H;                 // input width of the co head (cat: [xc[perm] | xo])
     float* const dxh_hd[3] = {e->dxh, e->dxh + BH, e->dxh + 2 * BH};
     // R4. dW1_h = dy1_h^T @ BN1(xin_h)
-    if (!ro) {
+    {
         auto r4 = [&](int hd0, int nh, int Kin) -> int {
             GemmArgs a = gemm_args(H, Kin, B, true, false, 0);
             float* dst[3];
@@ -1532,13 +1535,13 @@ int engine_backward(Ctx& c, const float* x0, const int64_t* batch) {
                 a.p[q].xb.has_bn = 1; a.p[q].xb.bn = bnref(c, bn_fc1 + 2 * hd, B, 0);
                 dst[q] = e->G + e->o_fc1_w[hd];
             }
-            return grad_gemm(c, a, nh, dst, fa, slab_off);
+            return grad_gemm(c, b, a, nh, dst);
         };
         if (e->cat) { RC(r4(0, 2, H)); STAGE(); RC(r4(2, 1, Wco)); STAGE(); }
         else { RC(r4(0, 3, H)); STAGE(); }
     }
     // R5. d(BN1 out)_h = dy1_h @ W1_h with the BN1-backward sums
-    if (!ro) {
+    {
         auto r5 = [&](int hd0, int nh, int Kin) -> int {
             GemmArgs a = gemm_args(B, Kin, H, false, false, 0);
             for (int q = 0; q < nh; ++q) {
@@ -1554,62 +1557,42 @@ int engine_backward(Ctx& c, const float* x0, const int64_t* batch) {
         RC(flush_finals(c)); STAGE();
     }
     // R6. BN1 backward + un-permute the random intervention -> d pooled
-    if (!ro) {
-        BnIn in[3];
-        for (int hd = 0; hd < 3; ++hd)
-            in[hd] = BnIn{dxh_hd[hd], xin[hd], bnref(c, bn_fc1 + 2 * hd, B, 0), bn_dsum(c, bn_fc1 + 2 * hd), bn_dprod(c, bn_fc1 + 2 * hd)};
-        hipLaunchKernelGGL(k_readout_bwd_tail, dim3(cdiv((int64_t)BH, 256)), dim3(256), 0, st, in[0], in[1], in[2], e->iperm, e->dpool, B, H, e->cat);
-        CAL_CHECK_LAUNCH("k_readout_bwd_tail"); STAGE();
+    BnIn in[3];
+    for (int hd = 0; hd < 3; ++hd)
+        in[hd] = BnIn{dxh_hd[hd], xin[hd], bnref(c, bn_fc1 + 2 * hd, B, 0), bn_dsum(c, bn_fc1 + 2 * hd), bn_dprod(c, bn_fc1 + 2 * hd)};
+    hipLaunchKernelGGL(k_readout_bwd_tail, dim3(cdiv((int64_t)BH, 256)), dim3(256), 0, st, in[0], in[1], in[2], e->iperm, e->dpool, B, H, e->cat);
+    CAL_CHECK_LAUNCH("k_readout_bwd_tail"); STAGE();
+    return 0;
+}
+
+// P2-P4. gradient w.r.t. the edge weights through propagate and through the normalisation
+int norm_bwd(Ctx& c, const float* gn2, const float* gself2) {
+    Engine* e = c.e;
+    const int N = c.N;
+    const int64_t E = c.E;
+    hipLaunchKernelGGL(k_normbwd_node2, dim3(cdiv(N, 32), 2), dim3(256), 0, c.st, csr_src(c), csr_dst(c), e->att, e->dis_co, e->gn, e->gself,
+                       e->ddeg, e->loop_w, N, E, gn2, gself2);
+    CAL_CHECK_LAUNCH("k_normbwd_node2"); STAGE();
+    if (E > 0) {
+        hipLaunchKernelGGL(k_normbwd_edge, dim3(cdiv(E, 256)), dim3(256), 0, c.st, e->row32, e->col32, e->att, e->dis_co, e->gn, e->ddeg,
+                           e->dl, N, E, gn2, e->no_edge_att ? 0.f : 1.f);
+        CAL_CHECK_LAUNCH("k_normbwd_edge"); STAGE();
     }
-    const bool gwb = use_gw(c);                 // wide per-graph backward (engine_gwide.hpp); its BatchNorm sums through the planes when the
-    const bool gw_st = gwb && e->striped && c.training;  // node-level readers of this batch (k_att_bwd, k_bn_bwd) are then the striped instantiations
-    const bool gcb = use_gcb(c) || gwb;
-    const bool agb = gcb && !gwb && T <= 256;           // per-graph attention backward (two workgroups per graph: one wave of the chip)
-    // P1. add-pool backward + ReLU of the causal/trivial convs: d(conv output)[v] = relu'(h_k[v]) * (gradient of the pooled row of v's
-    // graph) is never stored -- the transposed aggregation below (P5) builds it per gathered row from the activation, and the bias
-    // gradients are count x pooled-row gradient per graph (k_pool2 counted the positive rows).  Rounds 1-3 wrote and re-read the
-    // two [N, H] matrices (656 MB and 155 us per step at config 5).
-    // (per-graph fused backward: both are built while k_gconv_bwd stages dOut, and it emits gn / gself as well)
-    if (!gcb) {
-        if (use_gc(c)) { RC(launch_pool_cnt(c)); STAGE(); }             // the forward pooled inside k_gconv_fwd: no counts yet
-        d_cb.p = parts_alloc(c, (size_t)B * H); d_cb.P = B; d_cb.stride = H;
-        d_ob.p = parts_alloc(c, (size_t)B * H); d_ob.P = B; d_ob.stride = H;
-        if (!d_cb.p || !d_ob.p) { set_error("engine: partial-row workspace exhausted"); return 2; }
-        // (fused readout: d pooled is still two addends per row -- combined here into dpool, which that path leaves unused)
-        hipLaunchKernelGGL(k_pool_bias_grad, dim3(B, 2), dim3(256), 0, st, e->pcnt, ro ? e->dxh : e->dpool, ro ? e->dxh + 2 * (size_t)B * H : nullptr,
-                           e->iperm, e->dpool, d_cb.p, d_ob.p, B, H);
-        CAL_CHECK_LAUNCH("k_pool_bias_grad"); STAGE();
-    }
-    // P2-P4. gradient w.r.t. the edge weights through propagate and through the normalisation
-    auto norm_bwd = [&](const float* gn2, const float* gself2) -> int {
-        hipLaunchKernelGGL(k_normbwd_node2, dim3(cdiv(N, 32), 2), dim3(256), 0, st, gs, gd, e->att, e->dis_co, e->gn, e->gself, e->ddeg,
-                           e->loop_w, N, E, gn2, gself2);
-        CAL_CHECK_LAUNCH("k_normbwd_node2"); STAGE();
-        if (E > 0) {
-            hipLaunchKernelGGL(k_normbwd_edge, dim3(cdiv(E, 256)), dim3(256), 0, st, e->row32, e->col32, e->att, e->dis_co, e->gn, e->ddeg,
-                               e->dl, N, E, gn2, e->no_edge_att ? 0.f : 1.f);
-            CAL_CHECK_LAUNCH("k_normbwd_edge"); STAGE();
-        }
-        return 0;
-    };
-    // P5. dz_k = A_hat_k^T dZ_k with the SDDMM riding on it, then P2-P4 on its output.  The transposed aggregation gathers
-    // dZ_k[dst] for every out-edge of a source row anyway, so gn_e = <dZ_k[dst_e], z_k[src_e]> costs it one more row (z_k[src]) and a
-    // lane-group reduction per slot instead of a second pass over both matrices (the separate SDDMM kernel of rounds 1-3: 265 us per
-    // step at config 5).  Input self-loop edges have no slot: their gn entry is never read (k_normbwd_* skip them like the plan does).
-    if (!gcb) {
-        SpmmBranch b0{e->hco, e->dzco, nullptr, e->att, e->dis_co, Acc(), Acc(), nullptr, nullptr, nullptr};
-        SpmmBranch b1{e->hco + NH, e->dzco + NH, nullptr, e->att + E, e->dis_co + N, Acc(), Acc(), nullptr, nullptr, nullptr};
-        b0.sd_z = e->zco; b0.sd_gn = e->gn; b0.sd_gself = e->gself;
-        b1.sd_z = e->zco + NH; b1.sd_gn = e->gn + E; b1.sd_gself = e->gself + N;
-        b0.pb_g = e->dpool; b0.pb_batch = batch;
-        b1.pb_g = e->dpool + (size_t)B * H; b1.pb_batch = batch;
-        RC(launch_espmm(st, gs, SpmmBranch2{{b0, b1}}, 2, 0, e->loop_w, N, H, spmm_rpb(H, false)));
-        CAL_CHECK_LAUNCH("k_espmm(co,T)"); STAGE();
-        RC(norm_bwd(nullptr, nullptr));
-    }
+    return 0;
+}
+
+// P. the causal / trivial convolutions and the add-pool
+int bwd_co(Ctx& c, Bwd& b) {
+    Engine* e = c.e;
+    const Route& r = c.r;
+    const int N = c.N, B = c.B, T = c.T, H = e->H, L = e->L;
+    const int64_t E = c.E;
+    hipStream_t st = c.st;
+    const size_t NH = (size_t)N * H;
+    const bool ro = r.ro != Readout::Gemm;
     const float* x = e->h + (size_t)L * NH;
-    // P5-P7 fused per graph: dz_k stays in LDS; dX'_k arrives as one partial per output-column slice
-    if (gcb) {
+    if (r.co_bwd != Conv::Node) {
+        // P5-P7 fused per graph: dz_k stays in LDS; dX'_k arrives as one partial per output-column slice
         GconvBwdBranch gb[2];
         memset(gb, 0, sizeof(gb));
         float* dst[2]; double* dsum[2]; double* dprod[2];
@@ -1621,202 +1604,225 @@ int engine_backward(Ctx& c, const float* x0, const int64_t* batch) {
             else gb[k].gp0 = e->dpool + (size_t)k * B * H;
             gb[k].gn = e->gn + (size_t)k * E; gb[k].gself = e->gself + (size_t)k * N;
             gb[k].gn_stride = 2 * (size_t)E; gb[k].gself_stride = 2 * (size_t)N;
-            Deferred& db = k ? d_ob : d_cb;
-            db.p = parts_alloc(c, (size_t)T * H); db.P = T; db.stride = H;
-            if (!db.p) { set_error("engine: partial-row workspace exhausted"); return 2; }
+            Deferred& db = k ? b.d_ob : b.d_cb;
+            if (!defer(c, db, T, H).on()) return no_parts();
             gb[k].bias_parts = db.p;
             gb[k].ew = e->att + (size_t)k * E; gb[k].dis = e->dis_co + (size_t)k * N;
             gb[k].rs = e->anode + k; gb[k].rs_stride = 2; gb[k].bn = bnref(c, L + 1 + k, N, 0);
             gb[k].dxp0 = e->dXhco + (size_t)k * NH; gb[k].dxp1 = e->dzco + (size_t)k * NH;
-            gb[k].coef_in = gwb ? nullptr : e->coef + (size_t)(1 + k) * E;      // (the wide kernels walk the CSR by source: other slot order)
-            gb[k].gn_slot = agb ? 1 : 0;        // consumed by k_att_bwd_graph in slot order (else by k_normbwd_* in edge-id order)
+            gb[k].coef_in = r.co_bwd == Conv::Wide ? nullptr : e->coef + (size_t)(1 + k) * E;      // (the wide kernels walk the CSR by source: other slot order)
+            gb[k].gn_slot = r.att_bwd == Att::Graph ? 1 : 0;        // consumed by k_att_bwd_graph in slot order (else by k_normbwd_* in edge-id order)
             dst[k] = e->G + (k ? e->o_ow : e->o_cw); dsum[k] = bn_dsum(c, L + 1 + k); dprod[k] = bn_dprod(c, L + 1 + k);
         }
-        RC(gconv_bwd(c, gd, gb, 2, dst, dsum, dprod, fa, slab_off, true, gwb ? gw_st : striped_co(c), gwb ? &gs : nullptr)); STAGE();
+        RC(gconv_bwd(c, b, gb, 2, dst, dsum, dprod, r.st_co)); STAGE();
         RC(flush_finals(c)); STAGE();
-        // the edge-weight gradients through the normalisation are part of the per-graph attention backward below; big
-        // batches (a per-graph launch would be several waves of one-per-CU workgroups) keep the node- / edge-parallel kernels
-        if (!agb && !awb) {
+        // the edge-weight gradients through the normalisation are part of the per-graph attention backward; big batches (a per-graph
+        // launch would be several waves of one-per-CU workgroups) keep the node- / edge-parallel kernels
+        if (r.att_bwd == Att::Node) {
             const bool two = H > GC_N;
-            RC(norm_bwd(two ? e->gn + 2 * (size_t)E : nullptr, two ? e->gself + 2 * (size_t)N : nullptr));
+            RC(norm_bwd(c, two ? e->gn + 2 * (size_t)E : nullptr, two ? e->gself + 2 * (size_t)N : nullptr));
         }
+        return 0;
     }
-    // P6. dW_k = BN_k(a_k x)^T @ dz_k
-    if (!gcb) {
-        GemmArgs a = gemm_args(H, H, N, true, false, 0);
-        float* dst[2];
-        for (int k = 0; k < 2; ++k) {
-            a.p[k].A = x; a.p[k].B = e->dzco + (size_t)k * NH;
-            a.p[k].xa.rs = e->anode + k; a.p[k].xa.rs_stride = 2;
-            a.p[k].xa.has_bn = 1; a.p[k].xa.bn = bnref(c, L + 1 + k, N, 0);
-            dst[k] = e->G + (k ? e->o_ow : e->o_cw);
-        }
-    // P7. d(BN_k out) = dz_k @ W_k^T with the BN_k-backward sums (same launch as P6)
-        GemmArgs aw = a;
-        a = gemm_args(N, H, H, false, true, 0);
-        for (int k = 0; k < 2; ++k) {
-            a.p[k].A = e->dzco + (size_t)k * NH; a.p[k].B = e->P + (k ? e->o_ow : e->o_cw); a.p[k].C = e->dXhco + (size_t)k * NH;
-            a.p[k].aux = x; a.p[k].aux_rs = e->anode + k; a.p[k].aux_rs_stride = 2; a.p[k].has_aux = 1;
-            a.p[k].aux_bn = bnref(c, L + 1 + k, N, 0);
-            gemm_stats(c, a.p[k], N, H, bn_dsum(c, L + 1 + k), bn_dprod(c, L + 1 + k), true, H, striped_node(c));
-        }
-        RC(dual_gemm(c, a, 2, aw, 2, dst, fa, slab_off)); STAGE();
-        RC(flush_finals(c)); STAGE();
-    }
-    // P8. everything between the last backbone conv and the two causal convs
+    // P1. add-pool backward + ReLU of the causal/trivial convs: d(conv output)[v] = relu'(h_k[v]) * (gradient of the pooled row of v's
+    // graph) is never stored -- the transposed aggregation below (P5) builds it per gathered row from the activation, and the bias
+    // gradients are count x pooled-row gradient per graph (k_pool2 counted the positive rows).  Rounds 1-3 wrote and re-read the
+    // two [N, H] matrices (656 MB and 155 us per step at config 5).
+    if (r.co_fwd != Conv::Node) { RC(launch_pool_cnt(c)); STAGE(); }          // the forward pooled inside k_gconv_fwd: no counts yet
+    b.d_cb.p = parts_alloc(c, (size_t)B * H); b.d_cb.P = B; b.d_cb.stride = H;
+    b.d_ob.p = parts_alloc(c, (size_t)B * H); b.d_ob.P = B; b.d_ob.stride = H;
+    if (!b.d_cb.p || !b.d_ob.p) return no_parts();
+    // (fused readout: d pooled is still two addends per row -- combined here into dpool, which that path leaves unused)
+    hipLaunchKernelGGL(k_pool_bias_grad, dim3(B, 2), dim3(256), 0, st, e->pcnt, ro ? e->dxh : e->dpool, ro ? e->dxh + 2 * (size_t)B * H : nullptr,
+                       e->iperm, e->dpool, b.d_cb.p, b.d_ob.p, B, H);
+    CAL_CHECK_LAUNCH("k_pool_bias_grad"); STAGE();
+    // P5. dz_k = A_hat_k^T dZ_k with the SDDMM riding on it, then P2-P4 on its output.  The transposed aggregation gathers
+    // dZ_k[dst] for every out-edge of a source row anyway, so gn_e = <dZ_k[dst_e], z_k[src_e]> costs it one more row (z_k[src]) and a
+    // lane-group reduction per slot instead of a second pass over both matrices (the separate SDDMM kernel of rounds 1-3: 265 us per
+    // step at config 5).  Input self-loop edges have no slot: their gn entry is never read (k_normbwd_* skip them like the plan does).
     {
-        AttBwdArgs aa;
-        aa.x = x; aa.anode = e->anode; aa.dxhc = e->dXhco; aa.dxho = e->dXhco + NH;
-        const bool two = gcb && H > GC_N;               // second output-column slice of the fused backward
-        aa.dxhc2 = two ? e->dzco : nullptr; aa.dxho2 = two ? e->dzco + NH : nullptr;
-        aa.bnc = bnref(c, L + 1, N, 0); aa.bno = bnref(c, L + 2, N, 0);
-        aa.dsc = bn_dsum(c, L + 1); aa.dpc = bn_dprod(c, L + 1); aa.dso = bn_dsum(c, L + 2); aa.dpo = bn_dprod(c, L + 2); aa.dss = e->bn_plane;
-        aa.Wn = e->P + e->o_natt_w; aa.We = e->P + e->o_eatt_w; aa.dl = e->dl;
-        aa.fnode = e->no_node_att ? 0.f : 1.f; aa.fedge = e->no_edge_att ? 0.f : 1.f;
-        aa.gs = gs; aa.gd = gd; aa.dZ = e->dZ;
-        if (awb) {       // per graph of up to 256 nodes: the same with a sparse edge phase (engine_attwide.hpp); inputs in edge-id order
-            aa.dbias = L > 0 ? deferred_g(H, d_convb[L - 1]) : Acc();
-            aa.dWn = deferred_g(H + 4, d_dwn); aa.dWe = deferred_g(2 * H + 4, d_dwe);
-            if (!aa.dWn.on() || !aa.dWe.on()) { set_error("engine: partial-row workspace exhausted"); return 2; }
-            AttBwdWideArgs ag;
-            ag.a = aa; ag.gptr = e->gptr; ag.eptr = e->eptr; ag.row32 = e->row32; ag.col32 = e->col32; ag.att = e->att; ag.dis = e->dis_co;
-            ag.gn = e->gn; ag.gn2 = two ? e->gn + 2 * (size_t)E : nullptr;
-            ag.gself = e->gself; ag.gself2 = two ? e->gself + 2 * (size_t)N : nullptr;
-            ag.loop_w = e->loop_w; ag.E = E; ag.N = N; ag.status = e->status;
-            RC(with_g(H, [&](auto g) {
-                constexpr int G = decltype(g)::value;
-                hipLaunchKernelGGL((k_att_bwd_wide<4, G>), dim3(ag_split * T), dim3(512), 0, st, ag, 1, H, ag_split);
-                return 0;
-            }));
-            CAL_CHECK_LAUNCH("k_att_bwd_wide"); STAGE();
-        } else if (agb) {       // per graph: d deg, d edge logits and the row pass in one kernel (engine_attbwd.hpp)
-            aa.dbias = L > 0 ? deferred_g(H, d_convb[L - 1]) : Acc();
-            aa.dWn = deferred_g(H + 4, d_dwn); aa.dWe = deferred_g(2 * H + 4, d_dwe);
-            if (!aa.dWn.on() || !aa.dWe.on()) { set_error("engine: partial-row workspace exhausted"); return 2; }
-            AttBwdGraphArgs ag;
-            ag.a = aa; ag.gptr = e->gptr; ag.eptr = e->eptr; ag.att = e->wslot; ag.dis = e->dis_co;
-            ag.gn = e->gn; ag.gn2 = two ? e->gn + 2 * (size_t)E : nullptr;
-            ag.gself = e->gself; ag.gself2 = two ? e->gself + 2 * (size_t)N : nullptr;
-            ag.loop_w = e->loop_w; ag.E = E; ag.N = N; ag.status = e->status;
-            RC(with_g(H, [&](auto g) {
-                constexpr int G = decltype(g)::value;
-                hipLaunchKernelGGL((k_att_bwd_graph<4, G>), dim3(ag_split * T), dim3(512), 0, st, ag, 1, H, ag_split);
-                return 0;
-            }));
-            CAL_CHECK_LAUNCH("k_att_bwd_graph"); STAGE();
-        } else {
-        aa.dbias = L > 0 ? deferred(H, d_convb[L - 1]) : Acc();
-        aa.dWn = deferred(H + 4, d_dwn); aa.dWe = deferred(2 * H + 4, d_dwe);
-        if (!aa.dWn.on() || !aa.dWe.on()) { set_error("engine: partial-row workspace exhausted"); return 2; }
+        SpmmBranch b0{e->hco, e->dzco, nullptr, e->att, e->dis_co, Acc(), Acc(), nullptr, nullptr, nullptr};
+        SpmmBranch b1{e->hco + NH, e->dzco + NH, nullptr, e->att + E, e->dis_co + N, Acc(), Acc(), nullptr, nullptr, nullptr};
+        b0.sd_z = e->zco; b0.sd_gn = e->gn; b0.sd_gself = e->gself;
+        b1.sd_z = e->zco + NH; b1.sd_gn = e->gn + E; b1.sd_gself = e->gself + N;
+        b0.pb_g = e->dpool; b0.pb_batch = c.batch;
+        b1.pb_g = e->dpool + (size_t)B * H; b1.pb_batch = c.batch;
+        RC(launch_espmm(st, csr_src(c), SpmmBranch2{{b0, b1}}, 2, 0, e->loop_w, N, H, spmm_rpb(H, false)));
+        CAL_CHECK_LAUNCH("k_espmm(co,T)"); STAGE();
+        RC(norm_bwd(c, nullptr, nullptr));
+    }
+    // P6. dW_k = BN_k(a_k x)^T @ dz_k and P7. d(BN_k out) = dz_k @ W_k^T with the BN_k-backward sums, one launch
+    GemmArgs aw = gemm_args(H, H, N, true, false, 0);
+    float* dst[2];
+    for (int k = 0; k < 2; ++k) {
+        aw.p[k].A = x; aw.p[k].B = e->dzco + (size_t)k * NH;
+        aw.p[k].xa.rs = e->anode + k; aw.p[k].xa.rs_stride = 2;
+        aw.p[k].xa.has_bn = 1; aw.p[k].xa.bn = bnref(c, L + 1 + k, N, 0);
+        dst[k] = e->G + (k ? e->o_ow : e->o_cw);
+    }
+    GemmArgs a = gemm_args(N, H, H, false, true, 0);
+    for (int k = 0; k < 2; ++k) {
+        a.p[k].A = e->dzco + (size_t)k * NH; a.p[k].B = e->P + (k ? e->o_ow : e->o_cw); a.p[k].C = e->dXhco + (size_t)k * NH;
+        a.p[k].aux = x; a.p[k].aux_rs = e->anode + k; a.p[k].aux_rs_stride = 2; a.p[k].has_aux = 1;
+        a.p[k].aux_bn = bnref(c, L + 1 + k, N, 0);
+        gemm_stats(c, a.p[k], N, H, bn_dsum(c, L + 1 + k), bn_dprod(c, L + 1 + k), true, H, r.st_node);
+    }
+    RC(dual_gemm(c, b, a, 2, aw, 2, dst)); STAGE();
+    RC(flush_finals(c)); STAGE();
+    return 0;
+}
+
+// P8. everything between the last backbone conv and the two causal convs
+int bwd_att(Ctx& c, Bwd& b) {
+    Engine* e = c.e;
+    const Route& r = c.r;
+    const int N = c.N, T = c.T, H = e->H, L = e->L;
+    const int64_t E = c.E;
+    hipStream_t st = c.st;
+    const size_t NH = (size_t)N * H;
+    AttBwdArgs aa;
+    aa.x = e->h + (size_t)L * NH; aa.anode = e->anode; aa.dxhc = e->dXhco; aa.dxho = e->dXhco + NH;
+    const bool two = r.co_bwd != Conv::Node && H > GC_N;      // second output-column slice of the fused backward
+    aa.dxhc2 = two ? e->dzco : nullptr; aa.dxho2 = two ? e->dzco + NH : nullptr;
+    aa.bnc = bnref(c, L + 1, N, 0); aa.bno = bnref(c, L + 2, N, 0);
+    aa.dsc = bn_dsum(c, L + 1); aa.dpc = bn_dprod(c, L + 1); aa.dso = bn_dsum(c, L + 2); aa.dpo = bn_dprod(c, L + 2); aa.dss = e->bn_plane;
+    aa.Wn = e->P + e->o_natt_w; aa.We = e->P + e->o_eatt_w; aa.dl = e->dl;
+    aa.fnode = e->no_node_att ? 0.f : 1.f; aa.fedge = e->no_edge_att ? 0.f : 1.f;
+    aa.gs = csr_src(c); aa.gd = csr_dst(c); aa.dZ = e->dZ;
+    // one partial row per workgroup: r.ag_split per graph (k_att_bwd_graph / k_att_bwd_wide), or one per row block (k_att_bwd)
+    const int P = r.att_bwd == Att::Node ? cdiv(N, c.rpb_n) : r.ag_split * T;
+    aa.dbias = L > 0 ? defer(c, b.d_convb[L - 1], P, H) : Acc();
+    aa.dWn = defer(c, b.d_dwn, P, H + 4); aa.dWe = defer(c, b.d_dwe, P, 2 * H + 4);
+    if (!aa.dWn.on() || !aa.dWe.on()) return no_parts();
+    if (r.att_bwd == Att::Wide) {       // per graph of up to 256 nodes: with a sparse edge phase (engine_attwide.hpp); inputs in edge-id order
+        AttBwdWideArgs ag;
+        ag.a = aa; ag.gptr = e->gptr; ag.eptr = e->eptr; ag.row32 = e->row32; ag.col32 = e->col32; ag.att = e->att; ag.dis = e->dis_co;
+        ag.gn = e->gn; ag.gn2 = two ? e->gn + 2 * (size_t)E : nullptr;
+        ag.gself = e->gself; ag.gself2 = two ? e->gself + 2 * (size_t)N : nullptr;
+        ag.loop_w = e->loop_w; ag.E = E; ag.N = N; ag.status = e->status;
         RC(with_g(H, [&](auto g) {
             constexpr int G = decltype(g)::value;
-            if (striped_node(c) || gw_st) hipLaunchKernelGGL((k_att_bwd<4, G, true>), dim3(cdiv(N, c.rpb_n)), dim3(256), 0, st, aa, 1, N, H, c.rpb_n);
+            hipLaunchKernelGGL((k_att_bwd_wide<4, G>), dim3(r.ag_split * T), dim3(512), 0, st, ag, 1, H, r.ag_split);
+            return 0;
+        }));
+        CAL_CHECK_LAUNCH("k_att_bwd_wide"); STAGE();
+    } else if (r.att_bwd == Att::Graph) {       // per graph: d deg, d edge logits and the row pass in one kernel (engine_attbwd.hpp)
+        AttBwdGraphArgs ag;
+        ag.a = aa; ag.gptr = e->gptr; ag.eptr = e->eptr; ag.att = e->wslot; ag.dis = e->dis_co;
+        ag.gn = e->gn; ag.gn2 = two ? e->gn + 2 * (size_t)E : nullptr;
+        ag.gself = e->gself; ag.gself2 = two ? e->gself + 2 * (size_t)N : nullptr;
+        ag.loop_w = e->loop_w; ag.E = E; ag.N = N; ag.status = e->status;
+        RC(with_g(H, [&](auto g) {
+            constexpr int G = decltype(g)::value;
+            hipLaunchKernelGGL((k_att_bwd_graph<4, G>), dim3(r.ag_split * T), dim3(512), 0, st, ag, 1, H, r.ag_split);
+            return 0;
+        }));
+        CAL_CHECK_LAUNCH("k_att_bwd_graph"); STAGE();
+    } else {
+        // striped reader where the bnc / bno backward sums went to the planes
+        const bool sr = r.st_node || r.st_co;
+        RC(with_g(H, [&](auto g) {
+            constexpr int G = decltype(g)::value;
+            if (sr) hipLaunchKernelGGL((k_att_bwd<4, G, true>), dim3(cdiv(N, c.rpb_n)), dim3(256), 0, st, aa, 1, N, H, c.rpb_n);
             else hipLaunchKernelGGL((k_att_bwd<4, G>), dim3(cdiv(N, c.rpb_n)), dim3(256), 0, st, aa, 1, N, H, c.rpb_n);
             return 0;
         }));
         CAL_CHECK_LAUNCH("k_att_bwd"); STAGE();
-        }
     }
-    bool feat_done = false;     // the per-graph feature-layer backward (k_feat_bwd_mma) has run
-    // feature layer h0 = relu(BN0(x0) W_feat) per unit, fed from the first backbone layer's partial input gradients
-    // (engine_gconv_bwd.hpp: one MFMA product per unit, any F <= 160); nobn: no BatchNorm between h0 and that layer (GIN)
-    auto feat_bwd = [&](const float* p0, const float* p1, bool nobn) -> int {
-        FeatBwdArgs fb;
-        memset(&fb, 0, sizeof(fb));
-        fb.dy0 = p0; fb.dy1 = p1; fb.y = e->h;
-        if (!nobn) { fb.ubn = bnref(c, 1, N, 0); fb.udot_sum = bn_dsum(c, 1); fb.udot_prod = bn_dprod(c, 1); }
-        fb.x0 = x0; fb.W = e->P + e->o_feat_w; fb.bn0 = bnref(c, 0, N, 0);
-        // units: the graphs (tiles) of the per-graph kernels -- or, behind the wide convolutions (129-256-node graphs), uniform chunks
-        // of FB_T rows: the layer is row-wise, the chunks need not be graphs (k_feat_bwd with a null unit table)
-        const bool chunks = gwb;
-        const int U = chunks ? cdiv(N, FB_T) : T;
-        const size_t need = (size_t)U * F * H;
-        if (slab_off + need > e->slab_floats || fa.nst >= MAX_SLABS) { set_error("engine: slab workspace exhausted"); return 2; }
-        fb.slab = e->slabs + slab_off;
-        fa.st[fa.nst++] = SlabTask{e->slabs + slab_off, e->G + e->o_feat_w, F * H, U};
-        slab_off += need;
-        d_bn0.p = parts_alloc(c, (size_t)U * 2 * F); d_bn0.P = U; d_bn0.stride = 2 * F;
-        if (!d_bn0.p) { set_error("engine: partial-row workspace exhausted"); return 2; }
-        fb.parts = d_bn0.p;
-        const dim3 grid(U), blk(GB_NT);
-        if (F <= FB_F && !nobn) {
-            // few features (SPMotif: F = 10): the FMA-loop kernel is 1.7 us shorter than one MFMA tile behind three barriers
-            if (F <= 16) hipLaunchKernelGGL(k_feat_bwd<16>, grid, blk, 0, st, chunks ? (const int*)nullptr : (const int*)e->gptr, fb, H, F, e->status, N);
-            else hipLaunchKernelGGL(k_feat_bwd<FB_F>, grid, blk, 0, st, chunks ? (const int*)nullptr : (const int*)e->gptr, fb, H, F, e->status, N);
-        } else if (F <= 64) {
-            hipLaunchKernelGGL((k_feat_bwd_mma<8, true>), grid, blk, 0, st, e->gptr, fb, H, F, e->status);
-        } else {
-            if (nobn) hipLaunchKernelGGL((k_feat_bwd_mma<20, true>), grid, blk, 0, st, e->gptr, fb, H, F, e->status);
-            else hipLaunchKernelGGL((k_feat_bwd_mma<20, false>), grid, blk, 0, st, e->gptr, fb, H, F, e->status);
-        }
-        CAL_CHECK_LAUNCH("k_feat_bwd");
-        feat_done = true;
-        return 0;
-    };
-    // Q. backbone layers, last to first
-    Deferred d_gin_b1[MAX_LAYERS];
-    memset(d_gin_b1, 0, sizeof(d_gin_b1));
+    return 0;
+}
+
+// feature layer h0 = relu(BN0(x0) W_feat) per unit, fed from the first backbone layer's partial input gradients
+// (engine_gconv_bwd.hpp: one MFMA product per unit, any F <= 160); nobn: no BatchNorm between h0 and that layer (GIN)
+int bwd_feat_units(Ctx& c, Bwd& b, const float* x0, const float* p0, const float* p1, bool nobn) {
+    Engine* e = c.e;
+    const int N = c.N, H = e->H, F = e->F;
+    hipStream_t st = c.st;
+    FeatBwdArgs fb;
+    memset(&fb, 0, sizeof(fb));
+    fb.dy0 = p0; fb.dy1 = p1; fb.y = e->h;
+    if (!nobn) { fb.ubn = bnref(c, 1, N, 0); fb.udot_sum = bn_dsum(c, 1); fb.udot_prod = bn_dprod(c, 1); }
+    fb.x0 = x0; fb.W = e->P + e->o_feat_w; fb.bn0 = bnref(c, 0, N, 0);
+    // units: the graphs (tiles) of the per-graph kernels -- or, behind the wide convolutions (129-256-node graphs), uniform chunks
+    // of FB_T rows: the layer is row-wise, the chunks need not be graphs (k_feat_bwd with a null unit table)
+    const bool chunks = c.r.feat_chunks;
+    const int U = chunks ? cdiv(N, FB_T) : c.T;
+    fb.slab = slab_take(c, b, (size_t)U * F * H, e->G + e->o_feat_w, F * H, U);
+    if (!fb.slab) return no_slabs();
+    b.d_bn0.p = parts_alloc(c, (size_t)U * 2 * F); b.d_bn0.P = U; b.d_bn0.stride = 2 * F;
+    if (!b.d_bn0.p) return no_parts();
+    fb.parts = b.d_bn0.p;
+    const dim3 grid(U), blk(GB_NT);
+    if (F <= FB_F && !nobn) {
+        // few features (SPMotif: F = 10): the FMA-loop kernel is 1.7 us shorter than one MFMA tile behind three barriers
+        if (F <= 16) hipLaunchKernelGGL(k_feat_bwd<16>, grid, blk, 0, st, chunks ? (const int*)nullptr : (const int*)e->gptr, fb, H, F, e->status, N);
+        else hipLaunchKernelGGL(k_feat_bwd<FB_F>, grid, blk, 0, st, chunks ? (const int*)nullptr : (const int*)e->gptr, fb, H, F, e->status, N);
+    } else if (F <= 64) {
+        hipLaunchKernelGGL((k_feat_bwd_mma<8, true>), grid, blk, 0, st, e->gptr, fb, H, F, e->status);
+    } else {
+        if (nobn) hipLaunchKernelGGL((k_feat_bwd_mma<20, true>), grid, blk, 0, st, e->gptr, fb, H, F, e->status);
+        else hipLaunchKernelGGL((k_feat_bwd_mma<20, false>), grid, blk, 0, st, e->gptr, fb, H, F, e->status);
+    }
+    CAL_CHECK_LAUNCH("k_feat_bwd");
+    return 0;
+}
+
+// Q. backbone layers, last to first (and the feature layer's backward where it rides with layer 1)
+int bwd_backbone(Ctx& c, Bwd& b, const float* x0) {
+    Engine* e = c.e;
+    const Route& r = c.r;
+    const int N = c.N, T = c.T, H = e->H, F = e->F, L = e->L;
+    const int64_t E = c.E;
+    hipStream_t st = c.st;
+    const size_t NH = (size_t)N * H;
+    const CSR gd = csr_dst(c), gs = csr_src(c);
+    const int PN = cdiv(N, c.rpb_n);
+    const bool units = r.feat_bwd == FeatBwd::Units, two = H > GC_N;
     for (int i = L; i >= 1; --i) {
         float* dzi = e->dzi + (size_t)(i - 1) * NH;     // per layer: the side-stream dW GEMM reads it later
-        const bool gat = e->K > 0;
-        if (e->gin && gcb && e->max_edges <= GB_E) {
+        const float* hin = e->h + (size_t)(i - 1) * NH;
+        const bool st_i = i > 1 ? r.st_bb : r.st_bb1;    // this layer's BatchNorm-backward sums go to the accumulator planes
+        if (e->gin && r.bb_bwd == Conv::Graph64) {
             // GINConv backward per graph (engine_ggin.hpp): second Linear (+ the BatchNorm-backward sums behind the ReLU) |
             // BatchNorm backward, first Linear, transposed aggregation.  Partial input gradients (one per output-column
             // slice): PART 2 -> (dXh, gy[i-1]), PART 1 -> (z, gagg[i-1]); the layer below (or the mask pass in front of the
             // feature layer) adds the two and masks by h_{i-1} > 0.
             const int nsl = H / GC_N;
-            const bool two = nsl > 1;
             float* c0 = e->dXh; float* c1 = e->gy + (size_t)(i - 1) * NH;
             float* d0 = e->z; float* d1 = e->gagg + (size_t)(i - 1) * NH;
             const float* t1 = e->gt1 + (size_t)(i - 1) * NH;
-            if (slab_off + 2 * (size_t)T * H * H > e->slab_floats || fa.nst + 2 > MAX_SLABS) { set_error("engine: slab workspace exhausted"); return 2; }
+            if (b.slab_off + 2 * (size_t)T * H * H > e->slab_floats || b.fa.nst + 2 > MAX_SLABS) return no_slabs();
             GginBwdArgs ga;
             memset(&ga, 0, sizeof(ga));
             if (i == L) ga.dout = e->dZ;
             else {
                 ga.dy0 = e->z; ga.dy1 = two ? e->gagg + (size_t)i * NH : nullptr; ga.hmask = e->h + (size_t)i * NH;
-                Deferred& db = d_convb[i - 1];           // d b2 of this layer: column sums of the masked d h_i, one partial row per unit
-                db.p = parts_alloc(c, (size_t)T * H); db.P = T; db.stride = H;
-                if (!db.p) { set_error("engine: partial-row workspace exhausted"); return 2; }
-                ga.bias_parts = db.p;
+                // d b2 of this layer: column sums of the masked d h_i, one partial row per unit
+                if (!defer(c, b.d_convb[i - 1], T, H).on()) return no_parts();
+                ga.bias_parts = b.d_convb[i - 1].p;
             }
             ga.x = t1; ga.W = e->P + e->o_gin_w2[i - 1]; ga.bn = bnref(c, i, N, 0);
             ga.dxp0 = c0; ga.dxp1 = c1;
-            ga.slab = e->slabs + slab_off;
-            fa.st[fa.nst++] = SlabTask{ga.slab, e->G + e->o_gin_w2[i - 1], H * H, T};
-            slab_off += (size_t)T * H * H;
-            if (striped_gin(c)) { ga.dacc_sum = bn_dsum(c, i); ga.dacc_prod = bn_dprod(c, i); ga.dacc_ss = e->bn_plane; }
-            else {
-                double* pp = parts_alloc(c, (size_t)T * nsl * 2 * H);
-                if (!pp) { set_error("engine: partial-row workspace exhausted"); return 2; }
-                ga.dot_parts = pp;
-                final_task(c, pp, T * nsl, 2 * H, H, bn_dsum(c, i));
-                final_task(c, pp + H, T * nsl, 2 * H, H, bn_dprod(c, i));
-            }
+            ga.slab = slab_take(c, b, (size_t)T * H * H, e->G + e->o_gin_w2[i - 1], H * H, T);
+            RC(bn_bwd_sums(c, ga, T * nsl, bn_dsum(c, i), bn_dprod(c, i), st_i));
             hipLaunchKernelGGL((k_ggin_bwd<2>), dim3(T, nsl), dim3(GB_NT), 0, st, gd, e->gptr, e->eptr, ga, N, H, H, e->status);
             CAL_CHECK_LAUNCH("k_ggin_bwd<2>"); STAGE();
             RC(flush_finals(c)); STAGE();
             memset(&ga, 0, sizeof(ga));
             ga.dy0 = c0; ga.dy1 = two ? c1 : nullptr; ga.t1 = t1;
             ga.dot_sum = bn_dsum(c, i); ga.dot_prod = bn_dprod(c, i);
-            {
-                Deferred& db = d_gin_b1[i - 1];          // d b1: column sums of dt1
-                db.p = parts_alloc(c, (size_t)T * H); db.P = T; db.stride = H;
-                if (!db.p) { set_error("engine: partial-row workspace exhausted"); return 2; }
-                ga.bias_parts = db.p;
-            }
-            ga.x = e->h + (size_t)(i - 1) * NH; ga.W = e->P + e->o_conv_w[i - 1]; ga.bn = bnref(c, i, N, 0);
+            if (!defer(c, b.d_gin_b1[i - 1], T, H).on()) return no_parts();       // d b1: column sums of dt1
+            ga.bias_parts = b.d_gin_b1[i - 1].p;
+            ga.x = hin; ga.W = e->P + e->o_conv_w[i - 1]; ga.bn = bnref(c, i, N, 0);
             ga.dxp0 = d0; ga.dxp1 = d1;
-            ga.slab = e->slabs + slab_off;
-            fa.st[fa.nst++] = SlabTask{ga.slab, e->G + e->o_conv_w[i - 1], H * H, T};
-            slab_off += (size_t)T * H * H;
+            ga.slab = slab_take(c, b, (size_t)T * H * H, e->G + e->o_conv_w[i - 1], H * H, T);
             {
-                ProfScope ps(st, 10, 4.0 * N * H * H + 2.0 * (double)(c.E + N) * H, true);
+                ProfScope ps(st, 10, 4.0 * N * H * H + 2.0 * (double)(E + N) * H, true);
                 PROF_LAUNCH((k_ggin_bwd<1>), dim3(T, nsl), dim3(GB_NT), 0, st, gd, e->gptr, e->eptr, ga, N, H, H, e->status);
             }
             CAL_CHECK_LAUNCH("k_ggin_bwd<1>"); STAGE();
-            if (i == 1 && F <= FM_F && H <= FB_H) {
-                RC(feat_bwd(d0, two ? d1 : nullptr, true)); STAGE();
+            if (i == 1 && units) {
+                RC(bwd_feat_units(c, b, x0, d0, two ? d1 : nullptr, true)); STAGE();
             } else if (i == 1) {                         // the feature layer below takes d h0 masked by h0 > 0 in e->dZ
                 GinRowArgs gr;
                 memset(&gr, 0, sizeof(gr));
@@ -1837,7 +1843,7 @@ int engine_backward(Ctx& c, const float* x0, const int64_t* batch) {
                 GemmArgs a = gemm_args(H, H, N, true, false, 0);
                 a.p[0].A = e->dZ; a.p[0].B = yy;
                 float* dst[1] = {e->G + e->o_gin_w2[i - 1]};
-                RC(grad_gemm(c, a, 1, dst, fa, slab_off)); STAGE();
+                RC(grad_gemm(c, b, a, 1, dst)); STAGE();
             }
             {
                 GemmArgs a = gemm_args(N, H, H, false, false, 0);
@@ -1858,8 +1864,8 @@ int engine_backward(Ctx& c, const float* x0, const int64_t* batch) {
                 memset(&ga, 0, sizeof(ga));
                 ga.a = e->dXh; ga.y = yy; ga.t1 = t1; ga.out = dzi; ga.bn = bnref(c, i, N, 0);       // dt1
                 ga.dot_sum = bn_dsum(c, i); ga.dot_prod = bn_dprod(c, i);
-                ga.acc0 = deferred(H, d_gin_b1[i - 1]);
-                if (!ga.acc0.on()) { set_error("engine: partial-row workspace exhausted"); return 2; }
+                ga.acc0 = defer(c, b.d_gin_b1[i - 1], PN, H);
+                if (!ga.acc0.on()) return no_parts();
                 RC(gin_rows(c, 2, ga));
                 CAL_CHECK_LAUNCH("k_gin_bn_bwd"); STAGE();
             }
@@ -1867,7 +1873,7 @@ int engine_backward(Ctx& c, const float* x0, const int64_t* batch) {
                 GemmArgs a = gemm_args(H, H, N, true, false, 0);
                 a.p[0].A = dzi; a.p[0].B = agg;
                 float* dst[1] = {e->G + e->o_conv_w[i - 1]};
-                RC(grad_gemm(c, a, 1, dst, fa, slab_off)); STAGE();
+                RC(grad_gemm(c, b, a, 1, dst)); STAGE();
             }
             {
                 GemmArgs a = gemm_args(N, H, H, false, false, 0);
@@ -1882,289 +1888,290 @@ int engine_backward(Ctx& c, const float* x0, const int64_t* batch) {
             {
                 GinRowArgs ga;
                 memset(&ga, 0, sizeof(ga));
-                ga.a = e->z; ga.y = e->h + (size_t)(i - 1) * NH; ga.out = e->dZ;                     // masked by h_{i-1} > 0
-                ga.acc0 = i >= 2 ? deferred(H, d_convb[i - 2]) : Acc();                                  // d b2 of the layer below
+                ga.a = e->z; ga.y = hin; ga.out = e->dZ;                                                // masked by h_{i-1} > 0
+                ga.acc0 = i >= 2 ? defer(c, b.d_convb[i - 2], PN, H) : Acc();                           // d b2 of the layer below
                 RC(gin_rows(c, 3, ga));
                 CAL_CHECK_LAUNCH("k_gin_mask"); STAGE();
             }
             continue;
         }
-        if (gat && gcb && (H / e->K == 32 || H / e->K == 64) && e->max_edges <= GGB_E) {
-            // GATConv layer backward per graph (engine_ggat.hpp): attention backward + dX' (two slice partials) + dW / d att
-            // slabs.  As in the GCNConv path below, layer i < L builds its dOut from layer i+1's partials while staging
-            // (BatchNorm_{i+1}-backward + ReLU mask + bias sums: no k_bn_bwd launch, no dZ round trip); slice-0 partials
-            // ping-pong between dXh and z (idle in the fused forward), slice-1 partials are per layer.
+        // Per graph, layer i reads dOut = e->dZ (i == L, written by the attention backward) or builds it while staging from layer
+        // i+1's partial dX' (BatchNorm_{i+1}-backward + ReLU mask fused in: no k_bn_bwd launch, no dZ round trip); slice-0 partials
+        // ping-pong between dXh and z (idle in the fused forward), slice-1 partials are per layer.
+        float* p0 = ((L - i) & 1) ? e->z : e->dXh;
+        if (r.bb_bwd != Conv::Node && i < L && !defer(c, b.d_convb[i - 1], T, H).on()) return no_parts();   // bias of conv i: one partial row per graph
+        if (e->K > 0 && r.bb_bwd == Conv::Graph64) {
+            // GATConv layer backward per graph (engine_ggat.hpp): attention backward + dX' (two slice partials) + dW / d att slabs
             const int K = e->K, D = H / K, nsl = H / GC_N;
             const size_t nk = al((size_t)e->capN * K);
             const float* sc = e->gsc + (size_t)(i - 1) * 4 * nk;
-            const float* hin = e->h + (size_t)(i - 1) * NH;
-            float* p0 = ((L - i) & 1) ? e->z : e->dXh;
             GgatBwdArgs ga;
             memset(&ga, 0, sizeof(ga));
             ga.x = hin; ga.W = e->P + e->o_conv_w[i - 1]; ga.att = e->P + e->o_conv_att[i - 1];
             ga.z = e->gz + (size_t)(i - 1) * NH; ga.adst = sc; ga.asrc = sc + nk; ga.mx = sc + 2 * nk; ga.den = sc + 3 * nk;
             ga.bn = bnref(c, i, N, 0); ga.dxp0 = p0; ga.dxp1 = dzi;
             ga.heads = K; ga.D = D; ga.slope = e->gat_slope; ga.p = c.training ? e->gat_p : 0.f;
-            ga.seed = e->gat_seed[i - 1]; ga.ctr = (const uint64_t*)e->gat_ctr; ga.E = c.E;
+            ga.seed = e->gat_seed[i - 1]; ga.ctr = (const uint64_t*)e->gat_ctr; ga.E = E;
             if (i == L) ga.dout = e->dZ;
             else {
                 ga.dy0 = ((L - i - 1) & 1) ? e->z : e->dXh;
-                ga.dy1 = H > GC_N ? e->dzi + (size_t)i * NH : nullptr;
+                ga.dy1 = two ? e->dzi + (size_t)i * NH : nullptr;
                 ga.y = e->h + (size_t)i * NH;
                 ga.ubn = bnref(c, i + 1, N, 0); ga.udot_sum = bn_dsum(c, i + 1); ga.udot_prod = bn_dprod(c, i + 1);
-                Deferred& db = d_convb[i - 1];
-                db.p = parts_alloc(c, (size_t)T * H); db.P = T; db.stride = H;
-                if (!db.p) { set_error("engine: partial-row workspace exhausted"); return 2; }
-                ga.bias_parts = db.p;
+                ga.bias_parts = b.d_convb[i - 1].p;
             }
             const size_t need_w = (size_t)T * H * H, need_a = (size_t)T * 2 * H;
-            if (slab_off + need_w + need_a > e->slab_floats || fa.nst + 2 > MAX_SLABS) { set_error("engine: slab workspace exhausted"); return 2; }
-            ga.slab = e->slabs + slab_off;
-            fa.st[fa.nst++] = SlabTask{ga.slab, e->G + e->o_conv_w[i - 1], H * H, T};
-            slab_off += need_w;
-            ga.att_slab = e->slabs + slab_off;
-            fa.st[fa.nst++] = SlabTask{ga.att_slab, e->G + e->o_conv_att[i - 1], 2 * H, T};
-            slab_off += need_a;
-            if (striped_gat(c) && (i > 1 || (F <= FM_F && H <= FB_H))) {      // accumulator planes: the readers below are striped readers
-                ga.dacc_sum = bn_dsum(c, i); ga.dacc_prod = bn_dprod(c, i); ga.dacc_ss = e->bn_plane;
-            } else {
-                double* pp = parts_alloc(c, (size_t)T * nsl * 2 * H);
-                if (!pp) { set_error("engine: partial-row workspace exhausted"); return 2; }
-                ga.dot_parts = pp;
-                final_task(c, pp, T * nsl, 2 * H, H, bn_dsum(c, i));
-                final_task(c, pp + H, T * nsl, 2 * H, H, bn_dprod(c, i));
-            }
+            if (b.slab_off + need_w + need_a > e->slab_floats || b.fa.nst + 2 > MAX_SLABS) return no_slabs();
+            ga.slab = slab_take(c, b, need_w, e->G + e->o_conv_w[i - 1], H * H, T);
+            ga.att_slab = slab_take(c, b, need_a, e->G + e->o_conv_att[i - 1], 2 * H, T);
+            RC(bn_bwd_sums(c, ga, T * nsl, bn_dsum(c, i), bn_dprod(c, i), st_i));
             {
-                ProfScope ps(st, 8, 4.0 * N * H * H + 4.0 * (double)(c.E + N) * H, true);
+                ProfScope ps(st, 8, 4.0 * N * H * H + 4.0 * (double)(E + N) * H, true);
                 if (i == L) PROF_LAUNCH((k_ggat_bwd<false>), dim3(T, nsl), dim3(GB_NT), 0, st, gd, e->gptr, e->eptr, ga, N, H, H, e->status);
                 else PROF_LAUNCH((k_ggat_bwd<true>), dim3(T, nsl), dim3(GB_NT), 0, st, gd, e->gptr, e->eptr, ga, N, H, H, e->status);
             }
             CAL_CHECK_LAUNCH("k_ggat_bwd"); STAGE();
             RC(flush_finals(c)); STAGE();
-            if (i == 1 && F <= FM_F && H <= FB_H) {
-                // the feature layer's backward per graph, fed from this layer's partial dX' (as in the GCNConv path)
-                RC(feat_bwd(p0, H > GC_N ? dzi : nullptr, false)); STAGE();
-            } else if (i == 1) {       // the feature layer below is a plain GEMM: materialise dZ for it
-                BnBwdProb p{p0, hin, e->dZ, bnref(c, i, N, 0), bn_dsum(c, i), bn_dprod(c, i), Acc(), H > GC_N ? dzi : nullptr};
-                RC(with_g(H, [&](auto g) {
-                    constexpr int G = decltype(g)::value;
-                    hipLaunchKernelGGL((k_bn_bwd<4, G>), dim3(cdiv(N, c.rpb_n), 1), dim3(256), 0, st, BnBwdProb3{{p, p, p}}, 1, N, H, c.rpb_n);
-                    return 0;
-                }));
-                CAL_CHECK_LAUNCH("k_bn_bwd"); STAGE();
-            }
-            continue;
-        }
-        if (gcb && !gat) {
-            // Layer i reads dOut = e->dZ (i == L, written by k_att_bwd) or builds it while staging from layer i+1's
-            // partial dX' (BatchNorm_{i+1}-backward + ReLU mask fused in: no k_bn_bwd launch, no dZ round trip);
-            // slice-0 partials ping-pong between dXh and z (idle in the fused forward), slice-1 partials are per layer.
-            const float* hin = e->h + (size_t)(i - 1) * NH;
-            float* p0 = ((L - i) & 1) ? e->z : e->dXh;
+        } else if (r.bb_bwd != Conv::Node) {
+            // GCNConv per graph (engine_gconv_bwd.hpp), unit coefficients as the forward's first layer wrote them -- or per graph of
+            // up to 256 nodes (engine_gwide.hpp): CSR by source, the unit coefficients k_plan_graph left in that slot order, if it ran
             GconvBwdBranch gb;
             memset(&gb, 0, sizeof(gb));
             gb.x = hin; gb.W = e->P + e->o_conv_w[i - 1]; gb.dis = e->dis_unit; gb.bn = bnref(c, i, N, 0);
             gb.dxp0 = p0; gb.dxp1 = dzi;
-            gb.coef_in = e->coef;               // written by the forward's first fused layer
-            if (gwb) {                          // CSR by source: the unit coefficients k_plan_graph left in that slot order, if it ran
-                const bool fastp = e->node_ptr && e->edge_ptr && e->max_nodes > 0 && e->max_nodes <= GP_T2 && e->max_edges <= GP_E2;
-                gb.coef_in = fastp ? e->coef_src : nullptr;
-            }
+            gb.coef_in = r.bb_bwd != Conv::Wide ? e->coef : r.plan_coef ? e->coef_src : nullptr;
             if (i == L) gb.dout = e->dZ;
             else {
                 gb.dy0 = ((L - i - 1) & 1) ? e->z : e->dXh;
-                gb.dy1 = H > GC_N ? e->dzi + (size_t)i * NH : nullptr;
+                gb.dy1 = two ? e->dzi + (size_t)i * NH : nullptr;
                 gb.y = e->h + (size_t)i * NH;
                 gb.ubn = bnref(c, i + 1, N, 0); gb.udot_sum = bn_dsum(c, i + 1); gb.udot_prod = bn_dprod(c, i + 1);
-                Deferred& db = d_convb[i - 1];  // bias of conv i: column sums of dOut, one partial row per graph
-                db.p = parts_alloc(c, (size_t)T * H); db.P = T; db.stride = H;
-                if (!db.p) { set_error("engine: partial-row workspace exhausted"); return 2; }
-                gb.bias_parts = db.p;
+                gb.bias_parts = b.d_convb[i - 1].p;
             }
             float* dst[1] = {e->G + e->o_conv_w[i - 1]};
             double* dsum[1] = {bn_dsum(c, i)}; double* dprod[1] = {bn_dprod(c, i)};
-            { ProfScope ps(st, 4, 4.0 * N * H * H + 2.0 * (double)(c.E + N) * H, true); RC(gconv_bwd(c, gd, &gb, 1, dst, dsum, dprod, fa, slab_off, false, gwb ? gw_st : striped_bb(c) && (i > 1 || (F <= FM_F && H <= FB_H)), gwb ? &gs : nullptr)); } STAGE();
+            { ProfScope ps(st, 4, 4.0 * N * H * H + 2.0 * (double)(E + N) * H, true); RC(gconv_bwd(c, b, &gb, 1, dst, dsum, dprod, st_i)); } STAGE();
             RC(flush_finals(c)); STAGE();
-            if (i == 1 && (gwb ? F <= FB_F : F <= FM_F) && H <= FB_H) {
-                // the feature layer's backward per graph, fed from this layer's partial dX' (no k_bn_bwd, no dZ round trip)
-                // (wide graphs: the same FMA kernel over uniform 64-row chunks, F <= 64 -- round 6; it replaces k_bn_bwd + the dual GEMM + a finishing launch)
-                RC(feat_bwd(p0, H > GC_N ? dzi : nullptr, false)); STAGE();
-            } else if (i == 1) {       // the feature layer below is a plain GEMM: materialise dZ for it
-                BnBwdProb p{p0, hin, e->dZ, bnref(c, i, N, 0), bn_dsum(c, i), bn_dprod(c, i), Acc(), H > GC_N ? dzi : nullptr};
-                RC(with_g(H, [&](auto g) {
-                    constexpr int G = decltype(g)::value;
-                    if (gw_st) hipLaunchKernelGGL((k_bn_bwd<4, G, true>), dim3(cdiv(N, c.rpb_n), 1), dim3(256), 0, st, BnBwdProb3{{p, p, p}}, 1, N, H, c.rpb_n);
-                    else hipLaunchKernelGGL((k_bn_bwd<4, G>), dim3(cdiv(N, c.rpb_n), 1), dim3(256), 0, st, BnBwdProb3{{p, p, p}}, 1, N, H, c.rpb_n);
-                    return 0;
-                }));
-                CAL_CHECK_LAUNCH("k_bn_bwd"); STAGE();
-            }
+        }
+        // BatchNorm_i backward of layer i's input gradient (two slice partials q0 + q1, or one) into e->dZ, the bias sums of the layer
+        // below into `acc`; st: the striped instantiation (the site's sums are in the accumulator planes)
+        auto bn_bwd_dz = [&](const float* q0, const float* q1, Acc acc, bool st_rd) -> int {
+            BnBwdProb p{q0, hin, e->dZ, bnref(c, i, N, 0), bn_dsum(c, i), bn_dprod(c, i), acc, q1};
+            RC(with_g(H, [&](auto g) {
+                constexpr int G = decltype(g)::value;
+                if (st_rd) hipLaunchKernelGGL((k_bn_bwd<4, G, true>), dim3(PN, 1), dim3(256), 0, st, BnBwdProb3{{p, p, p}}, 1, N, H, c.rpb_n);
+                else hipLaunchKernelGGL((k_bn_bwd<4, G>), dim3(PN, 1), dim3(256), 0, st, BnBwdProb3{{p, p, p}}, 1, N, H, c.rpb_n);
+                return 0;
+            }));
+            CAL_CHECK_LAUNCH("k_bn_bwd"); STAGE();
+            return 0;
+        };
+        if (r.bb_bwd != Conv::Node) {
+            if (i > 1) continue;
+            // the feature layer's backward per graph (wide graphs: per 64-row chunk), fed from this layer's partial dX' -- or, when
+            // it is a plain GEMM, dZ materialised for it
+            if (units) { RC(bwd_feat_units(c, b, x0, p0, two ? dzi : nullptr, false)); STAGE(); }
+            else RC(bn_bwd_dz(p0, two ? dzi : nullptr, Acc(), r.st_bb1));
             continue;
         }
-        if (gat) {       // dz_i and d att_i from dOut_i (GATConv backward; alpha recomputed from the saved max / denominator)
+        if (e->K > 0) {       // dz_i and d att_i from dOut_i (GATConv backward; alpha recomputed from the saved max / denominator)
             const int K = e->K, D = H / K;
             const size_t nk = al((size_t)e->capN * K);
             const float* sc = e->gsc + (size_t)(i - 1) * 4 * nk;
-            ProfScope ps(st, 6, 4.0 * N * H * 4 + (double)(c.E + N) * (16 + 24.0 * K));
+            ProfScope ps(st, 6, 4.0 * N * H * 4 + (double)(E + N) * (16 + 24.0 * K));
             // d att: per-block partial rows parked in the slab area, summed by the final k_finish (no finishing launch)
             const size_t need = (size_t)gat_datt_parts(N) * 2 * H;
-            if (slab_off + need > e->slab_floats || fa.nst >= MAX_SLABS) { set_error("engine: slab workspace exhausted"); return 2; }
-            float* part = e->slabs + slab_off;
+            if (b.slab_off + need > e->slab_floats || b.fa.nst >= MAX_SLABS) return no_slabs();
+            float* part = e->slabs + b.slab_off;
             int nparts = 0;
             RC(gat_backward(e->rowptr_dst, e->nbr_dst, e->eid_dst, e->rowptr_src, e->nbr_src, e->eid_src,
                             e->gz + (size_t)(i - 1) * NH, e->P + e->o_conv_att[i - 1], sc, sc + nk, sc + 2 * nk, sc + 3 * nk, e->dZ,
                             e->gat_slope, c.training ? e->gat_p : 0.f, e->gat_seed[i - 1], (const uint64_t*)e->gat_ctr, dzi,
-                            e->G + e->o_conv_att[i - 1], e->gws, N, c.E, K, D, st, part, &nparts));
-            fa.st[fa.nst++] = SlabTask{part, e->G + e->o_conv_att[i - 1], 2 * H, nparts};
-            slab_off += need;
+                            e->G + e->o_conv_att[i - 1], e->gws, N, E, K, D, st, part, &nparts));
+            b.fa.st[b.fa.nst++] = SlabTask{part, e->G + e->o_conv_att[i - 1], 2 * H, nparts};
+            b.slab_off += need;
         } else {
             SpmmBranch br{e->dZ, dzi, nullptr, nullptr, e->dis_unit, Acc(), Acc(), nullptr, nullptr, nullptr};
-            ProfScope ps(st, 1, 2.0 * N * H * 4 + (double)(c.E + N) * 8 + (N + 1) * 4.0, true);
+            ProfScope ps(st, 1, 2.0 * N * H * 4 + (double)(E + N) * 8 + (N + 1) * 4.0, true);
             RC(launch_espmm(st, gs, SpmmBranch2{{br, br}}, 1, 0, e->loop_w, N, H, spmm_rpb(H, false)));
             CAL_CHECK_LAUNCH("k_espmm(T)");
         }
         STAGE();
-        const float* hin = e->h + (size_t)(i - 1) * NH;
         {
-            GemmArgs a = gemm_args(H, H, N, true, false, 0);
-            a.p[0].A = hin; a.p[0].B = dzi;
-            a.p[0].xa.has_bn = 1; a.p[0].xa.bn = bnref(c, i, N, 0);
+            GemmArgs aw = gemm_args(H, H, N, true, false, 0);
+            aw.p[0].A = hin; aw.p[0].B = dzi;
+            aw.p[0].xa.has_bn = 1; aw.p[0].xa.bn = bnref(c, i, N, 0);
             float* dst[1] = {e->G + e->o_conv_w[i - 1]};
-            GemmArgs aw = a;
-            a = gemm_args(N, H, H, false, true, 0);
+            GemmArgs a = gemm_args(N, H, H, false, true, 0);
             a.p[0].A = dzi; a.p[0].B = e->P + e->o_conv_w[i - 1]; a.p[0].C = e->dXh;
             a.p[0].aux = hin; a.p[0].has_aux = 1; a.p[0].aux_bn = bnref(c, i, N, 0);
-            gemm_stats(c, a.p[0], N, H, bn_dsum(c, i), bn_dprod(c, i), true, H, striped_node(c));
-            { ProfScope ps(st, 3, 4.0 * N * H * H); RC(dual_gemm(c, a, 1, aw, 1, dst, fa, slab_off)); } STAGE();
+            gemm_stats(c, a.p[0], N, H, bn_dsum(c, i), bn_dprod(c, i), true, H, r.st_node);
+            { ProfScope ps(st, 3, 4.0 * N * H * H); RC(dual_gemm(c, b, a, 1, aw, 1, dst)); } STAGE();
             RC(flush_finals(c)); STAGE();
         }
-        if (i == 1 && !feat_done && feat_rows(c)) {
+        if (i == 1 && r.feat_bwd == FeatBwd::Rows) {
             // the last BatchNorm backward feeds only the feature layer: dZ stays in registers (engine_feat.hpp)
-            const int P = cdiv(N, c.rpb_n), cols = (F + 1) * H;
-            FeatBwdRowsArgs fb{e->dXh, hin, bnref(c, 1, N, 0), bn_dsum(c, 1), bn_dprod(c, 1), x0, bnref(c, 0, N, 0), parts_alloc(c, (size_t)P * cols)};
+            const int cols = (F + 1) * H;
+            FeatBwdRowsArgs fb{e->dXh, hin, bnref(c, 1, N, 0), bn_dsum(c, 1), bn_dprod(c, 1), x0, bnref(c, 0, N, 0), parts_alloc(c, (size_t)PN * cols)};
             double* sums = parts_alloc(c, cols);
-            d_bn0.p = parts_alloc(c, 2 * (size_t)F); d_bn0.P = 1; d_bn0.stride = 2 * F;
-            if (!fb.parts || !sums || !d_bn0.p) { set_error("engine: partial-row workspace exhausted"); return 2; }
-            if (slab_off + (size_t)F * H > e->slab_floats || fa.nst >= MAX_SLABS) { set_error("engine: slab workspace exhausted"); return 2; }
-            float* dw = e->slabs + slab_off;
-            fa.st[fa.nst++] = SlabTask{dw, e->G + e->o_feat_w, F * H, 1};
-            slab_off += (size_t)F * H;
+            b.d_bn0.p = parts_alloc(c, 2 * (size_t)F); b.d_bn0.P = 1; b.d_bn0.stride = 2 * F;
+            if (!fb.parts || !sums || !b.d_bn0.p) return no_parts();
+            float* dw = slab_take(c, b, (size_t)F * H, e->G + e->o_feat_w, F * H, 1);
+            if (!dw) return no_slabs();
             RC(with_g_fp(H, F, [&](auto g, auto fp) {
-                hipLaunchKernelGGL((k_bn_bwd_feat<decltype(g)::value, decltype(fp)::value>), dim3(P), dim3(256), 0, st, fb, N, H, F, c.rpb_n);
+                hipLaunchKernelGGL((k_bn_bwd_feat<decltype(g)::value, decltype(fp)::value>), dim3(PN), dim3(256), 0, st, fb, N, H, F, c.rpb_n);
                 return 0;
             }));
             CAL_CHECK_LAUNCH("k_bn_bwd_feat"); STAGE();
-            final_task(c, fb.parts, P, cols, cols, sums);
+            final_task(c, fb.parts, PN, cols, cols, sums);
             RC(flush_finals(c)); STAGE();
-            hipLaunchKernelGGL(k_feat_bwd_final, dim3(F), dim3(256), 0, st, sums, e->P + e->o_feat_w, bnref(c, 0, N, 0), dw, d_bn0.p, H, F);
+            hipLaunchKernelGGL(k_feat_bwd_final, dim3(F), dim3(256), 0, st, sums, e->P + e->o_feat_w, bnref(c, 0, N, 0), dw, b.d_bn0.p, H, F);
             CAL_CHECK_LAUNCH("k_feat_bwd_final"); STAGE();
-            feat_done = true;
         } else {
-            BnBwdProb p{e->dXh, hin, e->dZ, bnref(c, i, N, 0), bn_dsum(c, i), bn_dprod(c, i),
-                        i >= 2 ? deferred(H, d_convb[i - 2]) : Acc()};
-            RC(with_g(H, [&](auto g) {
-                constexpr int G = decltype(g)::value;
-                if (striped_node(c)) hipLaunchKernelGGL((k_bn_bwd<4, G, true>), dim3(cdiv(N, c.rpb_n), 1), dim3(256), 0, st, BnBwdProb3{{p, p, p}}, 1, N, H, c.rpb_n);
-                else hipLaunchKernelGGL((k_bn_bwd<4, G>), dim3(cdiv(N, c.rpb_n), 1), dim3(256), 0, st, BnBwdProb3{{p, p, p}}, 1, N, H, c.rpb_n);
-                return 0;
-            }));
-            CAL_CHECK_LAUNCH("k_bn_bwd"); STAGE();
+            RC(bn_bwd_dz(e->dXh, nullptr, i >= 2 ? defer(c, b.d_convb[i - 2], PN, H) : Acc(), r.st_node));
         }
     }
-    // S. conv_feat weight and bn_feat affine gradients
-    if (!feat_done) {
-        GemmArgs a = gemm_args(F, H, N, true, false, 0);
-        a.p[0].A = x0; a.p[0].B = e->dZ;
-        a.p[0].xa.has_bn = 1; a.p[0].xa.bn = bnref(c, 0, N, 0);
-        float* dst[1] = {e->G + e->o_feat_w};
-        GemmArgs aw = a;
-        a = gemm_args(N, F, H, false, true, 0);
-        a.p[0].A = e->dZ; a.p[0].B = e->P + e->o_feat_w; a.p[0].C = nullptr;
-        a.p[0].aux = x0; a.p[0].has_aux = 1; a.p[0].aux_bn = bnref(c, 0, N, 0);
-        a.p[0].dot_sum = bn_dsum(c, 0); a.p[0].dot_prod = bn_dprod(c, 0);
-        {   // bn_feat's sums are only needed by the commit: keep the partial rows, no finalise launch
-            const int P0 = use_ks(N) ? gemm_ks_row_tiles(N) : gemm_row_tiles(N, F, H, false);
-            if ((size_t)P0 * F * 2 > 4096) {
-                d_bn0.p = parts_alloc(c, (size_t)P0 * 2 * F); d_bn0.P = P0; d_bn0.stride = 2 * F;
-                a.p[0].parts = d_bn0.p;
-            }
+    return 0;
+}
+
+// S. conv_feat weight and bn_feat affine gradients through the GEMM chain (unless they rode with layer 1 / the row kernels)
+int bwd_feat(Ctx& c, Bwd& b, const float* x0) {
+    Engine* e = c.e;
+    const int N = c.N, H = e->H, F = e->F;
+    if (c.r.feat_bwd != FeatBwd::Gemm) return 0;
+    GemmArgs aw = gemm_args(F, H, N, true, false, 0);
+    aw.p[0].A = x0; aw.p[0].B = e->dZ;
+    aw.p[0].xa.has_bn = 1; aw.p[0].xa.bn = bnref(c, 0, N, 0);
+    float* dst[1] = {e->G + e->o_feat_w};
+    GemmArgs a = gemm_args(N, F, H, false, true, 0);
+    a.p[0].A = e->dZ; a.p[0].B = e->P + e->o_feat_w; a.p[0].C = nullptr;
+    a.p[0].aux = x0; a.p[0].has_aux = 1; a.p[0].aux_bn = bnref(c, 0, N, 0);
+    a.p[0].dot_sum = bn_dsum(c, 0); a.p[0].dot_prod = bn_dprod(c, 0);
+    {   // bn_feat's sums are only needed by the commit: keep the partial rows, no finalise launch
+        const int P0 = use_ks(N) ? gemm_ks_row_tiles(N) : gemm_row_tiles(N, F, H, false);
+        if ((size_t)P0 * F * 2 > 4096) {
+            b.d_bn0.p = parts_alloc(c, (size_t)P0 * 2 * F); b.d_bn0.P = P0; b.d_bn0.stride = 2 * F;
+            a.p[0].parts = b.d_bn0.p;
         }
-        RC(dual_gemm(c, a, 1, aw, 1, dst, fa, slab_off)); STAGE();
     }
-    // commits: fp64 arena -> fp32 gradients
+    RC(dual_gemm(c, b, a, 1, aw, 1, dst)); STAGE();
+    return 0;
+}
+
+// commits: fp64 arena / partial rows -> fp32 gradients, the slab sums and (single-process steps) Adam in one k_finish
+int bwd_commit(Ctx& c, Bwd& b) {
+    Engine* e = c.e;
+    const int H = e->H, F = e->F, C = e->C, L = e->L;
+    FinishArgs& fa = b.fa;
+    auto commit_p = [&](const double* src, int P, int stride, int dst, int n, float scale) {
+        if (fa.nct < MAX_COMMITS) fa.ct[fa.nct] = CommitTask{src, P, stride, dst, n, scale};
+        fa.nct++;
+    };
+    auto commit_d = [&](const Deferred& d, int col, int dst, int n, float scale) { commit_p(d.p + col, d.P, d.stride, dst, n, scale); };
     for (int k = 0; k < e->nbn; ++k) {
-        const BNSlot& b = e->bn[k];
-        const int wp = (b.width + 3) / 4 * 4;
-        if (k == 0 && d_bn0.p) {
-            commit_p(d_bn0.p + F, d_bn0.P, d_bn0.stride, b.gamma, F, 1.f);
-            commit_p(d_bn0.p, d_bn0.P, d_bn0.stride, b.beta, F, 1.f);
+        const BNSlot& s = e->bn[k];
+        const int wp = (s.width + 3) / 4 * 4;
+        if (k == 0 && b.d_bn0.p) {
+            commit_d(b.d_bn0, F, s.gamma, F, 1.f);
+            commit_d(b.d_bn0, 0, s.beta, F, 1.f);
             continue;
         }
         // (the NSTRIPE accumulator planes of the site: engine.hpp, stripe_sum)
-        commit_p(e->arena + b.arena + 3 * wp, NSTRIPE, e->bn_plane, b.gamma, b.width, 1.f);   // d gamma = sum dyh * x_n
-        commit_p(e->arena + b.arena + 2 * wp, NSTRIPE, e->bn_plane, b.beta, b.width, 1.f);    // d beta  = sum dyh
+        commit_p(e->arena + s.arena + 3 * wp, NSTRIPE, e->bn_plane, s.gamma, s.width, 1.f);   // d gamma = sum dyh * x_n
+        commit_p(e->arena + s.arena + 2 * wp, NSTRIPE, e->bn_plane, s.beta, s.width, 1.f);    // d beta  = sum dyh
     }
     for (int i = 0; i < L; ++i) {
-        if (!d_convb[i].p) { set_error("engine: missing bias-gradient partials"); return 2; }
+        if (!b.d_convb[i].p) { set_error("engine: missing bias-gradient partials"); return 2; }
         // GCNConv / GATConv: the layer's bias; GINConv: the bias of its second Linear (the first one's has its own sums)
-        commit_p(d_convb[i].p, d_convb[i].P, d_convb[i].stride, e->gin ? e->o_gin_b2[i] : e->o_conv_b[i], H, 1.f);
+        commit_d(b.d_convb[i], 0, e->gin ? e->o_gin_b2[i] : e->o_conv_b[i], H, 1.f);
         if (e->gin) {
-            if (!d_gin_b1[i].p) { set_error("engine: missing bias-gradient partials"); return 2; }
-            commit_p(d_gin_b1[i].p, d_gin_b1[i].P, d_gin_b1[i].stride, e->o_conv_b[i], H, 1.f);
+            if (!b.d_gin_b1[i].p) { set_error("engine: missing bias-gradient partials"); return 2; }
+            commit_d(b.d_gin_b1[i], 0, e->o_conv_b[i], H, 1.f);
         }
     }
-    commit_p(d_cb.p, d_cb.P, d_cb.stride, e->o_cb, H, 1.f);
-    commit_p(d_ob.p, d_ob.P, d_ob.stride, e->o_ob, H, 1.f);
-    commit_p(d_dwn.p, d_dwn.P, d_dwn.stride, e->o_natt_w, H, 1.f);
-    commit_p(d_dwn.p, d_dwn.P, d_dwn.stride, e->o_natt_w + H, H, -1.f);
-    commit_p(d_dwn.p + H, d_dwn.P, d_dwn.stride, e->o_natt_b, 1, 1.f);
-    commit_p(d_dwn.p + H, d_dwn.P, d_dwn.stride, e->o_natt_b + 1, 1, -1.f);
-    commit_p(d_dwe.p, d_dwe.P, d_dwe.stride, e->o_eatt_w, 2 * H, 1.f);
-    commit_p(d_dwe.p, d_dwe.P, d_dwe.stride, e->o_eatt_w + 2 * H, 2 * H, -1.f);
-    commit_p(d_dwe.p + 2 * H, d_dwe.P, d_dwe.stride, e->o_eatt_b, 1, 1.f);
-    commit_p(d_dwe.p + 2 * H, d_dwe.P, d_dwe.stride, e->o_eatt_b + 1, 1, -1.f);
+    commit_d(b.d_cb, 0, e->o_cb, H, 1.f);
+    commit_d(b.d_ob, 0, e->o_ob, H, 1.f);
+    commit_d(b.d_dwn, 0, e->o_natt_w, H, 1.f);
+    commit_d(b.d_dwn, 0, e->o_natt_w + H, H, -1.f);
+    commit_d(b.d_dwn, H, e->o_natt_b, 1, 1.f);
+    commit_d(b.d_dwn, H, e->o_natt_b + 1, 1, -1.f);
+    commit_d(b.d_dwe, 0, e->o_eatt_w, 2 * H, 1.f);
+    commit_d(b.d_dwe, 0, e->o_eatt_w + 2 * H, 2 * H, -1.f);
+    commit_d(b.d_dwe, 2 * H, e->o_eatt_b, 1, 1.f);
+    commit_d(b.d_dwe, 2 * H, e->o_eatt_b + 1, 1, -1.f);
     for (int hd = 0; hd < 3; ++hd) {
-        commit(e->a_db1 + hd * H, e->o_fc1_b[hd], H, 1.f);
-        commit(e->a_db2 + hd * C, e->o_fc2_b[hd], C, 1.f);
+        commit_p(e->arena + e->a_db1 + hd * H, 1, 0, e->o_fc1_b[hd], H, 1.f);
+        commit_p(e->arena + e->a_db2 + hd * C, 1, 0, e->o_fc2_b[hd], C, 1.f);
     }
     if (fa.nct > MAX_COMMITS) { set_error("engine: too many commit tasks"); return 2; }
     join_side(c);
-    {
-        if (c.adam_in_finish) {
-            // Adam rides in this kernel: parameter ranges no task writes (gradients stored directly by the readout /
-            // single-slab GEMMs) become update-only tasks
-            fa.adam = AdamArgs{e->P, e->M1, e->M2, e->step, e->lr, e->beta1, e->beta2, e->eps, e->wd, e->grad_scale, 1};
-            std::vector<std::pair<int64_t, int64_t>> iv;
-            for (int i = 0; i < fa.nst; ++i) iv.push_back({fa.st[i].dst - e->G, (fa.st[i].dst - e->G) + fa.st[i].n});
-            for (int i = 0; i < fa.nct; ++i) iv.push_back({fa.ct[i].dst, (int64_t)fa.ct[i].dst + fa.ct[i].n});
-            std::sort(iv.begin(), iv.end());
-            int64_t pos = 0;
-            bool ok = true;
-            auto gap = [&](int64_t a, int64_t b) {
-                if (b <= a) return;
-                if (fa.nar >= MAX_ADAM_RANGES) { ok = false; return; }
-                fa.ar[fa.nar++] = AdamRange{a, b};
-            };
-            for (auto& r : iv) {
-                if (r.first < pos) { ok = false; break; }          // two tasks finish the same element: not expected
-                gap(pos, r.first);
-                pos = r.second;
-            }
-            gap(pos, e->nparam);
-            if (!ok || pos > e->nparam) {                          // keep the separate k_adam launch
-                fa.adam.on = 0; fa.nar = 0; c.adam_in_finish = 2;     // 2: k_adam follows, counter already advanced
-            }
+    if (c.adam_in_finish) {
+        // Adam rides in this kernel: parameter ranges no task writes (gradients stored directly by the readout /
+        // single-slab GEMMs) become update-only tasks
+        fa.adam = AdamArgs{e->P, e->M1, e->M2, e->step, e->lr, e->beta1, e->beta2, e->eps, e->wd, e->grad_scale, 1};
+        std::vector<std::pair<int64_t, int64_t>> iv;
+        for (int i = 0; i < fa.nst; ++i) iv.push_back({fa.st[i].dst - e->G, (fa.st[i].dst - e->G) + fa.st[i].n});
+        for (int i = 0; i < fa.nct; ++i) iv.push_back({fa.ct[i].dst, (int64_t)fa.ct[i].dst + fa.ct[i].n});
+        std::sort(iv.begin(), iv.end());
+        int64_t pos = 0;
+        bool ok = true;
+        auto gap = [&](int64_t a, int64_t b) {
+            if (b <= a) return;
+            if (fa.nar >= MAX_ADAM_RANGES) { ok = false; return; }
+            fa.ar[fa.nar++] = AdamRange{a, b};
+        };
+        for (auto& r : iv) {
+            if (r.first < pos) { ok = false; break; }          // two tasks finish the same element: not expected
+            gap(pos, r.first);
+            pos = r.second;
         }
-        int nblk = 0;
-        for (int i = 0; i < fa.nst; ++i) { fa.blk0[i] = nblk; nblk += std::max(1, cdiv(fa.st[i].n, 64)); }
-        for (int i = 0; i < fa.nct; ++i) { fa.blk0[fa.nst + i] = nblk; nblk += std::max(1, cdiv(fa.ct[i].n, 16)); }
-        for (int i = 0; i < fa.nar; ++i) { fa.blk0[fa.nst + fa.nct + i] = nblk; nblk += (int)cdiv(fa.ar[i].end - fa.ar[i].begin, 256); }
-        fa.blk0[fa.nst + fa.nct + fa.nar] = nblk;
-        hipLaunchKernelGGL(k_finish, dim3(nblk), dim3(256), 0, st, fa, e->G);
+        gap(pos, e->nparam);
+        if (!ok || pos > e->nparam) {                          // keep the separate k_adam launch
+            fa.adam.on = 0; fa.nar = 0; c.adam_in_finish = 2;     // 2: k_adam follows, counter already advanced
+        }
     }
+    int nblk = 0;
+    for (int i = 0; i < fa.nst; ++i) { fa.blk0[i] = nblk; nblk += std::max(1, cdiv(fa.st[i].n, 64)); }
+    for (int i = 0; i < fa.nct; ++i) { fa.blk0[fa.nst + i] = nblk; nblk += std::max(1, cdiv(fa.ct[i].n, 16)); }
+    for (int i = 0; i < fa.nar; ++i) { fa.blk0[fa.nst + fa.nct + i] = nblk; nblk += (int)cdiv(fa.ar[i].end - fa.ar[i].begin, 256); }
+    fa.blk0[fa.nst + fa.nct + fa.nar] = nblk;
+    hipLaunchKernelGGL(k_finish, dim3(nblk), dim3(256), 0, c.st, fa, e->G);
     CAL_CHECK_LAUNCH("k_finish"); STAGE();
     e->bn0_dirty_host = 0;          // bn_feat's statistics range is clean again behind this launch (PlanFold)
     return 0;
+}
+
+int engine_backward(Ctx& c, const float* x0) {
+    Engine* e = c.e;
+    Bwd b;
+    memset(&b, 0, sizeof(b));
+    FinishArgs& fa = b.fa;
+    fa.tick = (c.tick_in_finish && !c.adam_in_finish) ? e->step : nullptr;      // (adam_in_finish: k_zero_f64 did it)
+    fa.ticked = c.adam_in_finish ? e->step : nullptr;
+    fa.perm_ctr = c.draw_perm ? e->perm_ctr : nullptr;
+    fa.status = e->status;
+    fa.host_status = e->host_status;
+    { const int wp0 = (e->bn[0].width + 3) / 4 * 4; fa.bn0z = e->arena + e->bn[0].arena; fa.bn0z_n = 2 * wp0; fa.dirty = e->status + 3; }
+    RC(bwd_readout(c, b));
+    RC(bwd_co(c, b));
+    RC(bwd_att(c, b));
+    RC(bwd_backbone(c, b, x0));
+    RC(bwd_feat(c, b, x0));
+    return bwd_commit(c, b);
+}
+
+// The Ctx both entry points set up, with the route of a `mode` step
+void ctx_init(Ctx& c, Engine* e, void* stream, int64_t N, int64_t E, int64_t B, const int64_t* batch, int mode) {
+    memset(&c, 0, sizeof(c));
+    c.e = e; c.st = (hipStream_t)stream; c.N = (int)N; c.B = (int)B; c.E = E;
+    c.T = e->ntiles > 0 ? e->ntiles : (int)B;
+    c.batch = batch;
+    c.training = (mode & 1) ? 1 : 0;
+    c.want_grad = (mode & 2) ? 1 : 0;
+    // (16 k - 64 k rows: 512 workgroups -- a workgroup's prologue / column-sum epilogue over 32 rows was a third of k_att_bwd at 30 k rows)
+    c.rpb_n = std::max(32, cdiv(N, N >= 16384 && N <= 65536 ? 512 : 1024));
+    c.rpb_b = std::max(32, cdiv(B, 64));
+    c.r = make_route(c, c.want_grad);
 }
 
 }  // namespace
@@ -2183,41 +2190,30 @@ CAL_EXPORT int cal_engine_step(void* h, const float* x0, const int64_t* edge_ind
     CAL_REQUIRE(e && e->ws, "engine has no workspace");
     CAL_REQUIRE(N <= e->capN && E <= e->capE && B <= e->capB, "batch exceeds the workspace capacity");
     CAL_REQUIRE(N > 0 && B > 0, "empty batch");
-    Ctx c;
-    c.e = e; c.st = (hipStream_t)stream_; c.N = (int)N; c.B = (int)B; c.E = E;
     CAL_REQUIRE(e->ntiles <= B, "more tiles than graphs (cal_engine_set_tiles belongs to another batch)");
-    c.T = e->ntiles > 0 ? e->ntiles : (int)B;
-    c.batch = batch;
     CAL_REQUIRE(e->ntiles == 0 || (e->H % GC_N == 0 && e->H <= GC_K && e->node_ptr && e->edge_ptr && e->max_nodes > 0 && e->max_nodes <= 64 &&
                                    e->max_edges <= gc_edge_cap(64)),
                 "cal_engine_set_tiles needs the per-graph kernels: hidden in {64, 128}, the tiles' offsets (cal_engine_set_graph_ptrs) and bounds <= 64 nodes / 1024 edges");
-    c.training = (mode & 1) ? 1 : 0;
-    // (16 k - 64 k rows: 512 workgroups -- a workgroup's prologue / column-sum epilogue over 32 rows was a third of k_att_bwd at 30 k rows)
-    c.rpb_n = std::max(32, cdiv(N, e->rpb_div ? e->rpb_div : (N >= 16384 && N <= 65536 ? 512 : 1024)));
-    c.rpb_b = std::max(32, cdiv(B, 64));
-    c.parts_off = 0;
-    c.fin.nt = 0;
-    c.nfork = 0;
-    c.ro_done = 0;
-    c.adam_in_finish = ((mode & 4) && e->adam_fused) ? 1 : 0;
     const int want_grad = (mode & 2) ? 1 : 0;
-    c.draw_perm = (mode & 16) ? 1 : 0;
-    CAL_REQUIRE(!c.draw_perm || (e->perm_ctr && B <= ZP_CAP && want_grad), "mode bit 16 needs cal_engine_set_perm_rng, at most 1024 graphs per batch and the backward pass (its last kernel advances the permutation counter)");
-    CAL_REQUIRE(c.draw_perm || perm, "perm is null and the step does not draw its own (mode bit 16)");
-    if (c.draw_perm) perm = e->perm_dev;
-    c.y = y; c.perm = perm; c.wc = wc; c.wo = wo; c.wco = wco; c.want_grad = want_grad;
-    c.tick_in_finish = (mode & (4 | 8)) ? 1 : 0;
+    CAL_REQUIRE(!(mode & 16) || (e->perm_ctr && B <= ZP_CAP && want_grad), "mode bit 16 needs cal_engine_set_perm_rng, at most 1024 graphs per batch and the backward pass (its last kernel advances the permutation counter)");
+    CAL_REQUIRE((mode & 16) || perm, "perm is null and the step does not draw its own (mode bit 16)");
     CAL_REQUIRE(!(mode & 8) || want_grad, "mode bit 8 (Adam follows a gradient exchange) needs the backward pass");
-    CAL_REQUIRE(!want_grad || c.training, "backward needs a training-mode forward");
+    CAL_REQUIRE(!want_grad || (mode & 1), "backward needs a training-mode forward");
     CAL_REQUIRE(!(mode & 4) || want_grad, "the Adam update needs the backward pass in the same step");
+    Ctx c;
+    ctx_init(c, e, stream_, N, E, B, batch, mode);
+    c.adam_in_finish = ((mode & 4) && e->adam_fused) ? 1 : 0;
+    c.draw_perm = (mode & 16) ? 1 : 0;
+    c.y = y; c.perm = c.draw_perm ? e->perm_dev : perm; c.wc = wc; c.wo = wo; c.wco = wco;
+    c.tick_in_finish = (mode & (4 | 8)) ? 1 : 0;
     g_stage = 0;
     g_stage_names.clear();
     {
-        int rc = engine_forward(c, x0, edge_index, batch, y, perm, wc, wo, wco, want_grad);
+        int rc = engine_forward(c, x0, edge_index);
         if (rc == -12345) return 0;
         if (rc) return rc;
         if (want_grad) {
-            rc = engine_backward(c, x0, batch);
+            rc = engine_backward(c, x0);
             if (rc) join_side(c);
             if (rc == -12345) return 0;
             if (rc) return rc;
@@ -2240,22 +2236,14 @@ CAL_EXPORT int cal_engine_backward_from(void* h, const float* x0, const int64_t*
     Engine* e = (Engine*)h;
     CAL_REQUIRE(e && e->ws, "engine has no workspace");
     CAL_REQUIRE(N <= e->capN && E <= e->capE && B <= e->capB && N > 0 && B > 0, "bad batch sizes");
-    Ctx c;
-    c.e = e; c.st = (hipStream_t)stream_; c.N = (int)N; c.B = (int)B; c.E = E;
     CAL_REQUIRE(e->ntiles <= B, "more tiles than graphs (cal_engine_set_tiles belongs to another batch)");
-    c.T = e->ntiles > 0 ? e->ntiles : (int)B;
-    c.batch = batch;
-    c.training = 1;
-    // (16 k - 64 k rows: 512 workgroups -- a workgroup's prologue / column-sum epilogue over 32 rows was a third of k_att_bwd at 30 k rows)
-    c.rpb_n = std::max(32, cdiv(N, e->rpb_div ? e->rpb_div : (N >= 16384 && N <= 65536 ? 512 : 1024)));
-    c.rpb_b = std::max(32, cdiv(B, 64));
-    c.parts_off = 0; c.fin.nt = 0; c.nfork = 0;
-    c.y = nullptr; c.perm = nullptr; c.wc = c.wo = c.wco = 0.f; c.want_grad = 1;
-    c.tick_in_finish = 0; c.draw_perm = 0; c.ro_done = 0; c.adam_in_finish = 0;
+    Ctx c;
+    ctx_init(c, e, stream_, N, E, B, batch, 1);      // the route of the mode-1 forward it follows
+    c.want_grad = 1;
     hipLaunchKernelGGL(k_logsoftmax_bwd, dim3(1), dim3(256), 0, c.st, e->logp, dlogp, e->dzl, e->arena + e->a_db2, (int)B, e->C);
     CAL_CHECK_LAUNCH("k_logsoftmax_bwd");
     g_stage = 0;
-    int rc = engine_backward(c, x0, batch);
+    int rc = engine_backward(c, x0);
     if (rc) join_side(c);
     return rc == -12345 ? 0 : rc;
 }

@@ -38,7 +38,7 @@ struct BNRef {
 // rows against +5.0 us for partial rows + finishing kernel and +6.1 us for one row).  Producers that finish into a single row
 // (k_stats_final, plain atomics, plain stores) write plane 0 and leave the others zero, so a STRIPED reader (the *_st helpers
 // below) is right for either kind; the plain readers are right only for single-row sites -- the engine stripes a site only
-// when every kernel that reads it is a striped reader (engine.hip: striped_co / striped_bb / striped_gat / striped_gin / striped_feat / striped_node).  ss == 0 (no planes): the same value read
+// when every kernel that reads it is a striped reader (engine.hip: the st_* fields of Route).  ss == 0 (no planes): the same value read
 // NSTRIPE times and scaled back, exactly -- no branch in a kernel prologue (see bn_raw_load).
 constexpr int NSTRIPE = 4;
 __device__ __forceinline__ double stripe_sum(const double* __restrict__ p, int c, int ss) {

@@ -12,7 +12,7 @@
 //
 //   grid (nsplit B), 512 threads: nsplit = 2 workgroups per graph (same edge phase, one half of the rows each) for B <= 256,
 //   else one; graphs of at most
-//   64 nodes and GP_E stored edges -- the bounds of the per-graph fused backward (use_gcb in engine.hip).
+//   64 nodes and GP_E stored edges -- the bounds of the per-graph fused backward (make_route in engine.hip).
 //
 // Edge phase: only the by-destination CSR rows of the graph are read, and everything per edge arrives in SLOT order
 // (g from k_gconv_bwd<POOL> with gn_slot, the attention weights from k_gconv_fwd's w_out): one round of loads after

@@ -1,5 +1,5 @@
 // Fused readout path of the step engine (model.py:125-164 + train_causal.py:176-183 and their
-// backward) for mini-batches whose pooled matrix fits in LDS (see use_ro() in engine.hip:
+// backward) for mini-batches whose pooled matrix fits in LDS (see make_route in engine.hip:
 // roundup16(B)*(H+4) <= RO_LDS floats, B*H <= 16384, H % 16 == 0, B, H <= 256, B*C <= 2048, C <= 64):
 // four kernels instead of ten launches.
 //
