@@ -518,3 +518,74 @@ HOST_EXPORT int cal_collate_host(const float* X, const int64_t* EI, int64_t Etot
     HOST_REQUIRE(edges == Eout, "edge count mismatch");
     return 0;
 }
+
+// ---- explanations (model.py:97-111 edge / node scores): per-segment ranking, top-k selection, motif metrics.  Same keys,
+// order, k_g rule and integer rank sums as cal_amd/csrc/explain.hip, so masks, ranks and metrics agree bit for bit.
+namespace {
+constexpr int64_t kExplainLdsCap = 2048;
+
+inline uint32_t score_key(float s) {
+    if (s != s) return 1u;                                    // NaN: below every number
+    uint32_t u = 0u;
+    if (s != 0.f) memcpy(&u, &s, 4);                          // -0 ranks as +0
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+}  // namespace
+
+HOST_EXPORT int64_t cal_explain_ws(int64_t M, int64_t) { return 8 * (M > 0 ? M : 0) + 256; }
+HOST_EXPORT int64_t cal_explain_lds_cap(void) { return kExplainLdsCap; }
+
+HOST_EXPORT int cal_explain_rank(const float* score, int64_t stride, const int64_t* seg_ptr, int64_t B, int64_t M,
+                                 int64_t max_seg, double ratio, int64_t k, const uint8_t* gt, uint8_t* mask, int32_t* rank,
+                                 double* metrics, void*, int64_t, void*) {
+    HOST_REQUIRE(B >= 0 && M >= 0 && max_seg >= 0 && stride >= 1, "B, M, max_seg must be >= 0 and stride >= 1");
+    HOST_REQUIRE(k >= -2, "k must be >= 0, -1 (ratio) or -2 (ground-truth count)");
+    HOST_REQUIRE(k != -2 || gt, "k = -2 needs gt");
+    HOST_REQUIRE(k != -1 || ratio >= 0.0, "k = -1 needs a ratio >= 0");
+    HOST_REQUIRE(B == 0 || seg_ptr, "seg_ptr is null");
+    HOST_REQUIRE(M == 0 || (score && mask && rank), "score / mask / rank are null");
+    HOST_REQUIRE(max_seg < ((int64_t)1 << 30), "segments of 2^30 elements or more are not supported");
+#pragma omp parallel for schedule(dynamic, 16)
+    for (int64_t g = 0; g < B; ++g) {
+        int64_t lo = std::min(std::max(seg_ptr[g], (int64_t)0), M);
+        int64_t hi = std::min(std::max(seg_ptr[g + 1], lo), M);
+        const int64_t m = hi - lo;
+        double* row = metrics ? metrics + 4 * g : nullptr;
+        if (m > max_seg) {                                    // not ranked (max_seg must bound every segment)
+            for (int64_t q = 0; q < m; ++q) { rank[lo + q] = -1; mask[lo + q] = 0; }
+            if (row) for (int t = 0; t < 4; ++t) row[t] = NAN;
+            continue;
+        }
+        std::vector<uint32_t> key(m);
+        std::vector<int64_t> ord(m);
+        int64_t P = 0;
+        for (int64_t q = 0; q < m; ++q) {
+            key[q] = score_key(score[(lo + q) * stride]);
+            ord[q] = q;
+            if (gt) P += gt[lo + q] != 0;
+        }
+        std::sort(ord.begin(), ord.end(), [&](int64_t a, int64_t b) { return key[a] != key[b] ? key[a] > key[b] : a < b; });
+        int64_t kg = P;
+        if (k >= 0) kg = std::min(k, m);
+        else if (k == -1) { const double c = ceil(ratio * (double)m); kg = c < (double)m ? (int64_t)c : m; }
+        int64_t hits = 0, r2 = 0;
+        for (int64_t s = 0; s < m;) {                         // runs of equal keys: [s, e)
+            int64_t e = s + 1;
+            while (e < m && key[ord[e]] == key[ord[s]]) ++e;
+            const int64_t eq = e - s, less = m - e;
+            for (int64_t p = s; p < e; ++p) {
+                const int64_t i = lo + ord[p];
+                rank[i] = (int32_t)p;
+                mask[i] = p < kg;
+                if (gt && gt[i]) { hits += p < kg; r2 += 2 * less + eq + 1; }
+            }
+            s = e;
+        }
+        if (row) {
+            row[0] = (double)kg; row[1] = (double)hits; row[2] = (double)P;
+            row[3] = (P <= 0 || P >= m) ? NAN
+                     : ((double)r2 * 0.5 - (double)P * (double)(P + 1) * 0.5) / ((double)P * (double)(m - P));
+        }
+    }
+    return 0;
+}

@@ -391,6 +391,35 @@ class StepEngine:
         lp = self.buffer("logp", 3 * B * self.C).view(3, B, self.C)
         return lp[0], lp[1], lp[2]
 
+    def attention_scores(self, batch):
+        """Causal scores the latest ``forward`` of ``batch`` left, as views into the workspace (the next engine call overwrites
+        them): edge scores [E] (contiguous) and node scores [N] (stride 2).  Causal is column 1 of both soft masks, the
+        objects branch ``o`` (model.py:102-111: ``edge_weight_o = edge_att[:, 1]``, ``node_att[:, 1]``); column 0 is the
+        context branch, trained toward the uniform distribution.  Column e of the edge view is edge_index column e; a
+        self-loop edge of the input, which the convolutions drop and the step kernels leave unscored, gets the reference's
+        value here (softmax of the edge MLP on cat(x_v, x_v), one small launch after the step); under
+        ``without_edge_attention`` / ``without_node_attention`` every score is 0.5."""
+        x = batch.x if getattr(batch, "x", None) is not None else batch.feat
+        N, E = x.size(0), batch.edge_index.size(1)
+        edge = self.buffer("att", 2 * E)[E:]
+        node = self.buffer("anode", 2 * N)[1::2]
+        ei = batch.edge_index
+        if E and not getattr(batch, "no_self_loops", False):
+            loops = (ei[0] == ei[1]).nonzero().view(-1)
+            if loops.numel():
+                if getattr(self.model, "without_edge_attention", False):
+                    edge[loops] = 0.5
+                else:
+                    v = ei[0, loops].to(torch.int32)
+                    h = self.buffer("h", (self.L + 1) * N * self.H)[self.L * N * self.H:].view(N, self.H)
+                    att = torch.empty(2, loops.numel(), dtype=torch.float32, device=self.device)
+                    pq = torch.empty(4 * N, dtype=torch.float32, device=self.device)
+                    mlp = self.model.edge_att_mlp
+                    _lib.call("cal_edge_att_fwd", _p(h), _p(mlp.weight), _p(mlp.bias), _p(v), _p(v), _p(pq), _p(att),
+                              N, loops.numel(), self.H, _stream())
+                    edge[loops] = att[1]
+        return edge, node
+
     def logp_copy(self):
         """The latest forward's three [B, C] log-prob outputs as views of ONE private copy (the workspace buffer is
         overwritten by the next step; a caller may keep what a forward returned)."""

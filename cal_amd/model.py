@@ -140,6 +140,31 @@ class _CausalBase(torch.nn.Module):
         xco_logis = self.random_readout_layer(xc, xo, eval_random=eval_random, perm=perm)
         return xc_logis, xo_logis, xco_logis
 
+    def _attention_scores(self, data):
+        """Operator-level causal scores (model.py:85-111 up to the soft masks: backbone and attention, no convolutions or
+        readouts): edge ``edge_att[:, 1]`` [E] and node ``node_att[:, 1]`` [N], column 1 being the objects branch.  Runs in
+        the module's current mode; ``cal_amd.explain`` calls it in eval mode under ``no_grad``."""
+        x = data.x if data.x is not None else data.feat
+        edge_index = data.edge_index
+        plan = plan_of(data)
+        x = self.bn_feat(x)
+        x = self.conv_feat(x, edge_index, relu=True)
+        x = self._backbone(x, edge_index, plan)
+        if getattr(self, "without_edge_attention", False):
+            edge = torch.full((plan.E,), 0.5, dtype=x.dtype, device=x.device)
+        else:
+            edge = ops.edge_attention(x, self.edge_att_mlp.weight, self.edge_att_mlp.bias, plan)[1]
+        if getattr(self, "without_node_attention", False):
+            node = torch.full((x.size(0),), 0.5, dtype=x.dtype, device=x.device)
+        else:
+            node = ops.node_attention_split(x, self.node_att_mlp.weight, self.node_att_mlp.bias)[2][:, 1]
+        return edge, node
+
+    def explain(self, data, **kw):
+        """``cal_amd.explain.explain(self, data, **kw)``: per-graph top-k causal subgraphs of ``data``."""
+        from .explain import explain
+        return explain(self, data, **kw)
+
     def context_readout_layer(self, x):
         x = self.fc1_bn_c(x)
         x = ops.linear(x, self.fc1_c.weight, self.fc1_c.bias, relu=True)     # Linear + ReLU on the MFMA GEMM

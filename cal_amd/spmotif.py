@@ -104,6 +104,49 @@ def make_graph(context: str, shape: str, node_num: int, rng: np.random.Generator
                 y=torch.tensor([label], dtype=torch.long))
 
 
+_MOTIF_TABLES: Dict[torch.device, Tuple[torch.Tensor, torch.Tensor]] = {}
+
+
+def _motif_tables(dev) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(motif sizes [4], symmetric motif adjacency [4, 6, 6] bool) by class, built once per device."""
+    t = _MOTIF_TABLES.get(dev)
+    if t is None:
+        adj = torch.zeros(len(CLASS_LIST), 6, 6, dtype=torch.bool)
+        for c, s in enumerate(CLASS_LIST):
+            for a, b in _MOTIFS[s][1]:
+                adj[c, a, b] = adj[c, b, a] = True
+        sizes = torch.tensor([_MOTIFS[s][0] for s in CLASS_LIST], dtype=torch.long)
+        t = _MOTIF_TABLES[dev] = (sizes.to(dev), adj.to(dev))
+    return t
+
+
+def ground_truth(batch) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(node_gt [N], edge_gt [E]) bool tensors on the batch's device: the planted motif of every graph.
+
+    For graphs made by ``make_graph``, whose last ``n_s`` nodes are the motif of class ``CLASS_LIST[y]``: a node is ground
+    truth iff its local id is at least ``n_g - n_s``; an edge iff its local endpoint pair, less that base, is an edge of
+    the motif in either direction.  The plug-in edge and noise edges between motif nodes are not ground truth.  Graphs of
+    the reference generator (tests/golden/spmotif_ref_graphs.npz) place the motif nodes differently and are not covered."""
+    ei, bvec, y = batch.edge_index, batch.batch, batch.y.view(-1)
+    dev = ei.device
+    B = int(batch.num_graphs)
+    sizes, adj = _motif_tables(dev)
+    ptr = getattr(batch, "ptr", None)
+    if not torch.is_tensor(ptr) or ptr.numel() != B + 1:
+        ptr = torch.zeros(B + 1, dtype=torch.long, device=dev)
+        ptr[1:] = torch.cumsum(torch.bincount(bvec, minlength=B)[:B], 0)
+    ptr = ptr.to(dev)
+    yv = y.to(dev)
+    motif_base = ptr[1:] - sizes[yv]                     # first motif node of every graph (global id)
+    node_gt = torch.arange(bvec.numel(), device=dev) >= motif_base[bvec]
+    row, col = ei[0], ei[1]
+    g = bvec[row]
+    a = (row - motif_base[g]).clamp(0, 5)
+    b = (col - motif_base[g]).clamp(0, 5)
+    edge_gt = node_gt[row] & node_gt[col] & (bvec[col] == g) & adj[yv[g], a, b]
+    return node_gt, edge_gt
+
+
 def generate_dataset(data_num: int, node_num: int = 7, noise: float = 0.1,
                      max_degree: int = 10, seed: int = 666):
     """utils.graph_dataset_generate: {context: {shape: [Data]*data_num}}."""

@@ -257,6 +257,20 @@ CAL_API const char* cal_engine_stage_name(int k);
 CAL_API int cal_engine_profile(int on);
 CAL_API int64_t cal_engine_profile_read(double* out, int64_t cap);
 
+/* ---- explanations of the causal split (model.py:97-111): per-segment ranking, top-k selection, motif metrics ------ */
+/* Segment g = elements [seg_ptr[g], seg_ptr[g+1]) of score[i * stride] (stride 2 reads node_att[:, 1] in place), seg_ptr
+ * [B+1] int64.  Order: score descending, then element index ascending, NaN below every number; rank[i] = 0-based position
+ * in its segment; mask[i] = rank[i] < k_g with k_g = min(k, m_g) (k >= 0), min(m_g, ceil(ratio m_g)) (k = -1) or the
+ * segment's count of gt elements (k = -2, needs gt).  metrics (or null): [B, 4] fp64 rows k_g, hits (gt selected), P (gt in
+ * the segment), ROC-AUC from the ascending average ranks (NaN when P = 0 or P = m_g).  max_seg: host-known bound on every
+ * m_g, it picks the paths (a longer segment is not ranked: rank -1, mask 0, NaN metrics); above cal_explain_lds_cap()
+ * the call needs ws (16-byte aligned, cal_explain_ws bytes).  Every segment within the cap: one launch; else three. */
+CAL_API int64_t cal_explain_ws(int64_t M, int64_t B);
+CAL_API int64_t cal_explain_lds_cap(void);
+CAL_API int cal_explain_rank(const float* score, int64_t stride, const int64_t* seg_ptr, int64_t B, int64_t M,
+                             int64_t max_seg, double ratio, int64_t k, const uint8_t* gt, uint8_t* mask, int32_t* rank,
+                             double* metrics, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

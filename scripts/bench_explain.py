@@ -1,0 +1,93 @@
+"""Time the explanation path on the GPU: the HIP per-graph ranking (cal_explain_rank) alone, a torch-composed ranking of
+the same scores (stable sort by score, stable sort by graph id, masks), and eval_explanation against eval_acc_causal over
+the same loader.  Device events around synchronised regions, after warm-up; one JSON line per shape.
+
+    python scripts/bench_explain.py [--shapes headline,nodenum15,config5] [--iters 50]
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from cal_amd import model as M, spmotif, synth          # noqa: E402
+from cal_amd.data import Batch, DataLoader               # noqa: E402
+from cal_amd.explain import _Layout, _scores, eval_explanation, rank_segments   # noqa: E402
+from cal_amd.train_causal import eval_acc_causal         # noqa: E402
+
+SHAPES = {
+    "headline": dict(graphs=lambda n: spmotif.train_mix(n, node_num=7, seed=1), B=128),
+    "nodenum15": dict(graphs=lambda n: spmotif.train_mix(n, node_num=15, seed=1), B=128),
+    "config5": dict(graphs=lambda n: synth.ba_graphs(n, n=5000, seed=1), B=32),
+}
+
+
+def _time(fn, iters, warmup=5):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def torch_rank(score, gid, eptr, k):
+    """Torch-composed baseline: stable sort by score descending, then stable sort by graph id -> per-graph ranks, masks."""
+    o1 = torch.argsort(score, descending=True, stable=True)
+    o2 = torch.argsort(gid[o1], stable=True)
+    order = o1[o2]
+    rank = torch.empty_like(order)
+    rank[order] = torch.arange(order.numel(), device=score.device) - eptr[gid[order]]
+    return rank < k, rank
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="headline,nodenum15,config5")
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--batches", type=int, default=4)
+    a = ap.parse_args()
+    dev = "cuda"
+    args = argparse.Namespace(layers=3, hidden=128, with_random=True, without_node_attention=False,
+                              without_edge_attention=False, fc_num="222", cat_or_add="add", c=0.5, o=1.0, co=0.5,
+                              eval_random=False)
+    for name in a.shapes.split(","):
+        sh = SHAPES[name]
+        B = sh["B"]
+        torch.manual_seed(0)
+        m = M.CausalGCN(10, 4, args).to(dev).eval()
+        gs = sh["graphs"](B * a.batches)
+        b = Batch.from_data_list(gs[:B]).to(dev)
+        edge, node = _scores(m, b)
+        edge, node = edge.clone(), node.clone()
+        lay = _Layout(b)
+        node_gt, edge_gt = spmotif.ground_truth(b) if name != "config5" else (None, None)
+        kw = dict(k="gt", gt=edge_gt, metrics=True) if edge_gt is not None else dict(k=16)
+        t_rank = _time(lambda: rank_segments(edge, lay.edge_ptr, lay.max_edges, **kw), a.iters)
+        t_rank_nodes = _time(lambda: rank_segments(node, lay.ptr, lay.max_nodes, k=16), a.iters)
+        gid = b.batch[b.edge_index[0]]
+        t_torch = _time(lambda: torch_rank(edge, gid, lay.edge_ptr, 16), a.iters)
+        hm, hr, _ = rank_segments(edge, lay.edge_ptr, lay.max_edges, k=16)
+        tm, tr = torch_rank(edge, gid, lay.edge_ptr, 16)
+        same = bool(torch.equal(hr.long(), tr) and torch.equal(hm, tm))
+        out = dict(shape=name, graphs=B, edges=int(b.edge_index.size(1)), nodes=int(b.batch.numel()),
+                   max_edges=lay.max_edges, rank_edges_ms=round(t_rank, 4), rank_nodes_ms=round(t_rank_nodes, 4),
+                   torch_rank_edges_ms=round(t_torch, 4), hip_equals_torch=same)
+        if name != "config5":
+            loader = DataLoader(gs, batch_size=B, shuffle=False)
+            t_ee = _time(lambda: eval_explanation(m, loader, dev), max(3, a.iters // 10), warmup=2)
+            t_acc = _time(lambda: eval_acc_causal(m, loader, dev, args), max(3, a.iters // 10), warmup=2)
+            out.update(batches=a.batches, eval_explanation_ms=round(t_ee, 3), eval_acc_causal_ms=round(t_acc, 3))
+        print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
