@@ -20,6 +20,7 @@
 // with one wave per SIMD to hide it: 4.5-9 us per graph; the dense product is ~1 us.)
 #pragma once
 #include "engine_readout.hpp"     // RO_CLK profiling aid
+#include "engine_mma.hpp"         // 32 x 32 tile products, row mapping, tile stores
 
 namespace cal {
 
@@ -61,168 +62,7 @@ constexpr int GC_TILE_GRAPHS = 8;         // graphs per tile at most (the POOL b
 
 struct GconvBranch2 { GconvBranch b[2]; };
 
-typedef float gc_f32x16 __attribute__((ext_vector_type(16)));
-
-// ---- storing a 32 x 32 MFMA accumulator tile --------------------------------------------------------------------------
-// Lane (li, lk) of a 32x32 tile holds ONE column (li) of the rows (r & 3) + 8 (r >> 2) + 4 lk: stored as it lies that is 16
-// 4-byte store instructions per tile.  The four registers of a row group and the four lanes of a quad form a 4 x 4 block of
-// (row, column): transposed inside the quad (two DPP exchanges, no LDS) every lane holds four CONSECUTIVE columns of one
-// row, i.e. one 16-byte store -- 4 instructions per tile instead of 16, same bytes, same addresses.  Measured on
-// k_gconv_bwd (profiles/r3/store_burst.txt): the store phase of a workgroup is 3.4 us of its 12 us and stays 2.8 us with
-// the wide stores -- it is bound by BYTES (a workgroup's 64 KB leave its CU at ~20 GB/s), not by instruction issue; the wide
-// form is kept for the 0.5 us.
-__device__ __forceinline__ float gc_dpp_xor1(float v) { return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, true)); }   // quad_perm [1,0,3,2]
-__device__ __forceinline__ float gc_dpp_xor2(float v) { return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xF, 0xF, true)); }   // quad_perm [2,3,0,1]
-// in: lane q of the quad holds (v0..v3) = column q of rows 0..3; out: row q of columns 0..3
-__device__ __forceinline__ void gc_quad_transpose(float& v0, float& v1, float& v2, float& v3, int q) {
-    const bool o1 = q & 1, o2 = q & 2;
-    float r = gc_dpp_xor1(o1 ? v0 : v1);
-    if (o1) v0 = r; else v1 = r;
-    r = gc_dpp_xor1(o1 ? v2 : v3);
-    if (o1) v2 = r; else v3 = r;
-    r = gc_dpp_xor2(o2 ? v0 : v2);
-    if (o2) v0 = r; else v2 = r;
-    r = gc_dpp_xor2(o2 ? v1 : v3);
-    if (o2) v1 = r; else v3 = r;
-}
-// tile(row, col) -> base[row * ld + col] for the rows with row < nrow (base, ld: 16-byte aligned / a multiple of 4 floats);
-// f(v): applied to every element before the store (bias, ReLU ..)
-template <typename F>
-__device__ __forceinline__ void gc_store_tile(const gc_f32x16& acc, float* base, size_t ld, int nrow, int li, int lk, F f) {
-    const int q = li & 3, c4 = li & ~3;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        float v0 = f(acc[4 * g]), v1 = f(acc[4 * g + 1]), v2 = f(acc[4 * g + 2]), v3 = f(acc[4 * g + 3]);
-        gc_quad_transpose(v0, v1, v2, v3, q);
-        const int row = 8 * g + 4 * lk + q;
-        if (row < nrow) *reinterpret_cast<float4*>(base + (size_t)row * ld + c4) = make_float4(v0, v1, v2, v3);
-    }
-}
-__device__ __forceinline__ void gc_store_tile(const gc_f32x16& acc, float* base, size_t ld, int nrow, int li, int lk) {
-    gc_store_tile(acc, base, ld, nrow, li, lk, [](float v) { return v; });
-}
-
-// kred/32 blocks of 16 MFMA steps over k-major LDS operands A[k][row] (stride LDA) and B[k][col]
-// (stride LDB); TWO = this wave also owns row tile r0 + 2 (graphs with more than 64 nodes)
-template <bool TWO, int LDA, int LDB>
-__device__ __forceinline__ void gconv_mma(const float* As, const float* Bs, int kred, int r0, int ct, int li, int lk,
-                                          gc_f32x16& acc0, gc_f32x16& acc1) {
-    const float* a0p = As + r0 * 32 + li;
-    const float* a1p = As + (r0 + 2) * 32 + li;
-    const float* bp = Bs + ct * 32 + li;
-    float a0[2][16], a1[2][16], bv[2][16];
-    auto read_ops = [&](int kb, int s) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int k = kb * 32 + 2 * i + lk;
-            a0[s][i] = a0p[k * LDA];
-            if (TWO) a1[s][i] = a1p[k * LDA];
-            bv[s][i] = bp[k * LDB];
-        }
-    };
-    const int nkb = kred / 32;
-    read_ops(0, 0);
-    for (int kb = 0; kb < nkb; kb += 2) {
-        if (kb + 1 < nkb) read_ops(kb + 1, 1);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[0][i], bv[0][i], acc0, 0, 0, 0);
-            if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[0][i], bv[0][i], acc1, 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (kb + 1 < nkb) {
-            if (kb + 2 < nkb) read_ops(kb + 2, 0);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[1][i], bv[1][i], acc0, 0, 0, 0);
-                if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[1][i], bv[1][i], acc1, 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-}
-
-// z = x' W with the A operand ROW-MAJOR in k (x' rows as loaded: Xr[row * GC_LDX + k], stride 132 = 4 mod 32: conflict-free
-// 16 B reads) and B k-major (the W slice as loaded).  Lane (li, lk) takes the four consecutive k of every eight from its
-// row with one ds_read_b128 and the matching four B values with 4 B reads -- any bijection of k onto (MFMA step, lk) is a
-// valid reduction order when both operands share it.  Against the k-major x stage: no transposing scalar stores while
-// staging (8 float4 stores per lane instead of 32 scalar ones) and a third fewer LDS reads in the product.
-constexpr int GC_LDX = GC_K + 4;
-template <bool TWO, int LDB>
-__device__ __forceinline__ void gconv_mma_arow(const float* Xr, const float* Bs, int kred, int r0, int ct, int li, int lk,
-                                               gc_f32x16& acc0, gc_f32x16& acc1) {
-    const float* a0p = Xr + (r0 * 32 + li) * GC_LDX + 4 * lk;
-    const float* a1p = Xr + ((r0 + 2) * 32 + li) * GC_LDX + 4 * lk;
-    const float* bp = Bs + ct * 32 + li + 4 * lk * LDB;
-    float4 a0[2][4], a1[2][4];
-    float bv[2][16];
-    auto read_ops = [&](int kb, int s) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            a0[s][i] = *reinterpret_cast<const float4*>(a0p + kb * 32 + 8 * i);
-            if (TWO) a1[s][i] = *reinterpret_cast<const float4*>(a1p + kb * 32 + 8 * i);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bv[s][4 * i + j] = bp[(kb * 32 + 8 * i + j) * LDB];
-        }
-    };
-    auto mul = [&](int s) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float x[4] = {a0[s][i].x, a0[s][i].y, a0[s][i].z, a0[s][i].w};
-            const float y[4] = {TWO ? a1[s][i].x : 0.f, TWO ? a1[s][i].y : 0.f, TWO ? a1[s][i].z : 0.f, TWO ? a1[s][i].w : 0.f};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(x[j], bv[s][4 * i + j], acc0, 0, 0, 0);
-                if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(y[j], bv[s][4 * i + j], acc1, 0, 0, 0);
-            }
-        }
-    };
-    const int nkb = kred / 32;
-    read_ops(0, 0);
-    for (int kb = 0; kb < nkb; kb += 2) {
-        if (kb + 1 < nkb) read_ops(kb + 1, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        mul(0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (kb + 1 < nkb) {
-            if (kb + 2 < nkb) read_ops(kb + 2, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            mul(1);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-}
-
-// out = A z with BOTH operands row-major in the reduction index j (the adjacency block as At[i * LD + j], the z tile
-// transposed as Zt[col * LD + j], LD = 4 mod 32): 16 B reads, four MFMA steps per read (same k mapping as above)
-template <bool TWO, int LD>
-__device__ __forceinline__ void gconv_mma_rowk(const float* At, const float* Zt, int kred, int r0, int ct, int li, int lk,
-                                               gc_f32x16& acc0, gc_f32x16& acc1) {
-    const float* a0p = At + (r0 * 32 + li) * LD + 4 * lk;
-    const float* a1p = At + ((r0 + 2) * 32 + li) * LD + 4 * lk;
-    const float* bp = Zt + (ct * 32 + li) * LD + 4 * lk;
-    for (int k0 = 0; k0 < kred; k0 += 32) {
-        float4 a0[4], a1[4], bv[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            a0[i] = *reinterpret_cast<const float4*>(a0p + k0 + 8 * i);
-            if (TWO) a1[i] = *reinterpret_cast<const float4*>(a1p + k0 + 8 * i);
-            bv[i] = *reinterpret_cast<const float4*>(bp + k0 + 8 * i);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float x[4] = {a0[i].x, a0[i].y, a0[i].z, a0[i].w}, b[4] = {bv[i].x, bv[i].y, bv[i].z, bv[i].w};
-            const float y[4] = {TWO ? a1[i].x : 0.f, TWO ? a1[i].y : 0.f, TWO ? a1[i].z : 0.f, TWO ? a1[i].w : 0.f};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(x[j], b[j], acc0, 0, 0, 0);
-                if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(y[j], b[j], acc1, 0, 0, 0);
-            }
-        }
-    }
-}
+constexpr int GC_LDX = GC_K + 4;            // x' rows as loaded: Xr[row * GC_LDX + k], stride 132 = 4 mod 32 (conflict-free 16 B reads)
 
 template <bool RS, int T, int NT = 256, bool TILED = false>
 __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g, const int* __restrict__ gptr, const int* __restrict__ eptr,
@@ -411,9 +251,9 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
     if (r0 < R) {
         if (NT == 512) {                                 // this wave's half of the reduction range
             const int kofs = kh * (K >> 1);
-            gconv_mma_arow<false, GC_LDB>(As + kofs, Bs + kofs * GC_LDB, K >> 1, r0, ct, li, lk, acc0, acc1);
-        } else if (r0 + 2 < R) gconv_mma_arow<true, GC_LDB>(As, Bs, K, r0, ct, li, lk, acc0, acc1);
-        else gconv_mma_arow<false, GC_LDB>(As, Bs, K, r0, ct, li, lk, acc0, acc1);
+            mma_arow<false, GC_LDX, GC_LDB>(As + kofs, Bs + kofs * GC_LDB, K >> 1, r0, ct, li, lk, acc0, acc1);
+        } else if (r0 + 2 < R) mma_arow<true, GC_LDX, GC_LDB>(As, Bs, K, r0, ct, li, lk, acc0, acc1);
+        else mma_arow<false, GC_LDX, GC_LDB>(As, Bs, K, r0, ct, li, lk, acc0, acc1);
     }
     RO_CLK(36);
     __syncthreads();                                     // every wave is done reading both stages
@@ -432,7 +272,7 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
         if (NT == 256 && br.z) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = r0 * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                const int row = mma_row(r, lk, r0 * 32);
                 if (row < rows) br.z[(size_t)(g0 + row) * H + n0 + ct * 32 + li] = acc0[r];
             }
         }
@@ -445,7 +285,7 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
             if (br.z) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int row = (r0 + 2) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                    const int row = mma_row(r, lk, (r0 + 2) * 32);
                     if (row < rows) br.z[(size_t)(g0 + row) * H + n0 + ct * 32 + li] = acc1[r];
                 }
             }
@@ -468,7 +308,7 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
         if (br.z) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = r0 * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                const int row = mma_row(r, lk, r0 * 32);
                 if (row < rows) br.z[(size_t)(g0 + row) * H + n0 + ct * 32 + li] = acc0[r];
             }
         }
@@ -487,8 +327,8 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
 #pragma unroll
     for (int i = 0; i < 16; ++i) { acc0[i] = 0.f; acc1[i] = 0.f; }
     if (own && r0 < R) {
-        if (r0 + 2 < R) gconv_mma_rowk<true, LDT>(At, Zt, rowsP, r0, ct, li, lk, acc0, acc1);
-        else gconv_mma_rowk<false, LDT>(At, Zt, rowsP, r0, ct, li, lk, acc0, acc1);
+        if (r0 + 2 < R) mma_rowk_tile<true, LDT>(At, Zt, rowsP, r0, ct, li, lk, acc0, acc1);
+        else mma_rowk_tile<false, LDT>(At, Zt, rowsP, r0, ct, li, lk, acc0, acc1);
     }
     RO_CLK(38);
     // ---- epilogue: bias, ReLU, store, column sums of this graph ---------------------------------------------------
@@ -506,7 +346,7 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
     if (own && r0 < R) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = r0 * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+            const int row = mma_row(r, lk, r0 * 32);
             float v = acc0[r] + bias;
             if (relu) v = fmaxf(v, 0.f);
             acc0[r] = v;                                 // (stored below, four columns per lane)
@@ -517,7 +357,7 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
         if (r0 + 2 < R) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = (r0 + 2) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                const int row = mma_row(r, lk, (r0 + 2) * 32);
                 float v = acc1[r] + bias;
                 if (relu) v = fmaxf(v, 0.f);
                 acc1[r] = v;

@@ -70,97 +70,6 @@ struct GconvBwdBranch {
 
 struct GconvBwdBranch2 { GconvBwdBranch b[2]; };
 
-// acc[0] (+acc[1]) += A B over kred (multiple of 32) with k-major LDS operands A[k*LDA + row], B[k*LDB + col];
-// NA == 2: two row tiles (a0, a1) against b0; NB == 2: a0 against two column tiles (b0, b1).
-// ax(v, kstep) transforms an A element (identity or the BatchNorm affine of the lane's row).
-template <int NA, int NB, int LDA, int LDB, class AX>
-__device__ __forceinline__ void gb_mma(const float* a0, const float* a1, const float* b0, const float* b1, int kred, int lk,
-                                       AX ax, gc_f32x16 (&acc)[2]) {
-    static_assert(NA == 1 || NB == 1, "one of the operands is shared");
-    float av[2][2][16], bv[2][2][16];
-    auto read_ops = [&](int kb, int s) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int k = kb * 32 + 2 * i + lk;
-            av[s][0][i] = ax(a0[k * LDA]);
-            if (NA == 2) av[s][1][i] = ax(a1[k * LDA]);
-            bv[s][0][i] = b0[k * LDB];
-            if (NB == 2) bv[s][1][i] = b1[k * LDB];
-        }
-    };
-    auto mul = [&](int s) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s][0][i], bv[s][0][i], acc[0], 0, 0, 0);
-            if (NA == 2) acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s][1][i], bv[s][0][i], acc[1], 0, 0, 0);
-            if (NB == 2) acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s][0][i], bv[s][1][i], acc[1], 0, 0, 0);
-        }
-    };
-    const int nkb = kred / 32;
-    read_ops(0, 0);
-    for (int kb = 0; kb < nkb; kb += 2) {
-        if (kb + 1 < nkb) read_ops(kb + 1, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        mul(0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (kb + 1 < nkb) {
-            if (kb + 2 < nkb) read_ops(kb + 2, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            mul(1);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-}
-
-// One 32 x 32 tile from operands stored ROW-MAJOR IN k (A[row * LDA + k], B[col * LDB + k], strides = 4 mod 32 floats: 16 B
-// reads of 32 consecutive rows are bank-conflict free, 4 B reads would be 4-way conflicts): lane (li, lk) takes the four
-// consecutive k of every eight and feeds them to four MFMA steps -- any bijection of k onto (step, lk) is a valid reduction
-// order as long as A and B share it.  a_row / b_row point at this lane's row; kred % 32 == 0.
-__device__ __forceinline__ void gb_mma_rowk(const float* a_row, const float* b_row, int kred, int lk, gc_f32x16& acc) {
-    for (int k0 = 0; k0 < kred; k0 += 32) {
-        float4 av[4], bv[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int k = k0 + 8 * i + 4 * lk;
-            av[i] = *reinterpret_cast<const float4*>(a_row + k);
-            bv[i] = *reinterpret_cast<const float4*>(b_row + k);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i].x, bv[i].x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i].y, bv[i].y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i].z, bv[i].z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i].w, bv[i].w, acc, 0, 0, 0);
-        }
-    }
-}
-
-// the same with two row tiles of A against one tile of B (acc0: rows of a0_row, acc1: rows of a1_row); TWO = false: only acc0
-template <bool TWO>
-__device__ __forceinline__ void gb_mma_rowk2(const float* a0_row, const float* a1_row, const float* b_row, int kred, int lk,
-                                             gc_f32x16& acc0, gc_f32x16& acc1) {
-    for (int k0 = 0; k0 < kred; k0 += 32) {
-        float4 av[4], aw[4], bv[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int k = k0 + 8 * i + 4 * lk;
-            av[i] = *reinterpret_cast<const float4*>(a0_row + k);
-            if (TWO) aw[i] = *reinterpret_cast<const float4*>(a1_row + k);
-            bv[i] = *reinterpret_cast<const float4*>(b_row + k);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float a[4] = {av[i].x, av[i].y, av[i].z, av[i].w}, b[4] = {bv[i].x, bv[i].y, bv[i].z, bv[i].w};
-            const float a2[4] = {TWO ? aw[i].x : 0.f, TWO ? aw[i].y : 0.f, TWO ? aw[i].z : 0.f, TWO ? aw[i].w : 0.f};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j], b[j], acc0, 0, 0, 0);
-                if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a2[j], b[j], acc1, 0, 0, 0);
-            }
-        }
-    }
-}
-
 // LEAN (MODE 0 / 1, the single-branch launches; round 5): under 80 KB of LDS and 128 registers, so TWO workgroups share a CU
 // and a launch of more workgroups than CUs (a packed batch: 240 tiles x 2 slices at NCI1-like batches of 512 graphs) stops
 // running as two rounds of latency chains -- the W slice is not staged (waves 0-3 read their rows of it straight from L2 as
@@ -441,7 +350,7 @@ __global__ void __launch_bounds__(GB_NT, (LEAN ? 4 : 1)) k_gconv_bwd(const CSR g
         const int rt = w >> 1, ct = w & 1;              // waves 0-3: one tile each; waves 4-7 wait at the barriers
 #pragma unroll
         for (int i = 0; i < 16; ++i) { acc[0][i] = 0.f; acc[1][i] = 0.f; }
-        if (rt < R) gb_mma<1, 1, GB_LDJ, GB_LDD>(Ab + rt * 32 + li, nullptr, Ds + ct * 32 + li, nullptr, rowsP, lk, ident, acc);
+        if (rt < R) mma_kmajor<1, 1, GB_LDJ, GB_LDD>(Ab + rt * 32 + li, Ds + ct * 32 + li, rowsP, lk, ident, MmaIdent(), acc);
         if (POOL && w >= 4) {
             // waves 4-7 (idle during P1): gn / gself of this slice, 4 lanes per item (16 columns each) straight from LDS
             const int q4 = (t - 256) & 3, it0 = (t - 256) >> 2;
@@ -468,7 +377,7 @@ __global__ void __launch_bounds__(GB_NT, (LEAN ? 4 : 1)) k_gconv_bwd(const CSR g
         if (rt < R) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                const int row = mma_row(r, lk, rt * 32);
                 Ds[row * GB_LDD + ct * 32 + li] = acc[0][r];           // dz row-major over the dOut stage
             }
         }
@@ -482,8 +391,8 @@ __global__ void __launch_bounds__(GB_NT, (LEAN ? 4 : 1)) k_gconv_bwd(const CSR g
         // four MFMA steps per read; W is staged as loaded (no transposing scatter) and dz needs no transposed copy
         // (LEAN: the lane's W row -- 64 consecutive floats of row w * 32 + li -- comes straight from global memory / L2)
         const float* wrow = LEAN ? br.W + (size_t)min(w * 32 + li, K - 1) * H + ns0 : Ws + (w * 32 + li) * GB_LDD;
-        if (R == 2) gb_mma_rowk2<true>(Ds + li * GB_LDD, Ds + (32 + li) * GB_LDD, wrow, GC_N, lk, acc[0], acc[1]);
-        else gb_mma_rowk2<false>(Ds + li * GB_LDD, nullptr, wrow, GC_N, lk, acc[0], acc[1]);
+        if (R == 2) mma_rowk<true>(Ds + li * GB_LDD, Ds + (32 + li) * GB_LDD, wrow, GC_N, lk, acc[0], acc[1]);
+        else mma_rowk<false>(Ds + li * GB_LDD, nullptr, wrow, GC_N, lk, acc[0], acc[1]);
         const int k = w * 32 + li;
         float* dxp = sl ? br.dxp1 : br.dxp0;
         // x_hat of all rows first, as ONE batch of unconditional LDS reads (rows rows .. rowsP are zero, as are their dz;
@@ -494,7 +403,7 @@ __global__ void __launch_bounds__(GB_NT, (LEAN ? 4 : 1)) k_gconv_bwd(const CSR g
 #pragma unroll
         for (int q = 0; q < 2; ++q)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) xh[q][r] = Xs[(q * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk) * LDX + k];
+            for (int r = 0; r < 16; ++r) xh[q][r] = Xs[(mma_row(r, lk, q * 32)) * LDX + k];
 #pragma unroll
         for (int q = 0; q < 2; ++q)
 #pragma unroll
@@ -506,7 +415,7 @@ __global__ void __launch_bounds__(GB_NT, (LEAN ? 4 : 1)) k_gconv_bwd(const CSR g
         for (int q = 0; q < 2; ++q) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int i = q * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                const int i = mma_row(r, lk, q * 32);
                 const float v = acc[q][r];                   // (row tile 1 of a one-tile graph: zero accumulators)
                 f1[r & 3] += v;
                 f2[r & 3] = fmaf(v, xh[q][r], f2[r & 3]);
@@ -534,7 +443,7 @@ __global__ void __launch_bounds__(GB_NT, (LEAN ? 4 : 1)) k_gconv_bwd(const CSR g
         auto affine = [&](float v) { return fmaf(v, gam, bet); };
 #pragma unroll
         for (int i = 0; i < 16; ++i) { acc[0][i] = 0.f; acc[1][i] = 0.f; }
-        gb_mma<1, 2, LDX, GB_LDD>(Xs + wq * 32 + li, nullptr, Ds + li, Ds + 32 + li, rowsP, lk, affine, acc);
+        mma_kmajor<1, 2, LDX, GB_LDD>(Xs + wq * 32 + li, Ds + li, rowsP, lk, affine, MmaIdent(), acc);
 #pragma unroll
         for (int q = 0; q < 2; ++q) gc_store_tile(acc[q], slab + (size_t)(wq * 32) * H + ns0 + q * 32, H, 32, li, lk);
     }
@@ -778,7 +687,7 @@ __global__ void __launch_bounds__(GB_NT) k_feat_bwd_mma(const int* __restrict__ 
     float wv[16];
     auto load_w = [&](int ft) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) wv[r] = a.W[(size_t)min(ft * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk, F - 1) * H + ct * 32 + li];
+        for (int r = 0; r < 16; ++r) wv[r] = a.W[(size_t)min(mma_row(r, lk, ft * 32), F - 1) * H + ct * 32 + li];
     };
     load_w(w / nct);
     const int uc = min(t, H - 1), fc = min(max(t - 128, 0), F - 1);
@@ -875,7 +784,7 @@ __global__ void __launch_bounds__(GB_NT) k_feat_bwd_mma(const int* __restrict__ 
         gc_f32x16 acc[2];
 #pragma unroll
         for (int i = 0; i < 16; ++i) { acc[0][i] = 0.f; acc[1][i] = 0.f; }
-        gb_mma<1, 1, LDXN, LDZ>(Xn + ft * 32 + li, nullptr, Dz + ct * 32 + li, nullptr, rowsP, lk, ident, acc);
+        mma_kmajor<1, 1, LDXN, LDZ>(Xn + ft * 32 + li, Dz + ct * 32 + li, rowsP, lk, ident, MmaIdent(), acc);
         const int h = ct * 32 + li;
         const float csh = cs_s[h];
         float wc[16];
@@ -884,7 +793,7 @@ __global__ void __launch_bounds__(GB_NT) k_feat_bwd_mma(const int* __restrict__ 
         float p1[16], p2[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int f = ft * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+            const int f = mma_row(r, lk, ft * 32);
             const float pv = acc[0][r];
             acc[1][r] = fmaf(g0_s[min(f, FP - 1)], pv, b0_s[min(f, FP - 1)] * csh);         // this unit's dW_feat entry
             p1[r] = f < F ? wc[r] * csh : 0.f;
@@ -894,7 +803,7 @@ __global__ void __launch_bounds__(GB_NT) k_feat_bwd_mma(const int* __restrict__ 
         // its row (160 ds_bpermute shuffles per tile, each behind its own lgkmcnt wait, were ~4 us per tile)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int fl = (r & 3) + 8 * (r >> 2) + 4 * lk;
+            const int fl = mma_row(r, lk);
             red_s[w][0][fl][li] = p1[r];
             red_s[w][1][fl][li] = p2[r];
         }
@@ -914,7 +823,7 @@ __global__ void __launch_bounds__(GB_NT) k_feat_bwd_mma(const int* __restrict__ 
         // 4 us per tile), and the next tile's W rows are requested behind them, under the next product
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int f = ft * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+            const int f = mma_row(r, lk, ft * 32);
             if (f < F) slab[(size_t)f * H + h] = acc[1][r];
         }
         if (ft + fstep < nft) {

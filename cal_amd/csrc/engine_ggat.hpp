@@ -169,7 +169,7 @@ __global__ void __launch_bounds__(256) k_ggat_fwd(const CSR g, const int* __rest
     gc_f32x16 acc0, acc1;
 #pragma unroll
     for (int i = 0; i < 16; ++i) { acc0[i] = 0.f; acc1[i] = 0.f; }
-    if (r0 < R) gconv_mma_arow<false, GC_LDB>(As, Bs, K, r0, ct, li, lk, acc0, acc1);
+    if (r0 < R) mma_arow<false, GC_LDX, GC_LDB>(As, Bs, K, r0, ct, li, lk, acc0, acc1);
     __syncthreads();                                     // every wave is done reading both stages
     float* Zt = Bs;                                      // Zt[col * LDT + j] = z[j][col]: the z tile transposed (as k_gconv_fwd)
     float* At = As;                                      // At[(h * T + i) * LDT + j] = alpha of edge j -> i, head h0 + h
@@ -181,7 +181,7 @@ __global__ void __launch_bounds__(256) k_ggat_fwd(const CSR g, const int* __rest
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = r0 * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+            const int row = mma_row(r, lk, r0 * 32);
             if (row < rows) a.z[(size_t)(g0 + row) * H + n0 + ct * 32 + li] = acc0[r];
         }
     }
@@ -268,7 +268,7 @@ __global__ void __launch_bounds__(256) k_ggat_fwd(const CSR g, const int* __rest
     // ---- out tile = alpha_h z on the matrix cores: the 32-column tile ct lies in head (ct * 32) / D of the slice ----
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc0[i] = 0.f;
-    if (r0 < R) gconv_mma_rowk<false, LDT>(At + (size_t)((ct * 32) / D) * T * LDT, Zt, rowsP, r0, ct, li, lk, acc0, acc1);
+    if (r0 < R) mma_rowk_tile<false, LDT>(At + (size_t)((ct * 32) / D) * T * LDT, Zt, rowsP, r0, ct, li, lk, acc0, acc1);
     // ---- epilogue: bias, ReLU, store, column sums of this graph ---------------------------------------------------
     // (a lane's 16 terms of the column sums in fp32, masked and unguarded, as in k_gconv_fwd; the denominators in one batch)
     float f1[4] = {0.f, 0.f, 0.f, 0.f}, f2[4] = {0.f, 0.f, 0.f, 0.f};
@@ -277,10 +277,10 @@ __global__ void __launch_bounds__(256) k_ggat_fwd(const CSR g, const int* __rest
     if (r0 < R) {
         float idn[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) idn[r] = idn_s[(ct * 32) / D][min(r0 * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk, T - 1)];
+        for (int r = 0; r < 16; ++r) idn[r] = idn_s[(ct * 32) / D][min(mma_row(r, lk, r0 * 32), T - 1)];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = r0 * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+            const int row = mma_row(r, lk, r0 * 32);
             // softmax denominator of (row, head of this column tile), then bias; the backbone always applies ReLU (model.py:390)
             const float v = fmaxf(fmaf(acc0[r], idn[r], bias), 0.f);
             if (row < rows) a.out[(size_t)(g0 + row) * H + col] = v;
@@ -536,10 +536,10 @@ __global__ void __launch_bounds__(GB_NT) k_ggat_bwd(const CSR g, const int* __re
             float* Zh = ha ? Zt1 : Zt;
 #pragma unroll
             for (int i = 0; i < 16; ++i) { acc[0][i] = 0.f; acc[1][i] = 0.f; }
-            gb_mma_rowk(Ds + (rta * 32 + li) * GB_LDD + ha * D, Zr + (cta * 32 + li) * GB_LDD + ha * D, D, lk, acc[0]);      // (16 B reads: the 4 B form was a 4-way bank conflict)
+            mma_rowk(Ds + (rta * 32 + li) * GB_LDD + ha * D, Zr + (cta * 32 + li) * GB_LDD + ha * D, D, lk, acc[0]);      // (16 B reads: the 4 B form was a 4-way bank conflict)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int i = rta * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                const int i = mma_row(r, lk, rta * 32);
                 Zh[i * GB_LDJ + cta * 32 + li] = acc[0][r];
             }
         }
@@ -611,7 +611,7 @@ __global__ void __launch_bounds__(GB_NT) k_ggat_bwd(const CSR g, const int* __re
     if (w < 4) {
         if (rt < R) {
             const float* Bh = (ct * 32) / D ? Bk1 : Bk;
-            gb_mma<1, 1, GB_LDJ, GB_LDD>(Bh + rt * 32 + li, nullptr, Ds + ct * 32 + li, nullptr, rowsP, lk, ident, dzacc);
+            mma_kmajor<1, 1, GB_LDJ, GB_LDD>(Bh + rt * 32 + li, Ds + ct * 32 + li, rowsP, lk, ident, MmaIdent(), dzacc);
         }
     } else {
         const int q = t - 256;
@@ -659,7 +659,7 @@ __global__ void __launch_bounds__(GB_NT) k_ggat_bwd(const CSR g, const int* __re
         const float a_dst = att_s[hh * 2 * D + d], a_src = att_s[hh * 2 * D + D + d];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int j = rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+            const int j = mma_row(r, lk, rt * 32);
             const float v = dzacc[0][r] + dad_s[hh][j] * a_dst + das_s[hh][j] * a_src;
             Ds[j * GB_LDD + n] = v;
         }
@@ -684,8 +684,8 @@ __global__ void __launch_bounds__(GB_NT) k_ggat_bwd(const CSR g, const int* __re
     if (w < 4 && w * 32 < K) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) { acc[0][i] = 0.f; acc[1][i] = 0.f; }
-        if (R == 2) gb_mma_rowk2<true>(Ds + li * GB_LDD, Ds + (32 + li) * GB_LDD, Ws + (w * 32 + li) * GB_LDD, GC_N, lk, acc[0], acc[1]);
-        else gb_mma_rowk2<false>(Ds + li * GB_LDD, nullptr, Ws + (w * 32 + li) * GB_LDD, GC_N, lk, acc[0], acc[1]);
+        if (R == 2) mma_rowk<true>(Ds + li * GB_LDD, Ds + (32 + li) * GB_LDD, Ws + (w * 32 + li) * GB_LDD, GC_N, lk, acc[0], acc[1]);
+        else mma_rowk<false>(Ds + li * GB_LDD, nullptr, Ws + (w * 32 + li) * GB_LDD, GC_N, lk, acc[0], acc[1]);
         const int k = w * 32 + li;
         float* dxp = sl ? a.dxp1 : a.dxp0;
         // x_hat of all rows as ONE batch of unconditional LDS reads, masked afterwards, and a lane's 32 terms summed in
@@ -694,7 +694,7 @@ __global__ void __launch_bounds__(GB_NT) k_ggat_bwd(const CSR g, const int* __re
 #pragma unroll
         for (int q = 0; q < 2; ++q)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) xh[q][r] = Xs[(q * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk) * GB_LDX + k];
+            for (int r = 0; r < 16; ++r) xh[q][r] = Xs[(mma_row(r, lk, q * 32)) * GB_LDX + k];
 #pragma unroll
         for (int q = 0; q < 2; ++q)
 #pragma unroll
@@ -704,7 +704,7 @@ __global__ void __launch_bounds__(GB_NT) k_ggat_bwd(const CSR g, const int* __re
         for (int q = 0; q < 2; ++q) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int i = q * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                const int i = mma_row(r, lk, q * 32);
                 const float v = acc[q][r];                   // (row tile 1 of a one-tile graph: zero accumulators)
                 if (i < rows) dxp[(size_t)(g0 + i) * K + k] = v;
                 f1[r & 3] += v;
@@ -729,12 +729,12 @@ __global__ void __launch_bounds__(GB_NT) k_ggat_bwd(const CSR g, const int* __re
         auto affine = [&](float v) { return fmaf(v, gam, bet); };
 #pragma unroll
         for (int i = 0; i < 16; ++i) { acc[0][i] = 0.f; acc[1][i] = 0.f; }
-        gb_mma<1, 2, GB_LDX, GB_LDD>(Xs + wq * 32 + li, nullptr, Ds + li, Ds + 32 + li, rowsP, lk, affine, acc);
+        mma_kmajor<1, 2, GB_LDX, GB_LDD>(Xs + wq * 32 + li, Ds + li, rowsP, lk, affine, MmaIdent(), acc);
 #pragma unroll
         for (int q = 0; q < 2; ++q)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int kk = wq * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                const int kk = mma_row(r, lk, wq * 32);
                 slab[(size_t)kk * H + ns0 + q * 32 + li] = acc[q][r];
             }
     }

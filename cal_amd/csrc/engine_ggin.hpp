@@ -153,7 +153,7 @@ __global__ void __launch_bounds__(512, 2) k_ggin_fwd(const CSR g, const int* __r
     for (int i = 0; i < 16; ++i) { acc0[i] = 0.f; acc1[i] = 0.f; }
     if (r0 < R) {
         const int kofs = kh * (K >> 1);
-        gconv_mma_arow<false, GC_LDB>(As + kofs, Bs + kofs * GC_LDB, K >> 1, r0, ct, li, lk, acc0, acc1);
+        mma_arow<false, GC_LDX, GC_LDB>(As + kofs, Bs + kofs * GC_LDB, K >> 1, r0, ct, li, lk, acc0, acc1);
     }
     __syncthreads();                                     // every wave is done reading both stages
     float* Zt = Bs;                                      // Zt[col * LDT + j]
@@ -187,7 +187,7 @@ __global__ void __launch_bounds__(512, 2) k_ggin_fwd(const CSR g, const int* __r
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < 16; ++i) { acc0[i] = 0.f; acc1[i] = 0.f; }
-        if (own && r0 < R) gconv_mma_rowk<false, LDT>(At, Zt, rowsP, r0, ct, li, lk, acc0, acc1);
+        if (own && r0 < R) mma_rowk_tile<false, LDT>(At, Zt, rowsP, r0, ct, li, lk, acc0, acc1);
     }
     // ---- epilogue: bias (PART 2: ReLU), store, PART 1: column sums of this unit -----------------------------------------
     float f1[4] = {0.f, 0.f, 0.f, 0.f}, f2[4] = {0.f, 0.f, 0.f, 0.f};
@@ -196,7 +196,7 @@ __global__ void __launch_bounds__(512, 2) k_ggin_fwd(const CSR g, const int* __r
     if (own && r0 < R) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = r0 * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+            const int row = mma_row(r, lk, r0 * 32);
             float v = acc0[r] + bias;
             if (PART == 2) v = fmaxf(v, 0.f);
             if (row < rows) a.out[(size_t)(g0 + row) * H + col] = v;
@@ -243,43 +243,6 @@ struct GginBwdArgs {
     const float* t1;         // PART 1: [N,H] pre-BatchNorm activations
     const double* dot_sum; const double* dot_prod;   // PART 1: finalised s1, s2 [H]
 };
-
-// acc[q] (q = 0, 1: row tiles a0, a1) += A B over kred with k-major LDS operands A[k * LDA + row], B[k * LDB + col];
-// bx transforms the B element of column `col` (the lane's)
-template <int LDA, int LDB, class BX>
-__device__ __forceinline__ void ggin_mma_bx(const float* a0, const float* a1, const float* b0, int kred, int lk, BX bx, gc_f32x16 (&acc)[2]) {
-    float av[2][2][16], bv[2][16];
-    auto read_ops = [&](int kb, int s) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int k = kb * 32 + 2 * i + lk;
-            av[s][0][i] = a0[k * LDA];
-            av[s][1][i] = a1[k * LDA];
-            bv[s][i] = bx(b0[k * LDB]);
-        }
-    };
-    auto mul = [&](int s) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s][0][i], bv[s][i], acc[0], 0, 0, 0);
-            acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s][1][i], bv[s][i], acc[1], 0, 0, 0);
-        }
-    };
-    const int nkb = kred / 32;
-    read_ops(0, 0);
-    for (int kb = 0; kb < nkb; kb += 2) {
-        if (kb + 1 < nkb) read_ops(kb + 1, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        mul(0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (kb + 1 < nkb) {
-            if (kb + 2 < nkb) read_ops(kb + 2, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            mul(1);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-}
 
 template <int PART>
 __global__ void __launch_bounds__(GB_NT) k_ggin_bwd(const CSR g, const int* __restrict__ gptr, const int* __restrict__ eptr,
@@ -452,11 +415,11 @@ __global__ void __launch_bounds__(GB_NT) k_ggin_bwd(const CSR g, const int* __re
         const int rt = w >> 1, ct = w & 1;
 #pragma unroll
         for (int i = 0; i < 16; ++i) { acc[0][i] = 0.f; acc[1][i] = 0.f; }
-        if (w < 4 && rt < R) gb_mma<1, 1, GB_LDJ, GB_LDD>(Ab + rt * 32 + li, nullptr, Ds + ct * 32 + li, nullptr, rowsP, lk, ident, acc);
+        if (w < 4 && rt < R) mma_kmajor<1, 1, GB_LDJ, GB_LDD>(Ab + rt * 32 + li, Ds + ct * 32 + li, rowsP, lk, ident, MmaIdent(), acc);
         __syncthreads();                                 // every wave is done reading dOut
         if (w < 4 && rt < R) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) Ds[(rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk) * GB_LDD + ct * 32 + li] = acc[0][r];
+            for (int r = 0; r < 16; ++r) Ds[(mma_row(r, lk, rt * 32)) * GB_LDD + ct * 32 + li] = acc[0][r];
         }
         __syncthreads();
     }
@@ -464,8 +427,8 @@ __global__ void __launch_bounds__(GB_NT) k_ggin_bwd(const CSR g, const int* __re
     if (w < 4 && w * 32 < K) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) { acc[0][i] = 0.f; acc[1][i] = 0.f; }
-        if (R == 2) gb_mma_rowk2<true>(Ds + li * GB_LDD, Ds + (32 + li) * GB_LDD, Ws + (w * 32 + li) * GB_LDD, GC_N, lk, acc[0], acc[1]);
-        else gb_mma_rowk2<false>(Ds + li * GB_LDD, nullptr, Ws + (w * 32 + li) * GB_LDD, GC_N, lk, acc[0], acc[1]);
+        if (R == 2) mma_rowk<true>(Ds + li * GB_LDD, Ds + (32 + li) * GB_LDD, Ws + (w * 32 + li) * GB_LDD, GC_N, lk, acc[0], acc[1]);
+        else mma_rowk<false>(Ds + li * GB_LDD, nullptr, Ws + (w * 32 + li) * GB_LDD, GC_N, lk, acc[0], acc[1]);
         const int k = w * 32 + li;
         float* dxp = sl ? a.dxp1 : a.dxp0;
         if (PART == 2) {
@@ -473,7 +436,7 @@ __global__ void __launch_bounds__(GB_NT) k_ggin_bwd(const CSR g, const int* __re
 #pragma unroll
             for (int q = 0; q < 2; ++q)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) xh[q][r] = Xs[(q * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk) * GB_LDX + k];
+                for (int r = 0; r < 16; ++r) xh[q][r] = Xs[(mma_row(r, lk, q * 32)) * GB_LDX + k];
 #pragma unroll
             for (int q = 0; q < 2; ++q)
 #pragma unroll
@@ -484,7 +447,7 @@ __global__ void __launch_bounds__(GB_NT) k_ggin_bwd(const CSR g, const int* __re
             for (int q = 0; q < 2; ++q) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int i = q * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                    const int i = mma_row(r, lk, q * 32);
                     const float v = fmaf(xh[q][r], gam, bet) > 0.f ? acc[q][r] : 0.f;        // behind the ReLU of y = relu(BN(t1))
                     if (i < rows) dxp[(size_t)(g0 + i) * K + k] = v;
                     f1[r & 3] += v;
@@ -506,7 +469,7 @@ __global__ void __launch_bounds__(GB_NT) k_ggin_bwd(const CSR g, const int* __re
             for (int q = 0; q < 2; ++q) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int i = q * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                    const int i = mma_row(r, lk, q * 32);
                     if (i < rows) dxp[(size_t)(g0 + i) * K + k] = acc[q][r];
                 }
             }
@@ -519,12 +482,12 @@ __global__ void __launch_bounds__(GB_NT) k_ggin_bwd(const CSR g, const int* __re
         auto bxf = [&](float v) { return PART == 2 ? fmaxf(fmaf(v, gam, bet), 0.f) : v; };
 #pragma unroll
         for (int i = 0; i < 16; ++i) { acc[0][i] = 0.f; acc[1][i] = 0.f; }
-        ggin_mma_bx<GB_LDD, GB_LDX>(Ds + li, Ds + 32 + li, Xs + wq * 32 + li, rowsP, lk, bxf, acc);
+        mma_kmajor<2, 1, GB_LDD, GB_LDX>(Ds + li, Xs + wq * 32 + li, rowsP, lk, MmaIdent(), bxf, acc);
 #pragma unroll
         for (int q = 0; q < 2; ++q)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int n = q * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                const int n = mma_row(r, lk, q * 32);
                 slab[(size_t)(ns0 + n) * K + k] = acc[q][r];
             }
     }

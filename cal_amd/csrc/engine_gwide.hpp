@@ -165,7 +165,7 @@ __global__ void __launch_bounds__(GW_NT, 2) k_gw_fwd(const CSR g, const int* __r
     const int nk8 = K >> 3;
     // ---- every global load of the kernel, issued before the first wait -------------------------------------------------
     // node operand: wave w owns rows w * 32 .. + 31; lane (li, lk) takes the four consecutive k of every eight of ITS row
-    // (any bijection of k onto (MFMA step, lk) is a valid reduction order when both operands share it: gconv_mma_arow)
+    // (any bijection of k onto (MFMA step, lk) is a valid reduction order when both operands share it: mma_step4, engine_mma.hpp)
     const int arow = min(w * 32 + li, rows - 1);
     float4 xa[GW_K / 8];
     {
@@ -286,7 +286,7 @@ __global__ void __launch_bounds__(GW_NT, 2) k_gw_fwd(const CSR g, const int* __r
         for (int c = 0; c < CT; ++c) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = w * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                const int row = mma_row(r, lk, w * 32);
                 Zs[row * LDZ + c * 32 + li] = acc[c][r];
             }
             if (br.z) gc_store_tile(acc[c], br.z + (size_t)(g0 + w * 32) * H + n0 + c * 32, H, rows - w * 32, li, lk);
@@ -704,7 +704,7 @@ __global__ void __launch_bounds__(GW_NT, 2) k_gw_bwd(const CSR g, const int* __r
             for (int i = 0; i < 8; ++i) av[i] = *reinterpret_cast<const float4*>(ap + 8 * i);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int i = rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                const int i = mma_row(r, lk, rt * 32);
                 xh[r] = xk[(size_t)min(i, rows - 1) * K];
                 if (RS) rr[r] = rs_s[i];
             }
@@ -714,12 +714,7 @@ __global__ void __launch_bounds__(GW_NT, 2) k_gw_bwd(const CSR g, const int* __r
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[i] = 0.f;
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i].x, wb[i].x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i].y, wb[i].y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i].z, wb[i].z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i].w, wb[i].w, acc, 0, 0, 0);
-            }
+            for (int i = 0; i < 8; ++i) mma_step4(av[i], wb[i], acc);
             // (rows past the graph: their dz rows are zero, so is the product -- no mask; their x_hat is a clamped, finite read)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
