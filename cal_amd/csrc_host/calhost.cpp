@@ -589,3 +589,84 @@ HOST_EXPORT int cal_explain_rank(const float* score, int64_t stride, const int64
     }
     return 0;
 }
+
+// ---- subgraph extraction: keep masks -> the compacted (and optionally relabelled) batch, order preserved.  The same rules
+// as cal_amd/csrc/subgraph.hip (an edge that leaves its graph's node range is dropped); every integer output agrees bit for bit.
+HOST_EXPORT int64_t cal_subgraph_ws(int64_t N, int64_t E, int64_t B) {
+    N = N > 0 ? N : 0;
+    E = E > 0 ? E : 0;
+    B = B > 0 ? B : 0;
+    return 16 * B + 8 * N + N + E + 256;
+}
+
+HOST_EXPORT int cal_subgraph_extract(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                                     int64_t B, const uint8_t* edge_keep, const uint8_t* node_keep, int complement, int relabel,
+                                     const float* x, int64_t F, int64_t* edge_index_out, int64_t* ptr_out, int64_t* edge_ptr_out,
+                                     int64_t* batch_out, float* x_out, int64_t* node_map, int64_t* edge_map, int64_t* totals,
+                                     void*, int64_t, void*) {
+    HOST_REQUIRE(E >= 0 && N >= 0 && B >= 0 && F >= 0, "E, N, B, F must be >= 0");
+    HOST_REQUIRE(totals && ptr_out && edge_ptr_out, "totals / ptr_out / edge_ptr_out are null");
+    HOST_REQUIRE(B == 0 || (ptr && edge_ptr), "ptr / edge_ptr are null");
+    HOST_REQUIRE(E == 0 || (edge_index && edge_index_out && edge_map), "edge_index / edge_index_out / edge_map are null");
+    HOST_REQUIRE(!relabel || N == 0 || (node_map && batch_out), "relabel needs node_map and batch_out");
+    HOST_REQUIRE(!x_out || (x && relabel && F > 0), "x_out needs x, F > 0 and relabel");
+    const bool comp = complement != 0, from_edges = relabel && !node_keep;
+    std::vector<uint8_t> nflag(N, 0), eflag(E, 0);
+    std::vector<int64_t> newid(N, 0), src, dst;
+    src.reserve(E);
+    dst.reserve(E);
+    int64_t nt = 0, et = 0, mn = 0, me = 0;
+    for (int64_t g = 0; g < B; ++g) {
+        const int64_t nlo = std::min(std::max(ptr[g], (int64_t)0), N), nhi = std::min(std::max(ptr[g + 1], nlo), N);
+        const int64_t elo = std::min(std::max(edge_ptr[g], (int64_t)0), E), ehi = std::min(std::max(edge_ptr[g + 1], elo), E);
+        if (node_keep)
+            for (int64_t i = nlo; i < nhi; ++i) nflag[i] = (node_keep[i] != 0) != comp;
+        else if (from_edges)
+            for (int64_t i = nlo; i < nhi; ++i) nflag[i] = 0;
+        for (int64_t e = elo; e < ehi; ++e) {
+            const int64_t s = edge_index[e], d = edge_index[E + e];
+            bool k = s >= nlo && s < nhi && d >= nlo && d < nhi;
+            if (k && edge_keep) k = (edge_keep[e] != 0) != comp;
+            if (k && node_keep) k = nflag[s] && nflag[d];
+            eflag[e] = k;
+            if (k && from_edges) nflag[s] = nflag[d] = 1;
+        }
+        ptr_out[g] = std::min(nt, N);
+        edge_ptr_out[g] = std::min(et, E);
+        int64_t nc = 0, ec = 0;
+        for (int64_t i = nlo; i < nhi; ++i) {
+            if (relabel && !nflag[i]) continue;
+            const int64_t p = relabel ? nt + nc : i;
+            ++nc;
+            newid[i] = p;
+            if (p >= N) continue;
+            if (node_map) node_map[p] = i;
+            if (batch_out) batch_out[p] = g;
+            if (relabel && x_out)
+                for (int64_t c = 0; c < F; ++c) x_out[p * F + c] = x[i * F + c];
+        }
+        for (int64_t e = elo; e < ehi; ++e) {
+            if (!eflag[e]) continue;
+            const int64_t p = et + ec;
+            ++ec;
+            if (p >= E) continue;
+            const int64_t s = edge_index[e], d = edge_index[E + e];
+            src.push_back(relabel ? newid[s] : s);
+            dst.push_back(relabel ? newid[d] : d);
+            edge_map[p] = e;
+        }
+        nt += nc;
+        et += ec;
+        mn = std::max(mn, nc);
+        me = std::max(me, ec);
+    }
+    const int64_t Nt = std::min(nt, N), Et = std::min(et, E);
+    for (int64_t p = 0; p < Et; ++p) {                         // row 1 starts at E': a contiguous [2, E']
+        edge_index_out[p] = src[p];
+        edge_index_out[Et + p] = dst[p];
+    }
+    ptr_out[B] = Nt;
+    edge_ptr_out[B] = Et;
+    totals[0] = Nt; totals[1] = Et; totals[2] = mn; totals[3] = me;
+    return 0;
+}

@@ -10,6 +10,12 @@ column 1**: ``edge_att[:, 1]`` (``edge_weight_o``) per edge and ``node_att[:, 1]
   (``cal_explain_rank``: HIP on the GPU, libcalhost for CPU-resident models).
 * ``eval_explanation(model, loader, device)``: mean precision@k, recall@k and ROC-AUC of the causal edges / nodes
   against the SPMotif motif (``spmotif.ground_truth``), the explanation counterpart of ``eval_acc_causal``.
+* ``extract_subgraph(data, edge_mask=..., node_mask=..., complement=..., relabel=...)`` -> ``Batch``: the masked batch,
+  compacted in order on the device (``cal_subgraph_extract``: two launches and one read-back of the four totals), with the
+  layout facts the engine's per-graph kernels need; ``Explanation.to_batch`` is the same through an explanation's masks.
+* ``fidelity(model, data, ratio=... | k=...)`` / ``eval_fidelity(model, loader, device, ratios=...)``: does the prediction
+  rest on the explanation?  The model runs on the whole graph, on the explanation alone and on the graph without it;
+  accuracies, fidelity+ / fidelity- and sparsity per readout head.  Needs no ground truth.
 """
 from __future__ import annotations
 
@@ -21,7 +27,7 @@ import torch
 from . import _lib
 from .plan import _p, _stream
 
-__all__ = ["Explanation", "explain", "eval_explanation", "rank_segments"]
+__all__ = ["Explanation", "explain", "eval_explanation", "rank_segments", "extract_subgraph", "fidelity", "eval_fidelity"]
 
 
 def _k_code(ratio, k) -> Tuple[int, float]:
@@ -106,6 +112,13 @@ class Explanation:
             cols = (self.edge_mask & (src >= lo) & (src < hi)).nonzero().view(-1)
         return nodes, self.edge_index[:, cols]
 
+    def to_batch(self, data, *, complement: bool = False, relabel: bool = False, use: str = "edges"):
+        """``extract_subgraph(data, ...)`` through this explanation's masks: ``use`` = ``"edges"`` (``edge_mask``), ``"nodes"``
+        (``node_mask``) or ``"both"``; ``complement``: the batch with the explanation removed.  ``data`` is the batch that
+        was explained."""
+        em, nm = _use_masks(use, self.edge_mask, self.node_mask)
+        return extract_subgraph(data, edge_mask=em, node_mask=nm, complement=complement, relabel=relabel)
+
 
 def _scores(model, data):
     """Eval-mode causal scores (edge [E], node [N]) of ``data`` with the identity permutation.  Engine-backed models: views
@@ -129,6 +142,7 @@ class _Layout:
         dev = data.edge_index.device
         lay = _layout_of(data, B)
         self.B = B
+        self.no_self_loops = bool(lay["no_self_loops"])
         self.ptr = lay["ptr"].to(dev)
         self.max_nodes = int(lay["max_nodes"] or 0)
         if self.max_nodes == 0 and B > 0 and data.batch.numel() > 0:
@@ -244,3 +258,200 @@ def eval_explanation(model, loader, device, *, k="gt", ratio=None) -> dict:
             tot, cnt = s[6 * j + 2 * i], s[6 * j + 2 * i + 1]
             out["%s_%s" % (part, key)] = tot / cnt if cnt else float("nan")
     return out
+
+
+def _use_masks(use: str, edge_mask, node_mask):
+    if use not in ("edges", "nodes", "both"):
+        raise ValueError('use must be "edges", "nodes" or "both"')
+    return (edge_mask if use != "nodes" else None), (node_mask if use != "edges" else None)
+
+
+def _keep8(mask, n: int, dev, what: str):
+    if mask is None:
+        return None
+    if mask.dim() != 1 or mask.numel() != n:
+        raise ValueError("%s must have one entry per %s" % (what, what.split("_")[0]))
+    return mask.to(device=dev, dtype=torch.bool).contiguous().view(torch.uint8)
+
+
+def extract_subgraph(data, *, edge_mask=None, node_mask=None, complement: bool = False, relabel: bool = False):
+    """The batch ``data`` restricted by a per-edge and / or per-node keep mask, as a ``cal_amd.data.Batch`` the engine can run.
+
+    ``edge_mask`` [E] / ``node_mask`` [N] (bool; ``None`` = keep all); ``complement`` reads each given mask inverted.  An edge
+    stays iff its mask keeps it and, with a ``node_mask``, both endpoints stay.  ``relabel=False``: every node stays, ids
+    unchanged, ``x`` / ``feat`` / ``batch`` are ``data``'s own tensors.  ``relabel=True``: the kept nodes are ``node_mask``
+    when given, else the nodes touched by a kept edge; they are renumbered densely in their original order and their feature
+    rows gathered (a graph may end with no node).  Kept elements keep their order, ``num_graphs`` and ``y`` are unchanged.
+    The result carries ``ptr``, ``edge_ptr``, ``max_nodes``, ``max_edges``, ``no_self_loops`` (inherited) -- so the engine
+    takes its per-graph route -- no tiles, and ``node_map`` / ``edge_map`` (int64: new element -> element of ``data``).
+
+    One ``cal_subgraph_extract`` call (HIP for CUDA tensors, libcalhost for CPU tensors) on the current stream and one
+    read-back of the four totals.  A batch whose edge columns are not grouped by graph is first reordered by graph (stable),
+    as the ranking does; its result is grouped."""
+    from .data import Batch
+    x = data.x if getattr(data, "x", None) is not None else getattr(data, "feat", None)
+    ei = data.edge_index
+    dev, host = ei.device, not ei.is_cuda
+    lay = _Layout(data)
+    B, E, N = lay.B, int(ei.size(1)), int(data.batch.numel())
+    ek = _keep8(edge_mask, E, dev, "edge_mask")
+    nk = _keep8(node_mask, N, dev, "node_mask")
+    if lay.order is not None:
+        ei = ei[:, lay.order]
+        ek = None if ek is None else ek[lay.order].contiguous()
+    ei = ei.contiguous()
+    gather = relabel and x is not None
+    if gather and x.dtype != torch.float32:
+        raise TypeError("relabel gathers float32 features")
+    F = int(x.size(1)) if gather else 0
+    wsb = _lib.query("cal_subgraph_ws", N, E, B, host=host)
+    sizes = (2 * E, B + 1, B + 1, N if relabel else 0, N, E, 4, (wsb + 7) // 8)
+    ints = torch.empty(sum(sizes), dtype=torch.long, device=dev)       # every integer output and the workspace: one allocation
+    ei_o, ptr_o, eptr_o, batch_o, nmap, emap, totals, ws = torch.split(ints, sizes)
+    x_o = torch.empty(N, F, dtype=torch.float32, device=dev) if gather else None
+    xin = x.contiguous() if gather else None
+    _lib.call("cal_subgraph_extract", _p(ei) if E else None, E, N, _p(lay.ptr.contiguous()), _p(lay.edge_ptr.contiguous()), B,
+              _p(ek), _p(nk), int(bool(complement)), int(bool(relabel)), _p(xin) if gather and N else None, F,
+              _p(ei_o) if E else None, _p(ptr_o), _p(eptr_o), _p(batch_o) if relabel and N else None,
+              _p(x_o) if gather and N else None, _p(nmap) if N else None, _p(emap) if E else None, _p(totals), _p(ws), 8 * sizes[-1],
+              None if host else _stream(), host=host)
+    n2, e2, mn, me = totals.tolist()                                   # the one read-back: the Batch needs them as host ints
+    b = Batch()
+    if relabel:
+        feats = None if x is None else x_o[:n2]
+        b.x, b.feat = (feats, None) if getattr(data, "x", None) is not None else (None, feats)
+        b.batch = batch_o[:n2]
+    else:
+        b.x, b.feat, b.batch = getattr(data, "x", None), getattr(data, "feat", None), data.batch
+    b.edge_index = ei_o[:2 * e2].view(2, e2)
+    b.y = getattr(data, "y", None)
+    b.ptr, b.edge_ptr, b.num_graphs = ptr_o, eptr_o, B
+    b.max_nodes, b.max_edges = int(mn), int(me)
+    b.no_self_loops = lay.no_self_loops
+    b.node_map = nmap[:n2]
+    b.edge_map = emap[:e2] if lay.order is None else lay.order[emap[:e2]]
+    return b
+
+
+_HEADS = ("c", "o", "co")          # the order of the model's three outputs (and of eval_acc_causal's reports)
+_FID = ("acc_full", "acc_keep", "acc_drop", "fid_plus", "fid_minus")
+
+
+def _log_probs(model, data) -> torch.Tensor:
+    """Eval-mode log-probabilities [3, B, C] (heads c, o, co) of ``data`` with the identity permutation: the engine's forward
+    when the model has one, else the operator-level ``model(data)``."""
+    x = data.x if getattr(data, "x", None) is not None else data.feat
+    eng = model._engine_for(x)
+    if eng is not None:
+        eng.forward(data, None, training=False)
+        eng._fwd_token = getattr(eng, "_fwd_token", 0) + 1
+        return torch.stack(eng.logp_copy())
+    B = int(data.num_graphs)
+    return torch.stack(model(data, perm=torch.arange(B, device=x.device))[:3])
+
+
+def _untiled(data, lay):
+    """``data`` as the extractions of it look to the engine: the same tensors and layout facts, no tile packing -- so the
+    whole batch takes the route its subgraphs take and an extraction that keeps everything reproduces it bit for bit."""
+    if lay.order is not None or getattr(data, "tile_ptr", None) is None:
+        return data
+    from .data import Batch
+    b = Batch()
+    b.x, b.feat, b.edge_index, b.batch, b.y = data.x, data.feat, data.edge_index, data.batch, data.y
+    b.ptr, b.edge_ptr, b.num_graphs = lay.ptr, lay.edge_ptr, lay.B
+    b.max_nodes, b.max_edges, b.no_self_loops = lay.max_nodes, lay.max_edges, lay.no_self_loops
+    return b
+
+
+def _fidelity_sums(model, data, specs, use: str) -> torch.Tensor:
+    """One batch's fidelity sums [len(specs), 18] fp64 on the device, ``specs`` a list of (ratio, k): per head (c, o, co) the
+    hits on the full / kept / removed graph and the sums of p_full - p_drop and p_full - p_keep at the full graph's argmax;
+    then the graph count, the kept and the total element count.  One forward for the scores, one on the whole graph, two per
+    spec.  Called in eval mode under no_grad."""
+    edge, node = _scores(model, data)
+    edge, node = edge.clone(), node.clone()
+    lay = _Layout(data)
+    full = _log_probs(model, _untiled(data, lay))
+    y = data.y.view(-1)
+    yhat = full.argmax(-1, keepdim=True)                                # [3, B, 1]
+    pf = full.gather(-1, yhat).exp()
+    out = []
+    for ratio, k in specs:
+        em = lay.rank_edges(edge, ratio=ratio, k=k)[0] if use != "nodes" else None
+        nm = lay.rank_nodes(node, ratio=ratio, k=k)[0] if use != "edges" else None
+        rows = [(yhat.squeeze(-1) == y).sum(-1)]
+        gaps = []
+        for comp in (False, True):
+            sub = extract_subgraph(data, edge_mask=em, node_mask=nm, complement=comp, relabel=False)
+            lp = _log_probs(model, sub)
+            rows.append((lp.argmax(-1) == y).sum(-1))
+            gaps.append((pf - lp.gather(-1, yhat).exp()).sum((1, 2)))
+        kept = sum(m.sum() for m in (em, nm) if m is not None)
+        total = sum(m.numel() for m in (em, nm) if m is not None)
+        tail = torch.stack([torch.as_tensor(float(y.numel()), dtype=torch.float64, device=y.device), kept.to(torch.float64),
+                            torch.as_tensor(float(total), dtype=torch.float64, device=y.device)])
+        # [5, 3] -> head-major [3 x 5]: hits full, keep, drop, sum(p_full - p_drop), sum(p_full - p_keep)
+        tab = torch.stack([rows[0].double(), rows[1].double(), rows[2].double(), gaps[1].double(), gaps[0].double()])
+        out.append(torch.cat([tab.t().reshape(-1), tail]))
+    return torch.stack(out)
+
+
+def _fidelity_report(row) -> dict:
+    n, kept, total = row[15], row[16], row[17]
+    res = {}
+    for h, head in enumerate(_HEADS):
+        for j, key in enumerate(_FID):
+            res["%s_%s" % (key, head)] = row[5 * h + j] / n if n else float("nan")
+    res["sparsity"] = 1.0 - kept / total if total else float("nan")
+    res["graphs"] = int(n)
+    return res
+
+
+def fidelity(model, data, *, ratio=None, k=None, use: str = "edges") -> dict:
+    """Does ``model``'s prediction on ``data`` rest on its causal subgraph?  The top ``ratio`` / ``k`` of the causal scores
+    (as ``explain`` selects them; ``use``: the edge masks, the node masks or both) is extracted twice with ``relabel=False``
+    -- the explanation alone and the batch with it removed -- and the model runs in eval mode with the identity permutation
+    on the whole batch and on both.  Per readout head ``h`` in ``c``, ``o``, ``co``, with ŷ the head's argmax on the whole
+    graph and p its softmax probability:
+
+    * ``acc_full_h``, ``acc_keep_h``, ``acc_drop_h``: accuracy against ``data.y`` on the whole graph / explanation / rest;
+    * ``fid_plus_h``  = mean_g [p_full(ŷ_g) - p_drop(ŷ_g)] (high: the explanation is necessary);
+    * ``fid_minus_h`` = mean_g [p_full(ŷ_g) - p_keep(ŷ_g)] (low: the explanation is sufficient);
+
+    and ``sparsity`` = 1 - kept / total over the elements ``use`` names, ``graphs`` the batch size.  One read-back at the
+    end.  Like ``explain``, it leaves parameters, optimizer state, the engine's step counter, BatchNorm statistics, the RNG
+    states and ``model.training`` as they were."""
+    _k_code(ratio, k)
+    if k == "gt":
+        raise ValueError('fidelity has no ground truth: k must be an int >= 0')
+    _use_masks(use, None, None)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            sums = _fidelity_sums(model, data, [(ratio, k)], use)
+    finally:
+        model.train(was_training)
+    return _fidelity_report(sums[0].tolist())
+
+
+def eval_fidelity(model, loader, device, *, ratios=(0.1, 0.2, 0.3, 0.5), use: str = "edges") -> dict:
+    """``fidelity`` over a loader at every ratio of ``ratios``: ``{ratio: report}``, each report as ``fidelity`` returns it
+    with the means taken over all graphs of the loader.  The counterpart of ``eval_explanation`` for data without a ground
+    truth.  Per mini-batch one forward for the scores, one on the whole batch and, per ratio, one ranking call each for edges
+    and nodes, two extractions and two forwards; the sums stay on the device until one read-back at the end."""
+    ratios = [float(r) for r in ratios]
+    specs = [(r, None) for r in ratios]
+    for r, _ in specs:
+        _k_code(r, None)
+    _use_masks(use, None, None)
+    was_training = model.training
+    model.eval()
+    sums = torch.zeros(len(specs), 18, dtype=torch.float64, device=device)
+    try:
+        with torch.no_grad():
+            for data in loader:
+                sums += _fidelity_sums(model, data.to(device), specs, use)
+    finally:
+        model.train(was_training)
+    return {r: _fidelity_report(row) for r, row in zip(ratios, sums.tolist())}

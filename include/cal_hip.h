@@ -271,6 +271,26 @@ CAL_API int cal_explain_rank(const float* score, int64_t stride, const int64_t* 
                              int64_t max_seg, double ratio, int64_t k, const uint8_t* gt, uint8_t* mask, int32_t* rank,
                              double* metrics, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- subgraph extraction: a keep mask over a batch's edges / nodes -> the compacted batch, order preserved ---------- */
+/* Graph g owns the nodes [ptr[g], ptr[g+1]) and the edge_index ([2, E] int64) columns [edge_ptr[g], edge_ptr[g+1]) (ptr,
+ * edge_ptr: [B+1] int64).  edge_keep [E] / node_keep [N] uint8 or null; with `complement` each given mask is read inverted.
+ * An edge is kept iff edge_keep (when given), both endpoints kept (when node_keep is given) and both endpoints inside its
+ * graph's node range (an edge that leaves it is dropped).  relabel = 0: every node stays with its id (N' = N), x is not
+ * copied.  relabel = 1: the kept nodes are node_keep when given, else the nodes incident to a kept edge; they are renumbered
+ * densely in their original order, the endpoints rewritten, and row i of x_out [N, F] is row node_map[i] of x (x, x_out may be
+ * null).  Kept elements keep their relative order and B is unchanged (a graph may keep no edge and, with relabel, no node).
+ * Outputs, allocated at the bounds N / E: edge_index_out [2 E] (row 0 at [0, E'), row 1 at [E', 2 E'): a contiguous [2, E']),
+ * ptr_out / edge_ptr_out [B+1], batch_out [N] (graph of every new node; may be null with relabel = 0), node_map [N] / edge_map
+ * [E] (new element -> old element; node_map is the identity with relabel = 0 and may then be null) and totals [4] int64 on the
+ * device: N', E', max_nodes', max_edges'.  Every integer output is uniquely determined.  ws: 8-byte aligned,
+ * cal_subgraph_ws bytes.  Two launches on `stream`, no synchronisation; the caller reads totals back to slice the outputs. */
+CAL_API int64_t cal_subgraph_ws(int64_t N, int64_t E, int64_t B);
+CAL_API int cal_subgraph_extract(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                                 int64_t B, const uint8_t* edge_keep, const uint8_t* node_keep, int complement, int relabel,
+                                 const float* x, int64_t F, int64_t* edge_index_out, int64_t* ptr_out, int64_t* edge_ptr_out,
+                                 int64_t* batch_out, float* x_out, int64_t* node_map, int64_t* edge_map, int64_t* totals,
+                                 void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,8 @@
 """Time the explanation path on the GPU: the HIP per-graph ranking (cal_explain_rank) alone, a torch-composed ranking of
 the same scores (stable sort by score, stable sort by graph id, masks), and eval_explanation against eval_acc_causal over
-the same loader.  Device events around synchronised regions, after warm-up; one JSON line per shape.
+the same loader; and the fidelity leg: the HIP subgraph extraction (cal_subgraph_extract, with its one read-back) against the
+plain-torch composition of the same extraction (nonzero / cumsum / index_select) on the same device, and one whole fidelity()
+call.  Device events around synchronised regions, after warm-up; one JSON line per shape.
 
     python scripts/bench_explain.py [--shapes headline,nodenum15,config5] [--iters 50]
 """
@@ -16,7 +18,7 @@ sys.path.insert(0, ROOT)
 
 from cal_amd import model as M, spmotif, synth          # noqa: E402
 from cal_amd.data import Batch, DataLoader               # noqa: E402
-from cal_amd.explain import _Layout, _scores, eval_explanation, rank_segments   # noqa: E402
+from cal_amd.explain import _Layout, _scores, eval_explanation, extract_subgraph, fidelity, rank_segments   # noqa: E402
 from cal_amd.train_causal import eval_acc_causal         # noqa: E402
 
 SHAPES = {
@@ -47,6 +49,29 @@ def torch_rank(score, gid, eptr, k):
     rank = torch.empty_like(order)
     rank[order] = torch.arange(order.numel(), device=score.device) - eptr[gid[order]]
     return rank < k, rank
+
+
+def torch_extract(ei, ptr, eptr, batch, x, keep, relabel):
+    """Torch-composed extraction of an edge mask (edge columns grouped by graph): the kept columns in order, per-graph
+    offsets and bounds and, with relabel, the touched nodes renumbered by a cumsum and their rows gathered."""
+    B, N = ptr.numel() - 1, batch.numel()
+    emap = keep.nonzero().view(-1)
+    new = ei.index_select(1, emap)
+    ecnt = torch.bincount(batch[new[0]], minlength=B)
+    zero = torch.zeros(1, dtype=torch.long, device=ei.device)
+    eptr2 = torch.cat([zero, ecnt.cumsum(0)])
+    if relabel:
+        nodes = torch.zeros(N, dtype=torch.bool, device=ei.device)
+        nodes[new.view(-1)] = True
+        nmap = nodes.nonzero().view(-1)
+        new = (nodes.long().cumsum(0) - 1)[new]
+        batch, x = batch.index_select(0, nmap), x.index_select(0, nmap)
+        ncnt = torch.bincount(batch, minlength=B)
+        ptr = torch.cat([zero, ncnt.cumsum(0)])
+    else:
+        ncnt = ptr[1:] - ptr[:-1]
+    mn, me = torch.stack([ncnt.max(), ecnt.max()]).tolist()            # the bounds as host ints, like the HIP path's read-back
+    return new, ptr, eptr2, batch, x, emap, mn, me
 
 
 def main():
@@ -81,6 +106,22 @@ def main():
         out = dict(shape=name, graphs=B, edges=int(b.edge_index.size(1)), nodes=int(b.batch.numel()),
                    max_edges=lay.max_edges, rank_edges_ms=round(t_rank, 4), rank_nodes_ms=round(t_rank_nodes, 4),
                    torch_rank_edges_ms=round(t_torch, 4), hip_equals_torch=same)
+        # fidelity leg: extraction of the top 30 % of every graph's edges, HIP against the torch composition, and fidelity()
+        keep = rank_segments(edge, lay.edge_ptr, lay.max_edges, ratio=0.3)[0]
+        xf = b.x if b.x is not None else b.feat
+        for relabel in (False, True):
+            tag = "relabel" if relabel else "keep_ids"
+            t_hip = _time(lambda: extract_subgraph(b, edge_mask=keep, relabel=relabel), a.iters)
+            t_tor = _time(lambda: torch_extract(b.edge_index, lay.ptr, lay.edge_ptr, b.batch, xf, keep, relabel), a.iters)
+            sub = extract_subgraph(b, edge_mask=keep, relabel=relabel)
+            ref = torch_extract(b.edge_index, lay.ptr, lay.edge_ptr, b.batch, xf, keep, relabel)
+            same_x = torch.equal(sub.x if sub.x is not None else sub.feat, ref[4])
+            out["extract_%s_ms" % tag] = round(t_hip, 4)
+            out["torch_extract_%s_ms" % tag] = round(t_tor, 4)
+            out["extract_%s_equals_torch" % tag] = bool(torch.equal(sub.edge_index, ref[0]) and torch.equal(sub.edge_ptr, ref[2])
+                                                        and torch.equal(sub.ptr, ref[1]) and same_x
+                                                        and (sub.max_nodes, sub.max_edges) == (ref[6], ref[7]))
+        out["fidelity_ms"] = round(_time(lambda: fidelity(m, b, ratio=0.3), max(3, a.iters // 5), warmup=2), 4)
         if name != "config5":
             loader = DataLoader(gs, batch_size=B, shuffle=False)
             t_ee = _time(lambda: eval_explanation(m, loader, dev), max(3, a.iters // 10), warmup=2)
