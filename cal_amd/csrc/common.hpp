@@ -237,10 +237,12 @@ __device__ __forceinline__ void warm_kernargs() {
 }  // namespace cal
 
 namespace cal { inline const char* g_last_launch = ""; }     // name of the latest launch site (profiling aid)
+namespace cal { inline int64_t g_launches = 0; }             // launch sites passed so far (cal_launch_count)
 
 #define CAL_CHECK_LAUNCH(name)                                               \
     do {                                                                     \
         cal::g_last_launch = name;                                           \
+        ++cal::g_launches;                                                   \
         hipError_t e_ = hipGetLastError();                                   \
         if (e_ != hipSuccess) {                                              \
             cal::set_error("%s: %s", name, hipGetErrorString(e_));           \

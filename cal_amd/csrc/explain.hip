@@ -16,6 +16,12 @@
 //    order to ws; k_explain_rank_merge adds each element's count against every other chunk of its segment (binary
 //    searches on the sorted chunks, staged through LDS); k_explain_rank_large reduces the mask and the metrics.  A batch
 //    that mixes both kinds runs the three launches, the small segments finishing in the first.
+//
+// Undirected edges (cal_explain_rank_pairs): a column and its reverse (twin.hip) are one element.  k_pairs_compact writes the
+// symmetrised score of every column and compacts each segment's representatives (the lower column of a pair, every unpaired
+// column) in order to the front of the segment's rows in ws (a fixed-order ballot scan, as subgraph.hip compacts); the
+// kernels above rank those rows (their lengths come from seg_len instead of seg_ptr[g+1]); k_pairs_scatter gives both
+// columns of a pair the representative's rank and mask.  Two launches around the ranking's.
 #include <math.h>
 
 #include "common.hpp"
@@ -40,6 +46,7 @@ struct RankArgs {
     double* metrics;
     uint32_t* skey;    // ws: chunk keys in sorted order [M]      (large segments only)
     int32_t* r2;       // ws: 2 x ascending average rank [M]     (large segments only)
+    const int64_t* seg_len;   // or null: segment g is [seg_ptr[g], seg_ptr[g] + seg_len[g]) (compacted rows of the pair ranking)
 };
 
 __device__ __forceinline__ uint32_t score_key(float s) {
@@ -51,6 +58,7 @@ __device__ __forceinline__ uint32_t score_key(float s) {
 __device__ __forceinline__ void seg_range(const RankArgs& a, int64_t g, int64_t& lo, int64_t& m) {
     int64_t l = a.seg_ptr[g], h = a.seg_ptr[g + 1];
     l = l < 0 ? 0 : (l > a.M ? a.M : l);
+    if (a.seg_len) h = l + a.seg_len[g];
     h = h < l ? l : (h > a.M ? a.M : h);
     lo = l;
     m = h - l;
@@ -293,6 +301,151 @@ __global__ void __launch_bounds__(XNT) k_explain_rank_large(RankArgs a) {
     }
 }
 
+struct PairArgs {
+    const float* score;
+    int64_t stride;
+    const int64_t* seg_ptr;
+    int64_t B, M, max_seg;
+    const uint8_t* gt;
+    const int32_t* twin;
+    int reduce;                // 0 mean, 1 max, 2 min
+    float* score_out;
+    uint8_t* mask;
+    int32_t* rank;
+    float* cs;                 // ws: representatives' scores, compacted to the front of each segment's rows [M]
+    int32_t* crank;            // ws: their ranks [M]
+    int32_t* cpos;             // ws: row of a representative column [M]
+    uint8_t* cgt;              // ws: their ground truth [M]
+    uint8_t* cmask;            // ws: their masks [M]
+    int64_t* seg_len;          // ws: representatives per segment [B] (the segment's length where it is not ranked)
+};
+
+__device__ __forceinline__ void pair_range(const PairArgs& a, int64_t g, int64_t& lo, int64_t& m) {
+    int64_t l = a.seg_ptr[g], h = a.seg_ptr[g + 1];
+    l = l < 0 ? 0 : (l > a.M ? a.M : l);
+    h = h < l ? l : (h > a.M ? a.M : h);
+    lo = l;
+    m = h - l;
+}
+
+// the partner of column e of the segment [lo, lo + m), or -1: twin[e] inside the segment, not e itself, pointing back
+__device__ __forceinline__ int64_t pair_of(const PairArgs& a, int64_t e, int64_t lo, int64_t m) {
+    const int64_t t = a.twin[e];
+    return (t >= lo && t < lo + m && t != e && a.twin[t] == e) ? t : -1;
+}
+
+// position of this thread's flag among the set flags of the workgroup's NT threads (exclusive), their count in tot;
+// every thread of the workgroup calls it (two barriers)
+template <int NT>
+__device__ __forceinline__ int pair_excl(bool f, int* wcnt, int& tot) {
+    const unsigned long long b = __ballot(f);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int pre = __popcll(b & ((1ull << lane) - 1ull));
+    __syncthreads();
+    if (lane == 0) wcnt[w] = __popcll(b);
+    __syncthreads();
+    int base = 0, t = 0;
+#pragma unroll
+    for (int i = 0; i < NT / 64; ++i) {
+        const int v = wcnt[i];
+        base += i < w ? v : 0;
+        t += v;
+    }
+    tot = t;
+    return base + pre;
+}
+
+// grid B, NT threads: score_out of every column; the representatives' scores and ground truth compacted in order
+template <int NT>
+__global__ void __launch_bounds__(NT) k_pairs_compact(PairArgs a) {
+    __shared__ int wcnt[NT / 64];
+    const int64_t g = blockIdx.x;
+    int64_t lo, m;
+    pair_range(a, g, lo, m);
+    const bool bad = m > a.max_seg;
+    int64_t carry = 0;
+    for (int64_t base = 0; base < m; base += NT) {
+        const int64_t q = base + threadIdx.x, e = lo + q;
+        bool f = false;
+        float sym = 0.f;
+        uint8_t pos_gt = 0;
+        if (q < m) {
+            const int64_t t = pair_of(a, e, lo, m);
+            sym = a.score[e * a.stride];
+            if (a.gt) pos_gt = a.gt[e] != 0;
+            if (t >= 0) {                                          // x: the lower column's score, so both columns get the same bits
+                const float o = a.score[t * a.stride];
+                const float x = e < t ? sym : o, y = e < t ? o : sym;
+                if (a.reduce == 0) sym = (x + y) * 0.5f;
+                else if (x != x || y != y) sym = __builtin_nanf("");
+                else if (a.reduce == 1) sym = x >= y ? x : y;
+                else sym = x <= y ? x : y;
+                if (a.gt) pos_gt |= a.gt[t] != 0;
+            }
+            a.score_out[e] = sym;
+            f = !bad && (t < 0 || e < t);
+        }
+        int tot;
+        const int pos = pair_excl<NT>(f, wcnt, tot);
+        if (f) {
+            const int64_t p = lo + carry + pos;
+            a.cs[p] = sym;
+            a.cgt[p] = pos_gt;
+            a.cpos[e] = (int32_t)p;
+        }
+        carry += tot;
+    }
+    if (threadIdx.x == 0) a.seg_len[g] = bad ? m : carry;
+}
+
+// grid B, NT threads: rank and mask of every column from its representative's row
+template <int NT>
+__global__ void __launch_bounds__(NT) k_pairs_scatter(PairArgs a) {
+    const int64_t g = blockIdx.x;
+    int64_t lo, m;
+    pair_range(a, g, lo, m);
+    const bool bad = m > a.max_seg;
+    for (int64_t q = threadIdx.x; q < m; q += NT) {
+        const int64_t e = lo + q;
+        int32_t r = -1;
+        uint8_t s = 0;
+        if (!bad) {
+            const int64_t t = pair_of(a, e, lo, m);
+            int64_t p = a.cpos[t >= 0 && t < e ? t : e];
+            p = p < 0 ? 0 : (p >= a.M ? a.M - 1 : p);
+            r = a.crank[p];
+            s = a.cmask[p];
+        }
+        a.rank[e] = r;
+        a.mask[e] = s;
+    }
+}
+
+int rank_launch(const RankArgs& a, hipStream_t stream) {
+    const bool large = a.max_seg > XS;
+    const int64_t nch = large ? (a.max_seg + XS - 1) / XS : 1;
+    const int eff = (int)(a.max_seg < XS ? a.max_seg : XS);
+    int G = 64;
+    while (G < eff && G < XNT) G <<= 1;
+    const int cap = (eff > 0 ? (eff + G - 1) / G : 1) * G;
+    const int NT = G <= 256 ? 256 : G;
+    const int spb = NT / G;
+    const size_t lds = (((size_t)5 * spb * cap + 7) & ~(size_t)7) + (size_t)(NT / 64) * 8;
+    const dim3 grid((unsigned)((a.B + spb - 1) / spb), (unsigned)nch);
+    CAL_REQUIRE(grid.x <= 0x7FFFFFFFu, "too many segments");
+    if (NT == 256) hipLaunchKernelGGL(k_explain_rank_lds<256>, grid, dim3(256), lds, stream, a, G, cap);
+    else if (NT == 512) hipLaunchKernelGGL(k_explain_rank_lds<512>, grid, dim3(512), lds, stream, a, G, cap);
+    else hipLaunchKernelGGL(k_explain_rank_lds<1024>, grid, dim3(1024), lds, stream, a, G, cap);
+    CAL_CHECK_LAUNCH("k_explain_rank_lds");
+    if (large) {
+        hipLaunchKernelGGL(k_explain_rank_merge, dim3((unsigned)a.B, (unsigned)nch), dim3(XNT), 0, stream, a);
+        CAL_CHECK_LAUNCH("k_explain_rank_merge");
+        hipLaunchKernelGGL(k_explain_rank_large, dim3((unsigned)a.B), dim3(XNT), 0, stream, a);
+        CAL_CHECK_LAUNCH("k_explain_rank_large");
+    }
+    return 0;
+}
+
 }  // namespace
 }  // namespace cal
 
@@ -322,27 +475,49 @@ CAL_EXPORT int cal_explain_rank(const float* score, int64_t stride, const int64_
     CAL_REQUIRE(nch <= 65535, "max_seg too large");
     CAL_REQUIRE(!large || (ws && ws_bytes >= cal_explain_ws(M, B) && aligned16(ws)),
                 "segments above cal_explain_lds_cap() need a 16-byte aligned ws of cal_explain_ws(M, B) bytes");
-    const int eff = (int)(max_seg < XS ? max_seg : XS);
-    int G = 64;
-    while (G < eff && G < XNT) G <<= 1;
-    const int cap = (eff > 0 ? (eff + G - 1) / G : 1) * G;
     RankArgs a{score, stride, seg_ptr, B, M, max_seg, ratio, k, gt, mask, rank, metrics,
                large ? (uint32_t*)ws : nullptr,
                large ? (int32_t*)((char*)ws + ((4 * M + 15) / 16) * 16) : nullptr};
-    const int NT = G <= 256 ? 256 : G;
-    const int spb = NT / G;
-    const size_t lds = (((size_t)5 * spb * cap + 7) & ~(size_t)7) + (size_t)(NT / 64) * 8;
-    const dim3 grid((unsigned)((B + spb - 1) / spb), (unsigned)nch);
-    CAL_REQUIRE(grid.x <= 0x7FFFFFFFu, "too many segments");
-    if (NT == 256) hipLaunchKernelGGL(k_explain_rank_lds<256>, grid, dim3(256), lds, stream, a, G, cap);
-    else if (NT == 512) hipLaunchKernelGGL(k_explain_rank_lds<512>, grid, dim3(512), lds, stream, a, G, cap);
-    else hipLaunchKernelGGL(k_explain_rank_lds<1024>, grid, dim3(1024), lds, stream, a, G, cap);
-    CAL_CHECK_LAUNCH("k_explain_rank_lds");
-    if (large) {
-        hipLaunchKernelGGL(k_explain_rank_merge, dim3((unsigned)B, (unsigned)nch), dim3(XNT), 0, stream, a);
-        CAL_CHECK_LAUNCH("k_explain_rank_merge");
-        hipLaunchKernelGGL(k_explain_rank_large, dim3((unsigned)B), dim3(XNT), 0, stream, a);
-        CAL_CHECK_LAUNCH("k_explain_rank_large");
-    }
+    return rank_launch(a, stream);
+}
+
+CAL_EXPORT int64_t cal_explain_pairs_ws(int64_t M, int64_t B) {
+    M = M > 0 ? M : 0;
+    B = B > 0 ? B : 0;
+    return 14 * M + 8 * B + 512 + cal_explain_ws(M, B);
+}
+
+CAL_EXPORT int cal_explain_rank_pairs(const float* score, int64_t stride, const int64_t* seg_ptr, int64_t B, int64_t M,
+                                      int64_t max_seg, double ratio, int64_t k, const uint8_t* gt, const int32_t* twin,
+                                      int reduce, float* score_out, uint8_t* mask, int32_t* rank, double* metrics, void* ws,
+                                      int64_t ws_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    CAL_REQUIRE(B >= 0 && M >= 0 && max_seg >= 0 && stride >= 1, "B, M, max_seg must be >= 0 and stride >= 1");
+    CAL_REQUIRE(k >= -2, "k must be >= 0, -1 (ratio) or -2 (ground-truth count)");
+    CAL_REQUIRE(k != -2 || gt, "k = -2 needs gt");
+    CAL_REQUIRE(k != -1 || ratio >= 0.0, "k = -1 needs a ratio >= 0");
+    CAL_REQUIRE(reduce >= 0 && reduce <= 2, "reduce must be 0 (mean), 1 (max) or 2 (min)");
+    CAL_REQUIRE(B == 0 || seg_ptr, "seg_ptr is null");
+    CAL_REQUIRE(M == 0 || (score && twin && score_out && mask && rank), "score / twin / score_out / mask / rank are null");
+    CAL_REQUIRE(M < ((int64_t)1 << 31), "2^31 columns or more are not supported (twin is int32)");
+    CAL_REQUIRE(max_seg < ((int64_t)1 << 30), "segments of 2^30 elements or more are not supported");
+    if (B == 0) return 0;
+    CAL_REQUIRE((max_seg + XS - 1) / XS <= 65535, "max_seg too large");
+    CAL_REQUIRE(B <= 0x7FFFFFFF, "too many segments");
+    CAL_REQUIRE(ws && ws_bytes >= cal_explain_pairs_ws(M, B) && aligned16(ws),
+                "ws must be 16-byte aligned and hold cal_explain_pairs_ws(M, B) bytes");
+    char* w = (char*)ws;
+    const int64_t m16 = ((M + 15) / 16) * 16;                    // (every array starts 16-byte aligned)
+    PairArgs p{score, stride, seg_ptr, B, M, max_seg, gt, twin, reduce, score_out, mask, rank,
+               (float*)w, (int32_t*)(w + 4 * m16), (int32_t*)(w + 8 * m16), (uint8_t*)(w + 12 * m16),
+               (uint8_t*)(w + 13 * m16), (int64_t*)(w + 14 * m16)};
+    char* rw = w + 14 * m16 + ((8 * B + 15) / 16) * 16;
+    hipLaunchKernelGGL(k_pairs_compact<256>, dim3((unsigned)B), dim3(256), 0, stream, p);
+    CAL_CHECK_LAUNCH("k_pairs_compact");
+    RankArgs a{p.cs, 1, seg_ptr, B, M, max_seg, ratio, k, gt ? p.cgt : nullptr, p.cmask, p.crank, metrics,
+               (uint32_t*)rw, (int32_t*)(rw + ((4 * M + 15) / 16) * 16), p.seg_len};
+    if (rank_launch(a, stream) != 0) return 1;
+    hipLaunchKernelGGL(k_pairs_scatter<256>, dim3((unsigned)B), dim3(256), 0, stream, p);
+    CAL_CHECK_LAUNCH("k_pairs_scatter");
     return 0;
 }

@@ -200,6 +200,7 @@ using namespace cal;
 
 CAL_EXPORT const char* cal_last_error() { return g_err; }
 CAL_EXPORT int cal_version() { return 100; }
+CAL_EXPORT int64_t cal_launch_count() { return g_launches; }
 
 // Build both CSR views.  `work` must hold 4*(N+1) + 4*E ints; `status` one int (bit0: edge index out of
 // range, bit1: batch vector not sorted / out of range) -- zeroed here, read by the caller when it

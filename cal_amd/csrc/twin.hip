@@ -1,0 +1,396 @@
+// Reverse-edge ("twin") map of a batch of graphs stored as both directions of every undirected edge.
+//
+// Graph g owns the nodes [ptr[g], ptr[g+1]) and the edge_index columns [edge_ptr[g], edge_ptr[g+1]).  Among the columns of g
+// equal to (u, v), u != v, the j-th in ascending column order pairs with the j-th column of g equal to (v, u): twin[e] is the
+// partner's global column index, -1 when there is no j-th partner.  A self loop is its own twin; a column with an endpoint
+// outside its graph's node range gets -1 and pairs with nothing.  So twin[twin[e]] == e wherever twin[e] >= 0, and the output
+// is uniquely determined (duplicates allowed).  totals[0] = columns with twin < 0, totals[1] = self loops.
+//
+// A column becomes the 64-bit key ((min(u,v) - lo) n_g + (max(u,v) - lo)) << 1 | (u > v): the two directions of an edge differ
+// in bit 0 only, and ascending key order keeps them adjacent.  Positions come from counting, not from sorting: with
+// lt = #{key_j < key_i}, eq = #{key_j == key_i}, j = #{key_j == key_i, j < i} and eqp = #{key_j == key_i ^ 1}, element i sits
+// at sorted[lt + j] and its partner, if j < eqp, at sorted[lt + eq + j] (u < v) or sorted[lt - eqp + j] (u > v).
+//
+//  * segments of at most S = TS columns: k_twin_lds, one group of G threads per segment (G = 64 .. 1024 as in explain.hip,
+//    256-thread workgroups hold 256 / G segments).  Keys [cap] u64 and sorted [cap] i32 in LDS (24 KB at the cap); every lane
+//    counts its element against the whole row read as 128-bit broadcasts (two keys per read, every lane the same address: no
+//    bank conflict; the only scattered LDS access is the one write to sorted[]).  One launch.
+//  * larger segments: the same kernel sorts every S-column chunk and writes its keys and column indices in sorted order to
+//    ws; k_twin_merge (one workgroup per large segment) finds each column's occurrence number and its partner by binary
+//    searches over the chunks staged through LDS; k_twin_totals sums the workgroups' counts.  Three launches.
+//
+// No value is accumulated atomically.  Every workgroup writes its two counts to ws; the totals are their sum in workgroup
+// order.  In the one-launch path the workgroup that finishes last does that sum, and the only way to know it is last is a
+// completion ticket (one atomicInc per workgroup on a wrapping counter, nothing else): the integer result does not depend on
+// which workgroup that is.  The large path needs no ticket.
+#include <atomic>
+
+#include "common.hpp"
+
+namespace cal {
+namespace {
+
+constexpr int TS = 2048;       // LDS capacity S (columns of one segment / chunk) == cal_explain_lds_cap()
+constexpr int TNT = 1024;      // threads of the large-segment workgroups
+constexpr int TIT = TS / TNT;  // columns per lane at the widest group
+constexpr uint64_t kPad = ~0ull;   // key of a column that pairs with nothing, and of the LDS rows' padding
+constexpr int kTickets = 64;   // concurrent one-launch calls (on different streams) that may be in flight
+
+__device__ unsigned int g_twin_ticket[kTickets];   // zero at load; atomicInc wraps each back to zero
+
+struct TwinArgs {
+    const int64_t* ei;         // [2, E]
+    int64_t E;
+    const int64_t* ptr;        // [B + 1]
+    const int64_t* eptr;       // [B + 1]
+    int64_t B, max_edges;
+    int32_t* twin;             // [E]
+    int64_t* totals;           // [2]
+    int64_t* part;             // ws: [2 x workgroups] columns with twin < 0, self loops
+    uint64_t* skey;            // ws: chunk keys in sorted order [E]          (large segments only)
+    int32_t* sidx;             // ws: their column indices inside the segment (large segments only)
+    int ticket;                // slot of g_twin_ticket, -1: no ticket (the large path)
+    int nblk;                  // workgroups of the first launch (grid.x)
+};
+
+__device__ __forceinline__ void twin_ranges(const TwinArgs& a, int64_t g, int64_t& nlo, int64_t& nn, int64_t& elo, int64_t& m) {
+    nlo = a.ptr[g];
+    nn = a.ptr[g + 1] - nlo;
+    nn = nn < 0 ? 0 : nn;
+    int64_t l = a.eptr[g], h = a.eptr[g + 1];
+    l = l < 0 ? 0 : (l > a.E ? a.E : l);
+    h = h < l ? l : (h > a.E ? a.E : h);
+    elo = l;
+    m = h - l;
+}
+
+__device__ __forceinline__ uint64_t edge_key(const TwinArgs& a, int64_t e, int64_t nlo, int64_t nn, bool& self) {
+    const int64_t u = a.ei[e], v = a.ei[a.E + e];
+    self = false;
+    if (u < nlo || u >= nlo + nn || v < nlo || v >= nlo + nn) return kPad;
+    self = u == v;
+    const uint64_t x = (uint64_t)(u - nlo), y = (uint64_t)(v - nlo);
+    return (((x < y ? x : y) * (uint64_t)nn + (x < y ? y : x)) << 1) | (uint64_t)(u > v);
+}
+
+// sum over the workgroup's NT threads, every thread gets it (two barriers); fixed order: wave butterflies, waves in order
+template <int NT>
+__device__ __forceinline__ long long twin_wg_sum(long long v, long long* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    long long t = 0;
+#pragma unroll
+    for (int i = 0; i < NT / 64; ++i) t += red[i];
+    return t;
+}
+
+// first index of an ascending row of n keys that is >= key (lower) / > key (upper)
+__device__ __forceinline__ int lower_of(const uint64_t* s, int n, uint64_t key) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (s[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+__device__ __forceinline__ int upper_of(const uint64_t* s, int n, uint64_t key) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (s[mid] <= key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// grid (ceil(B / (NT / G)), chunks), NT threads; dynamic LDS: keys [NT/G][cap] u64, sorted [NT/G][cap] i32, [NT/64] i64.
+// cap = G x (columns per lane) >= min(max_edges, S).  Segments of at most cap columns are finished here (chunk 0 only); a
+// segment above S (then G = NT = 1024, cap = S) gets its chunk blockIdx.y sorted into ws; one above max_edges gets -1.
+template <int NT>
+__global__ void __launch_bounds__(NT) k_twin_lds(TwinArgs a, int G, int cap) {
+    extern __shared__ __align__(16) uint64_t tlds[];
+    __shared__ int last;
+    const int spb = NT / G, grp = threadIdx.x / G, lt = threadIdx.x % G;
+    uint64_t* sk = tlds + (size_t)grp * cap;
+    int32_t* so = reinterpret_cast<int32_t*>(tlds + (size_t)spb * cap) + (size_t)grp * cap;
+    long long* red = reinterpret_cast<long long*>(reinterpret_cast<char*>(tlds) + (size_t)12 * spb * cap);
+    const int64_t g = (int64_t)blockIdx.x * spb + grp;
+    const int64_t c = blockIdx.y;
+    int64_t nlo = 0, nn = 0, elo = 0, m = 0;
+    if (g < a.B) twin_ranges(a, g, nlo, nn, elo, m);
+    const bool bad = g < a.B && m > a.max_edges;
+    const bool full = g < a.B && !bad && m <= cap && c == 0;
+    const bool chunk = g < a.B && !bad && m > cap;               // (m > S here: cap = S whenever max_edges > S)
+    const int64_t ulo = chunk ? c * TS : 0;
+    const int un = full ? (int)m : (chunk && ulo < m ? (int)(m - ulo < TS ? m - ulo : TS) : 0);
+    const int nq = (un + 1) & ~1;
+    const int64_t base = elo + ulo;
+    const int nit = cap / G;
+
+    uint64_t ki[TIT];
+    bool self[TIT];
+#pragma unroll
+    for (int it = 0; it < TIT; ++it) {
+        const int q = lt + it * G;
+        ki[it] = kPad;
+        self[it] = false;
+        if (it < nit && q < nq) {
+            if (q < un) ki[it] = edge_key(a, base + q, nlo, nn, self[it]);
+            sk[q] = ki[it];
+        }
+    }
+    long long unp = 0, nself = 0;
+    if (bad && c == 0) {
+        for (int64_t q = lt; q < m; q += G) {
+            a.twin[elo + q] = -1;
+            ++unp;
+        }
+    }
+    __syncthreads();
+
+    int ltc[TIT], eqc[TIT], eqb[TIT], eqp[TIT];
+#pragma unroll
+    for (int it = 0; it < TIT; ++it) ltc[it] = eqc[it] = eqb[it] = eqp[it] = 0;
+    for (int j = 0; j < nq; j += 2) {
+        const ulonglong2 kv = *reinterpret_cast<const ulonglong2*>(sk + j);
+        const uint64_t kj[2] = {kv.x, kv.y};
+#pragma unroll
+        for (int it = 0; it < TIT; ++it) {
+            if (it < nit) {
+                const int q = lt + it * G;
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    ltc[it] += kj[t] < ki[it];
+                    const int e = kj[t] == ki[it];
+                    eqc[it] += e;
+                    eqb[it] += e & (j + t < q);
+                    eqp[it] += kj[t] == (ki[it] ^ 1ull);
+                }
+            }
+        }
+    }
+
+    int slot[TIT];
+#pragma unroll
+    for (int it = 0; it < TIT; ++it) {
+        const int q = lt + it * G;
+        slot[it] = -1;
+        if (it < nit && q < un) {
+            const int pos = ltc[it] + eqb[it];
+            if (chunk) {                                           // the chunk in sorted order (kPad columns last)
+                a.skey[base + pos] = ki[it];
+                a.sidx[base + pos] = (int32_t)(ulo + q);
+            } else if (ki[it] != kPad && !self[it]) {
+                so[pos] = q;
+                if (eqb[it] < eqp[it]) slot[it] = ((ki[it] & 1ull) ? ltc[it] - eqp[it] : ltc[it] + eqc[it]) + eqb[it];
+            }
+        }
+    }
+    __syncthreads();
+    if (full) {
+#pragma unroll
+        for (int it = 0; it < TIT; ++it) {
+            const int q = lt + it * G;
+            if (it < nit && q < un) {
+                int32_t t = -1;
+                if (self[it]) {
+                    t = (int32_t)(base + q);
+                    ++nself;
+                } else if (slot[it] >= 0) {
+                    t = (int32_t)(base + so[slot[it]]);
+                }
+                a.twin[base + q] = t;
+                unp += t < 0;
+            }
+        }
+    }
+
+    if (c != 0) return;                                            // (uniform; the chunks' workgroups counted nothing)
+    unp = twin_wg_sum<NT>(unp, red);
+    nself = twin_wg_sum<NT>(nself, red);
+    if (threadIdx.x == 0) {
+        a.part[2 * blockIdx.x] = unp;
+        a.part[2 * blockIdx.x + 1] = nself;
+    }
+    if (a.ticket < 0) return;
+    if (threadIdx.x == 0) {
+        __threadfence();
+        last = atomicInc(&g_twin_ticket[a.ticket], (unsigned)(a.nblk - 1)) == (unsigned)(a.nblk - 1);
+    }
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    long long s0 = 0, s1 = 0;
+    for (int i = threadIdx.x; i < a.nblk; i += NT) {
+        s0 += __hip_atomic_load(a.part + 2 * i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s1 += __hip_atomic_load(a.part + 2 * i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    s0 = twin_wg_sum<NT>(s0, red);
+    s1 = twin_wg_sum<NT>(s1, red);
+    if (threadIdx.x == 0) {
+        a.totals[0] = s0;
+        a.totals[1] = s1;
+    }
+}
+
+// grid B, TNT threads: the twins of one large segment from its sorted chunks; its counts to part[2 (nblk + g)]
+__global__ void __launch_bounds__(TNT) k_twin_merge(TwinArgs a) {
+    __shared__ __align__(16) uint64_t sk[TS];
+    __shared__ long long red[TNT / 64];
+    const int64_t g = blockIdx.x;
+    int64_t nlo, nn, elo, m;
+    twin_ranges(a, g, nlo, nn, elo, m);
+    const bool act = m > TS && m <= a.max_edges;                  // (uniform over the workgroup)
+    const int64_t nch = act ? (m + TS - 1) / TS : 0;
+    long long unp = 0, nself = 0;
+    for (int64_t c = 0; c < nch; ++c) {
+        const int un = (int)(m - c * TS < TS ? m - c * TS : TS);
+        uint64_t ki[TIT];
+        int64_t j[TIT], tw[TIT];
+        int32_t idx[TIT];
+        bool open[TIT];                                            // still looking for its partner
+#pragma unroll
+        for (int it = 0; it < TIT; ++it) {
+            const int t = threadIdx.x + it * TNT;
+            ki[it] = t < un ? a.skey[elo + c * TS + t] : kPad;
+            idx[it] = t < un ? a.sidx[elo + c * TS + t] : 0;
+            j[it] = 0;
+            tw[it] = -1;
+            open[it] = false;
+        }
+        // occurrence number: equal keys of the chunks before, then of this chunk's sorted order (ties by column index)
+        for (int64_t cc = 0; cc <= c; ++cc) {
+            const int n2 = (int)(m - cc * TS < TS ? m - cc * TS : TS);
+            for (int t = threadIdx.x; t < n2; t += TNT) sk[t] = a.skey[elo + cc * TS + t];
+            __syncthreads();
+#pragma unroll
+            for (int it = 0; it < TIT; ++it) {
+                if (ki[it] != kPad) {
+                    const int lb = lower_of(sk, n2, ki[it]);
+                    j[it] += cc < c ? upper_of(sk, n2, ki[it]) - lb : (int)(threadIdx.x + it * TNT) - lb;
+                }
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int it = 0; it < TIT; ++it) {
+            if (ki[it] != kPad) {
+                const int64_t e = elo + idx[it];
+                if (a.ei[e] == a.ei[a.E + e]) tw[it] = e;
+                else open[it] = true;
+            }
+        }
+        // the j-th column with the reversed key, walking the chunks in column order
+        for (int64_t cc = 0; cc < nch; ++cc) {
+            const int n2 = (int)(m - cc * TS < TS ? m - cc * TS : TS);
+            for (int t = threadIdx.x; t < n2; t += TNT) sk[t] = a.skey[elo + cc * TS + t];
+            __syncthreads();
+#pragma unroll
+            for (int it = 0; it < TIT; ++it) {
+                if (open[it]) {
+                    const uint64_t p = ki[it] ^ 1ull;
+                    const int lb = lower_of(sk, n2, p), cnt = upper_of(sk, n2, p) - lb;
+                    if (j[it] < cnt) {
+                        tw[it] = elo + a.sidx[elo + cc * TS + lb + j[it]];
+                        open[it] = false;
+                    } else {
+                        j[it] -= cnt;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int it = 0; it < TIT; ++it) {
+            if ((int)threadIdx.x + it * TNT < un) {
+                const int64_t e = elo + idx[it];
+                a.twin[e] = (int32_t)tw[it];
+                unp += tw[it] < 0;
+                nself += tw[it] == e;
+            }
+        }
+    }
+    unp = twin_wg_sum<TNT>(unp, red);
+    nself = twin_wg_sum<TNT>(nself, red);
+    if (threadIdx.x == 0) {
+        a.part[2 * (a.nblk + g)] = unp;
+        a.part[2 * (a.nblk + g) + 1] = nself;
+    }
+}
+
+// one workgroup: totals = the sum of the np workgroup counts, in order
+__global__ void __launch_bounds__(TNT) k_twin_totals(TwinArgs a, int64_t np) {
+    __shared__ long long red[TNT / 64];
+    long long s0 = 0, s1 = 0;
+    for (int64_t i = threadIdx.x; i < np; i += TNT) {
+        s0 += a.part[2 * i];
+        s1 += a.part[2 * i + 1];
+    }
+    s0 = twin_wg_sum<TNT>(s0, red);
+    s1 = twin_wg_sum<TNT>(s1, red);
+    if (threadIdx.x == 0) {
+        a.totals[0] = s0;
+        a.totals[1] = s1;
+    }
+}
+
+std::atomic<unsigned> g_twin_calls{0};
+
+}  // namespace
+}  // namespace cal
+
+using namespace cal;
+
+CAL_EXPORT int64_t cal_edge_twin_ws(int64_t E, int64_t B) {
+    E = E > 0 ? E : 0;
+    B = B > 0 ? B : 0;
+    return 32 * B + 12 * E + 256;
+}
+
+CAL_EXPORT int cal_edge_twin(const int64_t* edge_index, int64_t E, const int64_t* ptr, const int64_t* edge_ptr, int64_t B,
+                             int64_t max_edges, int32_t* twin, int64_t* totals, void* ws, int64_t ws_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    CAL_REQUIRE(E >= 0 && B >= 0 && max_edges >= 0, "E, B, max_edges must be >= 0");
+    CAL_REQUIRE(E < ((int64_t)1 << 31), "2^31 columns or more are not supported (twin is int32)");
+    CAL_REQUIRE(totals, "totals is null");
+    CAL_REQUIRE(B == 0 || (ptr && edge_ptr), "ptr / edge_ptr are null");
+    CAL_REQUIRE(E == 0 || (edge_index && twin), "edge_index / twin are null");
+    if (B == 0) {
+        if (hipMemsetAsync(totals, 0, 2 * sizeof(int64_t), stream) != hipSuccess) {
+            cal::set_error("cal_edge_twin: hipMemsetAsync failed");
+            return 1;
+        }
+        return 0;
+    }
+    CAL_REQUIRE(ws && ws_bytes >= cal_edge_twin_ws(E, B) && (reinterpret_cast<uintptr_t>(ws) & 7) == 0,
+                "ws must be 8-byte aligned and hold cal_edge_twin_ws(E, B) bytes");
+    const bool large = max_edges > TS;
+    const int64_t nch = large ? (max_edges + TS - 1) / TS : 1;
+    CAL_REQUIRE(nch <= 65535, "max_edges too large");
+    const int eff = (int)(max_edges < TS ? max_edges : TS);
+    int G = 64;
+    while (G < eff && G < TNT) G <<= 1;
+    const int cap = (eff > 0 ? (eff + G - 1) / G : 1) * G;
+    const int NT = G <= 256 ? 256 : G;
+    const int spb = NT / G;
+    const int64_t nblk = (B + spb - 1) / spb;
+    CAL_REQUIRE(nblk <= 0x7FFFFFFF, "too many segments");
+    char* w = (char*)ws;
+    TwinArgs a{edge_index, E, ptr, edge_ptr, B, max_edges, twin, totals, (int64_t*)w, (uint64_t*)(w + 32 * B),
+               (int32_t*)(w + 32 * B + 8 * E), large ? -1 : (int)(g_twin_calls.fetch_add(1) % kTickets), (int)nblk};
+    const size_t lds = (size_t)12 * spb * cap + (size_t)(NT / 64) * 8;
+    const dim3 grid((unsigned)nblk, (unsigned)nch);
+    if (NT == 256) hipLaunchKernelGGL(k_twin_lds<256>, grid, dim3(256), lds, stream, a, G, cap);
+    else if (NT == 512) hipLaunchKernelGGL(k_twin_lds<512>, grid, dim3(512), lds, stream, a, G, cap);
+    else hipLaunchKernelGGL(k_twin_lds<1024>, grid, dim3(1024), lds, stream, a, G, cap);
+    CAL_CHECK_LAUNCH("k_twin_lds");
+    if (large) {
+        hipLaunchKernelGGL(k_twin_merge, dim3((unsigned)B), dim3(TNT), 0, stream, a);
+        CAL_CHECK_LAUNCH("k_twin_merge");
+        hipLaunchKernelGGL(k_twin_totals, dim3(1), dim3(TNT), 0, stream, a, nblk + B);
+        CAL_CHECK_LAUNCH("k_twin_totals");
+    }
+    return 0;
+}

@@ -670,3 +670,123 @@ HOST_EXPORT int cal_subgraph_extract(const int64_t* edge_index, int64_t E, int64
     totals[0] = Nt; totals[1] = Et; totals[2] = mn; totals[3] = me;
     return 0;
 }
+
+// ---- undirected explanations: the reverse-edge map and the ranking of edge pairs.  The same pairing rule, representatives,
+// symmetrised scores and compaction order as cal_amd/csrc/twin.hip and explain.hip, so every output agrees bit for bit.
+HOST_EXPORT int64_t cal_edge_twin_ws(int64_t E, int64_t B) { return 32 * (B > 0 ? B : 0) + 12 * (E > 0 ? E : 0) + 256; }
+
+HOST_EXPORT int cal_edge_twin(const int64_t* edge_index, int64_t E, const int64_t* ptr, const int64_t* edge_ptr, int64_t B,
+                              int64_t max_edges, int32_t* twin, int64_t* totals, void*, int64_t, void*) {
+    HOST_REQUIRE(E >= 0 && B >= 0 && max_edges >= 0, "E, B, max_edges must be >= 0");
+    HOST_REQUIRE(E < ((int64_t)1 << 31), "2^31 columns or more are not supported (twin is int32)");
+    HOST_REQUIRE(totals, "totals is null");
+    HOST_REQUIRE(B == 0 || (ptr && edge_ptr), "ptr / edge_ptr are null");
+    HOST_REQUIRE(E == 0 || (edge_index && twin), "edge_index / twin are null");
+    int64_t unp = 0, nself = 0;
+    std::vector<std::pair<uint64_t, int64_t>> keys;
+    for (int64_t g = 0; g < B; ++g) {
+        const int64_t nlo = ptr[g], nn = std::max(ptr[g + 1] - nlo, (int64_t)0);
+        const int64_t elo = std::min(std::max(edge_ptr[g], (int64_t)0), E), ehi = std::min(std::max(edge_ptr[g + 1], elo), E);
+        if (ehi - elo > max_edges) {
+            for (int64_t e = elo; e < ehi; ++e) twin[e] = -1;
+            unp += ehi - elo;
+            continue;
+        }
+        keys.clear();
+        for (int64_t e = elo; e < ehi; ++e) {
+            const int64_t u = edge_index[e], v = edge_index[E + e];
+            twin[e] = -1;
+            if (u < nlo || u >= nlo + nn || v < nlo || v >= nlo + nn) continue;
+            if (u == v) { twin[e] = (int32_t)e; ++nself; continue; }
+            const uint64_t x = (uint64_t)(std::min(u, v) - nlo), y = (uint64_t)(std::max(u, v) - nlo);
+            keys.emplace_back(((x * (uint64_t)nn + y) << 1) | (uint64_t)(u > v), e);
+        }
+        std::sort(keys.begin(), keys.end());                  // by key, then column index
+        for (size_t s = 0; s < keys.size();) {                 // one undirected edge: its (u < v) columns, then its (u > v) columns
+            const uint64_t und = keys[s].first >> 1;
+            size_t mid = s, end;
+            while (mid < keys.size() && keys[mid].first == (und << 1)) ++mid;
+            end = mid;
+            while (end < keys.size() && keys[end].first == ((und << 1) | 1)) ++end;
+            const size_t np = std::min(mid - s, end - mid);
+            for (size_t j = 0; j < np; ++j) {
+                twin[keys[s + j].second] = (int32_t)keys[mid + j].second;
+                twin[keys[mid + j].second] = (int32_t)keys[s + j].second;
+            }
+            s = end;
+        }
+        for (int64_t e = elo; e < ehi; ++e) unp += twin[e] < 0;
+    }
+    totals[0] = unp;
+    totals[1] = nself;
+    return 0;
+}
+
+HOST_EXPORT int64_t cal_explain_pairs_ws(int64_t M, int64_t B) {
+    return 14 * (M > 0 ? M : 0) + 8 * (B > 0 ? B : 0) + 512 + cal_explain_ws(M, B);
+}
+
+HOST_EXPORT int cal_explain_rank_pairs(const float* score, int64_t stride, const int64_t* seg_ptr, int64_t B, int64_t M,
+                                       int64_t max_seg, double ratio, int64_t k, const uint8_t* gt, const int32_t* twin,
+                                       int reduce, float* score_out, uint8_t* mask, int32_t* rank, double* metrics, void*,
+                                       int64_t, void*) {
+    HOST_REQUIRE(B >= 0 && M >= 0 && max_seg >= 0 && stride >= 1, "B, M, max_seg must be >= 0 and stride >= 1");
+    HOST_REQUIRE(k >= -2, "k must be >= 0, -1 (ratio) or -2 (ground-truth count)");
+    HOST_REQUIRE(k != -2 || gt, "k = -2 needs gt");
+    HOST_REQUIRE(k != -1 || ratio >= 0.0, "k = -1 needs a ratio >= 0");
+    HOST_REQUIRE(reduce >= 0 && reduce <= 2, "reduce must be 0 (mean), 1 (max) or 2 (min)");
+    HOST_REQUIRE(B == 0 || seg_ptr, "seg_ptr is null");
+    HOST_REQUIRE(M == 0 || (score && twin && score_out && mask && rank), "score / twin / score_out / mask / rank are null");
+    HOST_REQUIRE(M < ((int64_t)1 << 31), "2^31 columns or more are not supported (twin is int32)");
+    // the representatives of every segment, compacted in order into one contiguous batch of segments
+    std::vector<float> cs;
+    std::vector<uint8_t> cgt, cmask;
+    std::vector<int32_t> crank;
+    std::vector<int64_t> cptr(B + 1, 0), rep(M, -1), lens(B, 0);
+    int64_t longest = 0;
+    for (int64_t g = 0; g < B; ++g) {
+        const int64_t lo = std::min(std::max(seg_ptr[g], (int64_t)0), M), hi = std::min(std::max(seg_ptr[g + 1], lo), M);
+        const bool bad = hi - lo > max_seg;
+        for (int64_t e = lo; e < hi; ++e) {
+            int64_t t = twin[e];
+            if (!(t >= lo && t < hi && t != e && twin[t] == e)) t = -1;
+            float sym = score[e * stride];
+            uint8_t pos = gt ? gt[e] != 0 : 0;
+            if (t >= 0) {
+                const float o = score[t * stride], x = e < t ? sym : o, y = e < t ? o : sym;
+                if (reduce == 0) sym = (x + y) * 0.5f;
+                else if (x != x || y != y) sym = NAN;
+                else if (reduce == 1) sym = x >= y ? x : y;
+                else sym = x <= y ? x : y;
+                if (gt) pos |= gt[t] != 0;
+            }
+            score_out[e] = sym;
+            rep[e] = t >= 0 && t < e ? t : e;
+            if (bad || rep[e] != e) continue;
+            cs.push_back(sym);
+            cgt.push_back(pos);
+        }
+        // a segment that is not ranked keeps its length, so the ranking below marks it (NaN metrics)
+        if (bad) { cs.resize(cs.size() + (hi - lo), 0.f); cgt.resize(cgt.size() + (hi - lo), 0); }
+        cptr[g + 1] = (int64_t)cs.size();
+        lens[g] = cptr[g + 1] - cptr[g];
+        if (!bad) longest = std::max(longest, lens[g]);
+    }
+    const int64_t Mc = (int64_t)cs.size();
+    cmask.resize(Mc);
+    crank.resize(Mc);
+    const int rc = cal_explain_rank(cs.data(), 1, cptr.data(), B, Mc, std::min(max_seg, std::max(longest, (int64_t)0)), ratio, k,
+                                    gt ? cgt.data() : nullptr, cmask.data(), crank.data(), metrics, nullptr, 0, nullptr);
+    if (rc != 0) return rc;
+    for (int64_t g = 0; g < B; ++g) {
+        const int64_t lo = std::min(std::max(seg_ptr[g], (int64_t)0), M), hi = std::min(std::max(seg_ptr[g + 1], lo), M);
+        const bool bad = hi - lo > max_seg;
+        int64_t p = cptr[g];
+        for (int64_t e = lo; e < hi; ++e) {                    // (a representative comes before its partner)
+            if (bad) { rank[e] = -1; mask[e] = 0; continue; }
+            if (rep[e] == e) { rep[e] = p++; rank[e] = crank[rep[e]]; mask[e] = cmask[rep[e]]; }
+            else { const int64_t r = rep[rep[e]]; rank[e] = crank[r]; mask[e] = cmask[r]; }
+        }
+    }
+    return 0;
+}

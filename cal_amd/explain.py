@@ -16,6 +16,11 @@ column 1**: ``edge_att[:, 1]`` (``edge_weight_o``) per edge and ``node_att[:, 1]
 * ``fidelity(model, data, ratio=... | k=...)`` / ``eval_fidelity(model, loader, device, ratios=...)``: does the prediction
   rest on the explanation?  The model runs on the whole graph, on the explanation alone and on the graph without it;
   accuracies, fidelity+ / fidelity- and sparsity per readout head.  Needs no ground truth.
+* ``undirected="mean" | "max" | "min"`` on the four calls above: the graphs are undirected and stored as both directions of
+  every edge, but CAL's edge attention is not symmetric, so ``(u, v)`` and ``(v, u)`` carry different scores.  With the
+  keyword, ``edge_twins(data)`` (``cal_edge_twin``) pairs every column with its reverse and the pairs are ranked as one
+  element each (``cal_explain_rank_pairs``): one symmetrised score per undirected edge, symmetric masks, metrics over
+  undirected edges, and fidelity on subgraphs that are symmetric whenever the input was.
 """
 from __future__ import annotations
 
@@ -27,7 +32,19 @@ import torch
 from . import _lib
 from .plan import _p, _stream
 
-__all__ = ["Explanation", "explain", "eval_explanation", "rank_segments", "extract_subgraph", "fidelity", "eval_fidelity"]
+__all__ = ["Explanation", "explain", "eval_explanation", "rank_segments", "rank_segment_pairs", "edge_twins",
+           "extract_subgraph", "fidelity", "eval_fidelity"]
+
+_REDUCE = {"mean": 0, "max": 1, "min": 2}
+
+
+def _reduce_code(undirected) -> Optional[int]:
+    """``None`` (directed ranking) or the ``reduce`` argument of cal_explain_rank_pairs."""
+    if undirected is None:
+        return None
+    if undirected not in _REDUCE:
+        raise ValueError('undirected must be None, "mean", "max" or "min"')
+    return _REDUCE[undirected]
 
 
 def _k_code(ratio, k) -> Tuple[int, float]:
@@ -81,6 +98,46 @@ def rank_segments(score: torch.Tensor, seg_ptr: torch.Tensor, max_seg: int, *, r
     return mask.view(torch.bool), rank, met
 
 
+def rank_segment_pairs(score: torch.Tensor, seg_ptr: torch.Tensor, max_seg: int, twin: torch.Tensor, reduce: str = "mean", *,
+                       ratio=None, k=None, gt: Optional[torch.Tensor] = None, metrics: bool = False):
+    """One ``cal_explain_rank_pairs`` call: ``rank_segments`` with every column and its ``twin`` (int32 [M], as ``edge_twins``
+    gives it for columns grouped by graph) ranked as one element under the ``reduce`` of their two scores.
+
+    Returns ``(mask bool [M], rank int32 [M], metrics fp64 [B, 4] or None, score float32 [M])``: both columns of a pair carry
+    the pair's rank, mask and symmetrised score; ``k`` / ``ratio`` / the metrics count pairs, not columns."""
+    if score.dim() != 1 or score.dtype != torch.float32:
+        raise TypeError("score must be a 1-D float32 tensor")
+    rc = _reduce_code(reduce)
+    if rc is None:
+        raise ValueError('reduce must be "mean", "max" or "min"')
+    kc, rt = _k_code(ratio, k)
+    if kc == -2 and gt is None:
+        raise ValueError('k="gt" needs the ground truth')
+    dev = score.device
+    host = not score.is_cuda
+    M, B = score.numel(), seg_ptr.numel() - 1
+    if twin.numel() != M:
+        raise ValueError("twin must have one entry per score")
+    seg_ptr = seg_ptr.to(device=dev, dtype=torch.long).contiguous()
+    twin = twin.to(device=dev, dtype=torch.int32).contiguous()
+    stride = max(int(score.stride(0)), 1) if M else 1
+    mask = torch.empty(M, dtype=torch.uint8, device=dev)
+    rank = torch.empty(M, dtype=torch.int32, device=dev)
+    out = torch.empty(M, dtype=torch.float32, device=dev)
+    met = torch.empty(B, 4, dtype=torch.float64, device=dev) if metrics else None
+    g8 = None
+    if gt is not None:
+        if gt.numel() != M:
+            raise ValueError("gt must have one entry per score")
+        g8 = gt.to(device=dev, dtype=torch.bool).contiguous().view(torch.uint8)
+    wsb = _lib.query("cal_explain_pairs_ws", M, B, host=host)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    _lib.call("cal_explain_rank_pairs", _p(score) if M else None, stride, _p(seg_ptr), B, M, int(max_seg), rt, kc, _p(g8),
+              _p(twin) if M else None, rc, _p(out) if M else None, _p(mask) if M else None, _p(rank) if M else None, _p(met),
+              _p(ws), wsb, None if host else _stream(), host=host)
+    return mask.view(torch.bool), rank, met, out
+
+
 @dataclass
 class Explanation:
     """Per-graph causal explanation of a batch.  Scores are column 1 (the objects branch ``o``) of the soft masks:
@@ -88,7 +145,10 @@ class Explanation:
     calls.  ``*_rank`` is the 0-based position inside the element's graph (score descending, index ascending), ``*_mask``
     the selection ``rank < k_g``.  ``ptr`` / ``edge_ptr`` [B + 1] give each graph's node / edge ranges; ``edge_ptr`` is
     ``None`` when the batch's edge columns are not grouped by graph.  ``metrics`` (when a ground truth was given):
-    ``{"edge": [B, 4], "node": [B, 4]}`` fp64 rows ``k_g, hits, P, ROC-AUC``."""
+    ``{"edge": [B, 4], "node": [B, 4]}`` fp64 rows ``k_g, hits, P, ROC-AUC``.  With ``explain(..., undirected=...)``:
+    ``edge_twin`` int32 [E] is the reverse column of every edge column (-1: none, itself for a self loop), ``edge_score``
+    the symmetrised score, ``edge_rank`` / ``edge_mask`` / the edge metrics count undirected edges and
+    ``edge_mask[e] == edge_mask[edge_twin[e]]``; ``edge_twin`` is ``None`` otherwise."""
     edge_score: torch.Tensor
     node_score: torch.Tensor
     edge_mask: torch.Tensor
@@ -99,6 +159,7 @@ class Explanation:
     edge_ptr: Optional[torch.Tensor]
     edge_index: torch.Tensor
     metrics: Optional[dict] = None
+    edge_twin: Optional[torch.Tensor] = None
 
     def subgraph(self, g: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """Graph ``g``'s selected nodes (global ids, ascending) and selected edges ([2, k] global edge_index columns)."""
@@ -170,11 +231,65 @@ class _Layout:
         rank[self.order] = rank_s
         return mask, rank, met
 
+    def twins(self, edge_index):
+        """``(twin int32 [E], totals int64 [2])`` of one ``cal_edge_twin`` call over the columns in ``order`` (twin indexes that
+        order); totals = columns without a twin, self loops; both stay on the device.  Computed once per layout."""
+        if getattr(self, "_twins", None) is None:
+            ei = edge_index if self.order is None else edge_index[:, self.order]
+            ei = ei.to(torch.long).contiguous()
+            dev, host = ei.device, not ei.is_cuda
+            E = int(ei.size(1))
+            wsb = _lib.query("cal_edge_twin_ws", E, self.B, host=host)
+            buf = torch.empty(2 + (wsb + 7) // 8, dtype=torch.long, device=dev)      # totals and the workspace
+            twin = torch.empty(E, dtype=torch.int32, device=dev)
+            _lib.call("cal_edge_twin", _p(ei) if E else None, E, _p(self.ptr.contiguous()), _p(self.edge_ptr.contiguous()), self.B,
+                      int(self.max_edges), _p(twin) if E else None, _p(buf), _p(buf[2:]), 8 * (buf.numel() - 2),
+                      None if host else _stream(), host=host)
+            self._twins = (twin, buf[:2])
+        return self._twins
+
+    def caller_twin(self, twin):
+        """``twin`` (over the columns in ``order``) as a map between the caller's columns."""
+        if self.order is None:
+            return twin
+        out = torch.empty_like(twin)
+        mapped = self.order[twin.clamp(min=0).long()].to(torch.int32)
+        out[self.order] = torch.where(twin >= 0, mapped, twin)
+        return out
+
+    def rank_edge_pairs(self, score, edge_index, reduce, **kw):
+        """``rank_edges`` over undirected edges -> ``(mask, rank, metrics, symmetrised score)`` in the caller's column order."""
+        twin = self.twins(edge_index)[0]
+        if self.order is None:
+            return rank_segment_pairs(score, self.edge_ptr, self.max_edges, twin, reduce, **kw)
+        gt = kw.pop("gt", None)
+        res = rank_segment_pairs(score[self.order].contiguous(), self.edge_ptr, self.max_edges, twin, reduce,
+                                 gt=None if gt is None else gt[self.order], **kw)
+        mask, rank, sym = torch.empty_like(res[0]), torch.empty_like(res[1]), torch.empty_like(res[3])
+        mask[self.order], rank[self.order], sym[self.order] = res[0], res[1], res[3]
+        return mask, rank, res[2], sym
+
     def rank_nodes(self, score, **kw):
         return rank_segments(score, self.ptr, self.max_nodes, **kw)
 
 
-def explain(model, data, *, ratio=None, k=None, node_ratio=None, node_k=None, edge_gt=None, node_gt=None) -> Explanation:
+def edge_twins(data):
+    """The reverse-edge map of a batch: ``(twin int32 [E], n_unpaired, n_self)`` from one ``cal_edge_twin`` call (HIP for CUDA
+    tensors, libcalhost for CPU tensors; no read-back).
+
+    Inside each graph the j-th column equal to ``(u, v)``, ``u != v``, pairs with the j-th column equal to ``(v, u)`` (both in
+    ascending column order): ``twin[e]`` is the partner's column, ``-1`` without one; a self loop is its own twin; a column
+    with an endpoint outside its graph pairs with nothing.  So ``twin[twin[e]] == e`` wherever ``twin[e] >= 0``.
+    ``n_unpaired`` (columns with ``twin < 0``) and ``n_self`` (self loops) are 0-dim int64 tensors on ``data``'s device;
+    ``int()`` reads one back.  A batch whose columns are not grouped by graph is reordered by graph (stable), as the ranking
+    does, and the twin indices are mapped back to the caller's column order."""
+    lay = _Layout(data)
+    twin, totals = lay.twins(data.edge_index)
+    return lay.caller_twin(twin), totals[0], totals[1]
+
+
+def explain(model, data, *, ratio=None, k=None, node_ratio=None, node_k=None, edge_gt=None, node_gt=None,
+            undirected=None) -> Explanation:
     """Per-graph causal explanation of ``data`` by ``model`` (a CausalGCN / CausalGAT / CausalGIN).
 
     Exactly one of ``ratio`` (select ``ceil(ratio * m_g)`` edges of each graph) or ``k`` (the top ``k``; ``"gt"``: as many
@@ -182,7 +297,13 @@ def explain(model, data, *, ratio=None, k=None, node_ratio=None, node_k=None, ed
     edges' rule.  ``edge_gt`` / ``node_gt``: bool ground truth ([E] / [N], e.g. ``spmotif.ground_truth``) -> per-graph
     metrics.  One eval-mode forward with the identity permutation (the scores come before the readout), then one ranking
     call each for edges and nodes.  Parameters, optimizer state, the engine's step counter, BatchNorm statistics and the
-    Python / torch RNG states are left as they were, and ``model.training`` is restored."""
+    Python / torch RNG states are left as they were, and ``model.training`` is restored.
+
+    ``undirected`` = ``"mean"`` | ``"max"`` | ``"min"``: rank undirected edges.  Every edge column is paired with its reverse
+    (``edge_twins``); a pair is one element with that reduction of its two scores (an unpaired column keeps its own), ``k`` /
+    ``ratio`` / the edge metrics count pairs (one is ground truth iff either column is), and both columns receive the pair's
+    score, rank and mask.  Two more launches than the directed ranking, plus the twin map's one; nodes are ranked as before."""
+    _reduce_code(undirected)
     ek, er = k, ratio
     _k_code(er, ek)
     if node_ratio is None and node_k is None:
@@ -198,9 +319,16 @@ def explain(model, data, *, ratio=None, k=None, node_ratio=None, node_k=None, ed
         with torch.no_grad():
             edge, node = _scores(model, data)
             lay = _Layout(data)
-            em, er_, emet = lay.rank_edges(edge, ratio=er, k=ek, gt=edge_gt, metrics=edge_gt is not None)
+            twin = None
+            if undirected is None:
+                em, er_, emet = lay.rank_edges(edge, ratio=er, k=ek, gt=edge_gt, metrics=edge_gt is not None)
+                edge = edge.clone()
+            else:
+                em, er_, emet, edge = lay.rank_edge_pairs(edge, data.edge_index, undirected, ratio=er, k=ek, gt=edge_gt,
+                                                          metrics=edge_gt is not None)
+                twin = lay.caller_twin(lay.twins(data.edge_index)[0])
             nm, nr, nmet = lay.rank_nodes(node, ratio=node_ratio, k=node_k, gt=node_gt, metrics=node_gt is not None)
-            edge, node = edge.clone(), node.clone()
+            node = node.clone()
     finally:
         model.train(was_training)
     metrics = None
@@ -208,7 +336,7 @@ def explain(model, data, *, ratio=None, k=None, node_ratio=None, node_k=None, ed
         metrics = {"edge": emet, "node": nmet}
     return Explanation(edge_score=edge, node_score=node, edge_mask=em, node_mask=nm, edge_rank=er_, node_rank=nr,
                        ptr=lay.ptr, edge_ptr=lay.edge_ptr if lay.order is None else None, edge_index=data.edge_index,
-                       metrics=metrics)
+                       metrics=metrics, edge_twin=twin)
 
 
 _KEYS = ("precision", "recall", "auc")
@@ -226,13 +354,15 @@ def _accumulate(sums: torch.Tensor, met: torch.Tensor, off: int):
     sums[off:off + 6] += vals
 
 
-def eval_explanation(model, loader, device, *, k="gt", ratio=None) -> dict:
+def eval_explanation(model, loader, device, *, k="gt", ratio=None, undirected=None) -> dict:
     """Mean edge / node precision@k, recall@k and ROC-AUC of the causal scores against the SPMotif motif
     (``spmotif.ground_truth``), over the graphs where each is defined (precision: k_g > 0; recall: a motif; AUC: a motif
     and a non-motif element).  ``k="gt"`` selects as many elements as the graph's motif has (precision@k = recall@k);
     ``ratio`` selects ``ceil(ratio * m_g)`` instead.  Per mini-batch: one eval forward, the ground truth and one ranking
-    call each for edges and nodes; the sums stay on the device until one read-back at the end."""
+    call each for edges and nodes; the sums stay on the device until one read-back at the end.  ``undirected`` (as in
+    ``explain``): the edge figures are over undirected edges, one symmetrised score per edge."""
     from .spmotif import ground_truth
+    _reduce_code(undirected)
     if ratio is not None:
         k = None
     was_training = model.training
@@ -245,7 +375,10 @@ def eval_explanation(model, loader, device, *, k="gt", ratio=None) -> dict:
                 edge, node = _scores(model, data)
                 node_gt, edge_gt = ground_truth(data)
                 lay = _Layout(data)
-                _, _, emet = lay.rank_edges(edge, ratio=ratio, k=k, gt=edge_gt, metrics=True)
+                if undirected is None:
+                    emet = lay.rank_edges(edge, ratio=ratio, k=k, gt=edge_gt, metrics=True)[2]
+                else:
+                    emet = lay.rank_edge_pairs(edge, data.edge_index, undirected, ratio=ratio, k=k, gt=edge_gt, metrics=True)[2]
                 _, _, nmet = lay.rank_nodes(node, ratio=ratio, k=k, gt=node_gt, metrics=True)
                 _accumulate(sums, emet, 0)
                 _accumulate(sums, nmet, 6)
@@ -363,11 +496,12 @@ def _untiled(data, lay):
     return b
 
 
-def _fidelity_sums(model, data, specs, use: str) -> torch.Tensor:
+def _fidelity_sums(model, data, specs, use: str, undirected=None) -> torch.Tensor:
     """One batch's fidelity sums [len(specs), 18] fp64 on the device, ``specs`` a list of (ratio, k): per head (c, o, co) the
     hits on the full / kept / removed graph and the sums of p_full - p_drop and p_full - p_keep at the full graph's argmax;
     then the graph count, the kept and the total element count.  One forward for the scores, one on the whole graph, two per
-    spec.  Called in eval mode under no_grad."""
+    spec.  ``undirected``: the edge masks select undirected edges (both columns of a pair or neither); the twin map is built
+    once per batch.  Called in eval mode under no_grad."""
     edge, node = _scores(model, data)
     edge, node = edge.clone(), node.clone()
     lay = _Layout(data)
@@ -377,7 +511,12 @@ def _fidelity_sums(model, data, specs, use: str) -> torch.Tensor:
     pf = full.gather(-1, yhat).exp()
     out = []
     for ratio, k in specs:
-        em = lay.rank_edges(edge, ratio=ratio, k=k)[0] if use != "nodes" else None
+        if use == "nodes":
+            em = None
+        elif undirected is None:
+            em = lay.rank_edges(edge, ratio=ratio, k=k)[0]
+        else:
+            em = lay.rank_edge_pairs(edge, data.edge_index, undirected, ratio=ratio, k=k)[0]
         nm = lay.rank_nodes(node, ratio=ratio, k=k)[0] if use != "edges" else None
         rows = [(yhat.squeeze(-1) == y).sum(-1)]
         gaps = []
@@ -407,7 +546,7 @@ def _fidelity_report(row) -> dict:
     return res
 
 
-def fidelity(model, data, *, ratio=None, k=None, use: str = "edges") -> dict:
+def fidelity(model, data, *, ratio=None, k=None, use: str = "edges", undirected=None) -> dict:
     """Does ``model``'s prediction on ``data`` rest on its causal subgraph?  The top ``ratio`` / ``k`` of the causal scores
     (as ``explain`` selects them; ``use``: the edge masks, the node masks or both) is extracted twice with ``relabel=False``
     -- the explanation alone and the batch with it removed -- and the model runs in eval mode with the identity permutation
@@ -420,8 +559,13 @@ def fidelity(model, data, *, ratio=None, k=None, use: str = "edges") -> dict:
 
     and ``sparsity`` = 1 - kept / total over the elements ``use`` names, ``graphs`` the batch size.  One read-back at the
     end.  Like ``explain``, it leaves parameters, optimizer state, the engine's step counter, BatchNorm statistics, the RNG
-    states and ``model.training`` as they were."""
+    states and ``model.training`` as they were.
+
+    ``undirected`` (as in ``explain``): the edge masks select undirected edges, so the explanation and the rest are both
+    symmetric graphs whenever ``data`` is -- the kind of graph the model was trained on.  ``ratio`` / ``k`` then count
+    undirected edges; ``sparsity`` keeps counting edge columns."""
     _k_code(ratio, k)
+    _reduce_code(undirected)
     if k == "gt":
         raise ValueError('fidelity has no ground truth: k must be an int >= 0')
     _use_masks(use, None, None)
@@ -429,17 +573,19 @@ def fidelity(model, data, *, ratio=None, k=None, use: str = "edges") -> dict:
     model.eval()
     try:
         with torch.no_grad():
-            sums = _fidelity_sums(model, data, [(ratio, k)], use)
+            sums = _fidelity_sums(model, data, [(ratio, k)], use, undirected)
     finally:
         model.train(was_training)
     return _fidelity_report(sums[0].tolist())
 
 
-def eval_fidelity(model, loader, device, *, ratios=(0.1, 0.2, 0.3, 0.5), use: str = "edges") -> dict:
+def eval_fidelity(model, loader, device, *, ratios=(0.1, 0.2, 0.3, 0.5), use: str = "edges", undirected=None) -> dict:
     """``fidelity`` over a loader at every ratio of ``ratios``: ``{ratio: report}``, each report as ``fidelity`` returns it
     with the means taken over all graphs of the loader.  The counterpart of ``eval_explanation`` for data without a ground
     truth.  Per mini-batch one forward for the scores, one on the whole batch and, per ratio, one ranking call each for edges
-    and nodes, two extractions and two forwards; the sums stay on the device until one read-back at the end."""
+    and nodes, two extractions and two forwards; the sums stay on the device until one read-back at the end.  ``undirected``:
+    as in ``fidelity`` (one twin map per mini-batch, shared by the ratios)."""
+    _reduce_code(undirected)
     ratios = [float(r) for r in ratios]
     specs = [(r, None) for r in ratios]
     for r, _ in specs:
@@ -451,7 +597,7 @@ def eval_fidelity(model, loader, device, *, ratios=(0.1, 0.2, 0.3, 0.5), use: st
     try:
         with torch.no_grad():
             for data in loader:
-                sums += _fidelity_sums(model, data.to(device), specs, use)
+                sums += _fidelity_sums(model, data.to(device), specs, use, undirected)
     finally:
         model.train(was_training)
     return {r: _fidelity_report(row) for r, row in zip(ratios, sums.tolist())}

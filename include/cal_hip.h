@@ -33,6 +33,9 @@ extern "C" {
 
 CAL_API const char* cal_last_error(void);
 CAL_API int cal_version(void);
+/* kernel launches this library has enqueued so far in this process (every launch site counts itself; memsets do not):
+ * the difference around a call is the call's launch count */
+CAL_API int64_t cal_launch_count(void);
 
 /* ---- GraphPlan ---------------------------------------------------------------
  * COO -> CSR-by-destination and CSR-by-source with edge ids, explicit self loops
@@ -290,6 +293,36 @@ CAL_API int cal_subgraph_extract(const int64_t* edge_index, int64_t E, int64_t N
                                  const float* x, int64_t F, int64_t* edge_index_out, int64_t* ptr_out, int64_t* edge_ptr_out,
                                  int64_t* batch_out, float* x_out, int64_t* node_map, int64_t* edge_map, int64_t* totals,
                                  void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- undirected explanations: the reverse-edge ("twin") map and the ranking of edge pairs -------------------------- */
+/* Graph g owns the nodes [ptr[g], ptr[g+1]) and the edge_index ([2, E] int64) columns [edge_ptr[g], edge_ptr[g+1]), as in
+ * cal_subgraph_extract.  Among the columns of g equal to (u, v), u != v, the j-th in ascending column order pairs with the
+ * j-th column of g equal to (v, u): twin[e] (int32 [E]) is the partner's global column index, -1 when there is no j-th
+ * partner.  A self loop is its own twin (twin[e] = e); a column with an endpoint outside its graph's node range gets -1 and
+ * pairs with nothing.  So twin[twin[e]] == e wherever twin[e] >= 0, and the output is uniquely determined (duplicates
+ * allowed).  totals [2] int64 on the device: columns with twin < 0, self loops.  max_edges: host-known bound on every
+ * segment, it picks the paths (a longer segment gets -1 throughout).  ws: 8-byte aligned, cal_edge_twin_ws bytes.  Every
+ * segment within cal_explain_lds_cap(): one launch; else three.  No read-back, no synchronisation, on `stream`; no value is
+ * accumulated atomically (the one-launch path finds the workgroup that finishes last with a completion ticket, and that
+ * workgroup sums the per-workgroup counts in order). */
+CAL_API int64_t cal_edge_twin_ws(int64_t E, int64_t B);
+CAL_API int cal_edge_twin(const int64_t* edge_index, int64_t E, const int64_t* ptr, const int64_t* edge_ptr, int64_t B,
+                          int64_t max_edges, int32_t* twin, int64_t* totals, void* ws, int64_t ws_bytes, void* stream);
+/* cal_explain_rank over undirected edges: the arguments of cal_explain_rank (segments = each graph's columns) plus `twin`
+ * (as cal_edge_twin writes it; a column pairs with twin[e] iff that lies in its segment, differs from e and points back),
+ * `reduce` (0 mean, 1 max, 2 min) and score_out [M].  The lower column of a pair represents it; unpaired columns and self
+ * loops represent themselves; m'_g = representatives of g.  score_out[e], fp32: (s[e] + s[t]) * 0.5f, or the maximum /
+ * minimum of the two (NaN if either is, as torch.maximum / torch.minimum); s[e] for an unpaired column.  The representatives
+ * of a segment are ranked by that score descending, then column index ascending, NaN lowest; k_g = min(k, m'_g),
+ * min(m'_g, ceil(ratio m'_g)) or the ground-truth representatives (one is ground truth iff either of its columns is); both
+ * columns of a pair receive the representative's rank and mask.  metrics [B, 4]: k_g, hits, P, ROC-AUC over the
+ * representatives.  A segment above max_seg is not ranked (rank -1, mask 0, NaN metrics; score_out is still written).  ws:
+ * 16-byte aligned, cal_explain_pairs_ws bytes.  Two launches (symmetrise + compact, scatter) around cal_explain_rank's. */
+CAL_API int64_t cal_explain_pairs_ws(int64_t M, int64_t B);
+CAL_API int cal_explain_rank_pairs(const float* score, int64_t stride, const int64_t* seg_ptr, int64_t B, int64_t M,
+                                   int64_t max_seg, double ratio, int64_t k, const uint8_t* gt, const int32_t* twin, int reduce,
+                                   float* score_out, uint8_t* mask, int32_t* rank, double* metrics, void* ws, int64_t ws_bytes,
+                                   void* stream);
 
 #ifdef __cplusplus
 }

@@ -2,9 +2,12 @@
 the same scores (stable sort by score, stable sort by graph id, masks), and eval_explanation against eval_acc_causal over
 the same loader; and the fidelity leg: the HIP subgraph extraction (cal_subgraph_extract, with its one read-back) against the
 plain-torch composition of the same extraction (nonzero / cumsum / index_select) on the same device, and one whole fidelity()
-call.  Device events around synchronised regions, after warm-up; one JSON line per shape.
+call.  Device events around synchronised regions, after warm-up; one JSON line per shape.  ``--undirected`` prints one more
+line instead: explain() and eval_fidelity() at the SPMotif headline batch, directed against undirected ("mean"), and the
+twin map and the pair ranking alone, all in this one process.
 
     python scripts/bench_explain.py [--shapes headline,nodenum15,config5] [--iters 50]
+    python scripts/bench_explain.py --undirected [--iters 50]
 """
 import argparse
 import json
@@ -18,7 +21,8 @@ sys.path.insert(0, ROOT)
 
 from cal_amd import model as M, spmotif, synth          # noqa: E402
 from cal_amd.data import Batch, DataLoader               # noqa: E402
-from cal_amd.explain import _Layout, _scores, eval_explanation, extract_subgraph, fidelity, rank_segments   # noqa: E402
+from cal_amd.explain import (_Layout, _scores, eval_explanation, eval_fidelity, explain, extract_subgraph, fidelity,   # noqa: E402
+                             rank_segments)
 from cal_amd.train_causal import eval_acc_causal         # noqa: E402
 
 SHAPES = {
@@ -74,16 +78,49 @@ def torch_extract(ei, ptr, eptr, batch, x, keep, relabel):
     return new, ptr, eptr2, batch, x, emap, mn, me
 
 
+def undirected_line(m, dev, iters):
+    """explain / eval_fidelity at the headline batch, directed against undirected, in one process."""
+    sh = SHAPES["headline"]
+    B = sh["B"]
+    b = Batch.from_data_list(sh["graphs"](B)).to(dev)
+    node_gt, edge_gt = spmotif.ground_truth(b)
+    edge = _scores(m, b)[0].clone()
+
+    def twins():
+        return _Layout(b).twins(b.edge_index)
+
+    lay = _Layout(b)
+    lay.twins(b.edge_index)
+    out = dict(shape="headline", graphs=B, edges=int(b.edge_index.size(1)), max_edges=lay.max_edges,
+               unpaired=int(lay.twins(b.edge_index)[1][0]))
+    kw = dict(k="gt", edge_gt=edge_gt, node_gt=node_gt)
+    out["explain_directed_ms"] = round(_time(lambda: explain(m, b, **kw), iters), 4)
+    out["explain_undirected_ms"] = round(_time(lambda: explain(m, b, undirected="mean", **kw), iters), 4)
+    out["edge_twin_ms"] = round(_time(twins, iters), 4)
+    out["rank_edges_ms"] = round(_time(lambda: lay.rank_edges(edge, k="gt", gt=edge_gt, metrics=True), iters), 4)
+    out["rank_edge_pairs_ms"] = round(_time(lambda: lay.rank_edge_pairs(edge, b.edge_index, "mean", k="gt", gt=edge_gt,
+                                                                        metrics=True), iters), 4)
+    n = max(3, iters // 5)
+    out["eval_fidelity_directed_ms"] = round(_time(lambda: eval_fidelity(m, [b], dev), n, warmup=2), 4)
+    out["eval_fidelity_undirected_ms"] = round(_time(lambda: eval_fidelity(m, [b], dev, undirected="mean"), n, warmup=2), 4)
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="headline,nodenum15,config5")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--batches", type=int, default=4)
+    ap.add_argument("--undirected", action="store_true", help="the directed-against-undirected line at the headline batch")
     a = ap.parse_args()
     dev = "cuda"
     args = argparse.Namespace(layers=3, hidden=128, with_random=True, without_node_attention=False,
                               without_edge_attention=False, fc_num="222", cat_or_add="add", c=0.5, o=1.0, co=0.5,
                               eval_random=False)
+    if a.undirected:
+        torch.manual_seed(0)
+        undirected_line(M.CausalGCN(10, 4, args).to(dev).eval(), dev, a.iters)
+        return
     for name in a.shapes.split(","):
         sh = SHAPES[name]
         B = sh["B"]
