@@ -790,3 +790,88 @@ HOST_EXPORT int cal_explain_rank_pairs(const float* score, int64_t stride, const
     }
     return 0;
 }
+
+// ---- all-pairs intervention readout (cal_amd/csrc/intervene.hip): the same folded form, dot products accumulated in fp64 ----
+HOST_EXPORT int64_t cal_intervene_ws(int64_t, int64_t, int64_t, int64_t) { return 0; }
+
+HOST_EXPORT int cal_intervene_pairs(const float* xo, int64_t B, const float* xc, int64_t M, int64_t H, int64_t C, int cat,
+                                    const float* bn1_w, const float* bn1_b, const float* bn1_mean, const float* bn1_var, float bn1_eps,
+                                    const float* fc1_w, const float* fc1_b, const float* bn2_w, const float* bn2_b,
+                                    const float* bn2_mean, const float* bn2_var, float bn2_eps, const float* fc2_w,
+                                    const float* fc2_b, const int64_t* ref, float* p_do, int32_t* hits, float* p_min,
+                                    int32_t* j_min, float* logp_pairs, void*, int64_t, void*) {
+    HOST_REQUIRE(B >= 0, "B must be >= 0");
+    HOST_REQUIRE(M >= 1, "the bank is empty (M must be >= 1)");
+    HOST_REQUIRE(H >= 1 && C >= 1, "H and C must be >= 1");
+    if (B == 0) return 0;
+    HOST_REQUIRE(xo && xc && p_do && hits && p_min && j_min, "xo / xc / an output is null");
+    HOST_REQUIRE(bn1_w && bn1_b && bn1_mean && bn1_var && fc1_w && fc1_b && bn2_w && bn2_b && bn2_mean && bn2_var && fc2_w && fc2_b,
+                 "a parameter of the co head is null");
+    const int64_t Kin = cat ? 2 * H : H, koff = cat ? H : 0;
+    std::vector<double> s1(Kin), t1(Kin), cst(H), b2f(C);
+    std::vector<float> A((size_t)B * H), Cb((size_t)M * H), W2f((size_t)C * H);
+    for (int64_t k = 0; k < Kin; ++k) {
+        s1[k] = (double)bn1_w[k] / sqrt((double)bn1_var[k] + (double)bn1_eps);
+        t1[k] = (double)bn1_b[k] - (double)bn1_mean[k] * s1[k];
+    }
+    for (int64_t n = 0; n < H; ++n) {
+        double s = fc1_b[n];
+        for (int64_t k = 0; k < Kin; ++k) s += (double)fc1_w[n * Kin + k] * t1[k];
+        cst[n] = s;
+    }
+    for (int64_t c = 0; c < C; ++c) {
+        double s = fc2_b[c];
+        for (int64_t k = 0; k < H; ++k) {
+            const double sc = (double)bn2_w[k] / sqrt((double)bn2_var[k] + (double)bn2_eps);
+            W2f[c * H + k] = (float)((double)fc2_w[c * H + k] * sc);
+            s += (double)fc2_w[c * H + k] * ((double)bn2_b[k] - (double)bn2_mean[k] * sc);
+        }
+        b2f[c] = s;
+    }
+#pragma omp parallel for schedule(static)
+    for (int64_t r = 0; r < B + M; ++r) {
+        const bool isA = r < B;
+        const float* x = isA ? xo + r * H : xc + (r - B) * H;
+        float* out = isA ? A.data() + r * H : Cb.data() + (r - B) * H;
+        const int64_t ko = isA ? koff : 0;
+        for (int64_t n = 0; n < H; ++n) {
+            double s = isA ? cst[n] : 0.0;
+            for (int64_t k = 0; k < H; ++k) s += (double)fc1_w[n * Kin + ko + k] * s1[ko + k] * (double)x[k];
+            out[n] = (float)s;
+        }
+    }
+#pragma omp parallel for schedule(static)
+    for (int64_t g = 0; g < B; ++g) {
+        std::vector<float> h(H);
+        std::vector<double> z(C), ps(C, 0.0);
+        const int64_t rf = (ref && ref[g] >= 0 && ref[g] < C) ? ref[g] : -1;
+        int64_t nh = 0, jm = -1;
+        float mn = INFINITY;
+        for (int64_t j = 0; j < M; ++j) {
+            for (int64_t k = 0; k < H; ++k) h[k] = std::max(A[g * H + k] + Cb[j * H + k], 0.f);
+            int64_t arg = 0;
+            for (int64_t c = 0; c < C; ++c) {
+                double s = b2f[c];
+                for (int64_t k = 0; k < H; ++k) s += (double)h[k] * (double)W2f[c * H + k];
+                z[c] = s;
+                if (s > z[arg]) arg = c;
+            }
+            double se = 0.0;
+            for (int64_t c = 0; c < C; ++c) se += exp(z[c] - z[arg]);
+            const double lse = z[arg] + log(se);
+            for (int64_t c = 0; c < C; ++c) {
+                const float lp = (float)(z[c] - lse);
+                if (logp_pairs) logp_pairs[(g * M + j) * C + c] = lp;
+                const float p = expf(lp);
+                ps[c] += (double)p;
+                if (c == rf && (p < mn || jm < 0)) { mn = p; jm = j; }
+            }
+            nh += arg == rf;
+        }
+        for (int64_t c = 0; c < C; ++c) p_do[g * C + c] = (float)(ps[c] / (double)M);
+        hits[g] = rf < 0 ? 0 : (int32_t)nh;
+        p_min[g] = rf < 0 ? NAN : mn;
+        j_min[g] = rf < 0 ? -1 : (int32_t)jm;
+    }
+    return 0;
+}

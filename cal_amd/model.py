@@ -160,6 +160,34 @@ class _CausalBase(torch.nn.Module):
             node = ops.node_attention_split(x, self.node_att_mlp.weight, self.node_att_mlp.bias)[2][:, 1]
         return edge, node
 
+    def _pooled(self, data):
+        """Operator-level forward up to the add-pool (model.py:85-116): the pooled trivial rows ``xc`` [B, H] and objects rows
+        ``xo`` [B, H], the inputs of the three readouts.  Runs in the module's current mode; ``cal_amd.intervene`` calls it in
+        eval mode under ``no_grad``."""
+        x = data.x if data.x is not None else data.feat
+        edge_index = data.edge_index
+        plan = plan_of(data)
+        x = self.bn_feat(x)
+        x = self.conv_feat(x, edge_index, relu=True)
+        x = self._backbone(x, edge_index, plan)
+        if getattr(self, "without_edge_attention", False):
+            edge_att = torch.full((2, plan.E), 0.5, dtype=x.dtype, device=x.device)
+        else:
+            edge_att = ops.edge_attention(x, self.edge_att_mlp.weight, self.edge_att_mlp.bias, plan)
+        if getattr(self, "without_node_attention", False):
+            xc = 0.5 * x
+            xo = 0.5 * x
+        else:
+            xc, xo, _ = ops.node_attention_split(x, self.node_att_mlp.weight, self.node_att_mlp.bias)
+        xc = self.context_convs(self.bnc(xc), edge_index, edge_att[0], plan=plan, relu=True)
+        xo = self.objects_convs(self.bno(xo), edge_index, edge_att[1], plan=plan, relu=True)
+        return ops.add_pool(xc, plan), ops.add_pool(xo, plan)
+
+    def intervene(self, data, **kw):
+        """``cal_amd.intervene.intervene(self, data, **kw)``: the ``co`` head over every (graph, trivial partner) pair."""
+        from .intervene import intervene
+        return intervene(self, data, **kw)
+
     def explain(self, data, **kw):
         """``cal_amd.explain.explain(self, data, **kw)``: per-graph top-k causal subgraphs of ``data``."""
         from .explain import explain

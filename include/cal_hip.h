@@ -324,6 +324,26 @@ CAL_API int cal_explain_rank_pairs(const float* score, int64_t stride, const int
                                    float* score_out, uint8_t* mask, int32_t* rank, double* metrics, void* ws, int64_t ws_bytes,
                                    void* stream);
 
+/* ---- all-pairs intervention readout: the eval-mode `co` head (model.py:145-164) on every (objects row, trivial row) pair -----
+ * xo [B, H], xc [M, H] (the bank of trivial rows: the batch's own or any other set); cat = cat_or_add "cat".  The head's
+ * eval-mode parameters: fc1_bn_co (weight, bias, running mean, running var [Kin], eps), fc1_co ([H, Kin], [H]), fc2_bn_co ([H]),
+ * fc2_co ([C, H], [C]); Kin = 2H with cat, else H.  logp(g, j) = log_softmax(fc2(bn2(relu(fc1(bn1(x)))))), x = xc_j + xo_g or
+ * cat(xc_j, xo_g).  Outputs: p_do [B, C] = (1 / M) sum_j exp(logp(g, j)) (fp32 inside a chunk of 64 partners, fp64 across the
+ * chunks); with ref [B] int64 (the class each graph is judged against): hits [B] int32 = #{j : argmax_c logp(g, j) == ref[g]} (the
+ * lowest class on equal values), p_min [B] = min_j exp(logp(g, j)[ref[g]]), j_min [B] int32 = the lowest j attaining it; ref null
+ * or ref[g] outside [0, C): hits 0, p_min NaN, j_min -1 (nothing to read back).  logp_pairs [B, M, C] or null (inspection, tests).
+ * GPU: 1 <= H <= 256, 2 <= C <= 64 (the engine's limits), M >= 1, B, M bounded by memory; ws 16-byte aligned,
+ * cal_intervene_ws bytes.  THREE launches (fold the parameters and form the two halves of fc1's pre-activation on the matrix
+ * cores; the pair kernel; the chunk reduction in fixed order), no atomics, no synchronisation, no read-back: bit-reproducible and
+ * safe to capture.  B = 0: nothing is launched.  The host library takes any sizes and needs no ws. */
+CAL_API int64_t cal_intervene_ws(int64_t B, int64_t M, int64_t H, int64_t C);
+CAL_API int cal_intervene_pairs(const float* xo, int64_t B, const float* xc, int64_t M, int64_t H, int64_t C, int cat,
+                                const float* bn1_w, const float* bn1_b, const float* bn1_mean, const float* bn1_var, float bn1_eps,
+                                const float* fc1_w, const float* fc1_b, const float* bn2_w, const float* bn2_b,
+                                const float* bn2_mean, const float* bn2_var, float bn2_eps, const float* fc2_w,
+                                const float* fc2_b, const int64_t* ref, float* p_do, int32_t* hits, float* p_min,
+                                int32_t* j_min, float* logp_pairs, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
