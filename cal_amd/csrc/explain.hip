@@ -8,8 +8,8 @@
 // Scores become 32-bit keys that order like the floats (NaN -> 1, -0 -> +0; key 0 pads LDS rows and never counts), so the
 // rank of element i is a count: #{key_j > key_i} + #{key_j == key_i, j < i}.
 //
-//  * segments of at most S = XS elements: k_explain_rank_lds, one group of G threads per segment (G = 64 .. 1024, the
-//    smallest power of two covering the batch's largest segment; 256-thread workgroups hold 256 / G segments), keys in
+//  * segments of at most S = kSegCap elements: k_explain_rank_lds, one group of G threads per segment (the geometry of
+//    segment.hpp: G = 64 .. 1024 covers the batch's largest segment, 256-thread workgroups hold 256 / G segments), keys in
 //    LDS, every lane counts its element against the whole row read as uint4 broadcasts.  Ranking, mask and metrics in
 //    this one launch; the metrics are integer sums reduced in a fixed order (no atomics).
 //  * larger segments (m > S): the same kernel ranks every S-element chunk in LDS and writes the chunk's keys in sorted
@@ -19,19 +19,17 @@
 //
 // Undirected edges (cal_explain_rank_pairs): a column and its reverse (twin.hip) are one element.  k_pairs_compact writes the
 // symmetrised score of every column and compacts each segment's representatives (the lower column of a pair, every unpaired
-// column) in order to the front of the segment's rows in ws (a fixed-order ballot scan, as subgraph.hip compacts); the
-// kernels above rank those rows (their lengths come from seg_len instead of seg_ptr[g+1]); k_pairs_scatter gives both
-// columns of a pair the representative's rank and mask.  Two launches around the ranking's.
+// column) in order to the front of the segment's rows in ws (the fixed-order ballot scan of segment.hpp); the kernels above
+// rank those rows (their lengths come from seg_len instead of seg_ptr[g+1]); k_pairs_scatter gives both columns of a pair the
+// representative's rank and mask.  Two launches around the ranking's.
 #include <math.h>
 
-#include "common.hpp"
+#include "segment.hpp"
 
 namespace cal {
 namespace {
 
-constexpr int XS = 2048;       // LDS capacity S (elements of one segment / chunk)
-constexpr int XNT = 1024;      // threads of the large-segment workgroups
-constexpr int XIT = XS / XNT;  // elements per lane at the widest group
+constexpr int kIt = kSegCap / kSegWide;   // elements per lane at the widest group
 
 struct RankArgs {
     const float* score;
@@ -56,12 +54,11 @@ __device__ __forceinline__ uint32_t score_key(float s) {
 }
 
 __device__ __forceinline__ void seg_range(const RankArgs& a, int64_t g, int64_t& lo, int64_t& m) {
-    int64_t l = a.seg_ptr[g], h = a.seg_ptr[g + 1];
-    l = l < 0 ? 0 : (l > a.M ? a.M : l);
-    if (a.seg_len) h = l + a.seg_len[g];
-    h = h < l ? l : (h > a.M ? a.M : h);
-    lo = l;
-    m = h - l;
+    seg_clamp(a.seg_ptr, g, a.M, lo, m);
+    if (a.seg_len) {                                           // compacted rows: [lo, lo + seg_len[g]), clamped alike
+        const int64_t n = a.seg_len[g], room = a.M - lo;
+        m = n < 0 ? 0 : (n > room ? room : n);
+    }
 }
 
 // k_g of a segment of m elements with P positives (k >= 0: top k; -1: ceil(ratio m); -2: P)
@@ -83,39 +80,6 @@ __device__ __forceinline__ void put_metrics(double* row, int64_t kg, int64_t hit
     row[0] = (double)kg; row[1] = (double)hits; row[2] = (double)P; row[3] = auc;
 }
 
-// sum over the G consecutive threads (whole waves) of this thread's group, every thread of the group gets it; all threads
-// of the workgroup call it (two barriers).  Fixed order: wave butterflies, then the group's wave partials in wave order.
-__device__ __forceinline__ int64_t group_total(int64_t v, int G, long long* red) {
-    long long s = v;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    const int nw = G >> 6, w0 = (int)(threadIdx.x / G) * nw;
-    long long t = 0;
-    for (int i = 0; i < nw; ++i) t += red[w0 + i];
-    return t;
-}
-
-// count of keys > key (gt) and >= key (ge) in a descending row of n keys
-__device__ __forceinline__ int count_gt(const uint32_t* s, int n, uint32_t key) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (s[mid] > key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-__device__ __forceinline__ int count_ge(const uint32_t* s, int n, uint32_t key) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (s[mid] >= key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // grid (ceil(B / (NT / G)), chunks), NT threads; dynamic LDS: keys [NT/G][cap] u32, gt flags [NT/G][cap] u8, then (8-byte
 // aligned) [NT/64] i64.
 // cap = G x (elements per lane) >= min(max_seg, S).  Segments of at most cap elements are finished here (chunk 0 only); a
@@ -132,13 +96,10 @@ __global__ void __launch_bounds__(NT) k_explain_rank_lds(RankArgs a, int G, int 
     const int64_t c = blockIdx.y;
     int64_t lo = 0, m = 0;
     if (g < a.B) seg_range(a, g, lo, m);
-    const bool bad = g < a.B && m > a.max_seg;
-    const bool full = g < a.B && !bad && m <= cap && c == 0;
-    const bool chunk = g < a.B && !bad && m > cap;             // (m > S here: cap = S whenever max_seg > S)
-    const int64_t ulo = chunk ? c * XS : 0;
-    const int un = full ? (int)m : (chunk && ulo < m ? (int)(m - ulo < XS ? m - ulo : XS) : 0);
-    const int nq = (un + 3) & ~3;
-    const int64_t base = lo + ulo;
+    const SegUnit u = seg_unit(g < a.B, m, a.max_seg, cap, c);
+    const bool bad = u.bad, full = u.full, chunk = u.chunk;
+    const int un = u.un, nq = (un + 3) & ~3;
+    const int64_t base = lo + u.ulo;
 
     int64_t pc = 0;
     for (int q = lt; q < nq; q += G) {
@@ -163,10 +124,10 @@ __global__ void __launch_bounds__(NT) k_explain_rank_lds(RankArgs a, int G, int 
     __syncthreads();
 
     const int nit = cap / G;
-    uint32_t ki[XIT];
-    int gtc[XIT], eqc[XIT], eqb[XIT];
+    uint32_t ki[kIt];
+    int gtc[kIt], eqc[kIt], eqb[kIt];
 #pragma unroll
-    for (int it = 0; it < XIT; ++it) {
+    for (int it = 0; it < kIt; ++it) {
         const int q = lt + it * G;
         ki[it] = (it < nit && q < un) ? sk[q] : 0u;
         gtc[it] = eqc[it] = eqb[it] = 0;
@@ -175,7 +136,7 @@ __global__ void __launch_bounds__(NT) k_explain_rank_lds(RankArgs a, int G, int 
         const uint4 kv = *reinterpret_cast<const uint4*>(sk + j);
         const uint32_t kj[4] = {kv.x, kv.y, kv.z, kv.w};
 #pragma unroll
-        for (int it = 0; it < XIT; ++it) {
+        for (int it = 0; it < kIt; ++it) {
             if (it < nit) {
                 const int q = lt + it * G;
 #pragma unroll
@@ -191,7 +152,7 @@ __global__ void __launch_bounds__(NT) k_explain_rank_lds(RankArgs a, int G, int 
 
     if (chunk) {                                                  // local rank + the chunk's keys in sorted order
 #pragma unroll
-        for (int it = 0; it < XIT; ++it) {
+        for (int it = 0; it < kIt; ++it) {
             const int q = lt + it * G;
             if (it < nit && q < un) {
                 const int r = gtc[it] + eqb[it];
@@ -206,7 +167,7 @@ __global__ void __launch_bounds__(NT) k_explain_rank_lds(RankArgs a, int G, int 
     int64_t hits = 0, r2 = 0;
     if (full) {
 #pragma unroll
-        for (int it = 0; it < XIT; ++it) {
+        for (int it = 0; it < kIt; ++it) {
             const int q = lt + it * G;
             if (it < nit && q < un) {
                 const int r = gtc[it] + eqb[it];
@@ -227,34 +188,37 @@ __global__ void __launch_bounds__(NT) k_explain_rank_lds(RankArgs a, int G, int 
     }
 }
 
-// grid (B, chunks), XNT threads: element counts against every chunk of its (large) segment -> final rank, 2 x average rank
-__global__ void __launch_bounds__(XNT) k_explain_rank_merge(RankArgs a) {
-    __shared__ uint32_t sk[XS];
+// grid (B, chunks), kSegWide threads: element counts against every chunk of its (large) segment -> final rank, 2 x average
+// rank
+__global__ void __launch_bounds__(kSegWide) k_explain_rank_merge(RankArgs a) {
+    __shared__ uint32_t sk[kSegCap];
     const int64_t g = blockIdx.x, c = blockIdx.y;
     int64_t lo, m;
     seg_range(a, g, lo, m);
-    if (m <= XS || m > a.max_seg || c * XS >= m) return;          // (uniform over the workgroup)
-    const int64_t ulo = c * XS;
-    const int un = (int)(m - ulo < XS ? m - ulo : XS);
-    uint32_t ki[XIT];
-    int64_t before[XIT], gtt[XIT], eqt[XIT];
+    if (m <= kSegCap || m > a.max_seg || c * kSegCap >= m) return;   // (uniform over the workgroup)
+    const int64_t ulo = c * kSegCap;
+    const int un = (int)(m - ulo < kSegCap ? m - ulo : kSegCap);
+    uint32_t ki[kIt];
+    int64_t before[kIt], gtt[kIt], eqt[kIt];
 #pragma unroll
-    for (int it = 0; it < XIT; ++it) {
-        const int q = threadIdx.x + it * XNT;
+    for (int it = 0; it < kIt; ++it) {
+        const int q = threadIdx.x + it * kSegWide;
         const bool v = q < un;
         ki[it] = v ? score_key(a.score[(lo + ulo + q) * a.stride]) : 0u;
         before[it] = v ? a.rank[lo + ulo + q] : 0;
         gtt[it] = eqt[it] = 0;
     }
-    const int64_t nch = (m + XS - 1) / XS;
+    const int64_t nch = (m + kSegCap - 1) / kSegCap;
     for (int64_t cc = 0; cc < nch; ++cc) {
-        const int n2 = (int)(m - cc * XS < XS ? m - cc * XS : XS);
-        for (int t = threadIdx.x; t < n2; t += XNT) sk[t] = a.skey[lo + cc * XS + t];
+        const int n2 = (int)(m - cc * kSegCap < kSegCap ? m - cc * kSegCap : kSegCap);
+        for (int t = threadIdx.x; t < n2; t += kSegWide) sk[t] = a.skey[lo + cc * kSegCap + t];
         __syncthreads();
 #pragma unroll
-        for (int it = 0; it < XIT; ++it) {
-            if ((int)threadIdx.x + it * XNT < un) {
-                const int ng = count_gt(sk, n2, ki[it]), ne = count_ge(sk, n2, ki[it]);
+        for (int it = 0; it < kIt; ++it) {
+            if ((int)threadIdx.x + it * kSegWide < un) {
+                const uint32_t key = ki[it];                      // (a descending row: the keys > key, then those == key)
+                const int ng = first_false(sk, n2, [key](uint32_t x) { return x > key; });
+                const int ne = first_false(sk, n2, [key](uint32_t x) { return x >= key; });
                 gtt[it] += ng;
                 eqt[it] += ne - ng;
                 if (cc < c) before[it] += ne;                          // equal keys of an earlier chunk: lower index
@@ -264,8 +228,8 @@ __global__ void __launch_bounds__(XNT) k_explain_rank_merge(RankArgs a) {
         __syncthreads();
     }
 #pragma unroll
-    for (int it = 0; it < XIT; ++it) {
-        const int q = threadIdx.x + it * XNT;
+    for (int it = 0; it < kIt; ++it) {
+        const int q = threadIdx.x + it * kSegWide;
         if (q < un) {
             a.rank[lo + ulo + q] = (int32_t)before[it];
             a.r2[lo + ulo + q] = (int32_t)(2 * (m - gtt[it] - eqt[it]) + eqt[it] + 1);
@@ -273,20 +237,20 @@ __global__ void __launch_bounds__(XNT) k_explain_rank_merge(RankArgs a) {
     }
 }
 
-// grid B, XNT threads: mask and metrics of the large segments
-__global__ void __launch_bounds__(XNT) k_explain_rank_large(RankArgs a) {
-    __shared__ long long red[XNT / 64];
+// grid B, kSegWide threads: mask and metrics of the large segments
+__global__ void __launch_bounds__(kSegWide) k_explain_rank_large(RankArgs a) {
+    __shared__ long long red[kSegWide / 64];
     const int64_t g = blockIdx.x;
     int64_t lo, m;
     seg_range(a, g, lo, m);
-    if (m <= XS || m > a.max_seg) return;
+    if (m <= kSegCap || m > a.max_seg) return;
     int64_t pc = 0;
     if (a.gt)
-        for (int64_t q = threadIdx.x; q < m; q += XNT) pc += a.gt[lo + q] != 0;
-    const int64_t P = group_total(pc, XNT, red);
+        for (int64_t q = threadIdx.x; q < m; q += kSegWide) pc += a.gt[lo + q] != 0;
+    const int64_t P = wg_sum<kSegWide>(pc, red);
     const int64_t kg = sel_count(m, P, a.ratio, a.k);
     int64_t hits = 0, r2 = 0;
-    for (int64_t q = threadIdx.x; q < m; q += XNT) {
+    for (int64_t q = threadIdx.x; q < m; q += kSegWide) {
         const bool sel = a.rank[lo + q] < kg;
         a.mask[lo + q] = sel;
         if (a.gt && a.gt[lo + q]) {
@@ -295,8 +259,8 @@ __global__ void __launch_bounds__(XNT) k_explain_rank_large(RankArgs a) {
         }
     }
     if (a.metrics) {
-        hits = group_total(hits, XNT, red);
-        r2 = group_total(r2, XNT, red);
+        hits = wg_sum<kSegWide>(hits, red);
+        r2 = wg_sum<kSegWide>(r2, red);
         if (threadIdx.x == 0) put_metrics(a.metrics + 4 * g, kg, hits, P, seg_auc(m, P, r2));
     }
 }
@@ -320,39 +284,10 @@ struct PairArgs {
     int64_t* seg_len;          // ws: representatives per segment [B] (the segment's length where it is not ranked)
 };
 
-__device__ __forceinline__ void pair_range(const PairArgs& a, int64_t g, int64_t& lo, int64_t& m) {
-    int64_t l = a.seg_ptr[g], h = a.seg_ptr[g + 1];
-    l = l < 0 ? 0 : (l > a.M ? a.M : l);
-    h = h < l ? l : (h > a.M ? a.M : h);
-    lo = l;
-    m = h - l;
-}
-
 // the partner of column e of the segment [lo, lo + m), or -1: twin[e] inside the segment, not e itself, pointing back
 __device__ __forceinline__ int64_t pair_of(const PairArgs& a, int64_t e, int64_t lo, int64_t m) {
     const int64_t t = a.twin[e];
     return (t >= lo && t < lo + m && t != e && a.twin[t] == e) ? t : -1;
-}
-
-// position of this thread's flag among the set flags of the workgroup's NT threads (exclusive), their count in tot;
-// every thread of the workgroup calls it (two barriers)
-template <int NT>
-__device__ __forceinline__ int pair_excl(bool f, int* wcnt, int& tot) {
-    const unsigned long long b = __ballot(f);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int pre = __popcll(b & ((1ull << lane) - 1ull));
-    __syncthreads();
-    if (lane == 0) wcnt[w] = __popcll(b);
-    __syncthreads();
-    int base = 0, t = 0;
-#pragma unroll
-    for (int i = 0; i < NT / 64; ++i) {
-        const int v = wcnt[i];
-        base += i < w ? v : 0;
-        t += v;
-    }
-    tot = t;
-    return base + pre;
 }
 
 // grid B, NT threads: score_out of every column; the representatives' scores and ground truth compacted in order
@@ -361,7 +296,7 @@ __global__ void __launch_bounds__(NT) k_pairs_compact(PairArgs a) {
     __shared__ int wcnt[NT / 64];
     const int64_t g = blockIdx.x;
     int64_t lo, m;
-    pair_range(a, g, lo, m);
+    seg_clamp(a.seg_ptr, g, a.M, lo, m);
     const bool bad = m > a.max_seg;
     int64_t carry = 0;
     for (int64_t base = 0; base < m; base += NT) {
@@ -386,7 +321,7 @@ __global__ void __launch_bounds__(NT) k_pairs_compact(PairArgs a) {
             f = !bad && (t < 0 || e < t);
         }
         int tot;
-        const int pos = pair_excl<NT>(f, wcnt, tot);
+        const int pos = wg_excl<NT>(f, wcnt, tot);
         if (f) {
             const int64_t p = lo + carry + pos;
             a.cs[p] = sym;
@@ -403,7 +338,7 @@ template <int NT>
 __global__ void __launch_bounds__(NT) k_pairs_scatter(PairArgs a) {
     const int64_t g = blockIdx.x;
     int64_t lo, m;
-    pair_range(a, g, lo, m);
+    seg_clamp(a.seg_ptr, g, a.M, lo, m);
     const bool bad = m > a.max_seg;
     for (int64_t q = threadIdx.x; q < m; q += NT) {
         const int64_t e = lo + q;
@@ -421,26 +356,15 @@ __global__ void __launch_bounds__(NT) k_pairs_scatter(PairArgs a) {
     }
 }
 
-int rank_launch(const RankArgs& a, hipStream_t stream) {
-    const bool large = a.max_seg > XS;
-    const int64_t nch = large ? (a.max_seg + XS - 1) / XS : 1;
-    const int eff = (int)(a.max_seg < XS ? a.max_seg : XS);
-    int G = 64;
-    while (G < eff && G < XNT) G <<= 1;
-    const int cap = (eff > 0 ? (eff + G - 1) / G : 1) * G;
-    const int NT = G <= 256 ? 256 : G;
-    const int spb = NT / G;
-    const size_t lds = (((size_t)5 * spb * cap + 7) & ~(size_t)7) + (size_t)(NT / 64) * 8;
-    const dim3 grid((unsigned)((a.B + spb - 1) / spb), (unsigned)nch);
-    CAL_REQUIRE(grid.x <= 0x7FFFFFFFu, "too many segments");
-    if (NT == 256) hipLaunchKernelGGL(k_explain_rank_lds<256>, grid, dim3(256), lds, stream, a, G, cap);
-    else if (NT == 512) hipLaunchKernelGGL(k_explain_rank_lds<512>, grid, dim3(512), lds, stream, a, G, cap);
-    else hipLaunchKernelGGL(k_explain_rank_lds<1024>, grid, dim3(1024), lds, stream, a, G, cap);
+int rank_launch(const RankArgs& a, const SegGeom& q, hipStream_t stream) {
+    const size_t lds = (((size_t)5 * q.spb * q.cap + 7) & ~(size_t)7) + (size_t)(q.NT / 64) * 8;
+    CAL_REQUIRE(q.grid_ok(), "too many segments");
+    CAL_SEG_LAUNCH(k_explain_rank_lds, q, lds, stream, a);
     CAL_CHECK_LAUNCH("k_explain_rank_lds");
-    if (large) {
-        hipLaunchKernelGGL(k_explain_rank_merge, dim3((unsigned)a.B, (unsigned)nch), dim3(XNT), 0, stream, a);
+    if (q.large) {
+        hipLaunchKernelGGL(k_explain_rank_merge, dim3((unsigned)a.B, (unsigned)q.nch), dim3(kSegWide), 0, stream, a);
         CAL_CHECK_LAUNCH("k_explain_rank_merge");
-        hipLaunchKernelGGL(k_explain_rank_large, dim3((unsigned)a.B), dim3(XNT), 0, stream, a);
+        hipLaunchKernelGGL(k_explain_rank_large, dim3((unsigned)a.B), dim3(kSegWide), 0, stream, a);
         CAL_CHECK_LAUNCH("k_explain_rank_large");
     }
     return 0;
@@ -456,7 +380,7 @@ CAL_EXPORT int64_t cal_explain_ws(int64_t M, int64_t B) {
     return 8 * (M > 0 ? M : 0) + 256;
 }
 
-CAL_EXPORT int64_t cal_explain_lds_cap(void) { return XS; }
+CAL_EXPORT int64_t cal_explain_lds_cap(void) { return kSegCap; }
 
 CAL_EXPORT int cal_explain_rank(const float* score, int64_t stride, const int64_t* seg_ptr, int64_t B, int64_t M,
                                 int64_t max_seg, double ratio, int64_t k, const uint8_t* gt, uint8_t* mask, int32_t* rank,
@@ -470,15 +394,15 @@ CAL_EXPORT int cal_explain_rank(const float* score, int64_t stride, const int64_
     CAL_REQUIRE(M == 0 || (score && mask && rank), "score / mask / rank are null");
     CAL_REQUIRE(max_seg < ((int64_t)1 << 30), "segments of 2^30 elements or more are not supported");
     if (B == 0) return 0;
-    const bool large = max_seg > XS;
-    const int64_t nch = large ? (max_seg + XS - 1) / XS : 1;
-    CAL_REQUIRE(nch <= 65535, "max_seg too large");
+    const SegGeom q = seg_geom(max_seg, B);
+    const bool large = q.large;
+    CAL_REQUIRE(q.chunks_ok(), "max_seg too large");
     CAL_REQUIRE(!large || (ws && ws_bytes >= cal_explain_ws(M, B) && aligned16(ws)),
                 "segments above cal_explain_lds_cap() need a 16-byte aligned ws of cal_explain_ws(M, B) bytes");
     RankArgs a{score, stride, seg_ptr, B, M, max_seg, ratio, k, gt, mask, rank, metrics,
                large ? (uint32_t*)ws : nullptr,
                large ? (int32_t*)((char*)ws + ((4 * M + 15) / 16) * 16) : nullptr};
-    return rank_launch(a, stream);
+    return rank_launch(a, q, stream);
 }
 
 CAL_EXPORT int64_t cal_explain_pairs_ws(int64_t M, int64_t B) {
@@ -502,7 +426,8 @@ CAL_EXPORT int cal_explain_rank_pairs(const float* score, int64_t stride, const 
     CAL_REQUIRE(M < ((int64_t)1 << 31), "2^31 columns or more are not supported (twin is int32)");
     CAL_REQUIRE(max_seg < ((int64_t)1 << 30), "segments of 2^30 elements or more are not supported");
     if (B == 0) return 0;
-    CAL_REQUIRE((max_seg + XS - 1) / XS <= 65535, "max_seg too large");
+    const SegGeom q = seg_geom(max_seg, B);
+    CAL_REQUIRE(q.chunks_ok(), "max_seg too large");
     CAL_REQUIRE(B <= 0x7FFFFFFF, "too many segments");
     CAL_REQUIRE(ws && ws_bytes >= cal_explain_pairs_ws(M, B) && aligned16(ws),
                 "ws must be 16-byte aligned and hold cal_explain_pairs_ws(M, B) bytes");
@@ -516,7 +441,7 @@ CAL_EXPORT int cal_explain_rank_pairs(const float* score, int64_t stride, const 
     CAL_CHECK_LAUNCH("k_pairs_compact");
     RankArgs a{p.cs, 1, seg_ptr, B, M, max_seg, ratio, k, gt ? p.cgt : nullptr, p.cmask, p.crank, metrics,
                (uint32_t*)rw, (int32_t*)(rw + ((4 * M + 15) / 16) * 16), p.seg_len};
-    if (rank_launch(a, stream) != 0) return 1;
+    if (rank_launch(a, q, stream) != 0) return 1;
     hipLaunchKernelGGL(k_pairs_scatter<256>, dim3((unsigned)B), dim3(256), 0, stream, p);
     CAL_CHECK_LAUNCH("k_pairs_scatter");
     return 0;

@@ -10,10 +10,11 @@
 // Two launches, one workgroup per graph, any graph size (the graph is walked in chunks of one workgroup's threads):
 //  * k_subgraph_count: effective node flags and edge flags into ws, the graph's kept-node / kept-edge counts into ws.
 //  * k_subgraph_write: every workgroup sums the counts of the graphs before it (B is at most a few thousand) and the whole
-//    row (totals, the offset E' of the second edge_index row), then compacts its nodes and edges in order: per chunk a
-//    __ballot + popcount prefix inside each wave, the waves' counts through LDS, a running carry across the chunks.
+//    row (totals, the offset E' of the second edge_index row), then compacts its nodes and edges in order: per chunk the
+//    ballot scan of segment.hpp, a running carry across the chunks.
 // No grid depends on a value the device computed; the caller reads the four totals back once and slices the outputs.
-#include "common.hpp"
+// The clamped ranges, the fixed-order workgroup sums and the scan are segment.hpp's, shared with explain.hip and twin.hip.
+#include "segment.hpp"
 
 namespace cal {
 namespace {
@@ -43,73 +44,14 @@ struct SubArgs {
     uint8_t* eflag;            // ws: [E] effective edge flags
 };
 
-__device__ __forceinline__ void sub_range(const int64_t* p, int64_t g, int64_t M, int64_t& lo, int64_t& m) {
-    int64_t l = p[g], h = p[g + 1];
-    l = l < 0 ? 0 : (l > M ? M : l);
-    h = h < l ? l : (h > M ? M : h);
-    lo = l;
-    m = h - l;
-}
-
-// sum over the workgroup, every thread gets it (two barriers); fixed order: wave butterflies, then the waves in order
-template <int NT>
-__device__ __forceinline__ long long wg_sum(long long v, long long* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    long long t = 0;
-#pragma unroll
-    for (int i = 0; i < NT / 64; ++i) t += red[i];
-    return t;
-}
-
-template <int NT>
-__device__ __forceinline__ long long wg_max(long long v, long long* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const long long u = __shfl_xor(v, o, 64);
-        v = u > v ? u : v;
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    long long t = red[0];
-#pragma unroll
-    for (int i = 1; i < NT / 64; ++i) t = red[i] > t ? red[i] : t;
-    return t;
-}
-
-// position of this thread's flag among the set flags of the workgroup's NT threads (exclusive), their count in tot;
-// every thread of the workgroup calls it (two barriers)
-template <int NT>
-__device__ __forceinline__ int wg_excl(bool f, int* wcnt, int& tot) {
-    const unsigned long long b = __ballot(f);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int pre = __popcll(b & ((1ull << lane) - 1ull));
-    __syncthreads();
-    if (lane == 0) wcnt[w] = __popcll(b);
-    __syncthreads();
-    int base = 0, t = 0;
-#pragma unroll
-    for (int i = 0; i < NT / 64; ++i) {
-        const int v = wcnt[i];
-        base += i < w ? v : 0;
-        t += v;
-    }
-    tot = t;
-    return base + pre;
-}
-
 // grid B, NT threads
 template <int NT>
 __global__ void __launch_bounds__(NT) k_subgraph_count(SubArgs a) {
     __shared__ long long red[NT / 64];
     const int64_t g = blockIdx.x;
     int64_t nlo, nn, elo, em;
-    sub_range(a.ptr, g, a.N, nlo, nn);
-    sub_range(a.eptr, g, a.E, elo, em);
+    seg_clamp(a.ptr, g, a.N, nlo, nn);
+    seg_clamp(a.eptr, g, a.E, elo, em);
     const bool from_edges = a.relabel && !a.nkeep;            // kept nodes = the endpoints of the kept edges
     if (a.nkeep) {
         for (int64_t q = threadIdx.x; q < nn; q += NT) a.nflag[nlo + q] = (a.nkeep[nlo + q] != 0) != (a.complement != 0);
@@ -149,8 +91,8 @@ __global__ void __launch_bounds__(NT) k_subgraph_write(SubArgs a) {
     __shared__ int wcnt[NT / 64];
     const int64_t g = blockIdx.x;
     int64_t nlo, nn, elo, em;
-    sub_range(a.ptr, g, a.N, nlo, nn);
-    sub_range(a.eptr, g, a.E, elo, em);
+    seg_clamp(a.ptr, g, a.N, nlo, nn);
+    seg_clamp(a.eptr, g, a.E, elo, em);
 
     long long on = 0, oe = 0, tn = 0, te = 0, mn = 0, me = 0;
     for (int64_t h = threadIdx.x; h < a.B; h += NT) {

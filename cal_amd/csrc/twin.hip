@@ -11,10 +11,11 @@
 // lt = #{key_j < key_i}, eq = #{key_j == key_i}, j = #{key_j == key_i, j < i} and eqp = #{key_j == key_i ^ 1}, element i sits
 // at sorted[lt + j] and its partner, if j < eqp, at sorted[lt + eq + j] (u < v) or sorted[lt - eqp + j] (u > v).
 //
-//  * segments of at most S = TS columns: k_twin_lds, one group of G threads per segment (G = 64 .. 1024 as in explain.hip,
-//    256-thread workgroups hold 256 / G segments).  Keys [cap] u64 and sorted [cap] i32 in LDS (24 KB at the cap); every lane
-//    counts its element against the whole row read as 128-bit broadcasts (two keys per read, every lane the same address: no
-//    bank conflict; the only scattered LDS access is the one write to sorted[]).  One launch.
+//  * segments of at most S = kSegCap columns: k_twin_lds, one group of G threads per segment (the geometry of segment.hpp,
+//    shared with explain.hip: G = 64 .. 1024, 256-thread workgroups hold 256 / G segments).  Keys [cap] u64 and sorted [cap]
+//    i32 in LDS (24 KB at the cap); every lane counts its element against the whole row read as 128-bit broadcasts (two keys
+//    per read, every lane the same address: no bank conflict; the only scattered LDS access is the one write to sorted[]).
+//    One launch.
 //  * larger segments: the same kernel sorts every S-column chunk and writes its keys and column indices in sorted order to
 //    ws; k_twin_merge (one workgroup per large segment) finds each column's occurrence number and its partner by binary
 //    searches over the chunks staged through LDS; k_twin_totals sums the workgroups' counts.  Three launches.
@@ -25,14 +26,12 @@
 // which workgroup that is.  The large path needs no ticket.
 #include <atomic>
 
-#include "common.hpp"
+#include "segment.hpp"
 
 namespace cal {
 namespace {
 
-constexpr int TS = 2048;       // LDS capacity S (columns of one segment / chunk) == cal_explain_lds_cap()
-constexpr int TNT = 1024;      // threads of the large-segment workgroups
-constexpr int TIT = TS / TNT;  // columns per lane at the widest group
+constexpr int kIt = kSegCap / kSegWide;   // columns per lane at the widest group
 constexpr uint64_t kPad = ~0ull;   // key of a column that pairs with nothing, and of the LDS rows' padding
 constexpr int kTickets = 64;   // concurrent one-launch calls (on different streams) that may be in flight
 
@@ -57,11 +56,7 @@ __device__ __forceinline__ void twin_ranges(const TwinArgs& a, int64_t g, int64_
     nlo = a.ptr[g];
     nn = a.ptr[g + 1] - nlo;
     nn = nn < 0 ? 0 : nn;
-    int64_t l = a.eptr[g], h = a.eptr[g + 1];
-    l = l < 0 ? 0 : (l > a.E ? a.E : l);
-    h = h < l ? l : (h > a.E ? a.E : h);
-    elo = l;
-    m = h - l;
+    seg_clamp(a.eptr, g, a.E, elo, m);
 }
 
 __device__ __forceinline__ uint64_t edge_key(const TwinArgs& a, int64_t e, int64_t nlo, int64_t nn, bool& self) {
@@ -71,38 +66,6 @@ __device__ __forceinline__ uint64_t edge_key(const TwinArgs& a, int64_t e, int64
     self = u == v;
     const uint64_t x = (uint64_t)(u - nlo), y = (uint64_t)(v - nlo);
     return (((x < y ? x : y) * (uint64_t)nn + (x < y ? y : x)) << 1) | (uint64_t)(u > v);
-}
-
-// sum over the workgroup's NT threads, every thread gets it (two barriers); fixed order: wave butterflies, waves in order
-template <int NT>
-__device__ __forceinline__ long long twin_wg_sum(long long v, long long* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    long long t = 0;
-#pragma unroll
-    for (int i = 0; i < NT / 64; ++i) t += red[i];
-    return t;
-}
-
-// first index of an ascending row of n keys that is >= key (lower) / > key (upper)
-__device__ __forceinline__ int lower_of(const uint64_t* s, int n, uint64_t key) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (s[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-__device__ __forceinline__ int upper_of(const uint64_t* s, int n, uint64_t key) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (s[mid] <= key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 // grid (ceil(B / (NT / G)), chunks), NT threads; dynamic LDS: keys [NT/G][cap] u64, sorted [NT/G][cap] i32, [NT/64] i64.
@@ -120,19 +83,16 @@ __global__ void __launch_bounds__(NT) k_twin_lds(TwinArgs a, int G, int cap) {
     const int64_t c = blockIdx.y;
     int64_t nlo = 0, nn = 0, elo = 0, m = 0;
     if (g < a.B) twin_ranges(a, g, nlo, nn, elo, m);
-    const bool bad = g < a.B && m > a.max_edges;
-    const bool full = g < a.B && !bad && m <= cap && c == 0;
-    const bool chunk = g < a.B && !bad && m > cap;               // (m > S here: cap = S whenever max_edges > S)
-    const int64_t ulo = chunk ? c * TS : 0;
-    const int un = full ? (int)m : (chunk && ulo < m ? (int)(m - ulo < TS ? m - ulo : TS) : 0);
-    const int nq = (un + 1) & ~1;
-    const int64_t base = elo + ulo;
+    const SegUnit u = seg_unit(g < a.B, m, a.max_edges, cap, c);
+    const bool bad = u.bad, full = u.full, chunk = u.chunk;
+    const int un = u.un, nq = (un + 1) & ~1;
+    const int64_t ulo = u.ulo, base = elo + ulo;
     const int nit = cap / G;
 
-    uint64_t ki[TIT];
-    bool self[TIT];
+    uint64_t ki[kIt];
+    bool self[kIt];
 #pragma unroll
-    for (int it = 0; it < TIT; ++it) {
+    for (int it = 0; it < kIt; ++it) {
         const int q = lt + it * G;
         ki[it] = kPad;
         self[it] = false;
@@ -150,14 +110,14 @@ __global__ void __launch_bounds__(NT) k_twin_lds(TwinArgs a, int G, int cap) {
     }
     __syncthreads();
 
-    int ltc[TIT], eqc[TIT], eqb[TIT], eqp[TIT];
+    int ltc[kIt], eqc[kIt], eqb[kIt], eqp[kIt];
 #pragma unroll
-    for (int it = 0; it < TIT; ++it) ltc[it] = eqc[it] = eqb[it] = eqp[it] = 0;
+    for (int it = 0; it < kIt; ++it) ltc[it] = eqc[it] = eqb[it] = eqp[it] = 0;
     for (int j = 0; j < nq; j += 2) {
         const ulonglong2 kv = *reinterpret_cast<const ulonglong2*>(sk + j);
         const uint64_t kj[2] = {kv.x, kv.y};
 #pragma unroll
-        for (int it = 0; it < TIT; ++it) {
+        for (int it = 0; it < kIt; ++it) {
             if (it < nit) {
                 const int q = lt + it * G;
 #pragma unroll
@@ -172,9 +132,9 @@ __global__ void __launch_bounds__(NT) k_twin_lds(TwinArgs a, int G, int cap) {
         }
     }
 
-    int slot[TIT];
+    int slot[kIt];
 #pragma unroll
-    for (int it = 0; it < TIT; ++it) {
+    for (int it = 0; it < kIt; ++it) {
         const int q = lt + it * G;
         slot[it] = -1;
         if (it < nit && q < un) {
@@ -191,7 +151,7 @@ __global__ void __launch_bounds__(NT) k_twin_lds(TwinArgs a, int G, int cap) {
     __syncthreads();
     if (full) {
 #pragma unroll
-        for (int it = 0; it < TIT; ++it) {
+        for (int it = 0; it < kIt; ++it) {
             const int q = lt + it * G;
             if (it < nit && q < un) {
                 int32_t t = -1;
@@ -208,8 +168,8 @@ __global__ void __launch_bounds__(NT) k_twin_lds(TwinArgs a, int G, int cap) {
     }
 
     if (c != 0) return;                                            // (uniform; the chunks' workgroups counted nothing)
-    unp = twin_wg_sum<NT>(unp, red);
-    nself = twin_wg_sum<NT>(nself, red);
+    unp = wg_sum<NT>(unp, red);
+    nself = wg_sum<NT>(nself, red);
     if (threadIdx.x == 0) {
         a.part[2 * blockIdx.x] = unp;
         a.part[2 * blockIdx.x + 1] = nself;
@@ -227,55 +187,57 @@ __global__ void __launch_bounds__(NT) k_twin_lds(TwinArgs a, int G, int cap) {
         s0 += __hip_atomic_load(a.part + 2 * i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         s1 += __hip_atomic_load(a.part + 2 * i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    s0 = twin_wg_sum<NT>(s0, red);
-    s1 = twin_wg_sum<NT>(s1, red);
+    s0 = wg_sum<NT>(s0, red);
+    s1 = wg_sum<NT>(s1, red);
     if (threadIdx.x == 0) {
         a.totals[0] = s0;
         a.totals[1] = s1;
     }
 }
 
-// grid B, TNT threads: the twins of one large segment from its sorted chunks; its counts to part[2 (nblk + g)]
-__global__ void __launch_bounds__(TNT) k_twin_merge(TwinArgs a) {
-    __shared__ __align__(16) uint64_t sk[TS];
-    __shared__ long long red[TNT / 64];
+// grid B, kSegWide threads: the twins of one large segment from its sorted chunks; its counts to part[2 (nblk + g)]
+__global__ void __launch_bounds__(kSegWide) k_twin_merge(TwinArgs a) {
+    __shared__ __align__(16) uint64_t sk[kSegCap];
+    __shared__ long long red[kSegWide / 64];
     const int64_t g = blockIdx.x;
     int64_t nlo, nn, elo, m;
     twin_ranges(a, g, nlo, nn, elo, m);
-    const bool act = m > TS && m <= a.max_edges;                  // (uniform over the workgroup)
-    const int64_t nch = act ? (m + TS - 1) / TS : 0;
+    const bool act = m > kSegCap && m <= a.max_edges;            // (uniform over the workgroup)
+    const int64_t nch = act ? (m + kSegCap - 1) / kSegCap : 0;
     long long unp = 0, nself = 0;
     for (int64_t c = 0; c < nch; ++c) {
-        const int un = (int)(m - c * TS < TS ? m - c * TS : TS);
-        uint64_t ki[TIT];
-        int64_t j[TIT], tw[TIT];
-        int32_t idx[TIT];
-        bool open[TIT];                                            // still looking for its partner
+        const int un = (int)(m - c * kSegCap < kSegCap ? m - c * kSegCap : kSegCap);
+        uint64_t ki[kIt];
+        int64_t j[kIt], tw[kIt];
+        int32_t idx[kIt];
+        bool open[kIt];                                            // still looking for its partner
 #pragma unroll
-        for (int it = 0; it < TIT; ++it) {
-            const int t = threadIdx.x + it * TNT;
-            ki[it] = t < un ? a.skey[elo + c * TS + t] : kPad;
-            idx[it] = t < un ? a.sidx[elo + c * TS + t] : 0;
+        for (int it = 0; it < kIt; ++it) {
+            const int t = threadIdx.x + it * kSegWide;
+            ki[it] = t < un ? a.skey[elo + c * kSegCap + t] : kPad;
+            idx[it] = t < un ? a.sidx[elo + c * kSegCap + t] : 0;
             j[it] = 0;
             tw[it] = -1;
             open[it] = false;
         }
         // occurrence number: equal keys of the chunks before, then of this chunk's sorted order (ties by column index)
         for (int64_t cc = 0; cc <= c; ++cc) {
-            const int n2 = (int)(m - cc * TS < TS ? m - cc * TS : TS);
-            for (int t = threadIdx.x; t < n2; t += TNT) sk[t] = a.skey[elo + cc * TS + t];
+            const int n2 = (int)(m - cc * kSegCap < kSegCap ? m - cc * kSegCap : kSegCap);
+            for (int t = threadIdx.x; t < n2; t += kSegWide) sk[t] = a.skey[elo + cc * kSegCap + t];
             __syncthreads();
 #pragma unroll
-            for (int it = 0; it < TIT; ++it) {
-                if (ki[it] != kPad) {
-                    const int lb = lower_of(sk, n2, ki[it]);
-                    j[it] += cc < c ? upper_of(sk, n2, ki[it]) - lb : (int)(threadIdx.x + it * TNT) - lb;
+            for (int it = 0; it < kIt; ++it) {
+                if (ki[it] != kPad) {                                  // (an ascending row: the keys < k, then those == k)
+                    const uint64_t k = ki[it];
+                    const int lb = first_false(sk, n2, [k](uint64_t x) { return x < k; });
+                    const int ub = cc < c ? first_false(sk, n2, [k](uint64_t x) { return x <= k; }) : threadIdx.x + it * kSegWide;
+                    j[it] += ub - lb;
                 }
             }
             __syncthreads();
         }
 #pragma unroll
-        for (int it = 0; it < TIT; ++it) {
+        for (int it = 0; it < kIt; ++it) {
             if (ki[it] != kPad) {
                 const int64_t e = elo + idx[it];
                 if (a.ei[e] == a.ei[a.E + e]) tw[it] = e;
@@ -284,16 +246,17 @@ __global__ void __launch_bounds__(TNT) k_twin_merge(TwinArgs a) {
         }
         // the j-th column with the reversed key, walking the chunks in column order
         for (int64_t cc = 0; cc < nch; ++cc) {
-            const int n2 = (int)(m - cc * TS < TS ? m - cc * TS : TS);
-            for (int t = threadIdx.x; t < n2; t += TNT) sk[t] = a.skey[elo + cc * TS + t];
+            const int n2 = (int)(m - cc * kSegCap < kSegCap ? m - cc * kSegCap : kSegCap);
+            for (int t = threadIdx.x; t < n2; t += kSegWide) sk[t] = a.skey[elo + cc * kSegCap + t];
             __syncthreads();
 #pragma unroll
-            for (int it = 0; it < TIT; ++it) {
+            for (int it = 0; it < kIt; ++it) {
                 if (open[it]) {
                     const uint64_t p = ki[it] ^ 1ull;
-                    const int lb = lower_of(sk, n2, p), cnt = upper_of(sk, n2, p) - lb;
+                    const int lb = first_false(sk, n2, [p](uint64_t x) { return x < p; });
+                    const int cnt = first_false(sk, n2, [p](uint64_t x) { return x <= p; }) - lb;
                     if (j[it] < cnt) {
-                        tw[it] = elo + a.sidx[elo + cc * TS + lb + j[it]];
+                        tw[it] = elo + a.sidx[elo + cc * kSegCap + lb + j[it]];
                         open[it] = false;
                     } else {
                         j[it] -= cnt;
@@ -303,8 +266,8 @@ __global__ void __launch_bounds__(TNT) k_twin_merge(TwinArgs a) {
             __syncthreads();
         }
 #pragma unroll
-        for (int it = 0; it < TIT; ++it) {
-            if ((int)threadIdx.x + it * TNT < un) {
+        for (int it = 0; it < kIt; ++it) {
+            if ((int)threadIdx.x + it * kSegWide < un) {
                 const int64_t e = elo + idx[it];
                 a.twin[e] = (int32_t)tw[it];
                 unp += tw[it] < 0;
@@ -312,8 +275,8 @@ __global__ void __launch_bounds__(TNT) k_twin_merge(TwinArgs a) {
             }
         }
     }
-    unp = twin_wg_sum<TNT>(unp, red);
-    nself = twin_wg_sum<TNT>(nself, red);
+    unp = wg_sum<kSegWide>(unp, red);
+    nself = wg_sum<kSegWide>(nself, red);
     if (threadIdx.x == 0) {
         a.part[2 * (a.nblk + g)] = unp;
         a.part[2 * (a.nblk + g) + 1] = nself;
@@ -321,15 +284,15 @@ __global__ void __launch_bounds__(TNT) k_twin_merge(TwinArgs a) {
 }
 
 // one workgroup: totals = the sum of the np workgroup counts, in order
-__global__ void __launch_bounds__(TNT) k_twin_totals(TwinArgs a, int64_t np) {
-    __shared__ long long red[TNT / 64];
+__global__ void __launch_bounds__(kSegWide) k_twin_totals(TwinArgs a, int64_t np) {
+    __shared__ long long red[kSegWide / 64];
     long long s0 = 0, s1 = 0;
-    for (int64_t i = threadIdx.x; i < np; i += TNT) {
+    for (int64_t i = threadIdx.x; i < np; i += kSegWide) {
         s0 += a.part[2 * i];
         s1 += a.part[2 * i + 1];
     }
-    s0 = twin_wg_sum<TNT>(s0, red);
-    s1 = twin_wg_sum<TNT>(s1, red);
+    s0 = wg_sum<kSegWide>(s0, red);
+    s1 = wg_sum<kSegWide>(s1, red);
     if (threadIdx.x == 0) {
         a.totals[0] = s0;
         a.totals[1] = s1;
@@ -366,30 +329,20 @@ CAL_EXPORT int cal_edge_twin(const int64_t* edge_index, int64_t E, const int64_t
     }
     CAL_REQUIRE(ws && ws_bytes >= cal_edge_twin_ws(E, B) && (reinterpret_cast<uintptr_t>(ws) & 7) == 0,
                 "ws must be 8-byte aligned and hold cal_edge_twin_ws(E, B) bytes");
-    const bool large = max_edges > TS;
-    const int64_t nch = large ? (max_edges + TS - 1) / TS : 1;
-    CAL_REQUIRE(nch <= 65535, "max_edges too large");
-    const int eff = (int)(max_edges < TS ? max_edges : TS);
-    int G = 64;
-    while (G < eff && G < TNT) G <<= 1;
-    const int cap = (eff > 0 ? (eff + G - 1) / G : 1) * G;
-    const int NT = G <= 256 ? 256 : G;
-    const int spb = NT / G;
-    const int64_t nblk = (B + spb - 1) / spb;
-    CAL_REQUIRE(nblk <= 0x7FFFFFFF, "too many segments");
+    const SegGeom q = seg_geom(max_edges, B);
+    CAL_REQUIRE(q.chunks_ok(), "max_edges too large");
+    CAL_REQUIRE(q.grid_ok(), "too many segments");
+    const int64_t nblk = q.nblk;
     char* w = (char*)ws;
     TwinArgs a{edge_index, E, ptr, edge_ptr, B, max_edges, twin, totals, (int64_t*)w, (uint64_t*)(w + 32 * B),
-               (int32_t*)(w + 32 * B + 8 * E), large ? -1 : (int)(g_twin_calls.fetch_add(1) % kTickets), (int)nblk};
-    const size_t lds = (size_t)12 * spb * cap + (size_t)(NT / 64) * 8;
-    const dim3 grid((unsigned)nblk, (unsigned)nch);
-    if (NT == 256) hipLaunchKernelGGL(k_twin_lds<256>, grid, dim3(256), lds, stream, a, G, cap);
-    else if (NT == 512) hipLaunchKernelGGL(k_twin_lds<512>, grid, dim3(512), lds, stream, a, G, cap);
-    else hipLaunchKernelGGL(k_twin_lds<1024>, grid, dim3(1024), lds, stream, a, G, cap);
+               (int32_t*)(w + 32 * B + 8 * E), q.large ? -1 : (int)(g_twin_calls.fetch_add(1) % kTickets), (int)nblk};
+    const size_t lds = (size_t)12 * q.spb * q.cap + (size_t)(q.NT / 64) * 8;
+    CAL_SEG_LAUNCH(k_twin_lds, q, lds, stream, a);
     CAL_CHECK_LAUNCH("k_twin_lds");
-    if (large) {
-        hipLaunchKernelGGL(k_twin_merge, dim3((unsigned)B), dim3(TNT), 0, stream, a);
+    if (q.large) {
+        hipLaunchKernelGGL(k_twin_merge, dim3((unsigned)B), dim3(kSegWide), 0, stream, a);
         CAL_CHECK_LAUNCH("k_twin_merge");
-        hipLaunchKernelGGL(k_twin_totals, dim3(1), dim3(TNT), 0, stream, a, nblk + B);
+        hipLaunchKernelGGL(k_twin_totals, dim3(1), dim3(kSegWide), 0, stream, a, nblk + B);
         CAL_CHECK_LAUNCH("k_twin_totals");
     }
     return 0;

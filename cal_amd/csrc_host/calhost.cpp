@@ -530,6 +530,12 @@ inline uint32_t score_key(float s) {
     if (s != 0.f) memcpy(&u, &s, 4);                          // -0 ranks as +0
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
+
+// segment g of p clamped into [0, M] (seg_clamp of cal_amd/csrc/segment.hpp): [lo, hi)
+inline void seg_clamp(const int64_t* p, int64_t g, int64_t M, int64_t& lo, int64_t& hi) {
+    lo = std::min(std::max(p[g], (int64_t)0), M);
+    hi = std::min(std::max(p[g + 1], lo), M);
+}
 }  // namespace
 
 HOST_EXPORT int64_t cal_explain_ws(int64_t M, int64_t) { return 8 * (M > 0 ? M : 0) + 256; }
@@ -547,8 +553,8 @@ HOST_EXPORT int cal_explain_rank(const float* score, int64_t stride, const int64
     HOST_REQUIRE(max_seg < ((int64_t)1 << 30), "segments of 2^30 elements or more are not supported");
 #pragma omp parallel for schedule(dynamic, 16)
     for (int64_t g = 0; g < B; ++g) {
-        int64_t lo = std::min(std::max(seg_ptr[g], (int64_t)0), M);
-        int64_t hi = std::min(std::max(seg_ptr[g + 1], lo), M);
+        int64_t lo, hi;
+        seg_clamp(seg_ptr, g, M, lo, hi);
         const int64_t m = hi - lo;
         double* row = metrics ? metrics + 4 * g : nullptr;
         if (m > max_seg) {                                    // not ranked (max_seg must bound every segment)
@@ -617,8 +623,9 @@ HOST_EXPORT int cal_subgraph_extract(const int64_t* edge_index, int64_t E, int64
     dst.reserve(E);
     int64_t nt = 0, et = 0, mn = 0, me = 0;
     for (int64_t g = 0; g < B; ++g) {
-        const int64_t nlo = std::min(std::max(ptr[g], (int64_t)0), N), nhi = std::min(std::max(ptr[g + 1], nlo), N);
-        const int64_t elo = std::min(std::max(edge_ptr[g], (int64_t)0), E), ehi = std::min(std::max(edge_ptr[g + 1], elo), E);
+        int64_t nlo, nhi, elo, ehi;
+        seg_clamp(ptr, g, N, nlo, nhi);
+        seg_clamp(edge_ptr, g, E, elo, ehi);
         if (node_keep)
             for (int64_t i = nlo; i < nhi; ++i) nflag[i] = (node_keep[i] != 0) != comp;
         else if (from_edges)
@@ -686,7 +693,8 @@ HOST_EXPORT int cal_edge_twin(const int64_t* edge_index, int64_t E, const int64_
     std::vector<std::pair<uint64_t, int64_t>> keys;
     for (int64_t g = 0; g < B; ++g) {
         const int64_t nlo = ptr[g], nn = std::max(ptr[g + 1] - nlo, (int64_t)0);
-        const int64_t elo = std::min(std::max(edge_ptr[g], (int64_t)0), E), ehi = std::min(std::max(edge_ptr[g + 1], elo), E);
+        int64_t elo, ehi;
+        seg_clamp(edge_ptr, g, E, elo, ehi);
         if (ehi - elo > max_edges) {
             for (int64_t e = elo; e < ehi; ++e) twin[e] = -1;
             unp += ehi - elo;
@@ -745,7 +753,8 @@ HOST_EXPORT int cal_explain_rank_pairs(const float* score, int64_t stride, const
     std::vector<int64_t> cptr(B + 1, 0), rep(M, -1), lens(B, 0);
     int64_t longest = 0;
     for (int64_t g = 0; g < B; ++g) {
-        const int64_t lo = std::min(std::max(seg_ptr[g], (int64_t)0), M), hi = std::min(std::max(seg_ptr[g + 1], lo), M);
+        int64_t lo, hi;
+        seg_clamp(seg_ptr, g, M, lo, hi);
         const bool bad = hi - lo > max_seg;
         for (int64_t e = lo; e < hi; ++e) {
             int64_t t = twin[e];
@@ -779,7 +788,8 @@ HOST_EXPORT int cal_explain_rank_pairs(const float* score, int64_t stride, const
                                     gt ? cgt.data() : nullptr, cmask.data(), crank.data(), metrics, nullptr, 0, nullptr);
     if (rc != 0) return rc;
     for (int64_t g = 0; g < B; ++g) {
-        const int64_t lo = std::min(std::max(seg_ptr[g], (int64_t)0), M), hi = std::min(std::max(seg_ptr[g + 1], lo), M);
+        int64_t lo, hi;
+        seg_clamp(seg_ptr, g, M, lo, hi);
         const bool bad = hi - lo > max_seg;
         int64_t p = cptr[g];
         for (int64_t e = lo; e < hi; ++e) {                    // (a representative comes before its partner)

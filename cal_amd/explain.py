@@ -65,20 +65,19 @@ def _k_code(ratio, k) -> Tuple[int, float]:
     return int(k), 0.0
 
 
-def rank_segments(score: torch.Tensor, seg_ptr: torch.Tensor, max_seg: int, *, ratio=None, k=None,
-                  gt: Optional[torch.Tensor] = None, metrics: bool = False):
-    """One ``cal_explain_rank`` call over the segments ``[seg_ptr[g], seg_ptr[g+1])`` of the 1-D ``score`` (any stride).
-
-    Returns ``(mask bool [M], rank int32 [M], metrics fp64 [B, 4] or None)``; a metrics row is ``k_g, hits, P, AUC``.
-    ``max_seg`` must bound every segment's length (host int)."""
+def _rank_call(score, seg_ptr, max_seg, twin, reduce_code, ratio, k, gt, metrics):
+    """The one call behind ``rank_segments`` (``twin`` is ``None``: ``cal_explain_rank``) and ``rank_segment_pairs``
+    (``cal_explain_rank_pairs`` under ``reduce_code``) -> ``(mask, rank, metrics or None, symmetrised score or None)``."""
     if score.dim() != 1 or score.dtype != torch.float32:
         raise TypeError("score must be a 1-D float32 tensor")
     kc, rt = _k_code(ratio, k)
     if kc == -2 and gt is None:
         raise ValueError('k="gt" needs the ground truth')
-    dev = score.device
-    host = not score.is_cuda
+    dev, host = score.device, not score.is_cuda
     M, B = score.numel(), seg_ptr.numel() - 1
+    pairs = twin is not None
+    if pairs and twin.numel() != M:
+        raise ValueError("twin must have one entry per score")
     seg_ptr = seg_ptr.to(device=dev, dtype=torch.long).contiguous()
     stride = max(int(score.stride(0)), 1) if M else 1
     mask = torch.empty(M, dtype=torch.uint8, device=dev)
@@ -89,13 +88,32 @@ def rank_segments(score: torch.Tensor, seg_ptr: torch.Tensor, max_seg: int, *, r
         if gt.numel() != M:
             raise ValueError("gt must have one entry per score")
         g8 = gt.to(device=dev, dtype=torch.bool).contiguous().view(torch.uint8)
-    ws, wsb = None, 0
-    if max_seg > _lib.query("cal_explain_lds_cap", host=host):
+    out, wsb = None, 0
+    if pairs:
+        twin = twin.to(device=dev, dtype=torch.int32).contiguous()
+        out = torch.empty(M, dtype=torch.float32, device=dev)
+        wsb = _lib.query("cal_explain_pairs_ws", M, B, host=host)
+    elif max_seg > _lib.query("cal_explain_lds_cap", host=host):
         wsb = _lib.query("cal_explain_ws", M, B, host=host)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    _lib.call("cal_explain_rank", _p(score) if M else None, stride, _p(seg_ptr), B, M, int(max_seg), rt, kc, _p(g8),
-              _p(mask) if M else None, _p(rank) if M else None, _p(met), _p(ws), wsb, None if host else _stream(), host=host)
-    return mask.view(torch.bool), rank, met
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
+    sp, mp, rp = (_p(score), _p(mask), _p(rank)) if M else (None, None, None)      # (null when there is no element)
+    st = None if host else _stream()
+    if pairs:
+        _lib.call("cal_explain_rank_pairs", sp, stride, _p(seg_ptr), B, M, int(max_seg), rt, kc, _p(g8), _p(twin) if M else None,
+                  reduce_code, _p(out) if M else None, mp, rp, _p(met), _p(ws), wsb, st, host=host)
+    else:
+        _lib.call("cal_explain_rank", sp, stride, _p(seg_ptr), B, M, int(max_seg), rt, kc, _p(g8), mp, rp, _p(met), _p(ws), wsb, st,
+                  host=host)
+    return mask.view(torch.bool), rank, met, out
+
+
+def rank_segments(score: torch.Tensor, seg_ptr: torch.Tensor, max_seg: int, *, ratio=None, k=None,
+                  gt: Optional[torch.Tensor] = None, metrics: bool = False):
+    """One ``cal_explain_rank`` call over the segments ``[seg_ptr[g], seg_ptr[g+1])`` of the 1-D ``score`` (any stride).
+
+    Returns ``(mask bool [M], rank int32 [M], metrics fp64 [B, 4] or None)``; a metrics row is ``k_g, hits, P, AUC``.
+    ``max_seg`` must bound every segment's length (host int)."""
+    return _rank_call(score, seg_ptr, max_seg, None, None, ratio, k, gt, metrics)[:3]
 
 
 def rank_segment_pairs(score: torch.Tensor, seg_ptr: torch.Tensor, max_seg: int, twin: torch.Tensor, reduce: str = "mean", *,
@@ -105,37 +123,10 @@ def rank_segment_pairs(score: torch.Tensor, seg_ptr: torch.Tensor, max_seg: int,
 
     Returns ``(mask bool [M], rank int32 [M], metrics fp64 [B, 4] or None, score float32 [M])``: both columns of a pair carry
     the pair's rank, mask and symmetrised score; ``k`` / ``ratio`` / the metrics count pairs, not columns."""
-    if score.dim() != 1 or score.dtype != torch.float32:
-        raise TypeError("score must be a 1-D float32 tensor")
     rc = _reduce_code(reduce)
     if rc is None:
         raise ValueError('reduce must be "mean", "max" or "min"')
-    kc, rt = _k_code(ratio, k)
-    if kc == -2 and gt is None:
-        raise ValueError('k="gt" needs the ground truth')
-    dev = score.device
-    host = not score.is_cuda
-    M, B = score.numel(), seg_ptr.numel() - 1
-    if twin.numel() != M:
-        raise ValueError("twin must have one entry per score")
-    seg_ptr = seg_ptr.to(device=dev, dtype=torch.long).contiguous()
-    twin = twin.to(device=dev, dtype=torch.int32).contiguous()
-    stride = max(int(score.stride(0)), 1) if M else 1
-    mask = torch.empty(M, dtype=torch.uint8, device=dev)
-    rank = torch.empty(M, dtype=torch.int32, device=dev)
-    out = torch.empty(M, dtype=torch.float32, device=dev)
-    met = torch.empty(B, 4, dtype=torch.float64, device=dev) if metrics else None
-    g8 = None
-    if gt is not None:
-        if gt.numel() != M:
-            raise ValueError("gt must have one entry per score")
-        g8 = gt.to(device=dev, dtype=torch.bool).contiguous().view(torch.uint8)
-    wsb = _lib.query("cal_explain_pairs_ws", M, B, host=host)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    _lib.call("cal_explain_rank_pairs", _p(score) if M else None, stride, _p(seg_ptr), B, M, int(max_seg), rt, kc, _p(g8),
-              _p(twin) if M else None, rc, _p(out) if M else None, _p(mask) if M else None, _p(rank) if M else None, _p(met),
-              _p(ws), wsb, None if host else _stream(), host=host)
-    return mask.view(torch.bool), rank, met, out
+    return _rank_call(score, seg_ptr, max_seg, twin, rc, ratio, k, gt, metrics)
 
 
 @dataclass
@@ -181,16 +172,22 @@ class Explanation:
         return extract_subgraph(data, edge_mask=em, node_mask=nm, complement=complement, relabel=relabel)
 
 
-def _scores(model, data):
-    """Eval-mode causal scores (edge [E], node [N]) of ``data`` with the identity permutation.  Engine-backed models: views
-    into the engine's workspace; others: the operator-level backbone + attention (``_CausalBase._attention_scores``)."""
+def _eval_forward(model, data):
+    """``model``'s engine after one eval-mode forward of ``data`` with the identity permutation, or ``None`` (nothing ran)
+    when the model has no engine for ``data``."""
     x = data.x if getattr(data, "x", None) is not None else data.feat
     eng = model._engine_for(x)
     if eng is not None:
         eng.forward(data, None, training=False)          # identity permutation: no host RNG
         eng._fwd_token = getattr(eng, "_fwd_token", 0) + 1    # (a pending training-mode backward would now read eval activations)
-        return eng.attention_scores(data)
-    return model._attention_scores(data)
+    return eng
+
+
+def _scores(model, data):
+    """Eval-mode causal scores (edge [E], node [N]) of ``data`` with the identity permutation.  Engine-backed models: views
+    into the engine's workspace; others: the operator-level backbone + attention (``_CausalBase._attention_scores``)."""
+    eng = _eval_forward(model, data)
+    return eng.attention_scores(data) if eng is not None else model._attention_scores(data)
 
 
 class _Layout:
@@ -220,16 +217,22 @@ class _Layout:
         if self.max_edges == 0 and B > 0 and data.edge_index.size(1) > 0:
             self.max_edges = int((self.edge_ptr[1:] - self.edge_ptr[:-1]).max())
 
-    def rank_edges(self, score, **kw):
+    def _in_order(self, call, score, kw):
+        """``call(score, **kw)`` over the columns in ``order``: ``score`` and ``gt`` reordered by graph, every per-column
+        tensor of the result (all but the metrics, at index 2) scattered back to the caller's column order."""
         if self.order is None:
-            return rank_segments(score, self.edge_ptr, self.max_edges, **kw)
+            return call(score, **kw)
         gt = kw.pop("gt", None)
-        mask_s, rank_s, met = rank_segments(score[self.order].contiguous(), self.edge_ptr, self.max_edges,
-                                            gt=None if gt is None else gt[self.order], **kw)
-        mask, rank = torch.empty_like(mask_s), torch.empty_like(rank_s)
-        mask[self.order] = mask_s
-        rank[self.order] = rank_s
-        return mask, rank, met
+        res = call(score[self.order].contiguous(), gt=None if gt is None else gt[self.order], **kw)
+
+        def back(t):
+            out = torch.empty_like(t)
+            out[self.order] = t
+            return out
+        return tuple(r if i == 2 else back(r) for i, r in enumerate(res))
+
+    def rank_edges(self, score, **kw):
+        return self._in_order(lambda s, **k: rank_segments(s, self.edge_ptr, self.max_edges, **k), score, kw)
 
     def twins(self, edge_index):
         """``(twin int32 [E], totals int64 [2])`` of one ``cal_edge_twin`` call over the columns in ``order`` (twin indexes that
@@ -260,14 +263,7 @@ class _Layout:
     def rank_edge_pairs(self, score, edge_index, reduce, **kw):
         """``rank_edges`` over undirected edges -> ``(mask, rank, metrics, symmetrised score)`` in the caller's column order."""
         twin = self.twins(edge_index)[0]
-        if self.order is None:
-            return rank_segment_pairs(score, self.edge_ptr, self.max_edges, twin, reduce, **kw)
-        gt = kw.pop("gt", None)
-        res = rank_segment_pairs(score[self.order].contiguous(), self.edge_ptr, self.max_edges, twin, reduce,
-                                 gt=None if gt is None else gt[self.order], **kw)
-        mask, rank, sym = torch.empty_like(res[0]), torch.empty_like(res[1]), torch.empty_like(res[3])
-        mask[self.order], rank[self.order], sym[self.order] = res[0], res[1], res[3]
-        return mask, rank, res[2], sym
+        return self._in_order(lambda s, **k: rank_segment_pairs(s, self.edge_ptr, self.max_edges, twin, reduce, **k), score, kw)
 
     def rank_nodes(self, score, **kw):
         return rank_segments(score, self.ptr, self.max_nodes, **kw)
@@ -473,14 +469,11 @@ _FID = ("acc_full", "acc_keep", "acc_drop", "fid_plus", "fid_minus")
 def _log_probs(model, data) -> torch.Tensor:
     """Eval-mode log-probabilities [3, B, C] (heads c, o, co) of ``data`` with the identity permutation: the engine's forward
     when the model has one, else the operator-level ``model(data)``."""
-    x = data.x if getattr(data, "x", None) is not None else data.feat
-    eng = model._engine_for(x)
+    eng = _eval_forward(model, data)
     if eng is not None:
-        eng.forward(data, None, training=False)
-        eng._fwd_token = getattr(eng, "_fwd_token", 0) + 1
         return torch.stack(eng.logp_copy())
-    B = int(data.num_graphs)
-    return torch.stack(model(data, perm=torch.arange(B, device=x.device))[:3])
+    x = data.x if getattr(data, "x", None) is not None else data.feat
+    return torch.stack(model(data, perm=torch.arange(int(data.num_graphs), device=x.device))[:3])
 
 
 def _untiled(data, lay):
