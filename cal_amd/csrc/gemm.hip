@@ -17,16 +17,14 @@
 // epilogue, per-column sum / sum-of-squares of the output (the next BatchNorm's batch statistics)
 // and the BN-backward column sums, pre-reduced per workgroup in fp64 and either written as one
 // partial row per row-tile (large launches; finished by k_stats_final) or added atomically (small).
-#include "engine.hpp"
+#include "gemm_tile.hpp"
 
 namespace cal {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int BM = 64, BN = 64, BK = 32;   // BK = 64 measured slower (9.6 vs 8.8 us at K = 128)
-constexpr int NQ = BM * BK / 4 / 256;   // float4 per thread per operand tile
-constexpr int LDT = 65;   // LDS row stride (floats) for tiles filled by transposing scalar stores
-constexpr int LDD = 68;   // LDS row stride for tiles filled by direct 16B stores
+constexpr int BM = 64, BN = 64;
+constexpr int NQ = tile_nq<BM>();           // float4 per thread per operand tile
+constexpr int LDT = tile_ld<BM, true>();    // LDS row stride (floats) for tiles filled by transposing scalar stores
+constexpr int LDD = tile_ld<BM, false>();   // LDS row stride for tiles filled by direct 16B stores
 constexpr int XMAX = 512; // max feature width of a BN-transformed k-contiguous operand
 #ifdef CAL_GEMM_CLOCKS                    // profiling aid: phase timestamps (100 MHz) of workgroup (1,0,0)
 __device__ long long g_gemm_clk[16];
@@ -37,101 +35,26 @@ __device__ long long g_gemm_blk[2 * 2048];    // start / end timestamp of every 
 #endif
 constexpr int PRE_T = 4;  // K tiles a workgroup can preload at once (K chunk <= 128): see gemm_preloaded
 
-// Operand tiles.  The operand is logically T[mn][k] (mn = row of A / column of B).
-//   KC = true : memory is [mn][k] row-major (k contiguous)  -> transposing LDS store
-//   KC = false: memory is [k][mn] row-major (mn contiguous) -> direct 16 B LDS store
-// MODE 0 = interior tile: unconditional 16 B loads.
-// MODE 1 = ragged in mn only (last row / column tile; K range whole, 16 B aligned, and for !KC
-//          operands mn_end % 4 == 0): 16 B loads from a CLAMPED row / column group.  The rows or
-//          columns past the end then hold copies of valid data, which only ever reach accumulator
-//          rows / columns the epilogue never stores -- no zeroing, same speed as an interior tile
-//          (the scalar path made the one ragged workgroup of a [7315,128] launch the critical path:
-//          18 us against 5.6 us for its 229 neighbours).
-// MODE 2 = anything else: every element from a clamped (always valid) address, zeroed at store time.
-// No divergent control flow in any mode.
-template <bool KC, int MODE>
-__device__ __forceinline__ void tile_load(float4 (&r)[NQ], const float* __restrict__ p, int ld, int mn0, int mn_end,
-                                          int k0, int k_end) {
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        const int f = threadIdx.x + q * 256;
-        const int mn = KC ? f / (BK / 4) : (f % (BM / 4)) * 4;
-        const int k = KC ? (f % (BK / 4)) * 4 : f / (BM / 4);
-        if (MODE == 0) {
-            r[q] = KC ? *reinterpret_cast<const float4*>(p + (size_t)(mn0 + mn) * ld + k0 + k)
-                      : *reinterpret_cast<const float4*>(p + (size_t)(k0 + k) * ld + mn0 + mn);
-        } else if (MODE == 1) {
-            r[q] = KC ? *reinterpret_cast<const float4*>(p + (size_t)min(mn0 + mn, mn_end - 1) * ld + k0 + k)
-                      : *reinterpret_cast<const float4*>(p + (size_t)(k0 + k) * ld + min(mn0 + mn, mn_end - 4));
-        } else if (KC) {
-            const float* row = p + (size_t)min(mn0 + mn, mn_end - 1) * ld;
-            const int kl = k_end - 1;
-            r[q] = make_float4(row[min(k0 + k, kl)], row[min(k0 + k + 1, kl)], row[min(k0 + k + 2, kl)], row[min(k0 + k + 3, kl)]);
-        } else {
-            const float* row = p + (size_t)min(k0 + k, k_end - 1) * ld;
-            const int ml = mn_end - 1;
-            r[q] = make_float4(row[min(mn0 + mn, ml)], row[min(mn0 + mn + 1, ml)], row[min(mn0 + mn + 2, ml)], row[min(mn0 + mn + 3, ml)]);
-        }
-    }
-}
-
-// XF: 0 = plain, 1 = BN scale/shift on the feature axis, 2 = per-storage-row scale, then BN.
-// sc/sh: LDS tables indexed by (k - kb) for KC operands and by the tile-local mn for !KC ones.
-template <bool KC, int MODE, int XF>
-__device__ __forceinline__ void tile_store(const float4 (&r)[NQ], float* __restrict__ s, int mn0, int mn_end, int k0,
-                                           int k_end, int kb, const float* __restrict__ rsp, int rs_stride,
-                                           const float* sc, const float* sh) {
-    constexpr int LD = KC ? LDT : LDD;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        const int f = threadIdx.x + q * 256;
-        const int mn = KC ? f / (BK / 4) : (f % (BM / 4)) * 4;
-        const int k = KC ? (f % (BK / 4)) * 4 : f / (BM / 4);
-        float v[4] = {r[q].x, r[q].y, r[q].z, r[q].w};
-        if (XF > 0) {
-            float rs = 1.f;
-            if (XF == 2) rs = rsp[(size_t)(KC ? min(mn0 + mn, mn_end - 1) : min(k0 + k, k_end - 1)) * rs_stride];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int fi = KC ? (k0 + k + j - kb) : (mn + j);     // feature index into the tables
-                v[j] = fmaf(XF == 2 ? rs * v[j] : v[j], sc[fi], sh[fi]);
-            }
-        }
-        if (MODE == 2) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const bool ok = KC ? (mn0 + mn < mn_end && k0 + k + j < k_end) : (k0 + k < k_end && mn0 + mn + j < mn_end);
-                v[j] = ok ? v[j] : 0.f;
-            }
-        }
-        if (KC) {
-            s[(k + 0) * LD + mn] = v[0]; s[(k + 1) * LD + mn] = v[1];
-            s[(k + 2) * LD + mn] = v[2]; s[(k + 3) * LD + mn] = v[3];
-        } else {
-            *reinterpret_cast<float4*>(s + k * LD + mn) = make_float4(v[0], v[1], v[2], v[3]);
-        }
-    }
-}
-
+// Operand tiles: tile_load / tile_store of gemm_tile.hpp at T = 64, bounds modes 0 / 1 / 2.
 template <bool A_KC, bool B_KC, int XA, int XB, int MODE>
 __device__ __forceinline__ void gemm_kloop(const GemmArgs& a, const GemmProb& pr, float* As, float* Bs, int m0, int n0,
                                            int kb, int ke, const float* sca, const float* sha, const float* scb,
-                                           const float* shb, f32x16& acc, int wm, int wn, int li, int lk) {
+                                           const float* shb, gc_f32x16& acc, int wm, int wn, int li, int lk) {
     constexpr int LDA = A_KC ? LDT : LDD, LDB = B_KC ? LDT : LDD;
     constexpr int SA = BK * LDA, SB = BK * LDB;
     const int M = a.M, N = a.N;
     float4 ra[NQ], rb[NQ];
-    tile_load<A_KC, MODE>(ra, pr.A, a.lda, m0, M, kb, ke);
-    tile_load<B_KC, MODE>(rb, pr.B, a.ldb, n0, N, kb, ke);
-    tile_store<A_KC, MODE, XA>(ra, As, m0, M, kb, ke, kb, pr.xa.rs, pr.xa.rs_stride, sca, sha);
-    tile_store<B_KC, MODE, XB>(rb, Bs, n0, N, kb, ke, kb, pr.xb.rs, pr.xb.rs_stride, scb, shb);
+    tile_load<BM, A_KC, MODE>(ra, pr.A, a.lda, m0, M, kb, ke);
+    tile_load<BM, B_KC, MODE>(rb, pr.B, a.ldb, n0, N, kb, ke);
+    tile_store<BM, A_KC, MODE, XA>(ra, As, m0, M, kb, ke, kb, pr.xa.rs, pr.xa.rs_stride, sca, sha);
+    tile_store<BM, B_KC, MODE, XB>(rb, Bs, n0, N, kb, ke, kb, pr.xb.rs, pr.xb.rs_stride, scb, shb);
     __syncthreads();
     int st = 0;
     for (int k0 = kb; k0 < ke; k0 += BK) {
         const bool more = k0 + BK < ke;
         if (more) {
-            tile_load<A_KC, MODE>(ra, pr.A, a.lda, m0, M, k0 + BK, ke);
-            tile_load<B_KC, MODE>(rb, pr.B, a.ldb, n0, N, k0 + BK, ke);
+            tile_load<BM, A_KC, MODE>(ra, pr.A, a.lda, m0, M, k0 + BK, ke);
+            tile_load<BM, B_KC, MODE>(rb, pr.B, a.ldb, n0, N, k0 + BK, ke);
         }
         __builtin_amdgcn_sched_barrier(0);
         const float* as = As + st * SA + wm + li;
@@ -146,15 +69,13 @@ __device__ __forceinline__ void gemm_kloop(const GemmArgs& a, const GemmProb& pr
         for (int i = 0; i < BK / 2; ++i) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[i], acc, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
         if (more) {
-            tile_store<A_KC, MODE, XA>(ra, As + (st ^ 1) * SA, m0, M, k0 + BK, ke, kb, pr.xa.rs, pr.xa.rs_stride, sca, sha);
-            tile_store<B_KC, MODE, XB>(rb, Bs + (st ^ 1) * SB, n0, N, k0 + BK, ke, kb, pr.xb.rs, pr.xb.rs_stride, scb, shb);
+            tile_store<BM, A_KC, MODE, XA>(ra, As + (st ^ 1) * SA, m0, M, k0 + BK, ke, kb, pr.xa.rs, pr.xa.rs_stride, sca, sha);
+            tile_store<BM, B_KC, MODE, XB>(rb, Bs + (st ^ 1) * SB, n0, N, k0 + BK, ke, kb, pr.xb.rs, pr.xb.rs_stride, scb, shb);
         }
         __syncthreads();
         st ^= 1;
     }
 }
-
-__device__ __forceinline__ void pin4(float4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
 
 // Short reductions (K chunk <= PRE_T * BK = 128: every node-level GEMM of the hot path and the
 // 128-deep slices of the split-K weight gradients).  The streaming loop above pays one dependent
@@ -167,8 +88,8 @@ __device__ __forceinline__ void pre_issue(const GemmArgs& a, const GemmProb& pr,
 #pragma unroll
     for (int t = 0; t < PRE_T; ++t)
         if (t < nt) {
-            tile_load<A_KC, MODE>(ra[t], pr.A, a.lda, m0, a.M, kb + t * BK, ke);
-            tile_load<B_KC, MODE>(rb[t], pr.B, a.ldb, n0, a.N, kb + t * BK, ke);
+            tile_load<BM, A_KC, MODE>(ra[t], pr.A, a.lda, m0, a.M, kb + t * BK, ke);
+            tile_load<BM, B_KC, MODE>(rb[t], pr.B, a.ldb, n0, a.N, kb + t * BK, ke);
         }
     asm volatile("" ::: "memory");      // the loads stay here (not sunk next to their LDS stores), and nothing waits yet
 }
@@ -180,8 +101,8 @@ __device__ __forceinline__ void pre_commit(const GemmArgs& a, const GemmProb& pr
 #pragma unroll
     for (int t = 0; t < PRE_T; ++t)
         if (t < nt) {
-            tile_store<A_KC, MODE, XA>(ra[t], As + t * SA, m0, a.M, kb + t * BK, ke, kb, pr.xa.rs, pr.xa.rs_stride, sca, sha);
-            tile_store<B_KC, MODE, XB>(rb[t], Bs + t * SB, n0, a.N, kb + t * BK, ke, kb, pr.xb.rs, pr.xb.rs_stride, scb, shb);
+            tile_store<BM, A_KC, MODE, XA>(ra[t], As + t * SA, m0, a.M, kb + t * BK, ke, kb, pr.xa.rs, pr.xa.rs_stride, sca, sha);
+            tile_store<BM, B_KC, MODE, XB>(rb[t], Bs + t * SB, n0, a.N, kb + t * BK, ke, kb, pr.xb.rs, pr.xb.rs_stride, scb, shb);
         }
 }
 
@@ -238,28 +159,12 @@ __device__ __forceinline__ void gemm_block(const GemmArgs& a, int vecA, int vecB
     }
 
     // BN scale/shift tables of the transformed operands; one block also updates the running stats
-    if (XA > 0) {
-        const int cnt = A_KC ? (ke - kb) : min(BM, M - m0);
-        const int c0 = A_KC ? kb : m0;
-        for (int t = threadIdx.x; t < cnt; t += 256) {
-            bn_scale_shift<true>(pr.xa.bn, c0 + t, xsc[0][t], xsh[0][t]);
-            if (pr.xa.bn.update && by == 0 && split == 0 && (A_KC ? bx == 0 : true)) bn_update_running<true>(pr.xa.bn, c0 + t);
-        }
-        if (!A_KC) for (int t = cnt + threadIdx.x; t < BM; t += 256) { xsc[0][t] = 0.f; xsh[0][t] = 0.f; }
-    }
-    if (XB > 0) {
-        const int cnt = B_KC ? (ke - kb) : min(BN, N - n0);
-        const int c0 = B_KC ? kb : n0;
-        for (int t = threadIdx.x; t < cnt; t += 256) {
-            bn_scale_shift<true>(pr.xb.bn, c0 + t, xsc[1][t], xsh[1][t]);
-            if (pr.xb.bn.update && bx == 0 && split == 0 && (B_KC ? by == 0 : true)) bn_update_running<true>(pr.xb.bn, c0 + t);
-        }
-        if (!B_KC) for (int t = cnt + threadIdx.x; t < BN; t += 256) { xsc[1][t] = 0.f; xsh[1][t] = 0.f; }
-    }
+    if (XA > 0) xform_tables<A_KC, BM, true>(pr.xa.bn, xsc[0], xsh[0], kb, ke, m0, M, by == 0 && split == 0 && (A_KC ? bx == 0 : true));
+    if (XB > 0) xform_tables<B_KC, BN, true>(pr.xb.bn, xsc[1], xsh[1], kb, ke, n0, N, bx == 0 && split == 0 && (B_KC ? by == 0 : true));
     if (XA > 0 || XB > 0) __syncthreads();
     GEMM_CLK(1);
 
-    f32x16 acc, acc2;
+    gc_f32x16 acc, acc2;
 #pragma unroll
     for (int i = 0; i < 16; ++i) { acc[i] = 0.f; acc2[i] = 0.f; }
     if (pre) {
@@ -304,31 +209,17 @@ __device__ __forceinline__ void gemm_block(const GemmArgs& a, int vecA, int vecB
         else gemm_kloop<A_KC, B_KC, XA, XB, 2>(a, pr, As, Bs, m0, n0, kb, ke, xsc[0], xsh[0], xsc[1], xsh[1], acc, wm, wn, li, lk);
     }
     GEMM_CLK(4);
-    // C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
     const int col = n0 + wn + li;
     const bool cok = col < N;
     const float bv = (pr.bias && cok) ? pr.bias[col] : 0.f;
     const bool want_st = pr.st_sum != nullptr, want_dot = pr.dot_sum != nullptr;
     float amean = 0.f, arstd = 0.f;
-    float aux[16] = {};
+    EpiAux<1> ea = {};
     if (want_dot && cok) {
-        // aux values and their row scales as one batch of unconditional loads (no scale: the aux pointer again, stride 0, value
-        // ignored); a per-row `if (aux_rs)` made every row a load, a branch and a dependent second load (gemm_big.hip)
-        const bool has_rs = pr.aux_rs != nullptr;
-        const float* rsp = has_rs ? pr.aux_rs : pr.aux;
-        const size_t rstr = has_rs ? (size_t)pr.aux_rs_stride : 0;
-        float ars[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = min(m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * lk, M - 1);
-            aux[r] = pr.aux[(size_t)row * N + col];
-            ars[r] = rsp[(size_t)row * rstr];
-        }
+        ea.load(pr, m0 + wm, lk, M, N, {col});
         bn_mean_rstd<true>(pr.aux_bn, col, amean, arstd);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(aux[r]), "+v"(ars[r]));
-#pragma unroll
-        for (int r = 0; r < 16; ++r) aux[r] *= has_rs ? ars[r] : 1.f;
+        ea.pin();
+        ea.scale(pr);
     }
     // hipcc re-inserts `s_waitcnt vmcnt(0)` at the head of every guarded block below while a load issued
     // before them may still be pending on some path; on gfx9 stores count in vmcnt too, so each store then
@@ -336,49 +227,17 @@ __device__ __forceinline__ void gemm_block(const GemmArgs& a, int vecA, int vecB
     asm volatile("" :: "v"(bv), "v"(amean), "v"(arstd));
     if (want_dot) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) asm volatile("" :: "v"(aux[r]));
+        for (int r = 0; r < 16; ++r) asm volatile("" :: "v"(ea.v[0][r]));
     }
     double s1 = 0.0, s2 = 0.0;
     GEMM_CLK(6);
-    auto emit = [&](int r, int row) {
-        float v = acc[r] + bv;
-        if (a.relu) v = fmaxf(v, 0.f);
-        if (C) C[(size_t)row * a.ldc + col] = v;
-        if (want_st) { s1 += (double)v; s2 += (double)v * (double)v; }
-        if (want_dot) {
-            const float xn = (aux[r] - amean) * arstd;
-            s1 += (double)v;
-            s2 += (double)v * (double)xn;
-        }
-    };
-    if (m0 + BM <= M && n0 + BN <= N) {        // interior tile: no per-element guards, the 16 stores stream out
-#pragma unroll
-        for (int r = 0; r < 16; ++r) emit(r, m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * lk);
-    } else {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * lk;
-            if (row < M && cok) emit(r, row);
-        }
-    }
+    epi_walk(acc, ea.v[0], bv, amean, arstd, a.relu, C, a.ldc, m0 + wm, lk, col, M, m0 + BM <= M && n0 + BN <= N, cok, want_st, want_dot, s1, s2);
     GEMM_CLK(7);
     if (want_st || want_dot) {
-        s1 += __shfl_xor(s1, 32, 64);
-        s2 += __shfl_xor(s2, 32, 64);
-        if (lk == 0) { red[wave][0][li] = s1; red[wave][1][li] = s2; }
+        stat_fold(s1, s2, red[wave], li, lk);
         __syncthreads();
-        if (wave < 2 && lk == 0 && cok) {      // waves 0,1 own columns wn = 0 / 32; add the wm = 32 partner
-            const double t1 = red[wave][0][li] + red[wave + 2][0][li];
-            const double t2 = red[wave][1][li] + red[wave + 2][1][li];
-            if (pr.parts) {                     // one partial row per row tile: [gridDim.x][2][N]
-                pr.parts[((size_t)bx * 2 + 0) * N + col] = t1;
-                pr.parts[((size_t)bx * 2 + 1) * N + col] = t2;
-            } else {
-                const size_t po = (size_t)(bx % NSTRIPE) * pr.st_ss + col;
-                atomicAdd((want_st ? pr.st_sum : pr.dot_sum) + po, t1);
-                atomicAdd((want_st ? pr.st_sq : pr.dot_prod) + po, t2);
-            }
-        }
+        if (wave < 2 && lk == 0 && cok)        // waves 0,1 own columns wn = 0 / 32; add the wm = 32 partner
+            stat_commit(pr, want_st, bx, N, col, red[wave][0][li] + red[wave + 2][0][li], red[wave][1][li] + red[wave + 2][1][li]);
     }
     GEMM_CLK(5);
 #ifdef CAL_GEMM_CLOCKS
@@ -443,7 +302,7 @@ static int gemm_classify(bool a_kc, bool b_kc, const GemmArgs& a, int nbatch, in
     for (int b = 0; b < nbatch; ++b) {
         vecA = vecA && aligned16(a.p[b].A);
         vecB = vecB && aligned16(a.p[b].B);
-        const int ma = a.p[b].xa.has_bn ? (a.p[b].xa.rs ? 2 : 1) : 0, mb = a.p[b].xb.has_bn ? (a.p[b].xb.rs ? 2 : 1) : 0;
+        const int ma = xform_class(a.p[b].xa), mb = xform_class(a.p[b].xb);
         if ((a.p[b].xa.rs && !a.p[b].xa.has_bn) || (a.p[b].xb.rs && !a.p[b].xb.has_bn)) { set_error("launch_gemm: row scale without BN is not instantiated"); return 2; }
         if ((xa >= 0 && xa != ma) || (xb >= 0 && xb != mb)) { set_error("launch_gemm: mixed operand transforms in one batch"); return 2; }
         xa = ma; xb = mb;
@@ -477,9 +336,9 @@ int launch_gemm_dual(const GemmArgs& ax, int nbx, const GemmArgs& aw, int nbw, h
     g.gx2 = cdiv(aw.M, BM); g.gy2 = cdiv(aw.N, BN);
     const int n2 = g.gx2 * g.gy2 * nbw * aw.nsplit;
     const dim3 grid(g.n1 + n2);
-    if (xaw == 0) hipLaunchKernelGGL((k_gemm_dual<true, true, 0, 0, false, false, 0, 0>), grid, dim3(256), 0, stream, ax, vax, vbx, aw, vaw, vbw, g);
-    else if (xaw == 1) hipLaunchKernelGGL((k_gemm_dual<true, true, 0, 0, false, false, 1, 0>), grid, dim3(256), 0, stream, ax, vax, vbx, aw, vaw, vbw, g);
-    else hipLaunchKernelGGL((k_gemm_dual<true, true, 0, 0, false, false, 2, 0>), grid, dim3(256), 0, stream, ax, vax, vbx, aw, vaw, vbw, g);
+    with_xa(xaw, [&](auto x) {
+        hipLaunchKernelGGL((k_gemm_dual<true, true, 0, 0, false, false, decltype(x)::value, 0>), grid, dim3(256), 0, stream, ax, vax, vbx, aw, vaw, vbw, g);
+    });
     CAL_CHECK_LAUNCH("k_gemm_dual");
     return 0;
 }
@@ -501,17 +360,13 @@ int launch_gemm(bool transA, bool transB, const GemmArgs& a, int nbatch, hipStre
     bool ok = true;
     if (a_kc && !b_kc) {          // NN
         if (xb != 0) ok = false;
-        else if (xa == 0) launch_one<true, false, 0, 0>(a, grid, vecA, vecB, stream);
-        else if (xa == 1) launch_one<true, false, 1, 0>(a, grid, vecA, vecB, stream);
-        else launch_one<true, false, 2, 0>(a, grid, vecA, vecB, stream);
+        else with_xa(xa, [&](auto x) { launch_one<true, false, decltype(x)::value, 0>(a, grid, vecA, vecB, stream); });
     } else if (a_kc && b_kc) {    // NT
         if (xb != 0 || xa == 2) ok = false;
         else if (xa == 0) launch_one<true, true, 0, 0>(a, grid, vecA, vecB, stream);
         else launch_one<true, true, 1, 0>(a, grid, vecA, vecB, stream);
     } else if (!a_kc && !b_kc) {  // TN
-        if (xb == 0 && xa == 0) launch_one<false, false, 0, 0>(a, grid, vecA, vecB, stream);
-        else if (xb == 0 && xa == 1) launch_one<false, false, 1, 0>(a, grid, vecA, vecB, stream);
-        else if (xb == 0 && xa == 2) launch_one<false, false, 2, 0>(a, grid, vecA, vecB, stream);
+        if (xb == 0) with_xa(xa, [&](auto x) { launch_one<false, false, decltype(x)::value, 0>(a, grid, vecA, vecB, stream); });
         else if (xb == 1 && xa == 0) launch_one<false, false, 0, 1>(a, grid, vecA, vecB, stream);
         else ok = false;
     } else {                      // TT

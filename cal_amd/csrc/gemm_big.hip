@@ -7,73 +7,25 @@
 //   slab is fetched by half as many workgroups.  The 64 x 64 kernel stays the choice below ~16k rows, where its
 //   4x larger grid is what fills the 256 CUs (config 2: 115 row tiles).
 //
-// Same contract as gemm_block (engine.hpp GemmArgs / GemmProb): BatchNorm (+ row scale) applied to operand A while it
+// Same contract as every GEMM kernel (engine.hpp GemmArgs / GemmProb; the operand tiles and the epilogue pieces are those of gemm_tile.hpp): BatchNorm (+ row scale) applied to operand A while it
 // is staged, bias / ReLU epilogue, per-column statistics or BN-backward dot sums in fp64 (partial row per ROW TILE OF
 // 128 -- gemm_row_tiles() accounts for it -- or atomics), split-K slices into slabs.  Layouts: NN, NT (k-contiguous
 // operands, K % 32 == 0) and TN (weight gradients: K = node rows, any K, zero-filled tail).
-#include "engine.hpp"
+#include "gemm_tile.hpp"
 
 namespace cal {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 namespace big {
 
-constexpr int T = 128, BK = 32;
-constexpr int NQ = T * BK / 4 / 256;      // float4 per thread per operand tile (4)
-constexpr int LDT = T + 1;                // LDS row stride of tiles filled by transposing scalar stores (bank = 4 kq + mn)
-constexpr int LDD = T + 4;                // ... by direct 16 B stores
+constexpr int T = 128;
+constexpr int NQ = tile_nq<T>();          // float4 per thread per operand tile (4)
+constexpr int LDT = tile_ld<T, true>();   // LDS row stride of tiles filled by transposing scalar stores (bank = 4 kq + mn)
+constexpr int LDD = tile_ld<T, false>();  // ... by direct 16 B stores
 constexpr int XMAX = 512;                 // BN table width (k range of a k-contiguous operand, or the 128 tile columns)
 
-__device__ __forceinline__ void pin4(float4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
-
-// Operand tile T[mn][k] -> registers.  KC: memory [mn][k] (k contiguous); !KC: memory [k][mn].  Always 16 B loads from
-// clamped (valid) addresses: rows / columns past the end hold copies of valid data that only reach accumulator
-// entries the epilogue never stores; k rows past the end of a !KC operand are zeroed at store time.
-template <bool KC>
-__device__ __forceinline__ void load(float4 (&r)[NQ], const float* __restrict__ p, int ld, int mn0, int mn_end, int k0, int k_end) {
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        const int f = threadIdx.x + q * 256;
-        if (KC) {
-            const int mn = f / (BK / 4), k = (f % (BK / 4)) * 4;
-            r[q] = *reinterpret_cast<const float4*>(p + (size_t)min(mn0 + mn, mn_end - 1) * ld + k0 + k);
-        } else {
-            const int mn = (f % (T / 4)) * 4, k = f / (T / 4);
-            r[q] = *reinterpret_cast<const float4*>(p + (size_t)min(k0 + k, k_end - 1) * ld + min(mn0 + mn, mn_end - 4));
-        }
-    }
-}
-
-// XF: 0 plain, 1 BN scale/shift on the feature axis, 2 per-storage-row scale then BN (as gemm.hip tile_store)
-template <bool KC, int XF>
-__device__ __forceinline__ void store(const float4 (&r)[NQ], float* __restrict__ s, int mn0, int mn_end, int k0, int k_end,
-                                      int kb, const float* __restrict__ rsp, int rs_stride, const float* sc, const float* sh) {
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        const int f = threadIdx.x + q * 256;
-        const int mn = KC ? f / (BK / 4) : (f % (T / 4)) * 4;
-        const int k = KC ? (f % (BK / 4)) * 4 : f / (T / 4);
-        float v[4] = {r[q].x, r[q].y, r[q].z, r[q].w};
-        if (XF > 0) {
-            float rs = 1.f;
-            if (XF == 2) rs = rsp[(size_t)(KC ? min(mn0 + mn, mn_end - 1) : min(k0 + k, k_end - 1)) * rs_stride];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int fi = KC ? (k0 + k + j - kb) : (mn + j);
-                v[j] = fmaf(XF == 2 ? rs * v[j] : v[j], sc[fi], sh[fi]);
-            }
-        }
-        if (KC) {
-            s[(k + 0) * LDT + mn] = v[0]; s[(k + 1) * LDT + mn] = v[1];
-            s[(k + 2) * LDT + mn] = v[2]; s[(k + 3) * LDT + mn] = v[3];
-        } else {
-            const bool ok = k0 + k < k_end;
-            *reinterpret_cast<float4*>(s + k * LDD + mn) = ok ? make_float4(v[0], v[1], v[2], v[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
-}
-
+// Operand tiles: bounds mode 3 of gemm_tile.hpp -- always 16 B loads from clamped (valid) addresses: rows / columns past the end
+// hold copies of valid data that only reach accumulator entries the epilogue never stores; k rows past the end of a !KC
+// operand are zeroed at store time.
 template <bool A_KC, bool B_KC>
 struct Smem {
     static constexpr int LDA = A_KC ? LDT : LDD, LDB = B_KC ? LDT : LDD;
@@ -123,27 +75,21 @@ __device__ __forceinline__ void block(const GemmArgs& a, int bx, int by, int bz,
         while (wall_clock64() - t0 < wait) __builtin_amdgcn_s_sleep(32);
     }
     float4 ra0[NQ], rb0[NQ], ra1[NQ], rb1[NQ];
-    load<A_KC>(ra0, pr.A, a.lda, m0, M, kb, ke);
-    load<B_KC>(rb0, pr.B, a.ldb, n0, N, kb, ke);
+    tile_load<T, A_KC, 3>(ra0, pr.A, a.lda, m0, M, kb, ke);
+    tile_load<T, B_KC, 3>(rb0, pr.B, a.ldb, n0, N, kb, ke);
     if (nt > 1) {
-        load<A_KC>(ra1, pr.A, a.lda, m0, M, kb + BK, ke);
-        load<B_KC>(rb1, pr.B, a.ldb, n0, N, kb + BK, ke);
+        tile_load<T, A_KC, 3>(ra1, pr.A, a.lda, m0, M, kb + BK, ke);
+        tile_load<T, B_KC, 3>(rb1, pr.B, a.ldb, n0, N, kb + BK, ke);
     }
     if (XA > 0) {
-        const int cnt = A_KC ? (ke - kb) : min(T, M - m0);
-        const int c0 = A_KC ? kb : m0;
-        for (int t = threadIdx.x; t < cnt; t += 256) {
-            bn_scale_shift(pr.xa.bn, c0 + t, xsc[t], xsh[t]);
-            if (pr.xa.bn.update && by == 0 && split == 0 && (A_KC ? bx == 0 : true)) bn_update_running(pr.xa.bn, c0 + t);
-        }
-        if (!A_KC) for (int t = cnt + threadIdx.x; t < T; t += 256) { xsc[t] = 0.f; xsh[t] = 0.f; }
+        xform_tables<A_KC, T, false>(pr.xa.bn, xsc, xsh, kb, ke, m0, M, by == 0 && split == 0 && (A_KC ? bx == 0 : true));
         __syncthreads();
     }
-    store<A_KC, XA>(ra0, As, m0, M, kb, ke, kb, pr.xa.rs, pr.xa.rs_stride, xsc, xsh);
-    store<B_KC, 0>(rb0, Bs, n0, N, kb, ke, kb, nullptr, 0, nullptr, nullptr);
+    tile_store<T, A_KC, 3, XA>(ra0, As, m0, M, kb, ke, kb, pr.xa.rs, pr.xa.rs_stride, xsc, xsh);
+    tile_store<T, B_KC, 3, 0>(rb0, Bs, n0, N, kb, ke, kb, nullptr, 0, nullptr, nullptr);
     __syncthreads();
 
-    f32x16 acc[2][2];
+    gc_f32x16 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 16; ++i) { acc[0][0][i] = 0.f; acc[0][1][i] = 0.f; acc[1][0][i] = 0.f; acc[1][1][i] = 0.f; }
 
@@ -180,8 +126,8 @@ __device__ __forceinline__ void block(const GemmArgs& a, int bx, int by, int bz,
         read_ops(0, av[0], bv[0]);                       // the one LDS latency a tile exposes (right after the barrier)
         __builtin_amdgcn_sched_barrier(0);
         // group 0: + the global loads of tile t+2 and the operand reads of group 1
-        load<A_KC>(la, pr.A, a.lda, m0, M, kl, ke);
-        load<B_KC>(lb, pr.B, a.ldb, n0, N, kl, ke);
+        tile_load<T, A_KC, 3>(la, pr.A, a.lda, m0, M, kl, ke);
+        tile_load<T, B_KC, 3>(lb, pr.B, a.ldb, n0, N, kl, ke);
         read_ops(1, av[1], bv[1]);
         mma(0);
 #pragma unroll
@@ -208,8 +154,8 @@ __device__ __forceinline__ void block(const GemmArgs& a, int bx, int by, int bz,
             __builtin_amdgcn_sched_barrier(0);
         }
         // group 3: + the staging of tile t+1 (requested a whole tile ago) into the other LDS stage
-        store<A_KC, XA>(sa, As + (st ^ 1) * SA, m0, M, k0 + BK, ke, kb, pr.xa.rs, pr.xa.rs_stride, xsc, xsh);
-        store<B_KC, 0>(sb, Bs + (st ^ 1) * SB, n0, N, k0 + BK, ke, kb, nullptr, 0, nullptr, nullptr);
+        tile_store<T, A_KC, 3, XA>(sa, As + (st ^ 1) * SA, m0, M, k0 + BK, ke, kb, pr.xa.rs, pr.xa.rs_stride, xsc, xsh);
+        tile_store<T, B_KC, 3, 0>(sb, Bs + (st ^ 1) * SB, n0, N, k0 + BK, ke, kb, nullptr, 0, nullptr, nullptr);
         mma(3);
 #pragma unroll
         for (int i = 0; i < 12; ++i) {
@@ -226,105 +172,49 @@ __device__ __forceinline__ void block(const GemmArgs& a, int bx, int by, int bz,
         if (t + 1 < nt) tile(t + 1, ra1, rb1, ra0, rb0);
     }
 
-    // epilogue.  C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
+    // epilogue (gemm_tile.hpp), over the wave's 2 x 2 accumulators
     const bool want_st = pr.st_sum != nullptr, want_dot = pr.dot_sum != nullptr;
     const bool interior = m0 + T <= M && n0 + T <= N;
     double s1[2] = {0.0, 0.0}, s2[2] = {0.0, 0.0};
     // Everything the epilogue reads comes first, as ONE batch of unconditional loads on clamped rows / columns: the 4 x 16 aux
-    // values of the wave's four accumulators, the 2 x 16 row scales (no scale: the aux pointer again, stride 0, value ignored),
-    // the BatchNorm constants and the bias.  Per accumulator (16 loads, wait, 16 stores, four times) every tile paid four
-    // round trips; with `if (aux_rs) x *= aux_rs[row]` inside the loop every row was a load, a branch and a dependent second
-    // load (the two-branch backward, the only caller with row scales: 585 us per branch against 455 us without them).
-    float auxv[2][2][16], bvv[2] = {0.f, 0.f}, amean[2] = {0.f, 0.f}, arstd[2] = {0.f, 0.f};
+    // values of the wave's four accumulators, the 2 x 16 row scales, the BatchNorm constants and the bias.  Per accumulator
+    // (16 loads, wait, 16 stores, four times) every tile paid four round trips (the two-branch backward, the only caller
+    // with row scales: 585 us per branch against 455 us without them).
+    EpiAux<2> ea[2];
+    float bvv[2] = {0.f, 0.f}, amean[2] = {0.f, 0.f}, arstd[2] = {0.f, 0.f};
+    const int colc[2] = {min(n0 + wn + li, N - 1), min(n0 + wn + 32 + li, N - 1)};
 #pragma unroll
-    for (int sn = 0; sn < 2; ++sn) {
-        const int colc = min(n0 + wn + sn * 32 + li, N - 1);
-        if (pr.bias) bvv[sn] = pr.bias[colc];
-    }
+    for (int sn = 0; sn < 2; ++sn)
+        if (pr.bias) bvv[sn] = pr.bias[colc[sn]];
     if (want_dot) {
-        const bool has_rs = pr.aux_rs != nullptr;
-        const float* rsp = has_rs ? pr.aux_rs : pr.aux;
-        const size_t rstr = has_rs ? (size_t)pr.aux_rs_stride : 0;
-        float ars[2][16];
 #pragma unroll
-        for (int sm = 0; sm < 2; ++sm)
+        for (int sm = 0; sm < 2; ++sm) ea[sm].load(pr, m0 + wm + sm * 32, lk, M, N, colc);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const size_t row = (size_t)min(m0 + wm + sm * 32 + 4 * lk + (r & 3) + 8 * (r >> 2), M - 1);
-                ars[sm][r] = rsp[row * rstr];
+        for (int sn = 0; sn < 2; ++sn) bn_mean_rstd(pr.aux_bn, colc[sn], amean[sn], arstd[sn]);
 #pragma unroll
-                for (int sn = 0; sn < 2; ++sn) auxv[sn][sm][r] = pr.aux[row * N + min(n0 + wn + sn * 32 + li, N - 1)];
-            }
+        for (int sm = 0; sm < 2; ++sm) ea[sm].pin();
 #pragma unroll
-        for (int sn = 0; sn < 2; ++sn) bn_mean_rstd(pr.aux_bn, min(n0 + wn + sn * 32 + li, N - 1), amean[sn], arstd[sn]);
-#pragma unroll
-        for (int sm = 0; sm < 2; ++sm)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(ars[sm][r]), "+v"(auxv[0][sm][r]), "+v"(auxv[1][sm][r]));
-#pragma unroll
-        for (int sm = 0; sm < 2; ++sm)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float f = has_rs ? ars[sm][r] : 1.f;
-                auxv[0][sm][r] *= f; auxv[1][sm][r] *= f;
-            }
+        for (int sm = 0; sm < 2; ++sm) ea[sm].scale(pr);
     }
     // consume the loads before the guarded stores (else every store waits for the previous one: gemm.hip)
     asm volatile("" :: "v"(bvv[0]), "v"(bvv[1]), "v"(amean[0]), "v"(amean[1]), "v"(arstd[0]), "v"(arstd[1]));
 #pragma unroll
     for (int sn = 0; sn < 2; ++sn) {
         const int col = n0 + wn + sn * 32 + li;
-        const bool cok = col < N;
 #pragma unroll
-        for (int sm = 0; sm < 2; ++sm) {
-            const int rbase = m0 + wm + sm * 32 + 4 * lk;
-            const float (&aux)[16] = auxv[sn][sm];
-            auto emit = [&](int r, int row) {
-                float v = acc[sm][sn][r] + bvv[sn];
-                if (a.relu) v = fmaxf(v, 0.f);
-                if (C) C[(size_t)row * a.ldc + col] = v;
-                if (want_st) { s1[sn] += (double)v; s2[sn] += (double)v * (double)v; }
-                if (want_dot) {
-                    const float xn = (aux[r] - amean[sn]) * arstd[sn];
-                    s1[sn] += (double)v;
-                    s2[sn] += (double)v * (double)xn;
-                }
-            };
-            if (interior) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) emit(r, rbase + (r & 3) + 8 * (r >> 2));
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = rbase + (r & 3) + 8 * (r >> 2);
-                    if (row < M && cok) emit(r, row);
-                }
-            }
-        }
+        for (int sm = 0; sm < 2; ++sm)
+            epi_walk(acc[sm][sn], ea[sm].v[sn], bvv[sn], amean[sn], arstd[sn], a.relu, C, a.ldc, m0 + wm + sm * 32, lk, col, M, interior, col < N,
+                     want_st, want_dot, s1[sn], s2[sn]);
     }
     if (want_st || want_dot) {
 #pragma unroll
-        for (int sn = 0; sn < 2; ++sn) {
-            s1[sn] += __shfl_xor(s1[sn], 32, 64);
-            s2[sn] += __shfl_xor(s2[sn], 32, 64);
-            if (lk == 0) { red[wave][sn][0][li] = s1[sn]; red[wave][sn][1][li] = s2[sn]; }
-        }
+        for (int sn = 0; sn < 2; ++sn) stat_fold(s1[sn], s2[sn], red[wave][sn], li, lk);
         __syncthreads();
         if (wave < 2 && lk == 0) {          // waves 0,1 own columns wn = 0 / 64; add the wm = 64 partner (wave + 2)
 #pragma unroll
             for (int sn = 0; sn < 2; ++sn) {
-                const int col = n0 + wn + sn * 32 + li;
-                if (col < N) {
-                    const double t1 = red[wave][sn][0][li] + red[wave + 2][sn][0][li];
-                    const double t2 = red[wave][sn][1][li] + red[wave + 2][sn][1][li];
-                    if (pr.parts) {             // one partial row per 128-row tile: [row tiles][2][N]
-                        pr.parts[((size_t)bx * 2 + 0) * N + col] = t1;
-                        pr.parts[((size_t)bx * 2 + 1) * N + col] = t2;
-                    } else {
-                        atomicAdd((want_st ? pr.st_sum : pr.dot_sum) + col, t1);
-                        atomicAdd((want_st ? pr.st_sq : pr.dot_prod) + col, t2);
-                    }
-                }
+                const int col = n0 + wn + sn * 32 + li;         // one partial row per 128-row tile
+                if (col < N) stat_commit(pr, want_st, bx, N, col, red[wave][sn][0][li] + red[wave + 2][sn][0][li], red[wave][sn][1][li] + red[wave + 2][sn][1][li]);
             }
         }
     }
@@ -389,40 +279,22 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
 
 // ---- selection -----------------------------------------------------------------------------------------------
 // node-level products (M rows = nodes) on the 128 x 128 kernel: enough row tiles to fill the chip, k-contiguous K whole
-bool gemm_big_rows(int M, int K) { return M >= 16384 && K % big::BK == 0 && K >= big::BK && K <= big::XMAX; }
+bool gemm_big_rows(int M, int K) { return M >= 16384 && K % BK == 0 && K >= BK && K <= big::XMAX; }
 // weight gradients (K = nodes): worth it from 64 x 64 outputs up
 bool gemm_big_grad(int M, int N, int K) { return K >= 16384 && M >= 64 && N >= 64 && M % 4 == 0 && N % 4 == 0; }
 // split-K slice of such a gradient: 32 K tiles per workgroup (a 128 x 128 slab per ~60 us of matrix-core work); 64 from 64 k rows up,
 // where the slices are plenty either way and half as many slabs go through k_finish (config 5: 247 -> 124 MB, 48 -> 35 us)
 int gemm_big_grad_splits(int K) { return cdiv(K, K >= 65536 ? 2048 : 1024); }
 
-static bool big_aligned(const GemmArgs& a, int nbatch, bool xb_plain) {
-    bool ok = a.lda % 4 == 0 && a.ldb % 4 == 0 && xb_plain;
-    for (int b = 0; b < nbatch; ++b) {
-        ok = ok && aligned16(a.p[b].A) && aligned16(a.p[b].B) && !a.p[b].xb.has_bn && !a.p[b].xb.rs;
-        if (a.p[b].xa.rs && !a.p[b].xa.has_bn) ok = false;
-    }
-    return ok;
-}
-static int xa_class(const GemmArgs& a, int nbatch) {
-    int x = -1;
-    for (int b = 0; b < nbatch; ++b) {
-        const int m = a.p[b].xa.has_bn ? (a.p[b].xa.rs ? 2 : 1) : 0;
-        if (x >= 0 && x != m) return -1;
-        x = m;
-    }
-    return x;
-}
-
 // 1 = launched on the big kernel, 0 = not applicable (caller falls back to gemm.hip), < 0 = error
 int launch_gemm_big(bool transA, bool transB, const GemmArgs& a, int nbatch, hipStream_t stream) {
     const bool a_kc = !transA, b_kc = transB;
     if (!a_kc && b_kc) return 0;
     const bool rows = a_kc && gemm_big_rows(a.M, a.K) && a.nsplit == 1;
-    const bool grad = !a_kc && !b_kc && gemm_big_grad(a.M, a.N, a.K) && a.kchunk % big::BK == 0;
+    const bool grad = !a_kc && !b_kc && gemm_big_grad(a.M, a.N, a.K) && a.kchunk % BK == 0;
     if (!rows && !grad) return 0;
-    const int xa = xa_class(a, nbatch);
-    if (!big_aligned(a, nbatch, true) || xa < 0 || (a_kc && xa > 0 && a.kchunk > big::XMAX) || (!b_kc && a.N % 4 != 0)) {
+    const int xa = gemm_xa_class(a, nbatch);
+    if (!gemm_operands_plain_aligned(a, nbatch) || xa < 0 || (a_kc && xa > 0 && a.kchunk > big::XMAX) || (!b_kc && a.N % 4 != 0)) {
         for (int b = 0; b < nbatch; ++b)
             if (rows && a.p[b].parts) { set_error("launch_gemm_big: operands of a statistics GEMM must be 16-byte aligned"); return -2; }
         return 0;
@@ -430,17 +302,13 @@ int launch_gemm_big(bool transA, bool transB, const GemmArgs& a, int nbatch, hip
     const dim3 grid(cdiv(a.M, big::T), cdiv(a.N, big::T), nbatch * a.nsplit);
     using namespace big;
     if (a_kc && !b_kc) {
-        if (xa == 0) hipLaunchKernelGGL((k_gemm_big<true, false, 0>), grid, dim3(256), 0, stream, a);
-        else if (xa == 1) hipLaunchKernelGGL((k_gemm_big<true, false, 1>), grid, dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((k_gemm_big<true, false, 2>), grid, dim3(256), 0, stream, a);
+        with_xa(xa, [&](auto x) { hipLaunchKernelGGL((k_gemm_big<true, false, decltype(x)::value>), grid, dim3(256), 0, stream, a); });
     } else if (a_kc && b_kc) {
         if (xa == 0) hipLaunchKernelGGL((k_gemm_big<true, true, 0>), grid, dim3(256), 0, stream, a);
         else if (xa == 1) hipLaunchKernelGGL((k_gemm_big<true, true, 1>), grid, dim3(256), 0, stream, a);
         else return 0;
     } else {
-        if (xa == 0) hipLaunchKernelGGL((k_gemm_big<false, false, 0>), grid, dim3(256), 0, stream, a);
-        else if (xa == 1) hipLaunchKernelGGL((k_gemm_big<false, false, 1>), grid, dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((k_gemm_big<false, false, 2>), grid, dim3(256), 0, stream, a);
+        with_xa(xa, [&](auto x) { hipLaunchKernelGGL((k_gemm_big<false, false, decltype(x)::value>), grid, dim3(256), 0, stream, a); });
     }
     if (hipGetLastError() != hipSuccess) { set_error("k_gemm_big: launch failed"); return -2; }
     return 1;
@@ -448,9 +316,9 @@ int launch_gemm_big(bool transA, bool transB, const GemmArgs& a, int nbatch, hip
 
 // NT (ax) + TN (aw) in one grid; same return convention
 int launch_gemm_big_dual(const GemmArgs& ax, int nbx, const GemmArgs& aw, int nbw, hipStream_t stream) {
-    if (!(gemm_big_rows(ax.M, ax.K) && ax.nsplit == 1 && gemm_big_grad(aw.M, aw.N, aw.K) && aw.kchunk % big::BK == 0)) return 0;
-    const int xw = xa_class(aw, nbw);
-    if (!big_aligned(ax, nbx, true) || !big_aligned(aw, nbw, true) || xa_class(ax, nbx) != 0 || xw < 0) {
+    if (!(gemm_big_rows(ax.M, ax.K) && ax.nsplit == 1 && gemm_big_grad(aw.M, aw.N, aw.K) && aw.kchunk % BK == 0)) return 0;
+    const int xw = gemm_xa_class(aw, nbw);
+    if (!gemm_operands_plain_aligned(ax, nbx) || !gemm_operands_plain_aligned(aw, nbw) || gemm_xa_class(ax, nbx) != 0 || xw < 0) {
         for (int b = 0; b < nbx; ++b)
             if (ax.p[b].parts) { set_error("launch_gemm_big_dual: operands of a statistics GEMM must be 16-byte aligned"); return -2; }
         return 0;
@@ -459,9 +327,7 @@ int launch_gemm_big_dual(const GemmArgs& ax, int nbx, const GemmArgs& aw, int nb
     g.gx1 = cdiv(ax.M, big::T); g.gy1 = cdiv(ax.N, big::T); g.n1 = g.gx1 * g.gy1 * nbx;
     g.gx2 = cdiv(aw.M, big::T); g.gy2 = cdiv(aw.N, big::T); g.nz2 = nbw * aw.nsplit;
     const dim3 grid(g.n1 + g.gx2 * g.gy2 * nbw * aw.nsplit);
-    if (xw == 0) hipLaunchKernelGGL((big::k_gemm_big_dual<0>), grid, dim3(256), 0, stream, ax, aw, g);
-    else if (xw == 1) hipLaunchKernelGGL((big::k_gemm_big_dual<1>), grid, dim3(256), 0, stream, ax, aw, g);
-    else hipLaunchKernelGGL((big::k_gemm_big_dual<2>), grid, dim3(256), 0, stream, ax, aw, g);
+    with_xa(xw, [&](auto x) { hipLaunchKernelGGL((big::k_gemm_big_dual<decltype(x)::value>), grid, dim3(256), 0, stream, ax, aw, g); });
     if (hipGetLastError() != hipSuccess) { set_error("k_gemm_big_dual: launch failed"); return -2; }
     return 1;
 }

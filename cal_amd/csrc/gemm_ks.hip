@@ -8,12 +8,10 @@
 // tile is in flight at once and there is ONE round; the four partial accumulators are summed through
 // LDS and the epilogue (bias, ReLU, BN statistics / BN-backward sums, 16 B coalesced stores) runs
 // on the reduced tile.  4x more workgroups (916 for N = 7294) also means ~3.6 resident per CU.
-// Operand transforms and epilogues are those of gemm.hip (engine.hpp).
-#include "engine.hpp"
+// Operand transforms and epilogues are those of every GEMM kernel (engine.hpp; shared pieces: gemm_tile.hpp).
+#include "gemm_tile.hpp"
 
 namespace cal {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int TM = 32, TN = 32, TK = 32;      // per-wave K slice
 constexpr int LA = 33;                         // LDS stride of transposed (k-major) slices
@@ -40,14 +38,11 @@ __global__ void __launch_bounds__(256) k_gemm_ks(const GemmArgs a) {
     const bool vecC = (a.ldc % 4 == 0) && ((reinterpret_cast<uintptr_t>(pr.C) & 15) == 0);
 
     if (XA > 0) {
-        for (int t = threadIdx.x; t < K; t += 256) {
-            bn_scale_shift<true>(pr.xa.bn, t, xsc[t], xsh[t]);
-            if (pr.xa.bn.update && blockIdx.x == 0 && blockIdx.y == 0) bn_update_running<true>(pr.xa.bn, t);
-        }
+        xform_tables<true, 0, true>(pr.xa.bn, xsc, xsh, 0, K, 0, 0, blockIdx.x == 0 && blockIdx.y == 0);
         __syncthreads();
     }
 
-    f32x16 acc;
+    gc_f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
     float* as = smem + wave * TK * LA;
@@ -136,7 +131,7 @@ __global__ void __launch_bounds__(256) k_gemm_ks(const GemmArgs a) {
     // ---- reduce the four K-slice accumulators: Rs[w][row][col]
     __syncthreads();
 #pragma unroll
-    for (int r = 0; r < 16; ++r) Rs[wave * TM * TN + ((r & 3) + 8 * (r >> 2) + 4 * lk) * TN + li] = acc[r];
+    for (int r = 0; r < 16; ++r) Rs[wave * TM * TN + mma_row(r, lk) * TN + li] = acc[r];
     __syncthreads();
     const int row = threadIdx.x >> 3, c4 = (threadIdx.x & 7) * 4;       // 32 rows x 8 column quads
     float4 v = *reinterpret_cast<const float4*>(&Rs[row * TN + c4]);
@@ -191,8 +186,7 @@ __global__ void __launch_bounds__(256) k_gemm_ks(const GemmArgs a) {
             const int which = threadIdx.x / TN, c = threadIdx.x % TN;
             if (n0 + c < N) {
                 const double t = cred[0][which][c] + cred[1][which][c] + cred[2][which][c] + cred[3][which][c];
-                if (pr.parts) pr.parts[((size_t)blockIdx.x * 2 + which) * N + n0 + c] = t;
-                else atomicAdd((which ? (want_st ? pr.st_sq : pr.dot_prod) : (want_st ? pr.st_sum : pr.dot_sum)) + (size_t)(blockIdx.x % NSTRIPE) * pr.st_ss + n0 + c, t);
+                stat_commit1(pr, want_st, which, blockIdx.x, N, n0 + c, t);
             }
         }
     }
@@ -205,7 +199,7 @@ int launch_gemm_ks(bool transB, const GemmArgs& a, int nbatch, hipStream_t strea
     if (a.M == 0 || a.N == 0 || nbatch == 0) return 0;
     int xa = -1;
     for (int b = 0; b < nbatch; ++b) {
-        const int ma = a.p[b].xa.has_bn ? (a.p[b].xa.rs ? 2 : 1) : 0;
+        const int ma = xform_class(a.p[b].xa);
         if (a.p[b].xb.has_bn || a.p[b].xb.rs || (a.p[b].xa.rs && !a.p[b].xa.has_bn)) { set_error("launch_gemm_ks: unsupported operand transform"); return 2; }
         if (xa >= 0 && xa != ma) { set_error("launch_gemm_ks: mixed operand transforms in one batch"); return 2; }
         xa = ma;
@@ -213,13 +207,9 @@ int launch_gemm_ks(bool transB, const GemmArgs& a, int nbatch, hipStream_t strea
     if (xa > 0 && a.K > KS_XMAX) { set_error("launch_gemm_ks: K > %d with a BN-transformed operand", KS_XMAX); return 2; }
     dim3 grid(cdiv(a.M, TM), cdiv(a.N, TN), nbatch);
     if (transB) {
-        if (xa == 0) hipLaunchKernelGGL((k_gemm_ks<true, 0>), grid, dim3(256), 0, stream, a);
-        else if (xa == 1) hipLaunchKernelGGL((k_gemm_ks<true, 1>), grid, dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((k_gemm_ks<true, 2>), grid, dim3(256), 0, stream, a);
+        with_xa(xa, [&](auto x) { hipLaunchKernelGGL((k_gemm_ks<true, decltype(x)::value>), grid, dim3(256), 0, stream, a); });
     } else {
-        if (xa == 0) hipLaunchKernelGGL((k_gemm_ks<false, 0>), grid, dim3(256), 0, stream, a);
-        else if (xa == 1) hipLaunchKernelGGL((k_gemm_ks<false, 1>), grid, dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((k_gemm_ks<false, 2>), grid, dim3(256), 0, stream, a);
+        with_xa(xa, [&](auto x) { hipLaunchKernelGGL((k_gemm_ks<false, decltype(x)::value>), grid, dim3(256), 0, stream, a); });
     }
     CAL_CHECK_LAUNCH("k_gemm_ks");
     return 0;

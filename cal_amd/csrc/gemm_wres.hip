@@ -21,14 +21,14 @@
 //
 // Measured on MI355X at the config-5 shape (scripts/micro/gemm_wres.hip, profiles/r5/micro_gemm_wres.txt): the matrix cores
 // clock down under a dense fp32 MFMA stream on real data (1.95-2.2 GHz against 2.4), which caps every formulation.
-// Same contract as gemm_block (engine.hpp GemmArgs / GemmProb).
-#include "engine.hpp"
-#include <type_traits>
+// Same contract as every GEMM kernel (engine.hpp GemmArgs / GemmProb).  From gemm_tile.hpp: the accumulator row mapping, the fold of
+// the lane halves and the host-side classification.  k_wres's epilogue is laced into its MFMA stream and stays written out here,
+// and so do its table prologue and final commit: through the shared forms hipcc allocates the registers of the row-scale
+// instantiations (EPI = 3, 242-248 AGPRs) differently, and this kernel sits at its register budget.
+#include "gemm_tile.hpp"
 #include <cstdlib>
 
 namespace cal {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace wres {
 
@@ -127,7 +127,7 @@ __global__ void __launch_bounds__(NT) k_wres(const GemmArgs a, const int nbatch)
 #pragma unroll
         for (int u = 0; u < VPS; ++u) {
             const int e = VPS * s + u, nb = e >> 4, r = e & 15;
-            const size_t row = (size_t)min(blk * 32 + 4 * kq + (r & 3) + 8 * (r >> 2), M - 1);
+            const size_t row = (size_t)min(mma_row(r, 0, blk * 32 + 4 * kq), M - 1);
             dv[u] = auxb[row * auxld + nb * 32];
             dr[u] = has_rs ? aux_rs[row * aux_rs_stride] : 1.f;
         }
@@ -159,7 +159,7 @@ __global__ void __launch_bounds__(NT) k_wres(const GemmArgs a, const int nbatch)
 #pragma unroll
     for (int s = 0; s < NBUF - 1; ++s) issue(rb, s, abuf[s], ars[s]);
     readb(0, 0, bf[0]);
-    f32x16 acc[4], prev[4];
+    gc_f32x16 acc[4], prev[4];
     // one row block `cur` into `acc`; with HAVEP the 64 C values of row block `pb` held in `prev` leave VPG per 16-MFMA group.
     // No branch inside: a basic-block boundary would end the lacing of LDS reads and stores into the MFMA stream.
     auto block = [&](auto HAVEP, int cur, int pb, int nxt) {
@@ -208,7 +208,7 @@ __global__ void __launch_bounds__(NT) k_wres(const GemmArgs a, const int nbatch)
                     for (int nb = 0; nb < 4; ++nb) {
                         const float y = jj == 0 ? bb[nb].x : jj == 1 ? bb[nb].y : jj == 2 ? bb[nb].z : bb[nb].w;
                         if (s == 0 && j4 == 0 && jj == 0) {
-                            f32x16 z;
+                            gc_f32x16 z;
 #pragma unroll
                             for (int r = 0; r < 16; ++r) z[r] = 0.f;
                             acc[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(x, y, z, 0, 0, 0);
@@ -218,7 +218,7 @@ __global__ void __launch_bounds__(NT) k_wres(const GemmArgs a, const int nbatch)
                 if (havep) {
 #pragma unroll
                     for (int u = 0; u < VPG; ++u) {
-                        const int e = VPS * s + VPG * j4 + u, nb = e >> 4, r = e & 15, ro = (r & 3) + 8 * (r >> 2);
+                        const int e = VPS * s + VPG * j4 + u, nb = e >> 4, r = e & 15, ro = mma_row(r, 0);
                         emit(nb, prev[nb][r], cp, (size_t)ro * ldc + nb * 32, auxv[s % NAUX][VPG * j4 + u], auxr[s % NAUX][VPG * j4 + u], true);
                     }
                 }
@@ -232,7 +232,7 @@ __global__ void __launch_bounds__(NT) k_wres(const GemmArgs a, const int nbatch)
         }
     };
     // the wave's last block: plain epilogue, rows past M (a partial last block of the matrix) neither stored nor counted
-    auto drain = [&](const f32x16 (&acc)[4], int blk) {
+    auto drain = [&](const gc_f32x16 (&acc)[4], int blk) {
         const int rbase = blk * 32 + 4 * kq;
         float* cp = Cb + (size_t)rbase * ldc;
 #pragma unroll
@@ -240,13 +240,13 @@ __global__ void __launch_bounds__(NT) k_wres(const GemmArgs a, const int nbatch)
             float axv[16], axr[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const size_t row = (size_t)min(rbase + (r & 3) + 8 * (r >> 2), M - 1);
+                const size_t row = (size_t)min(mma_row(r, 0, rbase), M - 1);
                 axv[r] = want_dot ? auxb[row * auxld + nb * 32] : 0.f;
                 axr[r] = has_rs ? aux_rs[row * aux_rs_stride] : 1.f;
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int ro = (r & 3) + 8 * (r >> 2);
+                const int ro = mma_row(r, 0);
                 emit(nb, acc[nb][r], cp, (size_t)ro * ldc + nb * 32, axv[r], axr[r], rbase + ro < M);
             }
         }
@@ -273,8 +273,7 @@ __global__ void __launch_bounds__(NT) k_wres(const GemmArgs a, const int nbatch)
         double (*red)[4][2][32] = reinterpret_cast<double (*)[4][2][32]>(Ws);
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb) {
-            s1[nb] += __shfl_xor(s1[nb], 32, 64); s2[nb] += __shfl_xor(s2[nb], 32, 64);
-            if (kq == 0) { red[wave][nb][0][m] = s1[nb]; red[wave][nb][1][m] = s2[nb]; }
+            stat_fold(s1[nb], s2[nb], red[wave][nb], m, kq);
         }
         __syncthreads();
         {
@@ -317,7 +316,7 @@ __global__ void __launch_bounds__(TNT) k_tn(const GemmArgs a) {
             if (pr.xa.bn.update && split == 0 && (wave & 1) == 0 && ks == 0) bn_update_running(pr.xa.bn, mw0 + 2 * i + c);
         }
     }
-    f32x16 acc[2][4];
+    gc_f32x16 acc[2][4];
 #pragma unroll
     for (int c = 0; c < 2; ++c)
 #pragma unroll
@@ -352,13 +351,13 @@ __global__ void __launch_bounds__(TNT) k_tn(const GemmArgs a) {
             acc[1][3] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.w, acc[1][3], 0, 0, 0);
         }
     }
-    // accumulator (c, d), entry r of lane (i, ks): row m = mw0 + 2 * ((r & 3) + 8 * (r >> 2) + 4 * ks) + c, column n = nw0 + 4 * i + d
+    // accumulator (c, d), entry r of lane (i, ks): row m = mw0 + 2 * mma_row(r, ks) + c, column n = nw0 + 4 * i + d
     float* C = pr.C + (size_t)split * a.M * a.ldc;
 #pragma unroll
     for (int c = 0; c < 2; ++c)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int mm = mw0 + 2 * ((r & 3) + 8 * (r >> 2) + 4 * ks) + c;
+            const int mm = mw0 + 2 * mma_row(r, ks) + c;
             *reinterpret_cast<float4*>(C + (size_t)mm * a.ldc + nw0 + 4 * i) = make_float4(acc[c][0][r], acc[c][1][r], acc[c][2][r], acc[c][3][r]);
         }
 }
@@ -379,21 +378,6 @@ int gemm_wres_grad_splits(int K, int nbatch) {
 }
 int gemm_wres_parts() { return wres::PARTS; }
 
-static bool wres_aligned(const GemmArgs& a, int nbatch) {
-    bool ok = a.lda % 4 == 0 && a.ldb % 4 == 0;
-    for (int b = 0; b < nbatch; ++b)
-        ok = ok && aligned16(a.p[b].A) && aligned16(a.p[b].B) && !a.p[b].xb.has_bn && !a.p[b].xb.rs && !(a.p[b].xa.rs && !a.p[b].xa.has_bn);
-    return ok;
-}
-static int wres_xa_class(const GemmArgs& a, int nbatch) {
-    int x = -1;
-    for (int b = 0; b < nbatch; ++b) {
-        const int m = a.p[b].xa.has_bn ? (a.p[b].xa.rs ? 2 : 1) : 0;
-        if (x >= 0 && x != m) return -1;
-        x = m;
-    }
-    return x;
-}
 // epilogue class of a batch: 0 none, 1 statistics, 2 dot statistics, 3 dot statistics with a row scale, -1 mixed
 static int wres_epi_class(const GemmArgs& a, int nbatch) {
     int x = -1;
@@ -415,21 +399,19 @@ static void wres_launch_epi(int epi, const GemmArgs& a, int nbatch, hipStream_t 
 }
 template <bool B_KC, int KS>
 static void wres_launch_xa(int xa, int epi, const GemmArgs& a, int nbatch, hipStream_t stream) {
-    if (xa == 0) wres_launch_epi<B_KC, 0, KS>(epi, a, nbatch, stream);
-    else if (xa == 1) wres_launch_epi<B_KC, 1, KS>(epi, a, nbatch, stream);
-    else wres_launch_epi<B_KC, 2, KS>(epi, a, nbatch, stream);
+    with_xa(xa, [&](auto x) { wres_launch_epi<B_KC, decltype(x)::value, KS>(epi, a, nbatch, stream); });
 }
 
 // 1 = launched, 0 = not applicable (the caller goes on to gemm_big.hip / gemm.hip), < 0 = error
 int launch_gemm_wres(bool transA, bool transB, const GemmArgs& a, int nbatch, hipStream_t stream) {
     if (!transA) {
         if (!(gemm_wres_rows(a.M, a.N, a.K) && a.nsplit == 1)) return 0;
-        const int xa = wres_xa_class(a, nbatch), epi = wres_epi_class(a, nbatch);
+        const int xa = gemm_xa_class(a, nbatch), epi = wres_epi_class(a, nbatch);
         const int ncol = nbatch * (a.N / 128);
         const bool fits = ncol == 1 || ncol == 2 || ncol == 4;
         bool hasC = true;
         for (int b = 0; b < nbatch; ++b) hasC = hasC && a.p[b].C != nullptr;
-        if (!wres_aligned(a, nbatch) || xa < 0 || epi < 0 || !fits || !hasC) {
+        if (!gemm_operands_plain_aligned(a, nbatch) || xa < 0 || epi < 0 || !fits || !hasC) {
             for (int b = 0; b < nbatch; ++b)
                 if (a.p[b].parts && a.p[b].C) { set_error("launch_gemm_wres: a statistics GEMM sized for the weight-resident kernel cannot take this launch"); return -2; }      // (C == nullptr: sized by gemm_row_tiles(.., hasC = false) for the tile kernels)
             return 0;
@@ -441,14 +423,12 @@ int launch_gemm_wres(bool transA, bool transB, const GemmArgs& a, int nbatch, hi
     }
     if (transB) return 0;
     if (!(gemm_wres_grad(a.M, a.N, a.K) && a.kchunk % 2 == 0)) return 0;
-    const int xa = wres_xa_class(a, nbatch);
-    bool ok = wres_aligned(a, nbatch) && xa >= 0 && a.ldc % 4 == 0;
+    const int xa = gemm_xa_class(a, nbatch);
+    bool ok = gemm_operands_plain_aligned(a, nbatch) && xa >= 0 && a.ldc % 4 == 0;
     for (int b = 0; b < nbatch; ++b) ok = ok && a.p[b].C && aligned16(a.p[b].C) && !a.p[b].bias && !a.p[b].st_sum && !a.p[b].dot_sum && !a.relu;
     if (!ok) return 0;
     const dim3 grid(nbatch * a.nsplit);
-    if (xa == 0) hipLaunchKernelGGL((wres::k_tn<0>), grid, dim3(wres::TNT), 0, stream, a);
-    else if (xa == 1) hipLaunchKernelGGL((wres::k_tn<1>), grid, dim3(wres::TNT), 0, stream, a);
-    else hipLaunchKernelGGL((wres::k_tn<2>), grid, dim3(wres::TNT), 0, stream, a);
+    with_xa(xa, [&](auto x) { hipLaunchKernelGGL((wres::k_tn<decltype(x)::value>), grid, dim3(wres::TNT), 0, stream, a); });
     if (hipGetLastError() != hipSuccess) { set_error("k_tn: launch failed"); return -2; }
     return 1;
 }
