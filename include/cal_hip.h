@@ -253,6 +253,15 @@ CAL_API int cal_engine_set_graph_ptrs(void* engine, const int64_t* node_ptr, con
  * No reference counterpart (torch.use_deterministic_algorithms is the closest notion); SURVEY.md section 7 "determinism". */
 CAL_API int cal_engine_set_deterministic(void* engine, int on);
 CAL_API int cal_engine_debug_stop(int k);
+/* test hook (csrc/gemm_probe.hip, GPU only): a flat description of a batched GEMM -- sizes and flags iv, device pointers pv,
+ * doubles dv, all three HOST arrays laid out as the file's header comment says -- becomes a GemmArgs and goes to launcher
+ * sel: 0 launch_gemm, 1 launch_gemm_ks, 2 launch_gemm_big alone, 3 launch_gemm_wres alone, 4 launch_gemm_dual (iv2 / pv2:
+ * the TN set).  0 launched, 2 refused with a message, 3 an "alone" kernel declined.  Split-K slices stay slabs.
+ * cal_gemm_probe_plan: out[6] (host) = split-K factor, slices, slice length, partial rows of launch_gemm and of
+ * launch_gemm_ks, NSTRIPE -- what a caller needs to size its buffers */
+CAL_API int cal_gemm_probe_plan(int64_t M, int64_t N, int64_t K, int nbatch, int hasC, int64_t* out);
+CAL_API int cal_gemm_probe(int sel, const int64_t* iv, void* const* pv, const int64_t* iv2, void* const* pv2,
+                           const double* dv, void* stream);
 /* name of launch site k (1-based) of the latest untruncated cal_engine_step; "" past the end */
 CAL_API const char* cal_engine_stage_name(int k);
 /* live HIP-event timing of the node-level GEMMs (class 0, work = flops) and aggregations (class 1,
