@@ -932,36 +932,43 @@ int with_g_fp(int H, int F, Fn f) {
     });
 }
 
-// add-pool of the two causal branches (model.py:115-116) + the per-graph positive counts the node-level backward uses
-int launch_pool2(Ctx& c) {
-    Engine* e = c.e;
-    const int N = (int)c.N, B = (int)c.B, H = e->H;
-    const size_t NH = (size_t)N * H;
+// few large graphs: split every graph's rows over S workgroups (slices parked in dZco, a backward-only buffer that the
+// backward itself no longer writes; slices of >= 128 rows: at S = 4 the 256 workgroups of config 5 read its 328 MB at 3.3 TB/s)
+int pool2_slices(int N, int B) { return std::max(1, std::min(32, N / std::max(1, B * 128))); }
+// add-pool of the two causal branches (model.py:115-116) + the per-graph positive counts the node-level backward uses.
+// hc / ho [N, H], pooled [2, B, H], cnt [2, B, H] or null, slices: S x [4, B, H] floats when S = pool2_slices > 1
+int launch_pool2(hipStream_t st, const float* hc, const float* ho, const int* gptr, float* pooled, float* cnt, float* slices,
+                 int N, int B, int H) {
     const int tc = std::min(256, pow2ceil(H / 4));
-    // few large graphs: split every graph's rows over S workgroups (slices parked in dZco, a backward-only buffer that the
-    // backward itself no longer writes; slices of >= 128 rows: at S = 4 the 256 workgroups of config 5 read its 328 MB at 3.3 TB/s)
-    const int S = std::max(1, std::min(32, N / std::max(1, B * 128)));
-    hipLaunchKernelGGL((k_pool2<4>), dim3(B, 2, S), dim3(256), 0, c.st, e->hco, e->hco + NH, e->gptr, e->pooled,
-                       e->pooled + (size_t)B * H, H, tc, e->dZco, e->pcnt);
+    const int S = pool2_slices(N, B);
+    hipLaunchKernelGGL((k_pool2<4>), dim3(B, 2, S), dim3(256), 0, st, hc, ho, gptr, pooled, pooled + (size_t)B * H, H, tc, slices, cnt);
     CAL_CHECK_LAUNCH("k_pool2");
     if (S > 1) {
-        hipLaunchKernelGGL(k_pool2_sum, dim3(cdiv(4 * (int64_t)B * H, 256)), dim3(256), 0, c.st, e->dZco, S, 2 * (int64_t)B * H, e->pooled, e->pcnt);
+        hipLaunchKernelGGL(k_pool2_sum, dim3(cdiv(4 * (int64_t)B * H, 256)), dim3(256), 0, st, slices, S, 2 * (int64_t)B * H, pooled, cnt);
         CAL_CHECK_LAUNCH("k_pool2_sum");
     }
     return 0;
 }
-// the counts alone (forward pooled per graph inside k_gconv_fwd, backward node-level)
-int launch_pool_cnt(Ctx& c) {
+int launch_pool2(Ctx& c) {
     Engine* e = c.e;
-    const int N = (int)c.N, B = (int)c.B, H = e->H;
-    hipLaunchKernelGGL(k_zero_f32, dim3(cdiv(2 * (int64_t)B * H, 256)), dim3(256), 0, c.st, e->pcnt, 2 * (int64_t)B * H);
+    const size_t NH = (size_t)c.N * e->H;
+    return launch_pool2(c.st, e->hco, e->hco + NH, e->gptr, e->pooled, e->pcnt, e->dZco, (int)c.N, (int)c.B, e->H);
+}
+// the counts alone (forward pooled per graph inside k_gconv_fwd, backward node-level); cnt [2, B, H]
+int launch_pool_cnt(hipStream_t st, const float* hc, const float* ho, const int64_t* batch, float* cnt, int N, int B, int H, int rpb_n) {
+    hipLaunchKernelGGL(k_zero_f32, dim3(cdiv(2 * (int64_t)B * H, 256)), dim3(256), 0, st, cnt, 2 * (int64_t)B * H);
     CAL_CHECK_LAUNCH("k_zero_f32");
     return with_g(H, [&](auto g) {
         constexpr int G = decltype(g)::value;
-        hipLaunchKernelGGL((k_pool_cnt<4, G>), dim3(cdiv(N, c.rpb_n), 2), dim3(256), 0, c.st, e->hco, e->hco + (size_t)N * H, c.batch, e->pcnt, N, B, H, c.rpb_n);
+        hipLaunchKernelGGL((k_pool_cnt<4, G>), dim3(cdiv(N, rpb_n), 2), dim3(256), 0, st, hc, ho, batch, cnt, N, B, H, rpb_n);
         CAL_CHECK_LAUNCH("k_pool_cnt");
         return 0;
     });
+}
+int launch_pool_cnt(Ctx& c) {
+    Engine* e = c.e;
+    const size_t NH = (size_t)c.N * e->H;
+    return launch_pool_cnt(c.st, e->hco, e->hco + NH, c.batch, e->pcnt, (int)c.N, (int)c.B, e->H, c.rpb_n);
 }
 
 // The route of a step of this shape and mode (want_grad: a backward follows the forward in the same step)
@@ -2306,6 +2313,72 @@ CAL_EXPORT int cal_engine_debug_stop(int k) { g_stop_after = k; return 0; }
 // name of launch site k (1-based, as counted by cal_engine_debug_stop) in the latest untruncated step; "" past the end
 CAL_EXPORT const char* cal_engine_stage_name(int k) {
     return k >= 1 && k <= (int)g_stage_names.size() ? g_stage_names[k - 1] : "";
+}
+
+// Test hooks of the node-level sparse kernels (tests/test_gpu_sparse_contract.py): a flat description is copied field by field
+// into the kernels' own argument structs and handed to the launch code above.  No logic of their own, no twin in the host library.
+//
+// cal_sparse_probe_espmm -> launch_espmm.  All arrays in HOST memory; pointers inside pv are DEVICE pointers, 0 = null:
+//   iv[0..5]          nnz, nbranch (1 or 2), relu, N, H, rpb
+//   iv[6 + 2 b + ..]  branch b: 0 st_sum.stride, 1 st_sq.stride
+//   pv[0..2]          CSR ptr, nbr, eid
+//   pv[3 + 14 b + ..] branch b: 0 h, 1 out, 2 bias, 3 w, 4 dis, 5 st_sum.dst, 6 st_sum.parts, 7 st_sq.dst, 8 st_sq.parts,
+//                     9 sd_z, 10 sd_gn, 11 sd_gself, 12 pb_g, 13 pb_batch
+//   dv[0]             loop_w
+// The width rule is cal_engine_create's; every other refusal is launch_espmm's own (return code 2, cal_last_error).
+CAL_EXPORT int cal_sparse_probe_espmm(const int64_t* iv, void* const* pv, const double* dv, void* stream_) {
+    CAL_REQUIRE(iv && pv && dv, "description missing");
+    const int64_t nnz = iv[0], nbranch = iv[1], N = iv[3], H = iv[4], rpb = iv[5];
+    CAL_REQUIRE(nbranch == 1 || nbranch == 2, "one or two branches");
+    CAL_REQUIRE(H % 4 == 0 && H >= 4 && H <= 256, "hidden must be a multiple of 4 in [4, 256]");
+    CAL_REQUIRE(N >= 1 && N < (1ll << 31) && nnz >= 0 && nnz < (1ll << 31) && rpb >= 1 && rpb < (1ll << 31), "sizes out of range");
+    CSR csr;
+    csr.ptr = (const int*)pv[0]; csr.nbr = (const int*)pv[1]; csr.eid = (const int*)pv[2]; csr.nnz = (int)nnz;
+    SpmmBranch2 bb;
+    for (int b = 0; b < 2; ++b) {
+        const int64_t* ib = iv + 6 + 2 * std::min<int64_t>(b, nbranch - 1);
+        void* const* pb = pv + 3 + 14 * std::min<int64_t>(b, nbranch - 1);        // one branch: both slots alike, as the engine fills them
+        SpmmBranch& br = bb.b[b];
+        br.h = (const float*)pb[0]; br.out = (float*)pb[1]; br.bias = (const float*)pb[2]; br.w = (const float*)pb[3];
+        br.dis = (const float*)pb[4];
+        br.st_sum = Acc((double*)pb[5], (double*)pb[6], (int)ib[0]);
+        br.st_sq = Acc((double*)pb[7], (double*)pb[8], (int)ib[1]);
+        br.sd_z = (const float*)pb[9]; br.sd_gn = (float*)pb[10]; br.sd_gself = (float*)pb[11];
+        br.pb_g = (const float*)pb[12]; br.pb_batch = (const int64_t*)pb[13];
+    }
+    RC(launch_espmm((hipStream_t)stream_, csr, bb, (int)nbranch, (int)iv[2], (float)dv[0], (int)N, (int)H, (int)rpb));
+    CAL_CHECK_LAUNCH("k_espmm(probe)");
+    return 0;
+}
+// k_edge_att_deg exactly as fwd_att launches it, on a by-source CSR: att [2, E], dis_c / dis_o [N]
+CAL_EXPORT int cal_sparse_probe_edge_att(const int* ptr, const int* nbr, const int* eid, int64_t nnz, const float* pq, const float* be,
+                                         float* att, float* dis_c, float* dis_o, double loop_w, int64_t N, int64_t E, double fedge,
+                                         void* stream_) {
+    CAL_REQUIRE(ptr && nbr && eid && pq && be && att && dis_c && dis_o, "null argument");
+    CAL_REQUIRE(N >= 1 && N < (1ll << 31) && E >= 0 && nnz >= 0 && nnz < (1ll << 31), "sizes out of range");
+    CSR gs;
+    gs.ptr = ptr; gs.nbr = nbr; gs.eid = eid; gs.nnz = (int)nnz;
+    hipLaunchKernelGGL(k_edge_att_deg, dim3(cdiv(N, 32)), dim3(256), 0, (hipStream_t)stream_, gs, pq, be, att, dis_c, dis_o,
+                       (float)loop_w, (int)N, E, (float)fedge);
+    CAL_CHECK_LAUNCH("k_edge_att_deg(probe)");
+    return 0;
+}
+// sel 0: launch_pool2 with cnt, 1: launch_pool2 without cnt, 2: launch_pool_cnt (batch, rpb_n), 3: nothing is launched.  *S_out =
+// the row slices launch_pool2 cuts this batch into (slices: S x [4, B, H] floats when S > 1); sel 3 is how a caller sizes `slices`.
+CAL_EXPORT int cal_sparse_probe_pool(int sel, const float* hc, const float* ho, const int* gptr, const int64_t* batch, float* pooled,
+                                     float* cnt, float* slices, int64_t N, int64_t B, int64_t H, int64_t rpb_n, int64_t* S_out,
+                                     void* stream_) {
+    CAL_REQUIRE(sel >= 0 && sel <= 3 && S_out != nullptr, "bad selector");
+    CAL_REQUIRE(H % 4 == 0 && H >= 4 && H <= 256, "hidden must be a multiple of 4 in [4, 256]");
+    CAL_REQUIRE(N >= 1 && N < (1ll << 31) && B >= 1 && B < (1ll << 31), "sizes out of range");
+    const int S = pool2_slices((int)N, (int)B);
+    *S_out = S;
+    if (sel == 3) return 0;
+    CAL_REQUIRE(hc && ho && (sel == 2 ? batch != nullptr && cnt != nullptr && rpb_n >= 1 && rpb_n < (1ll << 31) : gptr != nullptr && pooled != nullptr),
+                "null argument");
+    if (sel == 2) return launch_pool_cnt((hipStream_t)stream_, hc, ho, batch, cnt, (int)N, (int)B, (int)H, (int)rpb_n);
+    CAL_REQUIRE(S == 1 || slices != nullptr, "row slices without a slice buffer");
+    return launch_pool2((hipStream_t)stream_, hc, ho, gptr, pooled, sel == 0 ? cnt : nullptr, slices, (int)N, (int)B, (int)H);
 }
 #ifdef CAL_BLK_CLOCKS
 CAL_EXPORT int cal_debug_blk_clocks(long long* out) {

@@ -262,6 +262,20 @@ CAL_API int cal_engine_debug_stop(int k);
 CAL_API int cal_gemm_probe_plan(int64_t M, int64_t N, int64_t K, int nbatch, int hasC, int64_t* out);
 CAL_API int cal_gemm_probe(int sel, const int64_t* iv, void* const* pv, const int64_t* iv2, void* const* pv2,
                            const double* dv, void* stream);
+/* test hooks (csrc/engine.hip, GPU only) of the node-level sparse kernels; the descriptions go field by field into the
+ * kernels' own argument structs and to the engine's own launch code.  0 launched, 2 refused with a message.
+ * cal_sparse_probe_espmm: launch_espmm.  HOST arrays iv (sizes, flags, strides), pv (DEVICE pointers, 0 = null) and
+ * dv (loop_w), laid out as the comment above its definition says.
+ * cal_sparse_probe_edge_att: k_edge_att_deg on a by-source CSR; att [2, E], dis_c / dis_o [N].
+ * cal_sparse_probe_pool: sel 0 add-pool of both branches with positive counts, 1 without counts, 2 the counts alone from the
+ * node -> graph map, 3 nothing is launched; *S_out = the row slices of the add-pool (slices: S x [4, B, H] floats when S > 1) */
+CAL_API int cal_sparse_probe_espmm(const int64_t* iv, void* const* pv, const double* dv, void* stream);
+CAL_API int cal_sparse_probe_edge_att(const int* ptr, const int* nbr, const int* eid, int64_t nnz, const float* pq, const float* be,
+                                      float* att, float* dis_c, float* dis_o, double loop_w, int64_t N, int64_t E, double fedge,
+                                      void* stream);
+CAL_API int cal_sparse_probe_pool(int sel, const float* hc, const float* ho, const int* gptr, const int64_t* batch, float* pooled,
+                                  float* cnt, float* slices, int64_t N, int64_t B, int64_t H, int64_t rpb_n, int64_t* S_out,
+                                  void* stream);
 /* name of launch site k (1-based) of the latest untruncated cal_engine_step; "" past the end */
 CAL_API const char* cal_engine_stage_name(int k);
 /* live HIP-event timing of the node-level GEMMs (class 0, work = flops) and aggregations (class 1,

@@ -6,6 +6,35 @@ import torch
 
 from cal_amd.data import Batch, Data
 
+CANARY = 12345.0
+NCAN = 256
+
+
+class Buf:
+    """n elements on the GPU with a canary block of NCAN elements behind them (the contract tests: every operand and output)"""
+
+    def __init__(self, pool, n, dtype=torch.float32, fill=None, data=None):
+        self.n = int(n)
+        self.full = torch.empty(self.n + NCAN, dtype=dtype, device="cuda")
+        self.full[self.n:] = CANARY
+        self.t = self.full[:self.n]
+        if data is not None:
+            self.t.copy_(data.reshape(-1).to(dtype))
+        elif fill is not None:
+            self.t.fill_(fill)
+        pool.append(self)
+
+    def ptr(self):
+        return self.full.data_ptr()
+
+    def intact(self):
+        return bool((self.full[self.n:] == CANARY).all().item())
+
+
+def pool_intact(pool):
+    return all(b.intact() for b in pool)
+
+
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 

@@ -36,42 +36,15 @@ import pytest
 import torch
 
 from tests import gemm_contract_ref as ref
+from tests.helpers import Buf, pool_intact as _pool_intact
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 BOUND = 2e-5
-CANARY = 12345.0
-NCAN = 256
 U24, U52 = 2.0 ** -24, 2.0 ** -52
 SEL_GEMM, SEL_KS, SEL_BIG, SEL_WRES, SEL_DUAL = range(5)
 IV_PROB, PV_PROB = 24, 40            # per-problem strides of the description (csrc/gemm_probe.hip)
 NAN = float("nan")
-
-
-# ---- buffers ----------------------------------------------------------------------------------------------------------
-class Buf:
-    """n elements on the device with a canary block behind them"""
-
-    def __init__(self, pool, n, dtype=torch.float32, fill=None, data=None):
-        self.n = int(n)
-        self.full = torch.empty(self.n + NCAN, dtype=dtype, device=DEV)
-        self.full[self.n:] = CANARY
-        self.t = self.full[:self.n]
-        if data is not None:
-            self.t.copy_(data.reshape(-1).to(dtype))
-        elif fill is not None:
-            self.t.fill_(fill)
-        pool.append(self)
-
-    def ptr(self):
-        return self.full.data_ptr()
-
-    def intact(self):
-        return bool((self.full[self.n:] == CANARY).all().item())
-
-
-def _pool_intact(pool):
-    return all(b.intact() for b in pool)
 
 
 def _plan(M, N, K, nbatch=1, hasC=True):
