@@ -261,6 +261,11 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
     constexpr int LDT = T + 4;                           // row stride of the two j-major tiles below (4 mod 32)
     float* Zt = Bs;                                      // Zt[col * LDT + j] = z[j][col]   (over the W stage)
     float* At = As;                                      // At[i * LDT + j] = weight of edge j -> i, times dis_i   (over the x stage)
+    // the z rows of row tile rt (for the POOL backward's SDDMM): 16-byte stores, four columns per lane, like the output tile
+    auto store_z = [&](const gc_f32x16& acc, int rt) {
+        const int c0 = n0 + ct * 32;
+        gc_store_tile<gc_site(WT_Z)>(acc, br.z + (size_t)(g0 + rt * 32) * H + c0, H, rows - rt * 32, li, lk, MmaIdent(), ((rows - rt * 32) * H - c0) * 4);
+    };
     const bool own = NT == 256 || kh == 0;               // the wave that finishes its tile (NT = 512: adds its partner's partial below)
     if (r0 < R && (NT == 256 || kh == 1)) {
         // an accumulator holds rows 8 g + 4 lk .. + 3 of its tile in elements 4 g .. 4 g + 3: four consecutive j of one column
@@ -269,26 +274,14 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
             const int row = r0 * 32 + 8 * gq + 4 * lk;
             *reinterpret_cast<float4*>(Zt + (ct * 32 + li) * LDT + row) = make_float4(acc0[4 * gq], acc0[4 * gq + 1], acc0[4 * gq + 2], acc0[4 * gq + 3]);
         }
-        if (NT == 256 && br.z) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = mma_row(r, lk, r0 * 32);
-                if (row < rows) br.z[(size_t)(g0 + row) * H + n0 + ct * 32 + li] = acc0[r];
-            }
-        }
+        if (NT == 256 && br.z) store_z(acc0, r0);
         if (NT == 256 && r0 + 2 < R) {
 #pragma unroll
             for (int gq = 0; gq < 4; ++gq) {
                 const int row = (r0 + 2) * 32 + 8 * gq + 4 * lk;
                 *reinterpret_cast<float4*>(Zt + (ct * 32 + li) * LDT + row) = make_float4(acc1[4 * gq], acc1[4 * gq + 1], acc1[4 * gq + 2], acc1[4 * gq + 3]);
             }
-            if (br.z) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = mma_row(r, lk, (r0 + 2) * 32);
-                    if (row < rows) br.z[(size_t)(g0 + row) * H + n0 + ct * 32 + li] = acc1[r];
-                }
-            }
+            if (br.z) store_z(acc1, r0 + 2);
         }
     }
     {
@@ -305,13 +298,7 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
             acc0[4 * gq] += p.x; acc0[4 * gq + 1] += p.y; acc0[4 * gq + 2] += p.z; acc0[4 * gq + 3] += p.w;
             *zp = make_float4(acc0[4 * gq], acc0[4 * gq + 1], acc0[4 * gq + 2], acc0[4 * gq + 3]);
         }
-        if (br.z) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = mma_row(r, lk, r0 * 32);
-                if (row < rows) br.z[(size_t)(g0 + row) * H + n0 + ct * 32 + li] = acc0[r];
-            }
-        }
+        if (br.z) store_z(acc0, r0);
     }
     // one lane per CSR slot (then one per self loop): duplicate edges accumulate through the LDS atomic.  One lane per
     // destination ROW walked a hub's 30 slots as 30 dependent LDS round trips (read source, read coefficient,
@@ -366,8 +353,10 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
                 f1[r & 3] += vm; f2[r & 3] = fmaf(vm, vm, f2[r & 3]);
             }
         }
-        gc_store_tile(acc0, br.out + (size_t)(g0 + r0 * 32) * H + n0 + ct * 32, H, rows - r0 * 32, li, lk);
-        if (r0 + 2 < R) gc_store_tile(acc1, br.out + (size_t)(g0 + (r0 + 2) * 32) * H + n0 + ct * 32, H, rows - (r0 + 2) * 32, li, lk);
+        // (the extent: from the tile's first word to the end of this graph's rows)
+        const int c0 = n0 + ct * 32;
+        gc_store_tile<gc_site(WT_OUT)>(acc0, br.out + (size_t)(g0 + r0 * 32) * H + c0, H, rows - r0 * 32, li, lk, MmaIdent(), ((rows - r0 * 32) * H - c0) * 4);
+        if (r0 + 2 < R) gc_store_tile<gc_site(WT_OUT)>(acc1, br.out + (size_t)(g0 + (r0 + 2) * 32) * H + c0, H, rows - (r0 + 2) * 32, li, lk, MmaIdent(), ((rows - (r0 + 2) * 32) * H - c0) * 4);
     }
     psum = (f1[0] + f1[1]) + (f1[2] + f1[3]);
     double s1 = ((double)f1[0] + (double)f1[1]) + ((double)f1[2] + (double)f1[3]);

@@ -422,8 +422,9 @@ __global__ void __launch_bounds__(GB_NT, (LEAN ? 4 : 1)) k_gconv_bwd(const CSR g
             }
         }
         // (16-byte stores, four columns per lane: gc_store_tile)
-        gc_store_tile(acc[0], dxp + (size_t)g0 * K + w * 32, K, rows, li, lk);
-        if (R == 2) gc_store_tile(acc[1], dxp + (size_t)(g0 + 32) * K + w * 32, K, rows - 32, li, lk);
+        // (the extent: from the tile's first word to the end of this graph's rows)
+        gc_store_tile<gc_site(WT_DXP)>(acc[0], dxp + (size_t)g0 * K + w * 32, K, rows, li, lk, MmaIdent(), (rows * K - w * 32) * 4);
+        if (R == 2) gc_store_tile<gc_site(WT_DXP)>(acc[1], dxp + (size_t)(g0 + 32) * K + w * 32, K, rows - 32, li, lk, MmaIdent(), ((rows - 32) * K - w * 32) * 4);
         double s1 = ((double)f1[0] + (double)f1[1]) + ((double)f1[2] + (double)f1[3]);
         double s2 = ((double)f2[0] + (double)f2[1]) + ((double)f2[2] + (double)f2[3]);
         s1 += __shfl_xor(s1, 32, 64);
@@ -445,7 +446,10 @@ __global__ void __launch_bounds__(GB_NT, (LEAN ? 4 : 1)) k_gconv_bwd(const CSR g
         for (int i = 0; i < 16; ++i) { acc[0][i] = 0.f; acc[1][i] = 0.f; }
         mma_kmajor<1, 2, LDX, GB_LDD>(Xs + wq * 32 + li, Ds + li, rowsP, lk, affine, MmaIdent(), acc);
 #pragma unroll
-        for (int q = 0; q < 2; ++q) gc_store_tile(acc[q], slab + (size_t)(wq * 32) * H + ns0 + q * 32, H, 32, li, lk);
+        for (int q = 0; q < 2; ++q) {
+            const int off = wq * 32 * H + ns0 + q * 32;      // (the extent: to the end of this graph's slab)
+            gc_store_tile<gc_site(WT_DW)>(acc[q], slab + off, H, 32, li, lk, MmaIdent(), (K * H - off) * 4);
+        }
     }
     BLK_CLK(1);
 }

@@ -4,7 +4,7 @@
 //   lane (li = lane & 31, lk = lane >> 5) feeds row / column li of the operands at reduction step 2 i + lk and holds
 //   column li of the result: register r of the accumulator is row mma_row(r, lk).
 //
-//   basics      gc_f32x16, mma_row, gc_quad_transpose, gc_store_tile
+//   basics      gc_f32x16, mma_row, gc_quad_transpose, gc_store_tile, gc_store16 (store policy: plain | write-through)
 //   products    mma_kmajor     both operands k-major    [k * LD + row]   (4 B reads, two-stage pipeline)
 //               mma_rowk       both operands row-major  [row * LD + k]   (16 B reads, four MFMA steps per read)
 //               mma_rowk_tile  the same, addressed by tile                (see there why it is a form of its own)
@@ -46,21 +46,70 @@ __device__ __forceinline__ void gc_quad_transpose(float& v0, float& v1, float& v
     r = gc_dpp_xor2(o2 ? v1 : v3);
     if (o2) v1 = r; else v3 = r;
 }
+// ---- store policy ------------------------------------------------------------------------------------------------------
+// A plain store leaves its line dirty in the L2 of the XCD that wrote it until the write-back at the end of the kernel; a
+// write-through store (sc1) sends the bytes on at once and drops the line, so a kernel that ends in a burst of tens of KB
+// per workgroup does not queue all of it behind its last instruction.  The result in memory is the same.  Rules of a
+// write-through site:
+//   - it stores 16 bytes per lane (gc_store_tile writes each 128-byte line whole with one instruction); 4- and 8-byte
+//     write-through stores cost several times more per byte, so 4-byte sites (gn / gself, k_feat_bwd_mma's scalar slab
+//     stores, the bias partials, the striped atomics) stay plain;
+//   - its bytes are not loaded again inside the same launch (the line is gone from this XCD's L2);
+//   - the store goes through a buffer resource {base, bytes}: base is the wave's own first tile word (wave-uniform: a kernel
+//     argument plus offsets of the workgroup / wave index), bytes what is left from that word to the end of what the
+//     workgroup owns (its graph's slab, its graph's rows) -- every call site subtracts the tile's offset from the owned
+//     extent, a negative value counts as 0.  An offset past it is dropped by the range check instead of landing in a
+//     neighbour's rows.  (The compiler schedules the buffer store and pads its hazards itself.)
+// Which sites write through is one mask, fixed by the A/B of profiles/r7/ab_writethrough.txt; -DCAL_WT_SITES=0x.. (through
+// CAL_HIPCC_EXTRA of build.py) overrides it for a profiling build, 0 = every store plain.  WT_Z was rejected by that A/B: the
+// bit is a profiling override only, the default build never compiles its write-through form and the suite does not cover it.
+enum class GcStore { Plain, WriteThrough };
+constexpr int WT_DW = 1;          // dW slab of k_gconv_bwd
+constexpr int WT_DXP = 2;         // dX' partial tiles of k_gconv_bwd
+constexpr int WT_Z = 4;           // z rows of the two-branch k_gconv_fwd (rejected: override only)
+constexpr int WT_OUT = 8;         // output tiles of k_gconv_fwd
+#ifndef CAL_WT_SITES
+#define CAL_WT_SITES 0x0B        // dW slabs, dX' partials, output tiles (A/B: profiles/r7/ab_writethrough.txt)
+#endif
+constexpr GcStore gc_site(int bit) { return (CAL_WT_SITES & bit) ? GcStore::WriteThrough : GcStore::Plain; }
+
+typedef unsigned int gc_u32x4 __attribute__((ext_vector_type(4)));
+// 16 bytes at base + byte_off; WriteThrough: base and bytes wave-uniform, dropped when byte_off + 16 > bytes
+template <GcStore P>
+__device__ __forceinline__ void gc_store16(float* base, int bytes, int byte_off, const float4& v) {
+    if constexpr (P == GcStore::WriteThrough) {
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, max(bytes, 0), 0x00020000);
+        const gc_u32x4 u = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
+        __builtin_amdgcn_raw_buffer_store_b128(u, rsrc, byte_off, 0, /*sc1*/ 16);
+    } else {
+        *reinterpret_cast<float4*>(reinterpret_cast<char*>(base) + byte_off) = v;
+    }
+}
+
 // tile(row, col) -> base[row * ld + col] for the rows with row < nrow (base, ld: 16-byte aligned / a multiple of 4 floats);
-// f(v): applied to every element before the store (bias, ReLU ..)
-template <typename F>
-__device__ __forceinline__ void gc_store_tile(const gc_f32x16& acc, float* base, size_t ld, int nrow, int li, int lk, F f) {
+// f(v): applied to every element before the store (bias, ReLU ..); bytes (WriteThrough only): what the caller owns from base on
+template <GcStore P, typename F>
+__device__ __forceinline__ void gc_store_tile(const gc_f32x16& acc, float* base, size_t ld, int nrow, int li, int lk, F f, int bytes) {
     const int q = li & 3, c4 = li & ~3;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         float v0 = f(acc[4 * g]), v1 = f(acc[4 * g + 1]), v2 = f(acc[4 * g + 2]), v3 = f(acc[4 * g + 3]);
         gc_quad_transpose(v0, v1, v2, v3, q);
         const int row = 8 * g + 4 * lk + q;
-        if (row < nrow) *reinterpret_cast<float4*>(base + (size_t)row * ld + c4) = make_float4(v0, v1, v2, v3);
+        if constexpr (P == GcStore::WriteThrough) {
+            if (row < nrow) gc_store16<P>(base, bytes, (row * (int)ld + c4) * 4, make_float4(v0, v1, v2, v3));
+        } else {
+            if (row < nrow) *reinterpret_cast<float4*>(base + (size_t)row * ld + c4) = make_float4(v0, v1, v2, v3);
+        }
     }
 }
+// the plain forms (a write-through site calls the one above: it has to name its extent)
+template <typename F>
+__device__ __forceinline__ void gc_store_tile(const gc_f32x16& acc, float* base, size_t ld, int nrow, int li, int lk, F f) {
+    gc_store_tile<GcStore::Plain>(acc, base, ld, nrow, li, lk, f, 0);
+}
 __device__ __forceinline__ void gc_store_tile(const gc_f32x16& acc, float* base, size_t ld, int nrow, int li, int lk) {
-    gc_store_tile(acc, base, ld, nrow, li, lk, MmaIdent());
+    gc_store_tile<GcStore::Plain>(acc, base, ld, nrow, li, lk, MmaIdent(), 0);
 }
 
 // ---- products ---------------------------------------------------------------------------------------------------------

@@ -262,6 +262,12 @@ CAL_API int cal_engine_debug_stop(int k);
 CAL_API int cal_gemm_probe_plan(int64_t M, int64_t N, int64_t K, int nbatch, int hasC, int64_t* out);
 CAL_API int cal_gemm_probe(int sel, const int64_t* iv, void* const* pv, const int64_t* iv2, void* const* pv2,
                            const double* dv, void* stream);
+/* test hook (csrc/store_probe.hip, GPU only): one 32 x 32 accumulator tile whose element (row, col) holds the bits
+ * 0x40000000 | row << 8 | col goes through gc_store_tile to buf[tile_off + row * ld + col], rows < nrow, with store policy
+ * 0 (plain) or 1 (write-through; `bytes` = the extent from the tile's first word past which its stores are dropped).
+ * 0 launched, 2 refused with a message (a tile or extent that leaves the buffer is refused, not launched). */
+CAL_API int cal_probe_store_tile(int policy, float* buf, int64_t buf_words, int64_t tile_off, int nrow, int ld, int64_t bytes,
+                                 void* stream);
 /* test hooks (csrc/engine.hip, GPU only) of the node-level sparse kernels; the descriptions go field by field into the
  * kernels' own argument structs and to the engine's own launch code.  0 launched, 2 refused with a message.
  * cal_sparse_probe_espmm: launch_espmm.  HOST arrays iv (sizes, flags, strides), pv (DEVICE pointers, 0 = null) and
