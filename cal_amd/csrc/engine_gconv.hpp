@@ -21,6 +21,7 @@
 #pragma once
 #include "engine_readout.hpp"     // RO_CLK profiling aid
 #include "engine_mma.hpp"         // 32 x 32 tile products, row mapping, tile stores
+#include "engine_gunit.hpp"       // unit extents, slot batch, operand tiles, BatchNorm tables, z tile / adjacency block, column sums
 
 namespace cal {
 
@@ -96,11 +97,12 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
         const int idx = t + u * NT, k = min(idx >> 4, K - 1), j4 = idx & 15;
         vb[u] = *reinterpret_cast<const float4*>(br.W + (size_t)k * H + n0 + 4 * j4);
     }
-    const int g0 = gptr[b], rows = gptr[b + 1] - g0, e0 = eptr[b], ne = eptr[b + 1] - e0;
+    const GUnit un = gunit_load(gptr, eptr, b);
+    const int g0 = un.g0, rows = un.rows, e0 = un.e0;
     const int tg0 = TILED ? (int)br.tile_gptr[b] : b, ng = TILED ? (int)br.tile_gptr[b + 1] - tg0 : 1;
     const bool want = br.st_sum.on();
-    if (rows <= 0) {                                     // empty graph: its partial rows still have to exist
-        if (br.bn.update && blockIdx.x == 0 && blockIdx.y == 0 && t < K) { const BNRaw r0 = bn_raw_load_st(br.bn, t); bn_raw_update_running(br.bn, r0, t); }
+    if (un.empty()) {                                    // empty graph: its partial rows still have to exist
+        gunit_empty_update_running(br.bn, t, K);
         if (t < GC_N) {
             if (want) { br.st_sum.add(n0 + t, 0.0); br.st_sq.add(n0 + t, 0.0); }
             if (br.pooled) for (int q = 0; q < ng; ++q) br.pooled[(size_t)(tg0 + q) * H + n0 + t] = 0.f;
@@ -108,29 +110,14 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
         return;
     }
     if (TILED && (ng < 1 || ng > GC_TILE_GRAPHS)) { if (t == 0) atomicOr(status, 8); return; }
-    if (rows > T || ne > ECAP || ne < 0) {            // the host's bounds were wrong: flag it, write nothing
-        if (t == 0) atomicOr(status, 8);
-        return;
-    }
+    if (un.exceeds<T, ECAP>()) { gunit_flag(un, status, t); return; }      // the host's bounds were wrong: flag it, write nothing
     RO_CLK(32);
     BLK_CLK(2);
-    const bool hasw = br.ew != nullptr;
     const int rowsP = (rows + 31) & ~31, R = rowsP >> 5, nkc = K >> 5, RB = (rowsP + RPP - 1) / RPP;
     // ---- every global load of the kernel, issued before the first wait -------------------------------------
-    // x rows: item (u, t) -> 32-wide k chunk kc, row block rr, row (t >> 3), float4 (t & 7) of the chunk:
-    // 8 lanes x 16 B per row (coalesced), and the transposing LDS stores below see only 2-way bank conflicts
     constexpr int UA = T * 32 / NT;                    // x float4s per lane: T rows x GC_K / 4 over NT lanes
     float4 va[UA];
-    {
-        int kc = 0, rr = 0;
-#pragma unroll
-        for (int u = 0; u < UA; ++u) {
-            const bool ok = kc < nkc;
-            const int r = min((ok ? rr : 0) * RPP + (t >> 3), rows - 1), k = ((ok ? kc : 0) << 5) + ((t & 7) << 2);
-            va[u] = *reinterpret_cast<const float4*>(br.x + (size_t)(g0 + r) * K + k);
-            if (++rr == RB) { rr = 0; ++kc; }
-        }
-    }
+    xrow_issue<UA, RPP>(va, br.x, un, K, nkc, RB, t);
     const int pv = g.ptr[g0 + min(t, rows)];
     const float dv = br.dis[g0 + min(t, rows - 1)];
     long long bgv = 0;
@@ -140,60 +127,41 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
 #pragma unroll
         for (int q = 0; q < NRS; ++q) rsv[q] = br.rs[(size_t)(g0 + min(q * RPP + (t >> 3), rows - 1)) * br.rs_stride];
     }
-    // CSR slots, BatchNorm constants, bias, coefficients: all unconditional on clamped indices / substituted pointers
-    // (see BNRaw in engine.hpp: guarded loads here cost four serial round trips behind the tile loads)
-    int nv[CU], ev[CU];
-    const int slot_hi = max(g.nnz - 1, 0);
-#pragma unroll
-    for (int u = 0; u < CU; ++u) {
-        const int s = min(e0 + max(min(t + u * NT, ne - 1), 0), slot_hi);
-        nv[u] = g.nbr[s];
-        ev[u] = g.eid[s];
-    }
+    // CSR slots, BatchNorm constants, bias, coefficients of an earlier kernel of this step, if any
+    GSlots<CU, true, true> slots;
+    slots.template load_ids<NT>(g, un, t);
     const int lane = t & 63, li = lane & 31, lk = lane >> 5;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
     const int kh = w >> 2, ct = w & 1, r0 = (w & 3) >> 1;     // kh: half of the first product's reduction range (NT = 512)
     const float* biasp = br.bias ? br.bias : br.W;       // W: any valid [>= H] float array; the value is masked below
     float bias = biasp[n0 + ct * 32 + li];
     BNRawS braws = bn_raws_load(br.bn, min(t, K - 1));       // (striped reader: the producer may be a per-graph kernel)
-    const float* coefp = br.coef_in ? br.coef_in : br.dis;
-    const int coef_hi = br.coef_in ? slot_hi : 0;
-    float cin[CU];                                       // coefficients of an earlier kernel of this step, if any
-#pragma unroll
-    for (int u = 0; u < CU; ++u) cin[u] = coefp[min(e0 + max(min(t + u * NT, ne - 1), 0), coef_hi)];
-    // all of the above stay in flight together: without the pins hipcc pairs every W load with its LDS store
-    // ("load, s_waitcnt vmcnt(0), ds_write" x 8: eight serial round trips, 5-30 us under 256-way contention)
+    slots.template load_coef<NT>(g, un, t, br.coef_in, br.dis);
+    // all of the above stay in flight together (engine_gunit.hpp)
 #pragma unroll
     for (int u = 0; u < UA; ++u) ro_pin(va[u]);
 #pragma unroll
     for (int u = 0; u < WU; ++u) ro_pin(vb[u]);
     bn_raws_pin(braws);
-#pragma unroll
-    for (int u = 0; u < CU; ++u) asm volatile("" : "+v"(nv[u]), "+v"(ev[u]), "+v"(cin[u]));
-    const BNRaw braw = bn_raws_sum(br.bn, braws);
+    slots.pin();
     asm volatile("" : "+v"(bias));
     if (!br.bias) bias = 0.f;
-    if (ne <= 0) {                                       // no slot of this graph exists: what the clamped loads fetched is not an index
+    slots.repair_empty(un);
+    bn_table_scale_shift(br.bn, braws, t, K, sc_s, sh_s);
+    {   // second round: edge coefficients dis_j * w_e (needs the neighbour / edge ids), into the slot batch
+        const bool hasw = br.ew != nullptr;
+        if (br.coef_in) {
 #pragma unroll
-        for (int u = 0; u < CU; ++u) { nv[u] = g0; ev[u] = 0; }
-    }
-    if (t < K) {
-        bn_raw_scale_shift(br.bn, braw, sc_s[t], sh_s[t]);
-        if (br.bn.update && blockIdx.x == 0 && blockIdx.y == 0) bn_raw_update_running(br.bn, braw, t);
-    }
-    // second round: edge coefficients dis_j * w_e (needs the neighbour / edge ids)
-    float cv[CU], wv[CU];
-    if (br.coef_in) {
+            for (int u = 0; u < CU; ++u) { slots.cv[u] = slots.cin[u]; slots.wv[u] = 1.f; }
+        } else {
+            const float* ewp = hasw ? br.ew : br.dis;
 #pragma unroll
-        for (int u = 0; u < CU; ++u) { cv[u] = cin[u]; wv[u] = 1.f; }
-    } else {
-        const float* ewp = hasw ? br.ew : br.dis;        // (masked when there are no edge weights)
-#pragma unroll
-        for (int u = 0; u < CU; ++u) {
-            const float c = br.dis[nv[u]];
-            const float wl = ewp[hasw ? ev[u] : 0];
-            wv[u] = hasw ? wl : 1.f;
-            cv[u] = c * wv[u];
+            for (int u = 0; u < CU; ++u) {
+                const float c = br.dis[slots.nv[u]];
+                const float wl = ewp[hasw ? slots.ev[u] : 0];
+                slots.wv[u] = hasw ? wl : 1.f;
+                slots.cv[u] = c * slots.wv[u];
+            }
         }
     }
     RO_CLK(33);
@@ -201,46 +169,21 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
     if (t <= rows) ptr_s[t] = pv - e0;
     if (t < rows) dis_s[t] = dv;
     if (TILED && t < rows) bg_s[t] = (unsigned char)min(max((int)(bgv - tg0), 0), ng - 1);
-#pragma unroll
-    for (int u = 0; u < CU; ++u) {
-        const int s = t + u * NT;
-        if (s < ne) {
-            const int loc = nv[u] - g0;
-            const bool inb = loc >= 0 && loc < rows;        // an edge that leaves its graph is not a mini-batch: flag it
-            en[s] = (short)(inb ? loc : 0); ec[s] = inb ? cv[u] : 0.f;
-            if (br.coef_out && blockIdx.y == 0) { br.coef_out[e0 + s] = cv[u]; if (br.w_out) br.w_out[e0 + s] = wv[u]; }
-            if (!inb) atomicOr(status, 16);
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < WU; ++u) {
-        const int idx = t + u * NT, k = idx >> 4, j4 = idx & 15;
-        if (k < K) *reinterpret_cast<float4*>(Bs + k * GC_LDB + 4 * j4) = vb[u];
-    }
+    slots.template stage<NT>(un, t, status, [&](int s, int u, int loc, bool inb) {
+        en[s] = (short)(inb ? loc : 0); ec[s] = inb ? slots.cv[u] : 0.f;
+        if (br.coef_out && blockIdx.y == 0) { br.coef_out[e0 + s] = slots.cv[u]; if (br.w_out) br.w_out[e0 + s] = slots.wv[u]; }
+    });
+    wslice_commit<NT, GC_LDB>(vb, Bs, K, t);
     RO_CLK(34);
     __syncthreads();                                     // BN tables
-    if (t < rows) {                                      // destination row of every CSR slot (stores only: no LDS latency chain)
-        const int s1 = ptr_s[t + 1];
-        for (int s = ptr_s[t]; s < s1; ++s) er[s] = (signed char)t;
-    }
-    {
-        int kc = 0, rr = 0;
-#pragma unroll
-        for (int u = 0; u < UA; ++u) {
-            if (kc < nkc) {
-                const int r = rr * RPP + (t >> 3), k = (kc << 5) + ((t & 7) << 2);
-                float x0 = va[u].x, x1 = va[u].y, x2 = va[u].z, x3 = va[u].w;
-                if (RS) {
-                    const float s = (NRS == 1 || rr == 0) ? rsv[0] : ((NRS == 2 || rr == 1) ? rsv[1] : (rr == 2 ? rsv[2] : rsv[3]));
-                    x0 *= s; x1 *= s; x2 *= s; x3 *= s;
-                }
-                *reinterpret_cast<float4*>(As + r * GC_LDX + k) =
-                    make_float4(fmaf(x0, sc_s[k], sh_s[k]), fmaf(x1, sc_s[k + 1], sh_s[k + 1]), fmaf(x2, sc_s[k + 2], sh_s[k + 2]),
-                                fmaf(x3, sc_s[k + 3], sh_s[k + 3]));
-            }
-            if (++rr == RB) { rr = 0; ++kc; }
+    gslots_dest_rows(er, ptr_s, t, rows);
+    xrow_commit<UA, RPP, GC_LDX>(va, As, nkc, RB, t, [&](float4 v, int rr, int k) {
+        if (RS) {
+            const float s = (NRS == 1 || rr == 0) ? rsv[0] : ((NRS == 2 || rr == 1) ? rsv[1] : (rr == 2 ? rsv[2] : rsv[3]));
+            v.x *= s; v.y *= s; v.z *= s; v.w *= s;
         }
-    }
+        return bn_affine4(v, sc_s, sh_s, k);
+    });
     __syncthreads();
     RO_CLK(35);
     BLK_CLK(3);
@@ -268,46 +211,20 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
     };
     const bool own = NT == 256 || kh == 0;               // the wave that finishes its tile (NT = 512: adds its partner's partial below)
     if (r0 < R && (NT == 256 || kh == 1)) {
-        // an accumulator holds rows 8 g + 4 lk .. + 3 of its tile in elements 4 g .. 4 g + 3: four consecutive j of one column
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-            const int row = r0 * 32 + 8 * gq + 4 * lk;
-            *reinterpret_cast<float4*>(Zt + (ct * 32 + li) * LDT + row) = make_float4(acc0[4 * gq], acc0[4 * gq + 1], acc0[4 * gq + 2], acc0[4 * gq + 3]);
-        }
+        z_park<LDT>(Zt, acc0, r0, ct, li, lk);
         if (NT == 256 && br.z) store_z(acc0, r0);
         if (NT == 256 && r0 + 2 < R) {
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const int row = (r0 + 2) * 32 + 8 * gq + 4 * lk;
-                *reinterpret_cast<float4*>(Zt + (ct * 32 + li) * LDT + row) = make_float4(acc1[4 * gq], acc1[4 * gq + 1], acc1[4 * gq + 2], acc1[4 * gq + 3]);
-            }
+            z_park<LDT>(Zt, acc1, r0 + 2, ct, li, lk);
             if (br.z) store_z(acc1, r0 + 2);
         }
     }
-    {
-        const int nz4 = (rowsP * LDT) >> 2;           // rows i < rowsP of the block (contiguous), as float4s
-        float4* z4 = reinterpret_cast<float4*>(At);
-        for (int idx = t; idx < nz4; idx += NT) z4[idx] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    adj_zero<NT>(At, (rowsP * LDT) >> 2, t);             // rows i < rowsP of the block (contiguous)
     __syncthreads();
     if (NT == 512 && kh == 0 && r0 < R) {                // z tile = this wave's half + the partner's (already in Zt)
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-            float4* zp = reinterpret_cast<float4*>(Zt + (ct * 32 + li) * LDT + r0 * 32 + 8 * gq + 4 * lk);
-            const float4 p = *zp;
-            acc0[4 * gq] += p.x; acc0[4 * gq + 1] += p.y; acc0[4 * gq + 2] += p.z; acc0[4 * gq + 3] += p.w;
-            *zp = make_float4(acc0[4 * gq], acc0[4 * gq + 1], acc0[4 * gq + 2], acc0[4 * gq + 3]);
-        }
+        z_combine<LDT, true>(Zt, acc0, r0, ct, li, lk);
         if (br.z) store_z(acc0, r0);
     }
-    // one lane per CSR slot (then one per self loop): duplicate edges accumulate through the LDS atomic.  One lane per
-    // destination ROW walked a hub's 30 slots as 30 dependent LDS round trips (read source, read coefficient,
-    // read-modify-write the block) while the other lanes idled -- the slowest row was the phase.
-    for (int s = t; s < ne; s += NT) {
-        const int i = er[s];
-        atomicAdd(&At[i * LDT + en[s]], dis_s[i] * ec[s]);
-    }
-    if (t < rows) atomicAdd(&At[t * LDT + t], dis_s[t] * dis_s[t] * loop_w);
+    adj_scatter<NT, LDT>(At, er, en, un, t, [&](int i, int s) { return dis_s[i] * ec[s]; }, [&](int i) { return dis_s[i] * dis_s[i] * loop_w; });
     __syncthreads();
     RO_CLK(37);
     // ---- out tile = A z on the matrix cores (reduction over the graph's rowsP nodes) ---------------------------
@@ -319,8 +236,6 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
     }
     RO_CLK(38);
     // ---- epilogue: bias, ReLU, store, column sums of this graph ---------------------------------------------------
-    // a lane's <= 32 terms of the column sums in fp32 (four chains, masked, no guards: inside the row guard every element
-    // was a branch with two fp64 conversions and two dependent fp64 adds), everything across lanes / graphs in fp64
     float f1[4] = {0.f, 0.f, 0.f, 0.f}, f2[4] = {0.f, 0.f, 0.f, 0.f};
     float psum = 0.f;
     const int col = n0 + ct * 32 + li;
@@ -359,12 +274,10 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
         if (r0 + 2 < R) gc_store_tile<gc_site(WT_OUT)>(acc1, br.out + (size_t)(g0 + (r0 + 2) * 32) * H + c0, H, rows - (r0 + 2) * 32, li, lk, MmaIdent(), ((rows - (r0 + 2) * 32) * H - c0) * 4);
     }
     psum = (f1[0] + f1[1]) + (f1[2] + f1[3]);
-    double s1 = ((double)f1[0] + (double)f1[1]) + ((double)f1[2] + (double)f1[3]);
-    double s2 = ((double)f2[0] + (double)f2[1]) + ((double)f2[2] + (double)f2[3]);
-    // lanes lk = 0 / 1 hold different rows of the same column; waves w and w ^ 2 hold the other row tiles
-    s1 += __shfl_xor(s1, 32, 64);
-    s2 += __shfl_xor(s2, 32, 64);
+    double s1, s2;
+    colsum_fold(f1, f2, s1, s2);
     psum += __shfl_xor(psum, 32, 64);
+    // (colsum_commit written out: the add-pool's fp32 sums share its store, barrier and lanes)
     if (own && lk == 0) { red[w & 3][0][li] = s1; red[w & 3][1][li] = s2; pool_s[w & 3][li] = psum; }
     __syncthreads();
     if (w < 2 && lk == 0) {

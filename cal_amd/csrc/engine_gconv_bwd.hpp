@@ -108,7 +108,8 @@ __global__ void __launch_bounds__(GB_NT, (LEAN ? 4 : 1)) k_gconv_bwd(const CSR g
     warm_kernargs<sizeof(CSR) + 2 * sizeof(void*) + sizeof(GconvBwdBranch2) + 32>();
     const GconvBwdBranch& br = bb.b[blockIdx.z];         // indexed in the kernel-argument segment (see k_gconv_fwd)
     const int b = blockIdx.x, sl = blockIdx.y, ns0 = sl * GC_N, t = threadIdx.x;
-    const int g0 = gptr[b], rows = gptr[b + 1] - g0, e0 = eptr[b], ne = eptr[b + 1] - e0;
+    const GUnit un = gunit_load(gptr, eptr, b);
+    const int g0 = un.g0, rows = un.rows, e0 = un.e0, ne = un.ne;
     const int pb = (MODE == 2 && !TILED && br.iperm) ? br.iperm[b] : b;         // row of the second pooled-gradient partial (scalar load, with the extents)
     const int tg0 = TILED ? (int)br.tile_gptr[b] : b, ng = TILED ? (int)br.tile_gptr[b + 1] - tg0 : 1;
     const int lane = t & 63, li = lane & 31, lk = lane >> 5;
@@ -123,7 +124,6 @@ __global__ void __launch_bounds__(GB_NT, (LEAN ? 4 : 1)) k_gconv_bwd(const CSR g
         for (int i = t; i < K * GC_N; i += GB_NT) slab[(size_t)(i / GC_N) * H + ns0 + i % GC_N] = 0.f;
         return;
     }
-    const bool hasw = br.ew != nullptr;
     const int rowsP = (rows + 31) & ~31, R = rowsP >> 5, K4 = K >> 2;
     // ---- every global load of the kernel, issued before the first wait ------------------------------------------
     RoBatch<float4, 2> bd, bd1, by;                      // dOut[g0 + j][ns0 + 4 n4 ..]: rows x 16 float4 (UP: dy0, dy1, y)
@@ -160,20 +160,9 @@ __global__ void __launch_bounds__(GB_NT, (LEAN ? 4 : 1)) k_gconv_bwd(const CSR g
     const int pn = g.ptr[g0 + min(t + 1, rows)];
     const float dv = br.dis[g0 + min(t, rows - 1)];
     const float rv = RS ? br.rs[(size_t)(g0 + min(t, rows - 1)) * br.rs_stride] : 1.f;
-    // CSR slots, coefficients and the BatchNorm constants: unconditional loads on clamped indices / substituted pointers,
-    // pinned below (BNRaw in engine.hpp: as guarded blocks these were up to ten serial round trips behind the tile loads)
-    int nv[2], ev[2];
-    const int slot_hi = max(g.nnz - 1, 0);
-    const float* coefp = br.coef_in ? br.coef_in : br.dis;
-    const int coef_hi = br.coef_in ? slot_hi : 0;
-    float cin[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int s = min(e0 + max(min(t + u * GB_NT, ne - 1), 0), slot_hi);
-        nv[u] = g.nbr[s];
-        ev[u] = g.eid[s];
-        cin[u] = coefp[min(s, coef_hi)];
-    }
+    // CSR slots, coefficients and the BatchNorm constants (engine_gunit.hpp)
+    GSlots<2, true, true> slots;
+    slots.template load<GB_NT>(g, un, t, br.coef_in, br.dis);
     // (striped readers, engine.hpp: the producers may be per-graph kernels.  Lanes 0 .. K-1 need this layer's BatchNorm, lanes
     //  256 .. 319 the upper one's constants of this slice's 64 columns: ONE register set, the pointers chosen per lane)
     const bool ulane = UP && t >= 256;
@@ -185,64 +174,43 @@ __global__ void __launch_bounds__(GB_NT, (LEAN ? 4 : 1)) k_gconv_bwd(const CSR g
     }
     bn_raws_pin(braws);
     if (UP) { stripe_pin(ud1s); stripe_pin(ud2s); }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) asm volatile("" : "+v"(nv[u]), "+v"(ev[u]), "+v"(cin[u]));
+    slots.pin();
     if (POOL && !TILED) { asm volatile("" : "+v"(gv), "+v"(gv1)); gv += br.gp1 ? gv1 : 0.f; }
     if (TILED) {                                         // second round: the permuted graph's pooled-gradient row
         asm volatile("" : "+v"(gv), "+v"(pbq), "+v"(bgv));
         const float* gp1 = br.gp1 ? br.gp1 : br.gp0;
         gv1 = gp1[(size_t)pbq * H + ns0 + (t & (GC_N - 1))];
     }
-    if (ne <= 0) { nv[0] = g0; nv[1] = g0; ev[0] = 0; ev[1] = 0; }   // no slot of this graph exists: the clamped loads fetched no index
-    if (UP && t >= 256 && t < 256 + GC_N) {
-        float m1, r1;
-        const BNRaw uraw = bn_raws_sum(br.ubn, braws);
-        const double ud1 = stripe_total(ud1s, br.ubn.ss), ud2 = stripe_total(ud2s, br.ubn.ss);
-        bn_raw_mean_rstd(br.ubn, uraw, m1, r1);
-        um_s[t - 256] = m1; ur_s[t - 256] = r1;
-        ug_s[t - 256] = uraw.g * r1;
-        u1_s[t - 256] = (float)(ud1 * (double)br.ubn.inv_n);
-        u2_s[t - 256] = (float)(ud2 * (double)br.ubn.inv_n);
-    }
-    if (t < K) {
-        float m1, r1;
-        const BNRaw braw = bn_raws_sum(br.bn, braws);
-        bn_raw_mean_rstd(br.bn, braw, m1, r1);
-        mean_s[t] = m1; rstd_s[t] = r1;
-        gam_s[t] = braw.g;
-        bet_s[t] = braw.b;
-    }
-    for (int i = t; i < (rowsP * GB_LDJ + 3) / 4; i += GB_NT) reinterpret_cast<float4*>(Ab)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    float cv[2];
-    if (br.coef_in) {
+    slots.repair_empty(un);
+    if (UP && t >= 256 && t < 256 + GC_N) bn_table_upper(br.ubn, braws, ud1s, ud2s, t - 256, um_s, ur_s, ug_s, u1_s, u2_s);
+    bn_table_hat(br.bn, braws, t, K, mean_s, rstd_s, gam_s, bet_s);
+    adj_zero<GB_NT>(Ab, (rowsP * GB_LDJ + 3) / 4, t);
+    {   // second round, as in k_gconv_fwd (wv is not used here)
+        const bool hasw = br.ew != nullptr;
+        if (br.coef_in) {
 #pragma unroll
-        for (int u = 0; u < 2; ++u) cv[u] = cin[u];
-    } else {
-        const float* ewp = hasw ? br.ew : br.dis;
+            for (int u = 0; u < 2; ++u) { slots.cv[u] = slots.cin[u]; slots.wv[u] = 1.f; }
+        } else {
+            const float* ewp = hasw ? br.ew : br.dis;
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const float c = br.dis[nv[u]];
-            const float wl = ewp[hasw ? ev[u] : 0];
-            cv[u] = hasw ? c * wl : c;
+            for (int u = 0; u < 2; ++u) {
+                const float c = br.dis[slots.nv[u]];
+                const float wl = ewp[hasw ? slots.ev[u] : 0];
+                slots.wv[u] = hasw ? wl : 1.f;
+                slots.cv[u] = c * slots.wv[u];
+            }
         }
     }
     // ---- stage everything in LDS -----------------------------------------------------------------------------------
     if (t <= rows) ptr_s[t] = pv - e0;
     if (t < rows) {
         dis_s[t] = dv; rs_s[t] = rv;
-        for (int s = pv - e0; s < pn - e0; ++s) er[s] = (unsigned char)t;      // destination row of every slot (stores only)
+        gslots_dest_rows(er, t, pv - e0, pn - e0);
     }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int s = t + u * GB_NT;
-        if (s < ne) {
-            const int loc = nv[u] - g0;
-            const bool inb = loc >= 0 && loc < rows;
-            en[s] = (unsigned char)(inb ? loc : 0); ec[s] = inb ? cv[u] : 0.f;
-            if (POOL && !LEAN) ee[s] = ev[u];
-            if (!inb) atomicOr(status, 16);
-        }
-    }
+    slots.template stage<GB_NT>(un, t, status, [&](int s, int u, int loc, bool inb) {
+        en[s] = (unsigned char)(inb ? loc : 0); ec[s] = inb ? slots.cv[u] : 0.f;
+        if (POOL && !LEAN) ee[s] = slots.ev[u];
+    });
     if (POOL && !TILED && t < GC_N) gv_s[t] = gv;
     if (TILED) {
         if (t < ng * GC_N) gv_s[t] = gv + (br.gp1 ? gv1 : 0.f);
@@ -328,13 +296,7 @@ __global__ void __launch_bounds__(GB_NT, (LEAN ? 4 : 1)) k_gconv_bwd(const CSR g
     // rows rows .. rowsP of dOut / x_hat: zero (they are reduced over in the products below)
     for (int i = t; i < (rowsP - rows) * GB_LDD; i += GB_NT) Ds[rows * GB_LDD + i] = 0.f;
     for (int i = t; i < (rowsP - rows) * LDX; i += GB_NT) Xs[rows * LDX + i] = 0.f;
-    // one lane per CSR slot, then one per self loop (LDS atomics: duplicate edges share an entry) -- a lane per ROW walked
-    // a hub's slots as a chain of dependent LDS round trips while the rest of the workgroup waited
-    for (int s = t; s < ne; s += GB_NT) {
-        const int j = er[s];
-        atomicAdd(&Ab[j * GB_LDJ + en[s]], dis_s[j] * ec[s]);
-    }
-    if (t < rows) atomicAdd(&Ab[t * GB_LDJ + t], dis_s[t] * dis_s[t] * loop_w);
+    adj_scatter<GB_NT, GB_LDJ>(Ab, er, en, un, t, [&](int j, int s) { return dis_s[j] * ec[s]; }, [&](int j) { return dis_s[j] * dis_s[j] * loop_w; });
     __syncthreads();
     if ((UP || POOL) && t < GC_N) {
         double tot = 0.0;
@@ -425,10 +387,8 @@ __global__ void __launch_bounds__(GB_NT, (LEAN ? 4 : 1)) k_gconv_bwd(const CSR g
         // (the extent: from the tile's first word to the end of this graph's rows)
         gc_store_tile<gc_site(WT_DXP)>(acc[0], dxp + (size_t)g0 * K + w * 32, K, rows, li, lk, MmaIdent(), (rows * K - w * 32) * 4);
         if (R == 2) gc_store_tile<gc_site(WT_DXP)>(acc[1], dxp + (size_t)(g0 + 32) * K + w * 32, K, rows - 32, li, lk, MmaIdent(), ((rows - 32) * K - w * 32) * 4);
-        double s1 = ((double)f1[0] + (double)f1[1]) + ((double)f1[2] + (double)f1[3]);
-        double s2 = ((double)f2[0] + (double)f2[1]) + ((double)f2[2] + (double)f2[3]);
-        s1 += __shfl_xor(s1, 32, 64);
-        s2 += __shfl_xor(s2, 32, 64);
+        double s1, s2;
+        colsum_fold(f1, f2, s1, s2);
         if (lk == 0) {
             if (br.dacc_sum) {
                 const size_t po = (size_t)stripe_of_block() * br.dacc_ss + k;
@@ -517,16 +477,8 @@ __global__ void __launch_bounds__(GB_NT) k_feat_bwd(const int* __restrict__ gptr
     StripeVal ud1s = stripe_load(a.udot_sum, uc, a.ubn.ss), ud2s = stripe_load(a.udot_prod, uc, a.ubn.ss);
     bn_raws_pin(uraws); bn_raw_pin(raw0);
     stripe_pin(ud1s); stripe_pin(ud2s);
-    if (t < H) {
-        float m1, r1;
-        const BNRaw uraw = bn_raws_sum(a.ubn, uraws);
-        const double ud1 = stripe_total(ud1s, a.ubn.ss), ud2 = stripe_total(ud2s, a.ubn.ss);
-        bn_raw_mean_rstd(a.ubn, uraw, m1, r1);
-        um_s[t] = m1; ur_s[t] = r1;
-        ug_s[t] = uraw.g * r1;
-        u1_s[t] = (float)(ud1 * (double)a.ubn.inv_n);
-        u2_s[t] = (float)(ud2 * (double)a.ubn.inv_n);
-    } else if (t - 128 < F && t >= 128) {
+    if (t < H) bn_table_upper(a.ubn, uraws, ud1s, ud2s, t, um_s, ur_s, ug_s, u1_s, u2_s);
+    else if (t - 128 < F && t >= 128) {
         const int f = t - 128;
         float m1, r1;
         bn_raw_mean_rstd(a.bn0, raw0, m1, r1);
@@ -700,16 +652,7 @@ __global__ void __launch_bounds__(GB_NT) k_feat_bwd_mma(const int* __restrict__ 
     StripeVal ud1s, ud2s;
     if (!NOBN) { uraws = bn_raws_load(a.ubn, uc); ud1s = stripe_load(a.udot_sum, uc, a.ubn.ss); ud2s = stripe_load(a.udot_prod, uc, a.ubn.ss); bn_raws_pin(uraws); stripe_pin(ud1s); stripe_pin(ud2s); }
     bn_raw_pin(raw0);
-    if (!NOBN && t < H) {
-        float m1, r1;
-        const double ud1 = stripe_total(ud1s, a.ubn.ss), ud2 = stripe_total(ud2s, a.ubn.ss);
-        const BNRaw uraw = bn_raws_sum(a.ubn, uraws);
-        bn_raw_mean_rstd(a.ubn, uraw, m1, r1);
-        um_s[t] = m1; ur_s[t] = r1;
-        ug_s[t] = uraw.g * r1;
-        u1_s[t] = (float)(ud1 * (double)a.ubn.inv_n);
-        u2_s[t] = (float)(ud2 * (double)a.ubn.inv_n);
-    }
+    if (!NOBN && t < H) bn_table_upper(a.ubn, uraws, ud1s, ud2s, t, um_s, ur_s, ug_s, u1_s, u2_s);
     if (t >= 128 && t - 128 < FP) {
         const int f = t - 128;
         float m1, r1;

@@ -59,49 +59,31 @@ __global__ void __launch_bounds__(256) k_ggat_fwd(const CSR g, const int* __rest
     __shared__ float ad_s[2][T], as_s[2][T], idn_s[2][T];
     __shared__ double red[4][2][32];
     const int b = blockIdx.x, n0 = blockIdx.y * GC_N, t = threadIdx.x;
-    const int g0 = gptr[b], rows = gptr[b + 1] - g0, e0 = eptr[b], ne = eptr[b + 1] - e0;
+    const GUnit un = gunit_load(gptr, eptr, b);
+    const int g0 = un.g0, rows = un.rows, e0 = un.e0, ne = un.ne;
     const bool want = a.st_sum.on();
-    if (rows <= 0) {
-        if (a.bn.update && blockIdx.x == 0 && blockIdx.y == 0 && t < K) { const BNRaw r0 = bn_raw_load_st(a.bn, t); bn_raw_update_running(a.bn, r0, t); }
+    if (un.empty()) {
+        gunit_empty_update_running(a.bn, t, K);
         if (t < GC_N && want) { a.st_sum.add(n0 + t, 0.0); a.st_sq.add(n0 + t, 0.0); }
         return;
     }
-    if (rows > T || ne > GG_E || ne < 0) {
-        if (t == 0) atomicOr(status, 8);
-        return;
-    }
+    if (un.exceeds<T, GG_E>()) { gunit_flag(un, status, t); return; }
     const int D = a.D, hs = GC_N / D, h0 = n0 / D;        // heads of this slice: h0 .. h0 + hs - 1
     const int rowsP = (rows + 31) & ~31, R = rowsP >> 5, nkc = K >> 5;
     // ---- every global load of the kernel, issued before the first wait -------------------------------------
     constexpr int UA = T / 8;
     float4 va[UA];
-    {
-        int kc = 0, rr = 0;
-#pragma unroll
-        for (int u = 0; u < UA; ++u) {
-            const bool ok = kc < nkc;
-            const int r = min(((ok ? rr : 0) << 5) + (t >> 3), rows - 1), k = ((ok ? kc : 0) << 5) + ((t & 7) << 2);
-            va[u] = *reinterpret_cast<const float4*>(a.x + (size_t)(g0 + r) * K + k);
-            if (++rr == R) { rr = 0; ++kc; }
-        }
-    }
+    xrow_issue<UA, 32>(va, a.x, un, K, nkc, R, t);       // (256 lanes: a row block is a 32-row tile)
     float4 vb[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
         const int idx = t + u * 256, k = min(idx >> 4, K - 1), j4 = idx & 15;
         vb[u] = *reinterpret_cast<const float4*>(a.W + (size_t)k * H + n0 + 4 * j4);
     }
-    // small operands: unconditional loads on clamped indices / substituted pointers, pinned with the tiles (branch-free
-    // prologue, BNRaw in engine.hpp)
+    // the small operands (engine_gunit.hpp)
     int pv = g.ptr[g0 + min(t, rows)];
-    int nv[4], ev[4];
-    const int slot_hi = max(g.nnz - 1, 0);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int s = min(e0 + max(min(t + u * 256, ne - 1), 0), slot_hi);
-        nv[u] = g.nbr[s];
-        ev[u] = g.eid[s];
-    }
+    GSlots<4, true, false> slots;
+    slots.template load<256>(g, un, t);
     float attv = a.att[(size_t)h0 * 2 * D + min(t, 2 * GC_N - 1)];       // hs heads x 2 D = 128 floats, contiguous
     const int lane = t & 63, li = lane & 31, lk = lane >> 5;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -114,56 +96,20 @@ __global__ void __launch_bounds__(256) k_ggat_fwd(const CSR g, const int* __rest
 #pragma unroll
     for (int u = 0; u < 8; ++u) ro_pin(vb[u]);
     bn_raws_pin(braws);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) asm volatile("" : "+v"(nv[u]), "+v"(ev[u]));
+    slots.pin();
     asm volatile("" : "+v"(pv), "+v"(attv), "+v"(bias));
-    const BNRaw braw = bn_raws_sum(a.bn, braws);
     if (!a.bias) bias = 0.f;
     if (t >= 2 * GC_N) attv = 0.f;
-    if (ne <= 0) {                                       // no slot of this graph exists: the clamped loads fetched no index
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { nv[u] = g0; ev[u] = 0; }
-    }
-    if (t < K) {
-        bn_raw_scale_shift(a.bn, braw, sc_s[t], sh_s[t]);
-        if (a.bn.update && blockIdx.x == 0 && blockIdx.y == 0) bn_raw_update_running(a.bn, braw, t);
-    }
+    slots.repair_empty(un);
+    bn_table_scale_shift(a.bn, braws, t, K, sc_s, sh_s);
     // ---- stage everything in LDS ---------------------------------------------------------------------------
     if (t <= rows) ptr_s[t] = pv - e0;
     if (t < 2 * GC_N) att_s[t] = attv;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int s = t + u * 256;
-        if (s < ne) {
-            const int loc = nv[u] - g0;
-            const bool inb = loc >= 0 && loc < rows;
-            en[s] = (signed char)(inb ? loc : -1); ee[s] = ev[u];
-            if (!inb) atomicOr(status, 16);
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        const int idx = t + u * 256, k = idx >> 4, j4 = idx & 15;
-        if (k < K) *reinterpret_cast<float4*>(Bs + k * GC_LDB + 4 * j4) = vb[u];
-    }
+    slots.template stage<256>(un, t, status, [&](int s, int u, int loc, bool inb) { en[s] = (signed char)(inb ? loc : -1); ee[s] = slots.ev[u]; });
+    wslice_commit<256, GC_LDB>(vb, Bs, K, t);
     __syncthreads();                                     // BN tables
-    if (t < rows) {                                      // destination row of every CSR slot (stores only)
-        const int s1 = ptr_s[t + 1];
-        for (int s = ptr_s[t]; s < s1; ++s) er[s] = (signed char)t;
-    }
-    {
-        int kc = 0, rr = 0;
-#pragma unroll
-        for (int u = 0; u < UA; ++u) {
-            if (kc < nkc) {
-                const int r = (rr << 5) + (t >> 3), k = (kc << 5) + ((t & 7) << 2);
-                *reinterpret_cast<float4*>(As + r * GC_LDX + k) =
-                    make_float4(fmaf(va[u].x, sc_s[k], sh_s[k]), fmaf(va[u].y, sc_s[k + 1], sh_s[k + 1]),
-                                fmaf(va[u].z, sc_s[k + 2], sh_s[k + 2]), fmaf(va[u].w, sc_s[k + 3], sh_s[k + 3]));
-            }
-            if (++rr == R) { rr = 0; ++kc; }
-        }
-    }
+    gslots_dest_rows(er, ptr_s, t, rows);
+    xrow_commit<UA, 32, GC_LDX>(va, As, nkc, R, t, [&](float4 v, int, int k) { return bn_affine4(v, sc_s, sh_s, k); });
     __syncthreads();
     // ---- z tile = BN(x) W on the matrix cores: wave w owns column tile w & 1 and row tile w >> 1 -----------------
     gc_f32x16 acc0, acc1;
@@ -174,21 +120,14 @@ __global__ void __launch_bounds__(256) k_ggat_fwd(const CSR g, const int* __rest
     float* Zt = Bs;                                      // Zt[col * LDT + j] = z[j][col]: the z tile transposed (as k_gconv_fwd)
     float* At = As;                                      // At[(h * T + i) * LDT + j] = alpha of edge j -> i, head h0 + h
     if (r0 < R) {
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-            const int row = r0 * 32 + 8 * gq + 4 * lk;
-            *reinterpret_cast<float4*>(Zt + (ct * 32 + li) * LDT + row) = make_float4(acc0[4 * gq], acc0[4 * gq + 1], acc0[4 * gq + 2], acc0[4 * gq + 3]);
-        }
+        z_park<LDT>(Zt, acc0, r0, ct, li, lk);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = mma_row(r, lk, r0 * 32);
             if (row < rows) a.z[(size_t)(g0 + row) * H + n0 + ct * 32 + li] = acc0[r];
         }
     }
-    {
-        float4* z4 = reinterpret_cast<float4*>(At);
-        for (int idx = t; idx < (2 * T * LDT) / 4; idx += 256) z4[idx] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    adj_zero<256>(At, (2 * T * LDT) / 4, t);
     __syncthreads();
     // ---- scores: one lane per (node, head of the slice) ----------------------------------------------------------
     const int pi = t & (T - 1), ph = t >> 6;             // this lane's (node, head-in-slice) pair
@@ -288,16 +227,9 @@ __global__ void __launch_bounds__(256) k_ggat_fwd(const CSR g, const int* __rest
             f1[r & 3] += vm; f2[r & 3] = fmaf(vm, vm, f2[r & 3]);
         }
     }
-    double s1 = ((double)f1[0] + (double)f1[1]) + ((double)f1[2] + (double)f1[3]);
-    double s2 = ((double)f2[0] + (double)f2[1]) + ((double)f2[2] + (double)f2[3]);
-    s1 += __shfl_xor(s1, 32, 64);
-    s2 += __shfl_xor(s2, 32, 64);
-    if (lk == 0) { red[w][0][li] = s1; red[w][1][li] = s2; }
-    __syncthreads();
-    if (w < 2 && lk == 0 && want) {
-        a.st_sum.add(col, red[w][0][li] + red[w + 2][0][li]);
-        a.st_sq.add(col, red[w][1][li] + red[w + 2][1][li]);
-    }
+    double s1, s2;
+    colsum_fold(f1, f2, s1, s2);
+    colsum_commit(red, true, want, w, li, lk, col, s1, s2, a.st_sum, a.st_sq);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -361,15 +293,16 @@ __global__ void __launch_bounds__(GB_NT) k_ggat_bwd(const CSR g, const int* __re
     BLK_CLK(0);
     warm_kernargs<(sizeof(GgatBwdArgs) + 64 < 1024 ? sizeof(GgatBwdArgs) + 64 : 1024)>();
     const int b = blockIdx.x, sl = blockIdx.y, ns0 = sl * GC_N, t = threadIdx.x;
-    const int g0 = gptr[b], rows = gptr[b + 1] - g0, e0 = eptr[b], ne = eptr[b + 1] - e0;
+    const GUnit un = gunit_load(gptr, eptr, b);
+    const int g0 = un.g0, rows = un.rows, e0 = un.e0, ne = un.ne;
     const int lane = t & 63, li = lane & 31, lk = lane >> 5;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
     const int D = a.D, hs = GC_N / D, h0 = ns0 / D;
     double* parts = a.dot_parts + ((size_t)sl * gridDim.x + b) * (2 * K);
     float* slab = a.slab + (size_t)b * K * H;
     float* aslab = a.att_slab + (size_t)b * a.heads * 2 * D + (size_t)h0 * 2 * D;      // this slice's hs * 2 D = 128 entries
-    if (rows <= 0 || rows > T || ne > GGB_E || ne < 0) {
-        if (rows > 0 && t == 0) atomicOr(status, 8);
+    if (un.empty() || un.exceeds<T, GGB_E>()) {
+        gunit_flag(un, status, t);
         if (!a.dacc_sum) for (int i = t; i < 2 * K; i += GB_NT) parts[i] = 0.0;
         for (int i = t; i < K * GC_N; i += GB_NT) slab[(size_t)(i / GC_N) * H + ns0 + i % GC_N] = 0.f;
         if (t < 2 * GC_N) aslab[t] = 0.f;
@@ -392,17 +325,10 @@ __global__ void __launch_bounds__(GB_NT) k_ggat_bwd(const CSR g, const int* __re
     ro_issue<GB_NT>(bz, rows, 16, [&](int j, int n4) { return *reinterpret_cast<const float4*>(a.z + (size_t)(g0 + j) * H + ns0 + 4 * n4); });
     ro_issue<GB_NT>(bx, rows, K4, [&](int i, int k4) { return *reinterpret_cast<const float4*>(a.x + (size_t)(g0 + i) * K + 4 * k4); });
     ro_issue<GB_NT>(bw, K, 16, [&](int k, int n4) { return *reinterpret_cast<const float4*>(a.W + (size_t)k * H + ns0 + 4 * n4); });
-    // the small operands: unconditional loads on clamped indices, pinned below (branch-free prologue, see BNRaw in engine.hpp:
-    // as selects / guarded blocks they were six serial round trips behind the tile loads)
+    // the small operands (engine_gunit.hpp)
     int pv = g.ptr[g0 + min(t, rows)], pn = g.ptr[g0 + min(t + 1, rows)];
-    int nv[2], ev[2];
-    const int slot_hi = max(g.nnz - 1, 0);
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int s = min(e0 + max(min(t + u * GB_NT, ne - 1), 0), slot_hi);
-        nv[u] = g.nbr[s];
-        ev[u] = g.eid[s];
-    }
+    GSlots<2, true, false> slots;
+    slots.template load<GB_NT>(g, un, t);
     // forward scores of this slice's heads: lane (kind, head, node) = (t >> 7, (t >> 6) & 1, t & 63)
     const int sn = t & 63, sh = (t >> 6) & 1, sk = t >> 7;
     const float* ssrc = sk == 0 ? a.adst : (sk == 1 ? a.asrc : (sk == 2 ? a.mx : a.den));
@@ -418,47 +344,24 @@ __global__ void __launch_bounds__(GB_NT) k_ggat_bwd(const CSR g, const int* __re
     }
     bn_raws_pin(braws);
     if (UP) { stripe_pin(ud1s); stripe_pin(ud2s); }
-    asm volatile("" : "+v"(pv), "+v"(pn), "+v"(nv[0]), "+v"(nv[1]), "+v"(ev[0]), "+v"(ev[1]), "+v"(scv), "+v"(attv));
-    if (ne <= 0) { nv[0] = g0; nv[1] = g0; ev[0] = 0; ev[1] = 0; }   // no slot of this graph exists: the clamped loads fetched no index
+    asm volatile("" : "+v"(pv), "+v"(pn));
+    slots.pin();
+    asm volatile("" : "+v"(scv), "+v"(attv));
+    slots.repair_empty(un);
     if (sh >= hs) scv = 0.f;
     if (t >= 2 * GC_N) attv = 0.f;
-    if (t < K) {
-        float m1, r1;
-        const BNRaw braw = bn_raws_sum(a.bn, braws);
-        bn_raw_mean_rstd(a.bn, braw, m1, r1);
-        mean_s[t] = m1; rstd_s[t] = r1;
-        gam_s[t] = braw.g;
-        bet_s[t] = braw.b;
-    }
+    bn_table_hat(a.bn, braws, t, K, mean_s, rstd_s, gam_s, bet_s);
     // ---- stage everything in LDS -----------------------------------------------------------------------------------
     if (t <= rows) ptr_s[t] = pv - e0;
-    if (t < rows) for (int s = pv - e0; s < pn - e0; ++s) er[s] = (signed char)t;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int s = t + u * GB_NT;
-        if (s < ne) {
-            const int loc = nv[u] - g0;
-            const bool inb = loc >= 0 && loc < rows;
-            en[s] = (signed char)(inb ? loc : -1); ee[s] = ev[u];
-            if (!inb) atomicOr(status, 16);
-        }
-    }
+    if (t < rows) gslots_dest_rows(er, t, pv - e0, pn - e0);
+    slots.template stage<GB_NT>(un, t, status, [&](int s, int u, int loc, bool inb) { en[s] = (signed char)(inb ? loc : -1); ee[s] = slots.ev[u]; });
     if (sh < hs) {
         float* dst = sk == 0 ? &ad_s[sh][sn] : (sk == 1 ? &as_s[sh][sn] : (sk == 2 ? &mx_s[sh][sn] : &dn_s[sh][sn]));
         *dst = sn < rows ? scv : (sk == 3 ? 1.f : 0.f);
     }
     if (t < 2 * GC_N) att_s[t] = attv;
     if (t < 2 * T) { dad_s[t >> 6][t & 63] = 0.f; das_s[t >> 6][t & 63] = 0.f; }
-    if (UP && t >= 256 && t < 256 + GC_N) {              // upper BatchNorm constants of this slice's 64 columns
-        float m1, r1;
-        const BNRaw uraw = bn_raws_sum(a.ubn, braws);
-        const double ud1 = stripe_total(ud1s, a.ubn.ss), ud2 = stripe_total(ud2s, a.ubn.ss);
-        bn_raw_mean_rstd(a.ubn, uraw, m1, r1);
-        um_s[t - 256] = m1; ur_s[t - 256] = r1;
-        ug_s[t - 256] = uraw.g * r1;
-        u1_s[t - 256] = (float)(ud1 * (double)a.ubn.inv_n);
-        u2_s[t - 256] = (float)(ud2 * (double)a.ubn.inv_n);
-    }
+    if (UP && t >= 256 && t < 256 + GC_N) bn_table_upper(a.ubn, braws, ud1s, ud2s, t - 256, um_s, ur_s, ug_s, u1_s, u2_s);     // this slice's 64 columns
     if (!UP) ro_commit<GB_NT>(bd, rows, 16, [&](int j, int n4, const float4 v) { *reinterpret_cast<float4*>(Ds + j * GB_LDD + 4 * n4) = v; });
     ro_commit<GB_NT>(bz, rows, 16, [&](int j, int n4, const float4 v) { *reinterpret_cast<float4*>(Zr + j * GB_LDD + 4 * n4) = v; });
     __syncthreads();                                     // BN constants (W stays in registers: its LDS tile holds the second head's blocks first)
@@ -711,10 +614,8 @@ __global__ void __launch_bounds__(GB_NT) k_ggat_bwd(const CSR g, const int* __re
                 f2[r & 3] = fmaf(v, xh[q][r], f2[r & 3]);
             }
         }
-        double s1 = ((double)f1[0] + (double)f1[1]) + ((double)f1[2] + (double)f1[3]);
-        double s2 = ((double)f2[0] + (double)f2[1]) + ((double)f2[2] + (double)f2[3]);
-        s1 += __shfl_xor(s1, 32, 64);
-        s2 += __shfl_xor(s2, 32, 64);
+        double s1, s2;
+        colsum_fold(f1, f2, s1, s2);
         if (lk == 0) {
             if (a.dacc_sum) {
                 const size_t po = (size_t)stripe_of_block() * a.dacc_ss + k;

@@ -51,6 +51,7 @@ __global__ void __launch_bounds__(512, 2) k_ggin_fwd(const CSR g, const int* __r
         vb[u] = *reinterpret_cast<const float4*>(a.W + (size_t)(n0 + col) * K + 4 * k4);
     }
     const int g0 = gptr[b], rows = gptr[b + 1] - g0, e0 = eptr[b], ne = eptr[b + 1] - e0;
+    const GUnit un{g0, rows, e0, ne};
     const bool want = PART == 1 && a.st_sum.on();
     if (rows <= 0) {
         if (PART == 2 && a.bn.update && blockIdx.x == 0 && blockIdx.y == 0 && t < K) { const BNRaw r0 = bn_raw_load_st(a.bn, t); bn_raw_update_running(a.bn, r0, t); }
@@ -99,11 +100,7 @@ __global__ void __launch_bounds__(512, 2) k_ggin_fwd(const CSR g, const int* __r
         }
     }
     asm volatile("" : "+v"(bias));
-    if (PART == 2 && t < K) {
-        const BNRaw braw = bn_raws_sum(a.bn, braws);
-        bn_raw_scale_shift(a.bn, braw, sc_s[t], sh_s[t]);
-        if (a.bn.update && blockIdx.x == 0 && blockIdx.y == 0) bn_raw_update_running(a.bn, braw, t);
-    }
+    if (PART == 2) bn_table_scale_shift(a.bn, braws, t, K, sc_s, sh_s);
     // ---- stage -----------------------------------------------------------------------------------------------------
     if (PART == 1) {
         if (t <= rows) ptr_s[t] = pv - e0;
@@ -158,32 +155,14 @@ __global__ void __launch_bounds__(512, 2) k_ggin_fwd(const CSR g, const int* __r
     __syncthreads();                                     // every wave is done reading both stages
     float* Zt = Bs;                                      // Zt[col * LDT + j]
     float* At = As;                                      // At[i * LDT + j]
-    if (r0 < R && kh == 1) {
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq)
-            *reinterpret_cast<float4*>(Zt + (ct * 32 + li) * LDT + r0 * 32 + 8 * gq + 4 * lk) =
-                make_float4(acc0[4 * gq], acc0[4 * gq + 1], acc0[4 * gq + 2], acc0[4 * gq + 3]);
-    }
-    if (PART == 1) {
-        const int nz4 = (rowsP * LDT) >> 2;
-        float4* z4 = reinterpret_cast<float4*>(At);
-        for (int idx = t; idx < nz4; idx += NT) z4[idx] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    if (r0 < R && kh == 1) z_park<LDT>(Zt, acc0, r0, ct, li, lk);
+    if (PART == 1) adj_zero<NT>(At, (rowsP * LDT) >> 2, t);
     __syncthreads();
-    if (kh == 0 && r0 < R) {                             // z tile = this wave's half + the partner's
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-            float4* zp = reinterpret_cast<float4*>(Zt + (ct * 32 + li) * LDT + r0 * 32 + 8 * gq + 4 * lk);
-            const float4 p = *zp;
-            acc0[4 * gq] += p.x; acc0[4 * gq + 1] += p.y; acc0[4 * gq + 2] += p.z; acc0[4 * gq + 3] += p.w;
-            if (PART == 1) *zp = make_float4(acc0[4 * gq], acc0[4 * gq + 1], acc0[4 * gq + 2], acc0[4 * gq + 3]);
-        }
-    }
+    if (kh == 0 && r0 < R) z_combine<LDT, PART == 1>(Zt, acc0, r0, ct, li, lk);      // z tile = this wave's half + the partner's
     const bool own = kh == 0;
     if (PART == 1) {
-        // unit adjacency block A + I: one lane per CSR slot (duplicate edges accumulate), one per self loop
-        for (int s = t; s < ne; s += NT) atomicAdd(&At[er[s] * LDT + en[s]], 1.f);
-        if (t < rows) atomicAdd(&At[t * LDT + t], 1.f);
+        // unit adjacency block A + I
+        adj_scatter<NT, LDT>(At, er, en, un, t, [](int, int) { return 1.f; }, [](int) { return 1.f; });
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < 16; ++i) { acc0[i] = 0.f; acc1[i] = 0.f; }
@@ -205,16 +184,9 @@ __global__ void __launch_bounds__(512, 2) k_ggin_fwd(const CSR g, const int* __r
         }
     }
     if (PART == 1) {
-        double s1 = ((double)f1[0] + (double)f1[1]) + ((double)f1[2] + (double)f1[3]);
-        double s2 = ((double)f2[0] + (double)f2[1]) + ((double)f2[2] + (double)f2[3]);
-        s1 += __shfl_xor(s1, 32, 64);
-        s2 += __shfl_xor(s2, 32, 64);
-        if (own && lk == 0) { red[w & 3][0][li] = s1; red[w & 3][1][li] = s2; }
-        __syncthreads();
-        if (w < 2 && lk == 0 && want) {
-            a.st_sum.add(col, red[w][0][li] + red[w + 2][0][li]);
-            a.st_sq.add(col, red[w][1][li] + red[w + 2][1][li]);
-        }
+        double s1, s2;
+        colsum_fold(f1, f2, s1, s2);
+        colsum_commit(red, own, want, w, li, lk, col, s1, s2, a.st_sum, a.st_sq);
     }
 }
 
@@ -259,7 +231,8 @@ __global__ void __launch_bounds__(GB_NT) k_ggin_bwd(const CSR g, const int* __re
     __shared__ float bs_s[GB_NT / 64][16][4];
     warm_kernargs<sizeof(CSR) + 2 * sizeof(void*) + sizeof(GginBwdArgs) + 32>();
     const int b = blockIdx.x, sl = blockIdx.y, ns0 = sl * GC_N, t = threadIdx.x;
-    const int g0 = gptr[b], rows = gptr[b + 1] - g0, e0 = eptr[b], ne = eptr[b + 1] - e0;
+    const GUnit un = gunit_load(gptr, eptr, b);
+    const int g0 = un.g0, rows = un.rows, e0 = un.e0, ne = un.ne;
     const int lane = t & 63, li = lane & 31, lk = lane >> 5;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
     double* parts = PART == 2 ? a.dot_parts + ((size_t)sl * gridDim.x + b) * (2 * K) : nullptr;
@@ -291,13 +264,12 @@ __global__ void __launch_bounds__(GB_NT) k_ggin_bwd(const CSR g, const int* __re
         const int idx = t + u * GB_NT, n = idx & 63, k4 = min(idx >> 6, K4 - 1);
         vw[u] = *reinterpret_cast<const float4*>(a.W + (size_t)(ns0 + n) * K + 4 * k4);
     }
-    int pv = 0, pn = 0, nv[2] = {0, 0};
+    int pv = 0, pn = 0;
+    GSlots<2, false, false> slots;
     if (PART == 1) {
         pv = g.ptr[g0 + min(t, rows)];
         pn = g.ptr[g0 + min(t + 1, rows)];
-        const int slot_hi = max(g.nnz - 1, 0);
-#pragma unroll
-        for (int u = 0; u < 2; ++u) nv[u] = g.nbr[min(e0 + max(min(t + u * GB_NT, ne - 1), 0), slot_hi)];
+        slots.template load<GB_NT>(g, un, t);
     }
     BNRawS braws = bn_raws_load(a.bn, PART == 2 ? min(t, K - 1) : ns0 + (t & (GC_N - 1)));      // (striped readers, engine.hpp)
     StripeVal ud1s, ud2s;
@@ -305,40 +277,19 @@ __global__ void __launch_bounds__(GB_NT) k_ggin_bwd(const CSR g, const int* __re
     bn_raws_pin(braws);
     if (PART == 1) {
         stripe_pin(ud1s); stripe_pin(ud2s);
-        asm volatile("" : "+v"(pv), "+v"(pn), "+v"(nv[0]), "+v"(nv[1]));
-        if (ne <= 0) { nv[0] = g0; nv[1] = g0; }
+        asm volatile("" : "+v"(pv), "+v"(pn));
+        slots.pin();
+        slots.repair_empty(un);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) ro_pin(vw[u]);
-    if (PART == 2 && t < K) {
-        float m1, r1;
-        const BNRaw braw = bn_raws_sum(a.bn, braws);
-        bn_raw_mean_rstd(a.bn, braw, m1, r1);
-        mean_s[t] = m1; rstd_s[t] = r1; gam_s[t] = braw.g; bet_s[t] = braw.b;
-    }
-    if (PART == 1 && t < GC_N) {
-        float m1, r1;
-        const BNRaw braw = bn_raws_sum(a.bn, braws);
-        const double ud1 = stripe_total(ud1s, a.bn.ss), ud2 = stripe_total(ud2s, a.bn.ss);
-        bn_raw_mean_rstd(a.bn, braw, m1, r1);
-        um_s[t] = m1; ur_s[t] = r1; ug_s[t] = braw.g * r1;
-        u1_s[t] = (float)(ud1 * (double)a.bn.inv_n);
-        u2_s[t] = (float)(ud2 * (double)a.bn.inv_n);
-    }
+    if (PART == 2) bn_table_hat(a.bn, braws, t, K, mean_s, rstd_s, gam_s, bet_s);
+    if (PART == 1 && t < GC_N) bn_table_upper(a.bn, braws, ud1s, ud2s, t, um_s, ur_s, ug_s, u1_s, u2_s);
     if (PART == 1) {
-        for (int i = t; i < (rowsP * GB_LDJ + 3) / 4; i += GB_NT) reinterpret_cast<float4*>(Ab)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        adj_zero<GB_NT>(Ab, (rowsP * GB_LDJ + 3) / 4, t);
         if (t <= rows) ptr_s[t] = pv - e0;
-        if (t < rows) for (int s = pv - e0; s < pn - e0; ++s) er[s] = (short)t;
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int s = t + u * GB_NT;
-            if (s < ne) {
-                const int loc = nv[u] - g0;
-                const bool inb = loc >= 0 && loc < rows;
-                en[s] = inb ? loc : 0;
-                if (!inb) atomicOr(status, 16);
-            }
-        }
+        if (t < rows) gslots_dest_rows(er, t, pv - e0, pn - e0);
+        slots.template stage<GB_NT>(un, t, status, [&](int s, int, int loc, bool inb) { en[s] = inb ? loc : 0; });
     }
     // W[ns, :]^T: Ws[k][n], lanes along n (conflict-free scalar stores)
 #pragma unroll
@@ -397,10 +348,7 @@ __global__ void __launch_bounds__(GB_NT) k_ggin_bwd(const CSR g, const int* __re
     }
     for (int i = t; i < (rowsP - rows) * GB_LDD; i += GB_NT) Ds[rows * GB_LDD + i] = 0.f;
     for (int i = t; i < (rowsP - rows) * GB_LDX; i += GB_NT) Xs[rows * GB_LDX + i] = 0.f;
-    if (PART == 1) {
-        for (int s = t; s < ne; s += GB_NT) atomicAdd(&Ab[er[s] * GB_LDJ + en[s]], 1.f);
-        if (t < rows) atomicAdd(&Ab[t * GB_LDJ + t], 1.f);
-    }
+    if (PART == 1) adj_scatter<GB_NT, GB_LDJ>(Ab, er, en, un, t, [](int, int) { return 1.f; }, [](int) { return 1.f; });
     __syncthreads();
     if (a.bias_parts && t < GC_N) {
         double tot = 0.0;
@@ -454,10 +402,8 @@ __global__ void __launch_bounds__(GB_NT) k_ggin_bwd(const CSR g, const int* __re
                     f2[r & 3] = fmaf(v, xh[q][r], f2[r & 3]);
                 }
             }
-            double s1 = ((double)f1[0] + (double)f1[1]) + ((double)f1[2] + (double)f1[3]);
-            double s2 = ((double)f2[0] + (double)f2[1]) + ((double)f2[2] + (double)f2[3]);
-            s1 += __shfl_xor(s1, 32, 64);
-            s2 += __shfl_xor(s2, 32, 64);
+            double s1, s2;
+            colsum_fold(f1, f2, s1, s2);
             if (lk == 0) {
                 if (a.dacc_sum) {
                     const size_t po = (size_t)stripe_of_block() * a.dacc_ss + k;

@@ -740,10 +740,8 @@ __global__ void __launch_bounds__(GW_NT, 2) k_gw_bwd(const CSR g, const int* __r
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        double s1 = ((double)f1[0] + (double)f1[1]) + ((double)f1[2] + (double)f1[3]);
-        double s2 = ((double)f2[0] + (double)f2[1]) + ((double)f2[2] + (double)f2[3]);
-        s1 += __shfl_xor(s1, 32, 64);
-        s2 += __shfl_xor(s2, 32, 64);
+        double s1, s2;
+        colsum_fold(f1, f2, s1, s2);
         if (lk == 0) { red[(w * 2 + 0) * 32 + li] = s1; red[(w * 2 + 1) * 32 + li] = s2; }
     }
     gc_f32x16 acc_p3;                                    // nsplit 4: this wave's half of the node range

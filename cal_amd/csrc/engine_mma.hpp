@@ -10,8 +10,9 @@
 //               mma_rowk_tile  the same, addressed by tile                (see there why it is a form of its own)
 //               mma_arow       A row-major, B k-major                     (two-stage pipeline)
 //               mma_step4      float4 x float4 -> four MFMA steps
-// Accumulator zeroing and the column-sum epilogues stay written out in the kernels: as helpers (by reference or by value)
-// they changed the instruction order hipcc emits for the kernels around them, and these kernels are latency-bound.
+// Accumulator zeroing stays written out in the kernels: as a helper (by reference or by value) it changed the instruction
+// order hipcc emits for the kernels around it, and these kernels are latency-bound.  What surrounds the products (unit
+// extents, slot batch, operand tiles, BatchNorm tables, column-sum epilogue) is engine_gunit.hpp.
 #pragma once
 #include "engine.hpp"
 
