@@ -37,6 +37,11 @@
 #include "engine_gwide.hpp"
 #include "engine_attwide.hpp"
 
+// gconv_bwd_att.hip: launches k_gconv_bwd_att (the per-graph GCNConv backward's ATT mode); structures as untyped pointers + sizes
+extern "C" int cal_launch_gconv_bwd_att(unsigned gx, unsigned gy, hipStream_t st, hipEvent_t e0, hipEvent_t e1, const void* csr, size_t csr_bytes,
+                                        const int* gptr, const int* eptr, const void* branches, size_t branches_bytes, float loop_w, int N, int H,
+                                        int K, int* status, const void* att, size_t att_bytes);
+
 namespace cal {
 
 constexpr int MAX_LAYERS = 6;
@@ -207,6 +212,8 @@ struct Engine {
                              // instead of partial rows + k_stats_final; CAL_AMD_STRIPED=0 keeps the finishing launches
     int fold_zero;           // 1: forward + backward steps on the per-graph plan have no k_zero_f64 launch (PlanFold); CAL_AMD_FOLD_ZERO=0: always the launch
     int bn0_dirty_host;      // host twin of the device word status[3]: a training forward has been enqueued since the last k_finish
+    int att_fold;            // 1: the per-graph attention backward runs inside the last backbone layer's k_gconv_bwd launch (its ATT mode);
+                             // CAL_AMD_ATT_FOLD=0 keeps the two launches
     int gwide;               // 1: graphs of 129 .. 256 nodes run the wide per-graph convolutions (engine_gwide.hpp); CAL_AMD_GWIDE=0: the node-level chain
     int ro_step;             // 1: training steps run the readout as one launch (k_ro_step); CAL_AMD_RO_STEP=0 keeps the four kernels
     float *dzl, *dyh1, *dy1, *dxh, *dpool, *dZco, *gn, *gself, *ddeg, *dl, *dzco, *dXhco, *dZ, *dzi, *dXh, *slabs;
@@ -275,6 +282,7 @@ CAL_EXPORT void* cal_engine_create(int64_t F, int64_t H, int64_t C, int64_t L) {
     { const char* v = getenv("CAL_AMD_STRIPED"); e->striped = !(v && v[0] == '0'); }
     { const char* v = getenv("CAL_AMD_GWIDE"); e->gwide = !(v && v[0] == '0'); }
     { const char* v = getenv("CAL_AMD_FOLD_ZERO"); e->fold_zero = !(v && v[0] == '0'); }
+    { const char* v = getenv("CAL_AMD_ATT_FOLD"); e->att_fold = !(v && v[0] == '0'); }
     e->bn0_dirty_host = 1;
     {
         // k_ro_step's 3 * H / 16 workgroups (133 KB of LDS each: one per CU) meet at spin barriers: they must all be
@@ -519,6 +527,9 @@ struct Route {
     // to the node-parallel pair), its backward does not; the per-graph forward and backward have bounds of their own
     Att att_fwd, att_bwd;
     int ag_split;                 // workgroups per graph of k_att_bwd_graph / k_att_bwd_wide
+    // the per-graph attention backward and the last backbone layer's backward are ONE launch (k_gconv_bwd's ATT mode builds dOut
+    // from the attention backward instead of reading e->dZ): GCN layers on the one-workgroup-per-CU k_gconv_bwd only
+    bool att_fold;
     // causal convolutions: forward per graph up to 128 nodes, backward only for 64-node graphs of <= 512 units; where the
     // forward pooled per graph and the backward is node-level, the backward counts the positive rows itself (launch_pool_cnt)
     Conv co_fwd, co_bwd;
@@ -827,7 +838,7 @@ int bn_bwd_sums(Ctx& c, Args& a, int P, double* dsum, double* dprod, bool st) {
 
 // Launch the per-graph fused backward for nb branches (2: the causal convolutions, 1: a backbone layer): slabs (one per graph)
 // and the BatchNorm-backward partial rows are registered like those of the GEMM path.  gb[k].dot_parts / .slab are filled in here.
-int gconv_bwd(Ctx& c, Bwd& b, GconvBwdBranch* gb, int nb, float** dst, double** dsum, double** dprod, bool st) {
+int gconv_bwd(Ctx& c, Bwd& b, GconvBwdBranch* gb, int nb, float** dst, double** dsum, double** dprod, bool st, const AttBwdGraphArgs* att = nullptr) {
     Engine* e = c.e;
     const bool co = nb == 2;
     const bool wide = (co ? c.r.co_bwd : c.r.bb_bwd) == Conv::Wide;
@@ -855,6 +866,17 @@ int gconv_bwd(Ctx& c, Bwd& b, GconvBwdBranch* gb, int nb, float** dst, double** 
     }
     const CSR gd = csr_dst(c);
     const dim3 grid(B, nsl, nb);
+    if (att) {      // ATT: dOut comes from the attention backward inside the launch (bwd_att)
+        if (co || lean || gb[0].dout) { set_error("k_gconv_bwd: the ATT mode is a one-branch, one-workgroup-per-CU launch"); return 2; }
+        // (the kernel is in gconv_bwd_att.hip, a code object of its own; inside a single-kernel ProfScope the dispatch carries its events)
+        if (cal_launch_gconv_bwd_att(grid.x, grid.y, c.st, g_prof_cur ? g_prof_cur->r.e0 : nullptr, g_prof_cur ? g_prof_cur->r.e1 : nullptr, &gd, sizeof(gd),
+                                     e->gptr, e->eptr, &b2, sizeof(b2), e->loop_w, c.N, H, H, e->status, att, sizeof(*att))) {
+            set_error("k_gconv_bwd_att: argument structures differ between engine.hip and gconv_bwd_att.hip"); return 2;
+        }
+        if (g_prof_cur) g_prof_cur->used = true;
+        CAL_CHECK_LAUNCH("k_att_bwd_graph");
+        return 0;
+    }
     // lean: the 80 KB instantiation, two workgroups per CU -- the two-branch launch at 128 graphs is twice the CUs, packed batches
     // and batches of > 128 graphs more (its two-branch gn goes out in slot order: only when k_att_bwd_graph consumes it)
     if (co && lean && e->ntiles > 0) PROF_LAUNCH((k_gconv_bwd<true, 2, true, true>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, e->status);
@@ -1019,6 +1041,7 @@ Route make_route(const Ctx& c, bool want_grad) {
     r.ag_split = aw ? std::max(1, std::min(8, e->num_cus / std::max(T, 1))) : 2;
     r.lean_bb = w1 > e->num_cus;
     r.lean_co = w2 > e->num_cus && r.att_bwd == Att::Graph;
+    r.att_fold = e->att_fold && gcn && r.att_bwd == Att::Graph && r.bb_bwd == Conv::Graph64 && L >= 1 && !r.lean_bb;
     // narrow feature matrices of big batches: the feature layer as row kernels (engine_feat.hpp) instead of tiled GEMMs
     const bool feat_rows = F <= FEAT_FMAX && N > 16384 && H % 4 == 0 && H <= 256 && group_for(H, 4) >= FEAT_FMAX;
     r.feat_fwd = feat_rows ? FeatFwd::Rows : FeatFwd::Gemm;
@@ -1679,6 +1702,40 @@ int bwd_co(Ctx& c, Bwd& b) {
     return 0;
 }
 
+// GCNConv layer i's backward per graph (engine_gconv_bwd.hpp), unit coefficients as the forward's first layer wrote them -- or per
+// graph of up to 256 nodes (engine_gwide.hpp): CSR by source, the unit coefficients k_plan_graph left in that slot order, if it ran.
+// Layer i reads dOut = e->dZ (i == L, written by the attention backward), or builds it while staging: from layer i+1's partial dX'
+// (BatchNorm_{i+1}-backward + ReLU mask fused in: no k_bn_bwd launch, no dZ round trip), or (att, i == L) from the attention
+// backward itself.  Slice-0 partials ping-pong between dXh and z (idle in the fused forward), slice-1 partials are per layer.
+// (one definition of the two per-layer choices for bwd_backbone and bb_gconv_bwd)
+float* bb_dxp0(const Engine* e, int i) { return ((e->L - i) & 1) ? e->z : e->dXh; }     // slice-0 partial dX' of layer i
+bool bb_striped(const Route& r, int i) { return i > 1 ? r.st_bb : r.st_bb1; }            // layer i's BatchNorm-backward sums go to the accumulator planes
+int bb_gconv_bwd(Ctx& c, Bwd& b, int i, const AttBwdGraphArgs* att) {
+    Engine* e = c.e;
+    const Route& r = c.r;
+    const int N = c.N, H = e->H, L = e->L;
+    const int64_t E = c.E;
+    const size_t NH = (size_t)N * H;
+    const bool two = H > GC_N;
+    GconvBwdBranch gb;
+    memset(&gb, 0, sizeof(gb));
+    gb.x = e->h + (size_t)(i - 1) * NH; gb.W = e->P + e->o_conv_w[i - 1]; gb.dis = e->dis_unit; gb.bn = bnref(c, i, N, 0);
+    gb.dxp0 = bb_dxp0(e, i); gb.dxp1 = e->dzi + (size_t)(i - 1) * NH;
+    gb.coef_in = r.bb_bwd != Conv::Wide ? e->coef : r.plan_coef ? e->coef_src : nullptr;
+    if (i == L) gb.dout = att ? nullptr : e->dZ;
+    else {
+        gb.dy0 = bb_dxp0(e, i + 1);
+        gb.dy1 = two ? e->dzi + (size_t)i * NH : nullptr;
+        gb.y = e->h + (size_t)i * NH;
+        gb.ubn = bnref(c, i + 1, N, 0); gb.udot_sum = bn_dsum(c, i + 1); gb.udot_prod = bn_dprod(c, i + 1);
+        gb.bias_parts = b.d_convb[i - 1].p;
+    }
+    float* dst[1] = {e->G + e->o_conv_w[i - 1]};
+    double* dsum[1] = {bn_dsum(c, i)}; double* dprod[1] = {bn_dprod(c, i)};
+    ProfScope ps(c.st, 4, 4.0 * N * H * H + 2.0 * (double)(E + N) * H, true);
+    return gconv_bwd(c, b, &gb, 1, dst, dsum, dprod, bb_striped(r, i), att);
+}
+
 // P8. everything between the last backbone conv and the two causal convs
 int bwd_att(Ctx& c, Bwd& b) {
     Engine* e = c.e;
@@ -1697,7 +1754,8 @@ int bwd_att(Ctx& c, Bwd& b) {
     aa.fnode = e->no_node_att ? 0.f : 1.f; aa.fedge = e->no_edge_att ? 0.f : 1.f;
     aa.gs = csr_src(c); aa.gd = csr_dst(c); aa.dZ = e->dZ;
     // one partial row per workgroup: r.ag_split per graph (k_att_bwd_graph / k_att_bwd_wide), or one per row block (k_att_bwd)
-    const int P = r.att_bwd == Att::Node ? cdiv(N, c.rpb_n) : r.ag_split * T;
+    // (folded into the last backbone layer's launch: one per unit, the column slices write disjoint columns)
+    const int P = r.att_bwd == Att::Node ? cdiv(N, c.rpb_n) : r.att_fold ? T : r.ag_split * T;
     aa.dbias = L > 0 ? defer(c, b.d_convb[L - 1], P, H) : Acc();
     aa.dWn = defer(c, b.d_dwn, P, H + 4); aa.dWe = defer(c, b.d_dwe, P, 2 * H + 4);
     if (!aa.dWn.on() || !aa.dWe.on()) return no_parts();
@@ -1719,6 +1777,12 @@ int bwd_att(Ctx& c, Bwd& b) {
         ag.gn = e->gn; ag.gn2 = two ? e->gn + 2 * (size_t)E : nullptr;
         ag.gself = e->gself; ag.gself2 = two ? e->gself + 2 * (size_t)N : nullptr;
         ag.loop_w = e->loop_w; ag.E = E; ag.N = N; ag.status = e->status;
+        if (r.att_fold) {
+            // one launch with layer L's backward (k_gconv_bwd's ATT mode): this site keeps its name, bwd_backbone launches nothing for L
+            RC(bb_gconv_bwd(c, b, L, &ag)); STAGE();
+            RC(flush_finals(c)); STAGE();
+            return 0;
+        }
         RC(with_g(H, [&](auto g) {
             constexpr int G = decltype(g)::value;
             hipLaunchKernelGGL((k_att_bwd_graph<4, G>), dim3(r.ag_split * T), dim3(512), 0, st, ag, 1, H, r.ag_split);
@@ -1788,7 +1852,7 @@ int bwd_backbone(Ctx& c, Bwd& b, const float* x0) {
     for (int i = L; i >= 1; --i) {
         float* dzi = e->dzi + (size_t)(i - 1) * NH;     // per layer: the side-stream dW GEMM reads it later
         const float* hin = e->h + (size_t)(i - 1) * NH;
-        const bool st_i = i > 1 ? r.st_bb : r.st_bb1;    // this layer's BatchNorm-backward sums go to the accumulator planes
+        const bool st_i = bb_striped(r, i);
         if (e->gin && r.bb_bwd == Conv::Graph64) {
             // GINConv backward per graph (engine_ggin.hpp): second Linear (+ the BatchNorm-backward sums behind the ReLU) |
             // BatchNorm backward, first Linear, transposed aggregation.  Partial input gradients (one per output-column
@@ -1902,10 +1966,9 @@ int bwd_backbone(Ctx& c, Bwd& b, const float* x0) {
             }
             continue;
         }
-        // Per graph, layer i reads dOut = e->dZ (i == L, written by the attention backward) or builds it while staging from layer
-        // i+1's partial dX' (BatchNorm_{i+1}-backward + ReLU mask fused in: no k_bn_bwd launch, no dZ round trip); slice-0 partials
-        // ping-pong between dXh and z (idle in the fused forward), slice-1 partials are per layer.
-        float* p0 = ((L - i) & 1) ? e->z : e->dXh;
+        // Per graph: slice-0 partials of dX' ping-pong between dXh and z (idle in the fused forward), slice-1 partials are per layer
+        // (bb_gconv_bwd for the GCN layers).
+        float* p0 = bb_dxp0(e, i);
         if (r.bb_bwd != Conv::Node && i < L && !defer(c, b.d_convb[i - 1], T, H).on()) return no_parts();   // bias of conv i: one partial row per graph
         if (e->K > 0 && r.bb_bwd == Conv::Graph64) {
             // GATConv layer backward per graph (engine_ggat.hpp): attention backward + dX' (two slice partials) + dW / d att slabs
@@ -1940,25 +2003,11 @@ int bwd_backbone(Ctx& c, Bwd& b, const float* x0) {
             CAL_CHECK_LAUNCH("k_ggat_bwd"); STAGE();
             RC(flush_finals(c)); STAGE();
         } else if (r.bb_bwd != Conv::Node) {
-            // GCNConv per graph (engine_gconv_bwd.hpp), unit coefficients as the forward's first layer wrote them -- or per graph of
-            // up to 256 nodes (engine_gwide.hpp): CSR by source, the unit coefficients k_plan_graph left in that slot order, if it ran
-            GconvBwdBranch gb;
-            memset(&gb, 0, sizeof(gb));
-            gb.x = hin; gb.W = e->P + e->o_conv_w[i - 1]; gb.dis = e->dis_unit; gb.bn = bnref(c, i, N, 0);
-            gb.dxp0 = p0; gb.dxp1 = dzi;
-            gb.coef_in = r.bb_bwd != Conv::Wide ? e->coef : r.plan_coef ? e->coef_src : nullptr;
-            if (i == L) gb.dout = e->dZ;
-            else {
-                gb.dy0 = ((L - i - 1) & 1) ? e->z : e->dXh;
-                gb.dy1 = two ? e->dzi + (size_t)i * NH : nullptr;
-                gb.y = e->h + (size_t)i * NH;
-                gb.ubn = bnref(c, i + 1, N, 0); gb.udot_sum = bn_dsum(c, i + 1); gb.udot_prod = bn_dprod(c, i + 1);
-                gb.bias_parts = b.d_convb[i - 1].p;
+            // GCNConv per graph (bb_gconv_bwd); layer L rode in the attention backward's launch when the route folds the two
+            if (!(i == L && r.att_fold)) {
+                RC(bb_gconv_bwd(c, b, i, nullptr)); STAGE();
+                RC(flush_finals(c)); STAGE();
             }
-            float* dst[1] = {e->G + e->o_conv_w[i - 1]};
-            double* dsum[1] = {bn_dsum(c, i)}; double* dprod[1] = {bn_dprod(c, i)};
-            { ProfScope ps(st, 4, 4.0 * N * H * H + 2.0 * (double)(E + N) * H, true); RC(gconv_bwd(c, b, &gb, 1, dst, dsum, dprod, st_i)); } STAGE();
-            RC(flush_finals(c)); STAGE();
         }
         // BatchNorm_i backward of layer i's input gradient (two slice partials q0 + q1, or one) into e->dZ, the bias sums of the layer
         // below into `acc`; st: the striped instantiation (the site's sums are in the accumulator planes)

@@ -17,6 +17,7 @@
 //   dW product (both only need dz), and twice as many loads are in flight while staging.
 #pragma once
 #include "engine_gconv.hpp"
+#include "engine_attphases.hpp"
 
 namespace cal {
 
@@ -69,6 +70,9 @@ struct GconvBwdBranch {
 };
 
 struct GconvBwdBranch2 { GconvBwdBranch b[2]; };
+// `ga` of the body in the modes that have no attention operands (a dependent type, so that the discarded ATT blocks compile)
+struct GconvBwdNoAtt {};
+template <int MODE> struct GconvBwdNoAttOf { using type = GconvBwdNoAtt; };
 
 // LEAN (MODE 0 / 1, the single-branch launches; round 5): under 80 KB of LDS and 128 registers, so TWO workgroups share a CU
 // and a launch of more workgroups than CUs (a packed batch: 240 tiles x 2 slices at NCI1-like batches of 512 graphs) stops
@@ -76,342 +80,22 @@ struct GconvBwdBranch2 { GconvBwdBranch b[2]; };
 // MFMA operands in P2: 16-byte reads of a 64 KB matrix every workgroup shares), the x_hat rows have no padding (no access to
 // them is strided by a row), CSR neighbours are 16-bit.  The POOL variant (MODE 2) also holds the z rows for the SDDMM: 140 KB,
 // one workgroup per CU.
+// ATT (MODE 3, the last backbone layer behind the per-graph attention backward): dOut is not materialised either -- it is the dZ
+// of k_att_bwd_graph (engine_attbwd.hpp), whose phases (engine_attphases.hpp) run here in front of the products: the loads of both kernels go out together
+// (one CSR slot batch serves both; the W slice and rows 32-63 as a second batch behind the BatchNorm table, or the kernel spills), the edge phase's three 64 x 65 blocks live in the W / x_hat stages (whose
+// registers wait, as the LEAN POOL variant's x_hat does), and the row phase walks all rows x all H columns (dl0 needs the
+// full-width dots) while only the lanes of this slice's columns write dOut and add to the column sums: the partial rows of
+// d bias_L / d Wn / d We are one per unit, the slices write disjoint columns, slice 0 the two scalars.  No dZ round trip, no
+// launch boundary, one prologue.
 // Chosen per launch (gconv_bwd in engine.hip): a launch of at most one workgroup per CU keeps the staged W slice -- with one
 // workgroup on a CU the two L2 round trips of P2's operand reads are exposed (config 2: 0.2386 -> 0.2418 ms with LEAN everywhere).
 template <bool RS, int MODE, bool TILED = false, bool LEAN = false>      // MODE 0: dOut given; 1: UP (from the upper layer's partials); 2: POOL (+ gn / gself)
 __global__ void __launch_bounds__(GB_NT, (LEAN ? 4 : 1)) k_gconv_bwd(const CSR g, const int* __restrict__ gptr, const int* __restrict__ eptr,
                                                    const GconvBwdBranch2 bb, float loop_w, int N, int H,
                                                    int K, int* __restrict__ status) {
-    constexpr int LDX = LEAN ? GC_K : GB_LDX;
-    __shared__ __attribute__((aligned(16))) float Ab[GB_T * GB_LDJ];       // adjacency block Ab[j][i]: dz_i += Ab[j][i] dOut_j
-    __shared__ __attribute__((aligned(16))) float Ds[GB_T * GB_LDD];       // dOut slice [j][n]; later dz [i][n]
-    __shared__ __attribute__((aligned(16))) float Ws[LEAN ? 4 : GC_K * GB_LDD];   // POOL: W[:, ns] as loaded: Ws[k_in][n] (row-major in n, 16 B operand reads)
-    __shared__ __attribute__((aligned(16))) float Xs[GB_T * LDX];          // x_hat rows [i][k_in] (normalised, no affine)
-    __shared__ float mean_s[GC_K], rstd_s[GC_K], gam_s[GC_K], bet_s[GC_K];
-    __shared__ int ptr_s[GB_T + 4];
-    __shared__ float dis_s[GB_T], rs_s[GB_T];
-    __shared__ unsigned char en[GB_E];                   // (local node index < 64)
-    __shared__ float ec[GB_E];
-    __shared__ float um_s[MODE == 1 ? GC_N : 1], ur_s[MODE == 1 ? GC_N : 1], ug_s[MODE == 1 ? GC_N : 1], u1_s[MODE == 1 ? GC_N : 1], u2_s[MODE == 1 ? GC_N : 1];     // UP: upper BatchNorm, this slice's columns
-    __shared__ float bs_s[GB_NT / 64][16][4];
-    __shared__ __attribute__((aligned(16))) float Zr_own[(MODE == 2 && !LEAN) ? GB_T * GB_LDD : 4];       // POOL: z slice rows [j][n]
-    // LEAN POOL: the z rows live in the x_hat stage until P1 and the SDDMM are done with them; x_hat is committed only then
-    // (its registers wait through P1) -- the two are never needed at the same time
-    float* const Zr = (MODE == 2 && LEAN) ? Xs : Zr_own;
-    __shared__ float gv_s[TILED ? GC_TILE_GRAPHS * GC_N : GC_N];   // POOL: gradient of this graph's pooled row (TILED: of every graph of the tile), slice columns
-    __shared__ unsigned char bg_s[TILED ? GB_T : 4];     // TILED: graph (inside the tile) of every row
-    __shared__ int ee[(MODE == 2 && !LEAN) ? GB_E : 1];  // POOL: edge id of CSR slot s (LEAN: gn goes out in slot order only, the caller vouches for gn_slot)
-    __shared__ unsigned char er[GB_E];                   // destination row of CSR slot s (< 64)
-    constexpr bool UP = MODE == 1, POOL = MODE == 2;
-    static_assert(!TILED || MODE == 2, "only the POOL variant looks at the graphs inside a tile");
-    BLK_CLK(0);
-    warm_kernargs<sizeof(CSR) + 2 * sizeof(void*) + sizeof(GconvBwdBranch2) + 32>();
-    const GconvBwdBranch& br = bb.b[blockIdx.z];         // indexed in the kernel-argument segment (see k_gconv_fwd)
-    const int b = blockIdx.x, sl = blockIdx.y, ns0 = sl * GC_N, t = threadIdx.x;
-    const GUnit un = gunit_load(gptr, eptr, b);
-    const int g0 = un.g0, rows = un.rows, e0 = un.e0, ne = un.ne;
-    const int pb = (MODE == 2 && !TILED && br.iperm) ? br.iperm[b] : b;         // row of the second pooled-gradient partial (scalar load, with the extents)
-    const int tg0 = TILED ? (int)br.tile_gptr[b] : b, ng = TILED ? (int)br.tile_gptr[b + 1] - tg0 : 1;
-    const int lane = t & 63, li = lane & 31, lk = lane >> 5;
-    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-    double* parts = br.dot_parts + ((size_t)sl * gridDim.x + b) * (2 * K);
-    float* slab = br.slab + (size_t)b * K * H;
-    if (rows <= 0 || rows > GB_T || ne > GB_E || ne < 0 || (TILED && (ng < 1 || ng > GC_TILE_GRAPHS))) {
-        // empty graph (or a violated bound, flagged): its partial row and its slab slice must still exist
-        if (rows > 0 && t == 0) atomicOr(status, 8);
-        if (!br.dacc_sum) for (int i = t; i < 2 * K; i += GB_NT) parts[i] = 0.0;
-        if ((UP || POOL) && t < GC_N) br.bias_parts[(size_t)b * H + ns0 + t] = 0.0;
-        for (int i = t; i < K * GC_N; i += GB_NT) slab[(size_t)(i / GC_N) * H + ns0 + i % GC_N] = 0.f;
-        return;
-    }
-    const int rowsP = (rows + 31) & ~31, R = rowsP >> 5, K4 = K >> 2;
-    // ---- every global load of the kernel, issued before the first wait ------------------------------------------
-    RoBatch<float4, 2> bd, bd1, by;                      // dOut[g0 + j][ns0 + 4 n4 ..]: rows x 16 float4 (UP: dy0, dy1, y)
-    RoBatch<float4, 4> bx, bw;                           // x[g0 + i][4 k4 ..]: rows x K/4;  W[k_in][ns0 + 4 n4 ..]: K x 16
-    RoBatch<float4, 2> bz;                               // POOL: z[g0 + j][ns0 + 4 n4 ..]
-    float gv = 0.f, gv1 = 0.f;
-    int pbq = 0;
-    long long bgv = 0;
-    if (POOL) {
-        ro_issue<GB_NT>(by, rows, 16, [&](int j, int n4) { return *reinterpret_cast<const float4*>(br.y + (size_t)(g0 + j) * H + ns0 + 4 * n4); });
-        ro_issue<GB_NT>(bz, rows, 16, [&](int j, int n4) { return *reinterpret_cast<const float4*>(br.z + (size_t)(g0 + j) * H + ns0 + 4 * n4); });
-        if (!TILED) {   // gradient of this graph's pooled row, slice columns: both partials unconditionally (gp1 absent: gp0 twice, weight 0)
-            const float* gp1 = br.gp1 ? br.gp1 : br.gp0;
-            gv = br.gp0[(size_t)b * H + ns0 + (t & (GC_N - 1))];
-            gv1 = gp1[(size_t)pb * H + ns0 + (t & (GC_N - 1))];
-        } else {        // lane (q = t / 64, column t % 64): graph tg0 + q of the tile; the permuted row's index is a load of its own
-            const int gq = tg0 + min(t >> 6, ng - 1);
-            gv = br.gp0[(size_t)gq * H + ns0 + (t & (GC_N - 1))];
-            pbq = br.iperm ? br.iperm[gq] : gq;
-            bgv = br.batch[g0 + min(t, rows - 1)];
-        }
-    } else {
-        const float* d0 = UP ? br.dy0 : br.dout;
-        ro_issue<GB_NT>(bd, rows, 16, [&](int j, int n4) { return *reinterpret_cast<const float4*>(d0 + (size_t)(g0 + j) * H + ns0 + 4 * n4); });
-        if (UP) {
-            const float* d1 = br.dy1 ? br.dy1 : br.dy0;
-            ro_issue<GB_NT>(bd1, rows, 16, [&](int j, int n4) { return *reinterpret_cast<const float4*>(d1 + (size_t)(g0 + j) * H + ns0 + 4 * n4); });
-            ro_issue<GB_NT>(by, rows, 16, [&](int j, int n4) { return *reinterpret_cast<const float4*>(br.y + (size_t)(g0 + j) * H + ns0 + 4 * n4); });
-        }
-    }
-    ro_issue<GB_NT>(bx, rows, K4, [&](int i, int k4) { return *reinterpret_cast<const float4*>(br.x + (size_t)(g0 + i) * K + 4 * k4); });
-    if (!LEAN) ro_issue<GB_NT>(bw, K, 16, [&](int k, int n4) { return *reinterpret_cast<const float4*>(br.W + (size_t)k * H + ns0 + 4 * n4); });
-    const int pv = g.ptr[g0 + min(t, rows)];
-    const int pn = g.ptr[g0 + min(t + 1, rows)];
-    const float dv = br.dis[g0 + min(t, rows - 1)];
-    const float rv = RS ? br.rs[(size_t)(g0 + min(t, rows - 1)) * br.rs_stride] : 1.f;
-    // CSR slots, coefficients and the BatchNorm constants (engine_gunit.hpp)
-    GSlots<2, true, true> slots;
-    slots.template load<GB_NT>(g, un, t, br.coef_in, br.dis);
-    // (striped readers, engine.hpp: the producers may be per-graph kernels.  Lanes 0 .. K-1 need this layer's BatchNorm, lanes
-    //  256 .. 319 the upper one's constants of this slice's 64 columns: ONE register set, the pointers chosen per lane)
-    const bool ulane = UP && t >= 256;
-    BNRawS braws = UP ? bn_raws_load2(br.bn, min(t, K - 1), br.ubn, ns0 + (t & (GC_N - 1)), ulane) : bn_raws_load(br.bn, min(t, K - 1));
-    StripeVal ud1s, ud2s;
-    if (UP) {
-        const int c = ns0 + (t & (GC_N - 1));
-        ud1s = stripe_load(br.udot_sum, c, br.ubn.ss); ud2s = stripe_load(br.udot_prod, c, br.ubn.ss);
-    }
-    bn_raws_pin(braws);
-    if (UP) { stripe_pin(ud1s); stripe_pin(ud2s); }
-    slots.pin();
-    if (POOL && !TILED) { asm volatile("" : "+v"(gv), "+v"(gv1)); gv += br.gp1 ? gv1 : 0.f; }
-    if (TILED) {                                         // second round: the permuted graph's pooled-gradient row
-        asm volatile("" : "+v"(gv), "+v"(pbq), "+v"(bgv));
-        const float* gp1 = br.gp1 ? br.gp1 : br.gp0;
-        gv1 = gp1[(size_t)pbq * H + ns0 + (t & (GC_N - 1))];
-    }
-    slots.repair_empty(un);
-    if (UP && t >= 256 && t < 256 + GC_N) bn_table_upper(br.ubn, braws, ud1s, ud2s, t - 256, um_s, ur_s, ug_s, u1_s, u2_s);
-    bn_table_hat(br.bn, braws, t, K, mean_s, rstd_s, gam_s, bet_s);
-    adj_zero<GB_NT>(Ab, (rowsP * GB_LDJ + 3) / 4, t);
-    {   // second round, as in k_gconv_fwd (wv is not used here)
-        const bool hasw = br.ew != nullptr;
-        if (br.coef_in) {
-#pragma unroll
-            for (int u = 0; u < 2; ++u) { slots.cv[u] = slots.cin[u]; slots.wv[u] = 1.f; }
-        } else {
-            const float* ewp = hasw ? br.ew : br.dis;
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const float c = br.dis[slots.nv[u]];
-                const float wl = ewp[hasw ? slots.ev[u] : 0];
-                slots.wv[u] = hasw ? wl : 1.f;
-                slots.cv[u] = c * slots.wv[u];
-            }
-        }
-    }
-    // ---- stage everything in LDS -----------------------------------------------------------------------------------
-    if (t <= rows) ptr_s[t] = pv - e0;
-    if (t < rows) {
-        dis_s[t] = dv; rs_s[t] = rv;
-        gslots_dest_rows(er, t, pv - e0, pn - e0);
-    }
-    slots.template stage<GB_NT>(un, t, status, [&](int s, int u, int loc, bool inb) {
-        en[s] = (unsigned char)(inb ? loc : 0); ec[s] = inb ? slots.cv[u] : 0.f;
-        if (POOL && !LEAN) ee[s] = slots.ev[u];
-    });
-    if (POOL && !TILED && t < GC_N) gv_s[t] = gv;
-    if (TILED) {
-        if (t < ng * GC_N) gv_s[t] = gv + (br.gp1 ? gv1 : 0.f);
-        if (t < rows) bg_s[t] = (unsigned char)min(max((int)(bgv - tg0), 0), ng - 1);
-    }
-    if (MODE == 0) ro_commit<GB_NT>(bd, rows, 16, [&](int j, int n4, const float4 v) { *reinterpret_cast<float4*>(Ds + j * GB_LDD + 4 * n4) = v; });
-    if (!LEAN) ro_commit<GB_NT>(bw, K, 16, [&](int k, int n4, const float4 v) { *reinterpret_cast<float4*>(Ws + k * GB_LDD + 4 * n4) = v; });
-    __syncthreads();                                     // per-column BN constants, row scales, zeroed Ab, CSR
-    auto commit_x = [&]() {
-        ro_commit<GB_NT>(bx, rows, K4, [&](int i, int k4, float4 v) {
-            const float s = RS ? rs_s[i] : 1.f;
-            const int k = 4 * k4;
-            v.x = (v.x * s - mean_s[k]) * rstd_s[k]; v.y = (v.y * s - mean_s[k + 1]) * rstd_s[k + 1];
-            v.z = (v.z * s - mean_s[k + 2]) * rstd_s[k + 2]; v.w = (v.w * s - mean_s[k + 3]) * rstd_s[k + 3];
-            *reinterpret_cast<float4*>(Xs + i * LDX + k) = v;
-        });
-    };
-    if (!(POOL && LEAN)) commit_x();
-    if (POOL) {
-        float cs[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int u = 0; u < 2; ++u) { ro_pin(by.v[u]); ro_pin(bz.v[u]); }
-        const int c = 4 * (t & 15);
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int j = (t >> 4) + u * (GB_NT / 16);
-            if (j < rows) {
-                const float4 yv = by.v[u];
-                const float* gvr = gv_s + (TILED ? bg_s[j] * GC_N : 0);
-                const float4 o = make_float4(yv.x > 0.f ? gvr[c] : 0.f, yv.y > 0.f ? gvr[c + 1] : 0.f,
-                                             yv.z > 0.f ? gvr[c + 2] : 0.f, yv.w > 0.f ? gvr[c + 3] : 0.f);
-                cs[0] += o.x; cs[1] += o.y; cs[2] += o.z; cs[3] += o.w;
-                *reinterpret_cast<float4*>(Ds + j * GB_LDD + c) = o;
-                *reinterpret_cast<float4*>(Zr + j * GB_LDD + c) = bz.v[u];
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            cs[q] += __shfl_xor(cs[q], 16, 64);
-            cs[q] += __shfl_xor(cs[q], 32, 64);
-        }
-        if (lane < 16) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) bs_s[t >> 6][lane][q] = cs[q];
-        }
-    }
-    if (UP) {
-        // dOut slice from the upper layer's partials: lane t always holds column group t % 16 (512 % 16 == 0), so
-        // its column sums stay in registers until the cross-lane reduction below
-        float cs[4] = {0.f, 0.f, 0.f, 0.f};
-        const bool two = br.dy1 != nullptr;
-#pragma unroll
-        for (int u = 0; u < 2; ++u) { ro_pin(bd.v[u]); ro_pin(bd1.v[u]); ro_pin(by.v[u]); }
-        const int c = 4 * (t & 15);
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {                   // item (u, t) = row t / 16 + 32 u, column group t % 16
-            const int j = (t >> 4) + u * (GB_NT / 16);
-            if (j < rows) {
-                const float4 v0 = bd.v[u], v1 = bd1.v[u], yv = by.v[u];
-                const float d[4] = {v0.x + (two ? v1.x : 0.f), v0.y + (two ? v1.y : 0.f), v0.z + (two ? v1.z : 0.f), v0.w + (two ? v1.w : 0.f)};
-                const float yy[4] = {yv.x, yv.y, yv.z, yv.w};
-                float o[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float yn = (yy[q] - um_s[c + q]) * ur_s[c + q];
-                    const float g1 = ug_s[c + q] * (d[q] - u1_s[c + q] - yn * u2_s[c + q]);
-                    o[q] = yy[q] > 0.f ? g1 : 0.f;
-                    cs[q] += o[q];
-                }
-                *reinterpret_cast<float4*>(Ds + j * GB_LDD + c) = make_float4(o[0], o[1], o[2], o[3]);
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            cs[q] += __shfl_xor(cs[q], 16, 64);
-            cs[q] += __shfl_xor(cs[q], 32, 64);
-        }
-        if (lane < 16) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) bs_s[t >> 6][lane][q] = cs[q];
-        }
-    }
-    // rows rows .. rowsP of dOut / x_hat: zero (they are reduced over in the products below)
-    for (int i = t; i < (rowsP - rows) * GB_LDD; i += GB_NT) Ds[rows * GB_LDD + i] = 0.f;
-    for (int i = t; i < (rowsP - rows) * LDX; i += GB_NT) Xs[rows * LDX + i] = 0.f;
-    adj_scatter<GB_NT, GB_LDJ>(Ab, er, en, un, t, [&](int j, int s) { return dis_s[j] * ec[s]; }, [&](int j) { return dis_s[j] * dis_s[j] * loop_w; });
-    __syncthreads();
-    if ((UP || POOL) && t < GC_N) {
-        double tot = 0.0;
-#pragma unroll
-        for (int k = 0; k < GB_NT / 64; ++k) tot += (double)bs_s[k][t >> 2][t & 3];
-        br.bias_parts[(size_t)b * H + ns0 + t] = tot;
-    }
-    BLK_CLK(2);
-    auto ident = [](float v) { return v; };
-    gc_f32x16 acc[2];
-    // ---- P1: dz[:, ns] = Ab^T dOut[:, ns]   (rows i x 64 columns, reduction over the graph's rowsP nodes) ------------
-    {
-        const int rt = w >> 1, ct = w & 1;              // waves 0-3: one tile each; waves 4-7 wait at the barriers
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { acc[0][i] = 0.f; acc[1][i] = 0.f; }
-        if (rt < R) mma_kmajor<1, 1, GB_LDJ, GB_LDD>(Ab + rt * 32 + li, Ds + ct * 32 + li, rowsP, lk, ident, MmaIdent(), acc);
-        if (POOL && w >= 4) {
-            // waves 4-7 (idle during P1): gn / gself of this slice, 4 lanes per item (16 columns each) straight from LDS
-            const int q4 = (t - 256) & 3, it0 = (t - 256) >> 2;
-            float* gn = br.gn + (size_t)sl * br.gn_stride;
-            float* gs = br.gself + (size_t)sl * br.gself_stride;
-            for (int it = it0; it - it0 < ne + rows; it += 64) {
-                const bool ok = it < ne + rows, isedge = it < ne;
-                const int itc = ok ? it : 0;
-                const int jd = isedge ? er[itc] : itc - ne, js = isedge ? en[itc] : itc - ne;      // destination / source row
-                const float4* a = reinterpret_cast<const float4*>(Ds + (ok ? jd : 0) * GB_LDD + 16 * q4);
-                const float4* bsrc = reinterpret_cast<const float4*>(Zr + (ok ? js : 0) * GB_LDD + 16 * q4);
-                float p = 0.f;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) p = dot4(a[k], bsrc[k], p);
-                p += __shfl_xor(p, 1, 64);
-                p += __shfl_xor(p, 2, 64);
-                if (ok && q4 == 0) {
-                    if (isedge) gn[(LEAN || br.gn_slot) ? e0 + itc : ee[itc]] = p; else gs[g0 + itc - ne] = p;
-                }
-            }
-        }
-        __syncthreads();                                 // every wave is done reading dOut (and the z rows)
-        if (POOL && LEAN) commit_x();                    // x_hat over the z rows (visible after the barrier below)
-        if (rt < R) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = mma_row(r, lk, rt * 32);
-                Ds[row * GB_LDD + ct * 32 + li] = acc[0][r];           // dz row-major over the dOut stage
-            }
-        }
-        __syncthreads();
-    }
-    // ---- P2: partial dX'[:, :] = dz[:, ns] W[:, ns]^T   (rows i x K columns, reduction over the 64 columns of ns) ------
-    if (w < 4 && w * 32 < K) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { acc[0][i] = 0.f; acc[1][i] = 0.f; }
-        // both operands row-major in the reduction index n (dz rows in Ds, W rows in Ws, stride 68 = 4 mod 32): 16 B reads,
-        // four MFMA steps per read; W is staged as loaded (no transposing scatter) and dz needs no transposed copy
-        // (LEAN: the lane's W row -- 64 consecutive floats of row w * 32 + li -- comes straight from global memory / L2)
-        const float* wrow = LEAN ? br.W + (size_t)min(w * 32 + li, K - 1) * H + ns0 : Ws + (w * 32 + li) * GB_LDD;
-        if (R == 2) mma_rowk<true>(Ds + li * GB_LDD, Ds + (32 + li) * GB_LDD, wrow, GC_N, lk, acc[0], acc[1]);
-        else mma_rowk<false>(Ds + li * GB_LDD, nullptr, wrow, GC_N, lk, acc[0], acc[1]);
-        const int k = w * 32 + li;
-        float* dxp = sl ? br.dxp1 : br.dxp0;
-        // x_hat of all rows first, as ONE batch of unconditional LDS reads (rows rows .. rowsP are zero, as are their dz;
-        // rows past rowsP hold stale LDS and are masked after the read): written as `q < R ? Xs[..] : 0` hipcc made 32
-        // branches, each with its own ds_read + s_waitcnt lgkmcnt(0) -- 3.6 us of a 13 us kernel -- and before that, with the
-        // read inside the guarded store block, one ~140 ns iteration at a time
-        float xh[2][16];
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) xh[q][r] = Xs[(mma_row(r, lk, q * 32)) * LDX + k];
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { asm volatile("" : "+v"(xh[q][r])); if (q >= R) xh[q][r] = 0.f; }
-        // this lane's 32 terms of the two column sums in fp32 (four independent chains), everything across lanes,
-        // workgroups and graphs in fp64 as before: 128 dependent fp64 conversions / adds per lane were 3.5 us here
-        float f1[4] = {0.f, 0.f, 0.f, 0.f}, f2[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int i = mma_row(r, lk, q * 32);
-                const float v = acc[q][r];                   // (row tile 1 of a one-tile graph: zero accumulators)
-                f1[r & 3] += v;
-                f2[r & 3] = fmaf(v, xh[q][r], f2[r & 3]);
-            }
-        }
-        // (16-byte stores, four columns per lane: gc_store_tile)
-        // (the extent: from the tile's first word to the end of this graph's rows)
-        gc_store_tile<gc_site(WT_DXP)>(acc[0], dxp + (size_t)g0 * K + w * 32, K, rows, li, lk, MmaIdent(), (rows * K - w * 32) * 4);
-        if (R == 2) gc_store_tile<gc_site(WT_DXP)>(acc[1], dxp + (size_t)(g0 + 32) * K + w * 32, K, rows - 32, li, lk, MmaIdent(), ((rows - 32) * K - w * 32) * 4);
-        double s1, s2;
-        colsum_fold(f1, f2, s1, s2);
-        if (lk == 0) {
-            if (br.dacc_sum) {
-                const size_t po = (size_t)stripe_of_block() * br.dacc_ss + k;
-                atomicAdd(br.dacc_sum + po, s1); atomicAdd(br.dacc_prod + po, s2);
-            } else { parts[k] = s1; parts[K + k] = s2; }
-        }
-    }
-    BLK_CLK(3);
-    // ---- P3: dW[:, ns] (this graph) = x'^T dz[:, ns]   (K rows x 64 columns, reduction over the graph's nodes) ---------
-    if (w >= 4 && (w - 4) * 32 < K) {
-        const int wq = w - 4, k = wq * 32 + li;
-        const float gam = gam_s[k], bet = bet_s[k];
-        auto affine = [&](float v) { return fmaf(v, gam, bet); };
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { acc[0][i] = 0.f; acc[1][i] = 0.f; }
-        mma_kmajor<1, 2, LDX, GB_LDD>(Xs + wq * 32 + li, Ds + li, rowsP, lk, affine, MmaIdent(), acc);
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int off = wq * 32 * H + ns0 + q * 32;      // (the extent: to the end of this graph's slab)
-            gc_store_tile<gc_site(WT_DW)>(acc[q], slab + off, H, 32, li, lk, MmaIdent(), (K * H - off) * 4);
-        }
-    }
-    BLK_CLK(1);
+    static_assert(MODE != 3, "the ATT mode is the kernel k_gconv_bwd_att (gconv_bwd_att.hip)");
+    [[maybe_unused]] const typename GconvBwdNoAttOf<MODE>::type ga{};    // (what the ATT blocks of the body name; they are discarded here)
+#include "engine_gconv_bwd_body.hpp"
 }
 
 // ------------------------------------------------------------------------------------------------------------------
