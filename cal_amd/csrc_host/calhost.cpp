@@ -801,6 +801,130 @@ HOST_EXPORT int cal_explain_rank_pairs(const float* score, int64_t stride, const
     return 0;
 }
 
+// ---- batch splice (cal_amd/csrc/splice.hip): the same order of nodes and columns, the same dropped columns and bridge rules, so
+// every integer output agrees bit for bit.  The count leaves each pair's valid-column counts in ws, as the device does.
+namespace {
+struct SpliceSide {
+    const int64_t* ei; int64_t E, N; const int64_t* ptr; const int64_t* eptr; int64_t B; const int64_t* pick; const int64_t* bridge;
+    void ranges(int64_t p, int64_t& nlo, int64_t& nhi, int64_t& elo, int64_t& ehi) const {
+        const int64_t g = pick[p];
+        nlo = nhi = elo = ehi = 0;
+        if (g < 0 || g >= B) return;
+        seg_clamp(ptr, g, N, nlo, nhi);
+        seg_clamp(eptr, g, E, elo, ehi);
+    }
+    bool valid(int64_t e, int64_t nlo, int64_t nhi) const {
+        const int64_t u = ei[e], v = ei[E + e];
+        return u >= nlo && u < nhi && v >= nlo && v < nhi;
+    }
+};
+inline bool splice_bridge(const SpliceSide& a, const SpliceSide& b, int64_t p, int64_t alo, int64_t ahi, int64_t blo, int64_t bhi,
+                          bool& asked) {
+    const int64_t ba = a.bridge ? a.bridge[p] : -1, bb = b.bridge ? b.bridge[p] : -1;
+    asked = ba >= 0 || bb >= 0;
+    return ba >= 0 && bb >= 0 && ba >= alo && ba < ahi && bb >= blo && bb < bhi;
+}
+}  // namespace
+
+HOST_EXPORT int64_t cal_graph_splice_ws(int64_t Ea, int64_t Eb, int64_t P) {
+    return 40 * (P > 0 ? P : 0) + 8 * (Ea > 0 ? Ea : 0) + 8 * (Eb > 0 ? Eb : 0) + 256;
+}
+
+#define SPLICE_REQUIRE_INPUTS()                                                                                                  \
+    HOST_REQUIRE(Ea >= 0 && Na >= 0 && Ba >= 0 && Eb >= 0 && Nb >= 0 && Bb >= 0 && P >= 0, "sizes must be >= 0");                \
+    HOST_REQUIRE(P == 0 || (ga && gb), "ga / gb are null");                                                                      \
+    HOST_REQUIRE((Ba == 0 || (ptr_a && eptr_a)) && (Bb == 0 || (ptr_b && eptr_b)), "ptr / edge_ptr are null");                   \
+    HOST_REQUIRE((Ea == 0 || eia) && (Eb == 0 || eib), "edge_index is null");                                                    \
+    HOST_REQUIRE((bridge_a == nullptr) == (bridge_b == nullptr), "bridge_a and bridge_b come together");                        \
+    HOST_REQUIRE(P == 0 || (ws && ws_bytes >= cal_graph_splice_ws(Ea, Eb, P)), "ws must hold cal_graph_splice_ws(Ea, Eb, P) bytes")
+
+HOST_EXPORT int cal_graph_splice_count(const int64_t* eia, int64_t Ea, int64_t Na, const int64_t* ptr_a, const int64_t* eptr_a,
+                                       int64_t Ba, const int64_t* eib, int64_t Eb, int64_t Nb, const int64_t* ptr_b,
+                                       const int64_t* eptr_b, int64_t Bb, const int64_t* ga, const int64_t* gb, int64_t P,
+                                       const int64_t* bridge_a, const int64_t* bridge_b, int64_t* ptr_out, int64_t* edge_ptr_out,
+                                       int64_t* totals, void* ws, int64_t ws_bytes, void*) {
+    SPLICE_REQUIRE_INPUTS();
+    HOST_REQUIRE(totals && ptr_out && edge_ptr_out, "totals / ptr_out / edge_ptr_out are null");
+    const SpliceSide A{eia, Ea, Na, ptr_a, eptr_a, Ba, ga, bridge_a}, B{eib, Eb, Nb, ptr_b, eptr_b, Bb, gb, bridge_b};
+    int64_t* cnt = (int64_t*)ws;
+    int64_t nt = 0, et = 0, mn = 0, me = 0, empty = 0, unput = 0;
+    for (int64_t p = 0; p < P; ++p) {
+        int64_t alo, ahi, aelo, aehi, blo, bhi, belo, behi, ea = 0, eb = 0;
+        A.ranges(p, alo, ahi, aelo, aehi);
+        B.ranges(p, blo, bhi, belo, behi);
+        for (int64_t e = aelo; e < aehi; ++e) ea += A.valid(e, alo, ahi);
+        for (int64_t e = belo; e < behi; ++e) eb += B.valid(e, blo, bhi);
+        bool asked;
+        const bool put = splice_bridge(A, B, p, alo, ahi, blo, bhi, asked);
+        const int64_t n = (ahi - alo) + (bhi - blo), m = ea + eb + (put ? 2 : 0);
+        cnt[p] = ea;
+        cnt[P + p] = eb;
+        ptr_out[p] = nt;
+        edge_ptr_out[p] = et;
+        nt += n;
+        et += m;
+        mn = std::max(mn, n);
+        me = std::max(me, m);
+        empty += n == 0;
+        unput += asked && !put;
+    }
+    ptr_out[P] = nt;
+    edge_ptr_out[P] = et;
+    totals[0] = nt; totals[1] = et; totals[2] = mn; totals[3] = me; totals[4] = empty; totals[5] = unput;
+    return 0;
+}
+
+HOST_EXPORT int cal_graph_splice_write(const int64_t* eia, int64_t Ea, int64_t Na, const int64_t* ptr_a, const int64_t* eptr_a,
+                                       int64_t Ba, const int64_t* eib, int64_t Eb, int64_t Nb, const int64_t* ptr_b,
+                                       const int64_t* eptr_b, int64_t Bb, const int64_t* ga, const int64_t* gb, int64_t P,
+                                       const int64_t* bridge_a, const int64_t* bridge_b, const float* xa, const float* xb, int64_t F,
+                                       const int64_t* ptr_out, const int64_t* edge_ptr_out, int64_t Nout, int64_t Eout,
+                                       int64_t* batch_out, float* x_out, int64_t* edge_index_out, int64_t* node_src,
+                                       int64_t* edge_src, void* ws, int64_t ws_bytes, void*) {
+    SPLICE_REQUIRE_INPUTS();
+    HOST_REQUIRE(Nout >= 0 && Eout >= 0 && F >= 0 && F < (1 << 22), "Nout, Eout must be >= 0 and 0 <= F < 2^22");
+    HOST_REQUIRE(P == 0 || (ptr_out && edge_ptr_out), "ptr_out / edge_ptr_out are null");
+    HOST_REQUIRE(Nout == 0 || (batch_out && node_src), "batch_out / node_src are null");
+    HOST_REQUIRE(Eout == 0 || (edge_index_out && edge_src), "edge_index_out / edge_src are null");
+    HOST_REQUIRE(!x_out || (F > 0 && (Na == 0 || xa) && (Nb == 0 || xb)), "x_out needs F > 0, xa and xb");
+    const SpliceSide A{eia, Ea, Na, ptr_a, eptr_a, Ba, ga, bridge_a}, B{eib, Eb, Nb, ptr_b, eptr_b, Bb, gb, bridge_b};
+    for (int64_t p = 0; p < P; ++p) {
+        int64_t alo, ahi, aelo, aehi, blo, bhi, belo, behi;
+        A.ranges(p, alo, ahi, aelo, aehi);
+        B.ranges(p, blo, bhi, belo, behi);
+        const int64_t n0 = ptr_out[p], an = ahi - alo;
+        int64_t i = n0, j = edge_ptr_out[p];
+        auto node = [&](const float* x, int64_t s, int64_t code) {
+            if (i >= Nout) return;
+            batch_out[i] = p;
+            node_src[i] = code;
+            if (x_out) memcpy(x_out + i * F, x + s * F, sizeof(float) * (size_t)F);
+            ++i;
+        };
+        auto col = [&](int64_t u, int64_t v, int64_t code) {
+            if (j >= Eout) return;
+            edge_index_out[j] = u;
+            edge_index_out[Eout + j] = v;
+            edge_src[j] = code;
+            ++j;
+        };
+        for (int64_t s = alo; s < ahi; ++s) node(xa, s, s);
+        for (int64_t s = blo; s < bhi; ++s) node(xb, s, -1 - s);
+        for (int64_t e = aelo; e < aehi; ++e)
+            if (A.valid(e, alo, ahi)) col(n0 + (eia[e] - alo), n0 + (eia[Ea + e] - alo), e);
+        for (int64_t e = belo; e < behi; ++e)
+            if (B.valid(e, blo, bhi)) col(n0 + an + (eib[e] - blo), n0 + an + (eib[Eb + e] - blo), -1 - e);
+        bool asked;
+        if (splice_bridge(A, B, p, alo, ahi, blo, bhi, asked)) {
+            const int64_t u = n0 + (bridge_a[p] - alo), v = n0 + an + (bridge_b[p] - blo);
+            col(u, v, CAL_SPLICE_BRIDGE);
+            col(v, u, CAL_SPLICE_BRIDGE);
+        }
+    }
+    return 0;
+}
+#undef SPLICE_REQUIRE_INPUTS
+
 // ---- all-pairs intervention readout (cal_amd/csrc/intervene.hip): the same folded form, dot products accumulated in fp64 ----
 HOST_EXPORT int64_t cal_intervene_ws(int64_t, int64_t, int64_t, int64_t) { return 0; }
 

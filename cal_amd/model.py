@@ -188,6 +188,12 @@ class _CausalBase(torch.nn.Module):
         from .intervene import intervene
         return intervene(self, data, **kw)
 
+    def structure_intervention(self, data, **kw):
+        """``cal_amd.splice.structure_intervention(self, data, **kw)``: the model on causal parts spliced with other graphs'
+        trivial parts."""
+        from .splice import structure_intervention
+        return structure_intervention(self, data, **kw)
+
     def explain(self, data, **kw):
         """``cal_amd.explain.explain(self, data, **kw)``: per-graph top-k causal subgraphs of ``data``."""
         from .explain import explain

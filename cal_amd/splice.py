@@ -1,0 +1,328 @@
+"""Structure-level interventions: splice the causal part of one graph with the trivial part of another and run the model on it.
+
+``intervene`` (intervene.py) evaluates CAL's backdoor adjustment on pooled rows: it pairs the pooled ``xo`` row of graph g with the
+pooled ``xc`` row of a partner, after the backbone has run.  Here the same experiment is done on graphs, the way SPMotif itself
+is built (a base plus a motif, ``spmotif.make_graph``): the causal nodes of graph g and the trivial nodes of graph j are joined
+into one graph, the whole model runs on it, and the prediction either follows the causal part or the trivial one.  A backbone
+that has already mixed trivial structure into ``xo`` passes ``intervene`` untouched; it does not pass this.
+
+* ``splice_batches(a, b, pairs_a, pairs_b, bridge=...)`` -> ``Batch``: per pair the disjoint union of one graph of ``a`` and one
+  graph of ``b`` (``cal_graph_splice_count`` / ``cal_graph_splice_write``: two launches and one read-back of the totals on the
+  GPU, libcalhost for CPU tensors), with the layout facts that keep the engine on its per-graph route.
+* ``structure_intervention(model, data, ratio=... | k=..., partners=...)`` (also ``model.structure_intervention``): the report.
+* ``eval_structure_intervention(model, loader, device, ratios=...)``: the same over a loader.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _lib
+from .explain import (_HEADS, _Layout, _k_code, _log_probs, _reduce_code, _scores, _untiled, extract_subgraph)
+from .plan import _p, _stream
+
+__all__ = ["splice_batches", "structure_intervention", "eval_structure_intervention", "BRIDGE"]
+
+#: ``edge_src`` of a bridge column (``CAL_SPLICE_BRIDGE``)
+BRIDGE = -(1 << 63)
+
+
+class _Source:
+    """What the operator reads of one batch: features, grouped edge columns, the two offset arrays."""
+
+    def __init__(self, data):
+        from .data import Batch
+        self.is_x = getattr(data, "x", None) is not None
+        self.x = data.x if self.is_x else getattr(data, "feat", None)
+        ei = data.edge_index
+        self.order = None
+        if isinstance(data, Batch) and data.ptr is not None and data.edge_ptr is not None:
+            self.B, self.ptr, self.edge_ptr = int(data.num_graphs), data.ptr, data.edge_ptr
+            self.no_self_loops = bool(data.no_self_loops)
+        else:
+            lay = _Layout(data)
+            self.B, self.ptr, self.edge_ptr, self.no_self_loops, self.order = lay.B, lay.ptr, lay.edge_ptr, lay.no_self_loops, lay.order
+            if self.order is not None:                     # columns not grouped by graph: stable graph order first
+                ei = ei[:, self.order]
+        self.dev = ei.device
+        self.ei = ei.to(torch.long).contiguous()
+        self.ptr = self.ptr.to(device=self.dev, dtype=torch.long).contiguous()
+        self.edge_ptr = self.edge_ptr.to(device=self.dev, dtype=torch.long).contiguous()
+        self.E = int(ei.size(1))
+        self.N = int(data.batch.numel()) if getattr(data, "batch", None) is not None else int(self.x.size(0))
+        self.y = getattr(data, "y", None)
+
+    def args(self):
+        return [_p(self.ei) if self.E else None, self.E, self.N, _p(self.ptr), _p(self.edge_ptr), self.B]
+
+
+def _pairs(t, n: int, dev, what: str):
+    if t is None:
+        return torch.arange(n, dtype=torch.long, device=dev)
+    t = torch.as_tensor(t)
+    if t.dim() != 1 or t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise TypeError("%s must be a 1-D integer tensor" % what)
+    return t.to(device=dev, dtype=torch.long).contiguous()
+
+
+def splice_batches(a, b, pairs_a=None, pairs_b=None, *, bridge=None):
+    """Per pair the disjoint union of one graph of ``a`` and one graph of ``b``, as a ``cal_amd.data.Batch`` the engine can run.
+
+    Result graph p is graph ``pairs_a[p]`` of ``a`` followed by graph ``pairs_b[p]`` of ``b`` (defaults: ``arange(Ba)`` /
+    ``arange(Bb)``); ``-1`` (or any id outside the batch) leaves that part out, a graph may appear in any number of pairs.  Nodes:
+    ``a``'s in their order, then ``b``'s; edge columns: ``a``'s, then ``b``'s, then the two columns of the bridge.  ``bridge``:
+    ``None``, ``"first"`` (an undirected edge between the first node of each part) or a pair of int64 [P] tensors of node ids of
+    ``a`` / ``b`` (``-1``: none); a bridge whose ids do not lie inside the two parts is not written and is counted in
+    ``bridges_unwritten``.  A source column that leaves its graph's node range is dropped.
+
+    The result carries ``x`` / ``feat`` as ``a`` does (row copies), ``edge_index``, ``batch``, ``ptr``, ``edge_ptr``,
+    ``num_graphs = P``, ``max_nodes``, ``max_edges``, ``no_self_loops`` (``a``'s and ``b``'s), no tiles, ``y = a.y[pairs_a]``
+    (``None`` when ``a`` has none or a pair has no ``a`` part), ``node_src`` / ``edge_src`` (int64: the source element, ``b``'s
+    encoded as ``-1 - id``, ``BRIDGE`` for a bridge column) and the host ints ``empty_graphs`` / ``bridges_unwritten``.
+
+    CUDA tensors: ``cal_graph_splice_count`` and ``cal_graph_splice_write`` on the current stream with one read-back of the
+    totals between them; CPU tensors: libcalhost.  Inputs other than ``Batch`` objects get their layout derived as in
+    ``extract_subgraph``; edge columns that are not grouped by graph are put in stable graph order first."""
+    from .data import Batch
+    A, Bs = _Source(a), _Source(b)
+    dev, host = A.dev, not A.ei.is_cuda
+    if Bs.dev != dev:
+        raise ValueError("a and b must be on one device")
+    if (A.x is None) != (Bs.x is None):
+        raise ValueError("a and b must both carry features or neither")
+    F = 0
+    if A.x is not None:
+        if A.x.dtype != torch.float32 or Bs.x.dtype != torch.float32:
+            raise TypeError("splice copies float32 features")
+        if A.x.dim() != 2 or Bs.x.dim() != 2 or A.x.size(1) != Bs.x.size(1):
+            raise ValueError("a and b must have the same number of feature columns")
+        F = int(A.x.size(1))
+    ga, gb = _pairs(pairs_a, A.B, dev, "pairs_a"), _pairs(pairs_b, Bs.B, dev, "pairs_b")
+    P = int(ga.numel())
+    if int(gb.numel()) != P:
+        raise ValueError("pairs_a and pairs_b must have one entry per result graph each (got %d and %d)" % (P, gb.numel()))
+    a_ok = (ga >= 0) & (ga < A.B)
+    ba = bb = None
+    if isinstance(bridge, str):
+        if bridge != "first":
+            raise ValueError('bridge must be None, "first" or a pair of id tensors')
+        b_ok = (gb >= 0) & (gb < Bs.B)
+        minus = torch.full((P,), -1, dtype=torch.long, device=dev)
+        ba = torch.where(a_ok, A.ptr[ga.clamp(0, max(A.B - 1, 0))], minus) if A.B else minus
+        bb = torch.where(b_ok, Bs.ptr[gb.clamp(0, max(Bs.B - 1, 0))], minus) if Bs.B else minus
+    elif bridge is not None:
+        if not (isinstance(bridge, (tuple, list)) and len(bridge) == 2):
+            raise ValueError('bridge must be None, "first" or a pair of id tensors')
+        ba, bb = _pairs(bridge[0], P, dev, "bridge[0]"), _pairs(bridge[1], P, dev, "bridge[1]")
+        if int(ba.numel()) != P or int(bb.numel()) != P:
+            raise ValueError("the bridge tensors must have one entry per result graph")
+    wsb = _lib.query("cal_graph_splice_ws", A.E, Bs.E, P, host=host)
+    sizes = (P + 1, P + 1, 6, (wsb + 7) // 8)
+    ptr_o, eptr_o, totals, ws = torch.split(torch.empty(sum(sizes), dtype=torch.long, device=dev), sizes)
+    st = None if host else _stream()
+    inputs = A.args() + Bs.args() + [_p(ga) if P else None, _p(gb) if P else None, P, _p(ba), _p(bb)]
+    _lib.call("cal_graph_splice_count", *inputs, _p(ptr_o), _p(eptr_o), _p(totals), _p(ws), 8 * sizes[-1], st, host=host)
+    # the one read-back: the Batch needs the totals as host ints (and y whether every pair has a part of a)
+    n2, e2, mn, me, empty, unput, bad = torch.cat([totals, (~a_ok).sum().view(1)]).tolist()
+    ints = torch.empty(2 * n2 + 3 * e2, dtype=torch.long, device=dev)
+    batch_o, nsrc, ei_o, esrc = torch.split(ints, (n2, n2, 2 * e2, e2))
+    x_o = torch.empty(n2, F, dtype=torch.float32, device=dev) if F else None
+    xa, xb = (A.x.contiguous(), Bs.x.contiguous()) if F else (None, None)
+    _lib.call("cal_graph_splice_write", *inputs, _p(xa) if F and A.N else None, _p(xb) if F and Bs.N else None, F, _p(ptr_o),
+              _p(eptr_o), n2, e2, _p(batch_o) if n2 else None, _p(x_o) if F and n2 else None, _p(ei_o) if e2 else None,
+              _p(nsrc) if n2 else None, _p(esrc) if e2 else None, _p(ws), 8 * sizes[-1], st, host=host)
+    for s, neg in ((A, False), (Bs, True)):                # columns that were reordered: back to the caller's numbering
+        if s.order is not None and e2:
+            m = (esrc < 0) & (esrc != BRIDGE) if neg else esrc >= 0
+            idx = (-1 - esrc if neg else esrc).clamp(0, max(s.E - 1, 0))
+            esrc = torch.where(m, -1 - s.order[idx] if neg else s.order[idx], esrc)
+    out = Batch()
+    out.x, out.feat = (x_o, None) if A.is_x or A.x is None else (None, x_o)
+    out.edge_index, out.batch = ei_o.view(2, e2), batch_o
+    out.y = A.y.view(-1)[ga] if A.y is not None and not bad else None
+    out.ptr, out.edge_ptr, out.num_graphs = ptr_o, eptr_o, P
+    out.max_nodes, out.max_edges = int(mn), int(me)
+    out.no_self_loops = A.no_self_loops and Bs.no_self_loops
+    out.node_src, out.edge_src = nsrc, esrc
+    out.empty_graphs, out.bridges_unwritten = int(empty), int(unput)
+    return out
+
+
+# ---- the report ---------------------------------------------------------------------------------------------------------------
+_PER_HEAD = ("acc_full", "acc_self", "acc_swap", "follow", "agree", "p_shift")
+_ROW = 6 * len(_HEADS) + 5          # per head the six sums, then: pairs with y_j != y_g, pairs, graphs, kept, total elements
+
+
+def _check_use(use):
+    if use not in ("nodes", "edges"):
+        raise ValueError('use must be "nodes" or "edges"')
+
+
+def _partner_rows(partners, B: int, dev, generator):
+    """The partner permutations of one batch, int64 [m, B] on ``dev``."""
+    if torch.is_tensor(partners):
+        if partners.dim() != 2 or partners.size(1) != B or partners.dtype != torch.long:
+            raise ValueError("partners as a tensor must be int64 [m, B] with B = %d graphs" % B)
+        return partners.to(dev)
+    if isinstance(partners, str):
+        if partners != "all":
+            raise ValueError('partners must be an int >= 0, "all" or an int64 [m, B] tensor')
+        g = torch.arange(B, device=dev)
+        return (g.view(1, B) + torch.arange(1, B, device=dev).view(-1, 1)) % max(B, 1)      # the B - 1 cyclic shifts
+    m = int(partners)
+    if m < 0:
+        raise ValueError("partners must be >= 0")
+    state = None if generator is not None else torch.get_rng_state()
+    try:
+        gdev = generator.device if generator is not None else "cpu"
+        rows = [torch.randperm(B, generator=generator, device=gdev) for _ in range(m)]
+    finally:
+        if state is not None:
+            torch.set_rng_state(state)
+    return torch.stack(rows).to(dev) if rows else torch.zeros(0, B, dtype=torch.long, device=dev)
+
+
+def _partition(data, lay, edge, node, ratio, k, use, undirected):
+    """-> (causal node mask bool [N], kept elements (0-dim tensor), total elements) of the ranking ``use`` names."""
+    if use == "nodes":
+        nm = lay.rank_nodes(node, ratio=ratio, k=k)[0]
+        return nm, nm.sum(), nm.numel()
+    if undirected is None:
+        em = lay.rank_edges(edge, ratio=ratio, k=k)[0]
+    else:
+        em = lay.rank_edge_pairs(edge, data.edge_index, undirected, ratio=ratio, k=k)[0]
+    touched = extract_subgraph(data, edge_mask=em, relabel=True).node_map          # the nodes incident to a selected edge
+    nm = torch.zeros(int(data.batch.numel()), dtype=torch.bool, device=em.device)
+    nm[touched] = True
+    return nm, em.sum(), em.numel()
+
+
+def _spliced_logp(model, causal, trivial, perm, bridge):
+    sp = splice_batches(causal, trivial, None, perm, bridge=bridge)
+    if sp.empty_graphs:
+        raise ValueError("%d spliced graphs have no node (the engine does not run zero-node graphs)" % sp.empty_graphs)
+    return _log_probs(model, sp), sp
+
+
+def _structure_forward(model, data, lay, scores, ratio, k, use, undirected, rows, bridge):
+    """The forwards of one batch at one selection: ``(full [3, B, C], identity splice [3, B, C], swaps [m, 3, B, C], causal node
+    mask, kept, total, the identity splice itself)``.  Called in eval mode under no_grad."""
+    nm, kept, total = _partition(data, lay, scores[0], scores[1], ratio, k, use, undirected)
+    causal = extract_subgraph(data, node_mask=nm, relabel=True)
+    trivial = extract_subgraph(data, node_mask=nm, complement=True, relabel=True)
+    full = _log_probs(model, _untiled(data, lay))
+    ident, sp = _spliced_logp(model, causal, trivial, None, bridge)
+    swaps = [_spliced_logp(model, causal, trivial, perm, bridge)[0] for perm in rows]
+    swaps = torch.stack(swaps) if swaps else full.new_zeros((0,) + tuple(full.shape))
+    return full, ident, swaps, nm, kept, total, sp
+
+
+def _structure_sums(model, data, specs, use, undirected, partners, generator, bridge) -> torch.Tensor:
+    """One batch's sums [len(specs), _ROW] fp64 on the device, ``specs`` a list of (ratio, k).  One forward for the scores; per
+    spec one on the whole graph, one on the identity splice and one per partner permutation."""
+    edge, node = _scores(model, data)
+    scores = (edge.clone(), node.clone())
+    lay = _Layout(data)
+    B = lay.B
+    y = data.y.view(-1)
+    dev = y.device
+    rows = _partner_rows(partners, B, dev, generator)
+    pair = rows != torch.arange(B, device=dev).view(1, B)                 # [m, B]: j != g
+    yj = y[rows]
+    differ = pair & (yj != y)
+    out = []
+    for ratio, k in specs:
+        full, ident, swaps, _, kept, total, _ = _structure_forward(model, data, lay, scores, ratio, k, use, undirected, rows, bridge)
+        yhat = full.argmax(-1)                                           # [3, B]
+        pf = full.gather(-1, yhat.unsqueeze(-1)).squeeze(-1).exp()
+        pred = swaps.argmax(-1).transpose(0, 1)                          # [3, m, B]
+        idx = yhat.view(3, 1, B, 1).expand(3, rows.size(0), B, 1)
+        ps = swaps.transpose(0, 1).gather(-1, idx).squeeze(-1).exp()     # [3, m, B]: p_swap of the whole graph's argmax
+        tab = torch.stack([(yhat == y).sum(-1).double(), (ident.argmax(-1) == y).sum(-1).double(),
+                           ((pred == y) & pair).sum((1, 2)).double(), ((pred == yj) & differ).sum((1, 2)).double(),
+                           ((pred == yhat.unsqueeze(1)) & pair).sum((1, 2)).double(),
+                           ((pf.unsqueeze(1) - ps).double() * pair).sum((1, 2))])                 # [6, 3]
+        tail = torch.stack([differ.sum().double(), pair.sum().double(), torch.as_tensor(float(B), dtype=torch.float64, device=dev),
+                            kept.double(), torch.as_tensor(float(total), dtype=torch.float64, device=dev)])
+        out.append(torch.cat([tab.t().reshape(-1), tail]))
+    return torch.stack(out)
+
+
+def _structure_report(row) -> dict:
+    nan = float("nan")
+    differ, pairs, n, kept, total = row[-5:]
+    den = (n, n, pairs, differ, pairs, pairs)
+    res = {}
+    for h, head in enumerate(_HEADS):
+        for j, key in enumerate(_PER_HEAD):
+            res["%s_%s" % (key, head)] = row[6 * h + j] / den[j] if den[j] else nan
+    res["sparsity"] = 1.0 - kept / total if total else nan
+    res["graphs"], res["pairs"] = int(n), int(pairs)
+    return res
+
+
+def _check_args(ratio, k, use, undirected, partners, bridge):
+    _k_code(ratio, k)
+    if k == "gt":
+        raise ValueError('structure_intervention has no ground truth: k must be an int >= 0')
+    _check_use(use)
+    _reduce_code(undirected)
+    if not (torch.is_tensor(partners) or partners == "all" or (isinstance(partners, int) and partners >= 0)):
+        raise ValueError('partners must be an int >= 0, "all" or an int64 [m, B] tensor')
+    if not (bridge is None or bridge == "first" or (isinstance(bridge, (tuple, list)) and len(bridge) == 2)):
+        raise ValueError('bridge must be None, "first" or a pair of id tensors')
+
+
+def structure_intervention(model, data, *, ratio=None, k=None, use: str = "nodes", undirected=None, partners=1, generator=None,
+                           bridge=None) -> dict:
+    """Does ``model``'s prediction follow the causal part of a graph when its trivial part is exchanged for another graph's?
+
+    One eval forward gives the causal scores; the top ``ratio`` / ``k`` (as ``explain`` selects them) becomes a node partition:
+    ``use="nodes"`` the node mask, ``use="edges"`` the nodes incident to a selected edge (``undirected`` as in ``explain``).  The
+    causal part is ``extract_subgraph(node_mask=causal, relabel=True)``, the trivial part its complement; for every partner
+    permutation the causal part of graph g is spliced with the trivial part of graph ``perm[g]`` (``splice_batches``; ``bridge``
+    joins the two parts by one undirected edge) and the model runs on the result.  The identity pairing always runs as well: the
+    original graph with its cross edges cut and its nodes reordered, the control.  ``partners``: an int m (m permutations from
+    ``torch.randperm(B, generator=generator)``), ``"all"`` (the B - 1 cyclic shifts, one forward of B graphs each) or an int64
+    [m, B] tensor of permutations.  Per readout head h in ``c``, ``o``, ``co``, with ŷ the head's argmax on the whole graph and
+    pairs the (g, j = perm[g]) with j != g:
+
+    * ``acc_full_h``, ``acc_self_h``: accuracy against ``data.y`` on the whole graph / the identity splice;
+    * ``acc_swap_h``: the share of pairs predicting ``y_g`` (the label of the causal part);
+    * ``follow_h``: among the pairs with ``y_j != y_g``, the share predicting ``y_j``, the trivial part's label (NaN without one);
+    * ``agree_h``: the share of pairs predicting ŷ_g;
+    * ``p_shift_h``: the mean over the pairs of ``p_full(ŷ_g) - p_swap(ŷ_g)``;
+
+    and ``graphs``, ``pairs``, ``sparsity`` (1 - kept / total over the ranked elements).  A spliced graph without a node raises
+    ``ValueError``.  The sums stay on the device: the read-backs are the splices' totals and one at the end.  Like ``explain``,
+    it leaves parameters, optimizer state, the engine's step counter, BatchNorm statistics, ``model.training`` and the RNG
+    states as they were (a given ``generator`` advances; without one the global torch state is restored)."""
+    _check_args(ratio, k, use, undirected, partners, bridge)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            sums = _structure_sums(model, data, [(ratio, k)], use, undirected, partners, generator, bridge)
+    finally:
+        model.train(was_training)
+    return _structure_report(sums[0].tolist())
+
+
+def eval_structure_intervention(model, loader, device, *, ratios=(0.3,), use: str = "nodes", undirected=None, partners=1,
+                                generator=None, bridge=None) -> dict:
+    """``structure_intervention`` over a loader at every ratio of ``ratios``: ``{ratio: report}``, the means taken over all graphs
+    and all pairs of the loader.  Per mini-batch one forward for the scores and one draw of the partner permutations, shared by
+    the ratios; the sums stay on the device until one read-back at the end (besides the splices' totals)."""
+    ratios = [float(r) for r in ratios]
+    for r in ratios:
+        _check_args(r, None, use, undirected, partners, bridge)
+    specs = [(r, None) for r in ratios]
+    was_training = model.training
+    model.eval()
+    sums = torch.zeros(len(specs), _ROW, dtype=torch.float64, device=device)
+    try:
+        with torch.no_grad():
+            for data in loader:
+                sums += _structure_sums(model, data.to(device), specs, use, undirected, partners, generator, bridge)
+    finally:
+        model.train(was_training)
+    return {r: _structure_report(row) for r, row in zip(ratios, sums.tolist())}

@@ -373,6 +373,42 @@ CAL_API int cal_intervene_pairs(const float* xo, int64_t B, const float* xc, int
                                 const float* fc2_b, const int64_t* ref, float* p_do, int32_t* hits, float* p_min,
                                 int32_t* j_min, float* logp_pairs, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- batch splice: per pair the disjoint union of one graph of batch A and one graph of batch B ----------------------------
+ * A batch is x [N, F] fp32 (or null, F = 0), edge_index [2, E] int64, ptr / edge_ptr [B+1] int64 as in cal_subgraph_extract; A and
+ * B share F.  Result graph p (of P) is graph ga[p] of A followed by graph gb[p] of B; an entry outside [0, Ba) / [0, Bb) counts
+ * as -1: that part is absent.  A source graph may appear in any number of pairs; Ba, Bb and P are independent.  Nodes of p: A's
+ * nodes of ga[p] in their order, then B's nodes of gb[p].  Columns of p: A's columns of ga[p] in their order, then B's, then --
+ * when bridge_a / bridge_b [P] (node ids of A / B, -1 for none; both null: no bridges) are both >= 0 and lie inside the node
+ * ranges of ga[p] / gb[p] -- the two columns (a', b') and (b', a').  A source column with an endpoint outside its graph's node
+ * range is dropped; endpoints are rewritten to the new numbering.  A pair with a bridge id >= 0 whose bridge is not written (an
+ * id outside its part, a part absent, the other id -1) is counted in totals[5].  Every integer output is uniquely determined.
+ *   cal_graph_splice_count: ONE launch.  ptr_out / edge_ptr_out [P+1] and totals [6] int64 on the device: N', E', max_nodes',
+ *     max_edges', result graphs with no node, bridges asked for and not written.  The per-pair counts stay in ws.
+ *   The caller reads totals back once and allocates the outputs exactly.
+ *   cal_graph_splice_write: ONE launch, with the same inputs, the same ws (untouched since the count) and Nout = totals[0],
+ *     Eout = totals[1].  batch_out [N'], x_out [N', F] (row copies; null with F = 0), edge_index_out (a contiguous [2, E']),
+ *     node_src [N'] (the source node id, B's encoded as -1 - id) and edge_src [E'] (the source column in the same encoding,
+ *     CAL_SPLICE_BRIDGE for a bridge column).  The rows are copied 16 bytes per lane when F % 4 == 0 and xa, xb, x_out are
+ *     16-byte aligned, else element by element (0 <= F < 2^22).
+ * ws: 8-byte aligned, cal_graph_splice_ws bytes.  Everything on `stream`, no synchronisation inside; no value that reaches an
+ * output is accumulated atomically (the count finds the workgroup that finishes last with a completion ticket, as cal_edge_twin
+ * does, and that workgroup scans the per-pair counts in order).  P = 0: nothing is launched (the count zeroes totals and the
+ * two offsets with memsets). */
+#define CAL_SPLICE_BRIDGE INT64_MIN
+CAL_API int64_t cal_graph_splice_ws(int64_t Ea, int64_t Eb, int64_t P);
+CAL_API int cal_graph_splice_count(const int64_t* eia, int64_t Ea, int64_t Na, const int64_t* ptr_a, const int64_t* eptr_a,
+                                   int64_t Ba, const int64_t* eib, int64_t Eb, int64_t Nb, const int64_t* ptr_b,
+                                   const int64_t* eptr_b, int64_t Bb, const int64_t* ga, const int64_t* gb, int64_t P,
+                                   const int64_t* bridge_a, const int64_t* bridge_b, int64_t* ptr_out, int64_t* edge_ptr_out,
+                                   int64_t* totals, void* ws, int64_t ws_bytes, void* stream);
+CAL_API int cal_graph_splice_write(const int64_t* eia, int64_t Ea, int64_t Na, const int64_t* ptr_a, const int64_t* eptr_a,
+                                   int64_t Ba, const int64_t* eib, int64_t Eb, int64_t Nb, const int64_t* ptr_b,
+                                   const int64_t* eptr_b, int64_t Bb, const int64_t* ga, const int64_t* gb, int64_t P,
+                                   const int64_t* bridge_a, const int64_t* bridge_b, const float* xa, const float* xb, int64_t F,
+                                   const int64_t* ptr_out, const int64_t* edge_ptr_out, int64_t Nout, int64_t Eout,
+                                   int64_t* batch_out, float* x_out, int64_t* edge_index_out, int64_t* node_src,
+                                   int64_t* edge_src, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
