@@ -220,8 +220,6 @@ struct Engine {
     size_t slab_floats;
     double* arena;
     double* parts; size_t parts_doubles;
-    // side stream for the weight-gradient GEMMs (off the critical path until the final commit)
-    hipStream_t side; hipEvent_t ev_fork[24], ev_join[24];
     int *rowptr_dst, *nbr_dst, *eid_dst, *rowptr_src, *nbr_src, *eid_src, *row32, *col32, *work, *status, *gptr, *iperm, *eptr;
     float* wslot;               // [2][E] attention edge weights (context, objects) in CSR-by-destination slot order
     float* coef_src;            // [E] unit-weight coefficients deg^-1/2 of the destination in CSR-by-SOURCE slot order (k_plan_graph, for the wide per-graph backward)
@@ -241,6 +239,7 @@ struct Engine {
 };
 
 static size_t al(size_t n) { return (n + 63) / 64 * 64; }   // 256 B granules (in floats/ints)
+static int env_on(const char* name) { const char* v = getenv(name); return !(v && v[0] == '0'); }   // CAL_AMD_* switches: on unless "0..."
 
 }  // namespace cal
 
@@ -277,12 +276,9 @@ CAL_EXPORT void* cal_engine_create(int64_t F, int64_t H, int64_t C, int64_t L) {
     memset(e, 0, sizeof(Engine));
     if (hipHostMalloc((void**)&e->host_status, 64, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) *e->host_status = 0;
     else { (void)hipGetLastError(); e->host_status = nullptr; }       // (no mirror: cal_engine_peek_status reports 0, check_status still works)
-    { const char* v = getenv("CAL_AMD_RO_STEP"); e->ro_step = !(v && v[0] == '0'); }
-    { const char* v = getenv("CAL_AMD_RO_ROWS"); e->ro_rows = !(v && v[0] == '0'); }
-    { const char* v = getenv("CAL_AMD_STRIPED"); e->striped = !(v && v[0] == '0'); }
-    { const char* v = getenv("CAL_AMD_GWIDE"); e->gwide = !(v && v[0] == '0'); }
-    { const char* v = getenv("CAL_AMD_FOLD_ZERO"); e->fold_zero = !(v && v[0] == '0'); }
-    { const char* v = getenv("CAL_AMD_ATT_FOLD"); e->att_fold = !(v && v[0] == '0'); }
+    e->ro_step = env_on("CAL_AMD_RO_STEP"); e->ro_rows = env_on("CAL_AMD_RO_ROWS"); e->striped = env_on("CAL_AMD_STRIPED");
+    e->gwide = env_on("CAL_AMD_GWIDE"); e->fold_zero = env_on("CAL_AMD_FOLD_ZERO"); e->att_fold = env_on("CAL_AMD_ATT_FOLD");
+    e->adam_fused = env_on("CAL_AMD_ADAM_FUSED");
     e->bn0_dirty_host = 1;
     {
         // k_ro_step's 3 * H / 16 workgroups (133 KB of LDS each: one per CU) meet at spin barriers: they must all be
@@ -293,25 +289,17 @@ CAL_EXPORT void* cal_engine_create(int64_t F, int64_t H, int64_t C, int64_t L) {
         e->num_cus = cus > 0 ? cus : 256;
         if (cus < 3 * ((int)H / RO_CW) * RBK_MAXRB + 8) e->ro_rows = 0;
     }
-    { const char* v = getenv("CAL_AMD_ADAM_FUSED"); e->adam_fused = !(v && v[0] == '0'); }
     e->F = (int)F; e->H = (int)H; e->C = (int)C; e->L = (int)L;
     e->loop_w = 1.f;
     e->grad_scale = 1.f;
     e->p2p_max_polls = 1 << 22;
     e->nbn = (int)L + 9;
-    if (hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) != hipSuccess) { set_error("cal_engine_create: side stream"); delete e; return nullptr; }
-    for (int i = 0; i < 24; ++i) {
-        hipEventCreateWithFlags(&e->ev_fork[i], hipEventDisableTiming);
-        hipEventCreateWithFlags(&e->ev_join[i], hipEventDisableTiming);
-    }
     return e;
 }
 
 CAL_EXPORT void cal_engine_destroy(void* h) {
     Engine* e = (Engine*)h;
     if (!e) return;
-    for (int i = 0; i < 24; ++i) { hipEventDestroy(e->ev_fork[i]); hipEventDestroy(e->ev_join[i]); }
-    hipStreamDestroy(e->side);
     if (e->p2p_host_status) hipHostFree(e->p2p_host_status);
     if (e->host_status) hipHostFree(e->host_status);
     delete e;
@@ -382,7 +370,6 @@ CAL_EXPORT int cal_engine_bind(void* h, float* P, float* G, float* M1, float* M2
     e->bn_plane = a - a_bn;
     a = a_bn + NSTRIPE * e->bn_plane;
     e->arena_n = a;
-    (void)C;
     return 0;
 }
 
@@ -557,7 +544,6 @@ struct Ctx {
     int64_t E;
     int training;
     int rpb_n, rpb_b;   // rows per block for node-level / graph-level row walkers
-    int nfork;          // weight-gradient GEMMs forked to the side stream so far
     const int64_t* y; const int64_t* perm; float wc, wo, wco; int want_grad;
     int draw_perm;      // the step draws its own intervention permutation (first kernel) into Engine::perm_dev
     int tick_in_finish; // the step ends with the Adam update: k_finish advances the step counter
@@ -568,12 +554,19 @@ struct Ctx {
 };
 
 // what the backward's phases share: the final commit's task list (k_finish), the bump allocator over Engine::slabs, and the
-// column sums kept as partial rows until that commit (no finalise launch)
-struct Deferred { double* p; int P; int stride; };
+// column sums kept as partial rows until that commit (no finalise launch).  Bwd::slabs / slabs_at / defer (below) are the
+// ledger of that workspace: the only code that writes fa.st[], fa.nst, slab_off or a Deferred's fields
+struct Deferred {
+    double* p; int P; int stride;
+    Acc acc() const { return Acc(nullptr, p, stride); }
+};
 struct Bwd {
     FinishArgs fa;
     size_t slab_off;
     Deferred d_convb[MAX_LAYERS], d_gin_b1[MAX_LAYERS], d_cb, d_ob, d_dwn, d_dwe, d_bn0;
+    float* slabs(Ctx& c, int S, int n, float* dst);
+    float* slabs_at(Ctx& c, size_t at, int S, int n, float* dst);
+    double* defer(Ctx& c, Deferred& d, int P, int cols);
 };
 
 BNRef bnref(const Ctx& c, int k, int rows, int update) {
@@ -695,50 +688,55 @@ int launch_espmm(hipStream_t st, const CSR& csr, const SpmmBranch2& bb, int nbra
 #define RC(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 int no_parts() { set_error("engine: partial-row workspace exhausted"); return 2; }
 int no_slabs() { set_error("engine: slab workspace exhausted"); return 2; }
-// `need` floats of the slab workspace whose S blocks of n k_finish sums into dst; null when exhausted
-float* slab_take(Ctx& c, Bwd& b, size_t need, float* dst, int n, int S) {
-    if (b.slab_off + need > c.e->slab_floats || b.fa.nst >= MAX_SLABS) return nullptr;
-    float* p = c.e->slabs + b.slab_off;
-    b.fa.st[b.fa.nst++] = SlabTask{p, dst, n, S};
-    b.slab_off += need;
+// S slabs of n floats that a kernel has already written `at` floats into the slab workspace (the row-blocked readout's, at its
+// front), summed into dst [n] by k_finish: recorded where they are, the allocator moves past them in 64-float granules; null
+// (no_slabs()'s error set) when they do not fit
+float* Bwd::slabs_at(Ctx& c, size_t at, int S, int n, float* dst) {
+    const size_t end = at + (size_t)S * n;
+    if (end > c.e->slab_floats || fa.nst >= MAX_SLABS) { no_slabs(); return nullptr; }
+    fa.st[fa.nst++] = SlabTask{c.e->slabs + at, dst, n, S};
+    slab_off = std::max(slab_off, al(end));
+    return c.e->slabs + at;
+}
+// the same, taken from the allocator (packed: no granule between two takes)
+float* Bwd::slabs(Ctx& c, int S, int n, float* dst) {
+    const size_t at = slab_off;
+    float* p = slabs_at(c, at, S, n, dst);
+    if (p) slab_off = at + (size_t)S * n;
     return p;
 }
-// deferred column sums: P partial rows of `cols`, summed by the final commit
-Acc defer(Ctx& c, Deferred& d, int P, int cols) {
+// deferred column sums: P partial rows of `cols` in d, summed by the final commit; null (error set) when the partial-row workspace
+// is exhausted or d has already been filled in this step
+double* Bwd::defer(Ctx& c, Deferred& d, int P, int cols) {
+    if (d.p) { set_error("engine: a deferred column sum was filled twice in one step"); return nullptr; }
     d.p = parts_alloc(c, (size_t)P * cols); d.P = P; d.stride = cols;
-    return d.p ? Acc(nullptr, d.p, cols) : Acc();
+    if (!d.p) no_parts();
+    return d.p;
 }
+// a null from the ledger: its error is set
+#define RCP(x) do { if (!(x)) return 2; } while (0)
+
+// Slabs of the row-blocked readout (k_ro_step<true>) at the front of the slab workspace, as float offsets from Engine::slabs: per
+// (head, row block) one [H,H] fc1 weight-gradient slab, then one [C,H] fc2 slab, head-major
+struct RoSlabs {
+    size_t nrb, hh, ch;
+    size_t w1(int hd) const { return hd * nrb * hh; }
+    size_t w2(int hd) const { return 3 * nrb * hh + hd * nrb * ch; }
+    size_t total() const { return 3 * nrb * (hh + ch); }
+};
+RoSlabs ro_slabs(int H, int C, int B) { return RoSlabs{(size_t)cdiv(B, RS_B), (size_t)H * H, (size_t)C * H}; }
+
 // split-K slabs of a weight-gradient GEMM (TN) when the reduction axis is long
 int grad_slabs(Ctx& c, Bwd& b, GemmArgs& a, int nbatch, float** dst) {
     gemm_set_split(a, splitk_for(a.M, a.N, a.K, nbatch));
-    for (int q = 0; q < nbatch; ++q) {
-        a.p[q].C = a.nsplit > 1 ? slab_take(c, b, (size_t)a.nsplit * a.M * a.N, dst[q], a.M * a.N, a.nsplit) : dst[q];
-        if (!a.p[q].C) return no_slabs();
-    }
+    for (int q = 0; q < nbatch; ++q) RCP(a.p[q].C = a.nsplit > 1 ? b.slabs(c, a.nsplit, a.M * a.N, dst[q]) : dst[q]);
     return 0;
 }
-// weight-gradient GEMM (TN) with split-K slabs when the reduction axis is long
+// weight-gradient GEMM (TN) with split-K slabs when the reduction axis is long, on the step's stream (a fork to a side stream
+// was a measured loss: DESIGN section 7, "Round-4 negatives")
 int grad_gemm(Ctx& c, Bwd& b, GemmArgs& a, int nbatch, float** dst) {
     RC(grad_slabs(c, b, a, nbatch, dst));
-    // fork: everything enqueued on the main stream so far (the producers of A and B) precedes it
-    hipStream_t s = c.st;
-    // Measured on MI355X / ROCm 7.2: forking the 9 dW GEMMs costs more than it hides (graph replay
-    // 514 -> 648 us per step, eager 523 -> 554 us: cross-stream edges serialise through heavier
-    // barrier packets), so the fork is compiled in but disabled.
-    constexpr bool kForkWeightGrads = false;
-    if (kForkWeightGrads && c.nfork < 24) {
-        hipEventRecord(c.e->ev_fork[c.nfork], c.st);
-        hipStreamWaitEvent(c.e->side, c.e->ev_fork[c.nfork], 0);
-        s = c.e->side;
-    }
-    int rc = launch_gemm(true, false, a, nbatch, s);
-    if (s != c.st) { hipEventRecord(c.e->ev_join[c.nfork], s); c.nfork++; }
-    return rc;
-}
-// the main stream waits for every forked GEMM (before the final commit, and on any early exit)
-void join_side(Ctx& c) {
-    for (int i = 0; i < c.nfork; ++i) hipStreamWaitEvent(c.st, c.e->ev_join[i], 0);
-    c.nfork = 0;
+    return launch_gemm(true, false, a, nbatch, c.st);
 }
 
 // dX (NT, `ax`) and dW (TN, `aw`, split-K slabs like grad_gemm) of one layer in a single launch when both
@@ -848,8 +846,7 @@ int gconv_bwd(Ctx& c, Bwd& b, GconvBwdBranch* gb, int nb, float** dst, double** 
     const int np2 = nsplit == 4 ? 2 : 1;                 // workgroups per (graph, slice) that leave BatchNorm-backward partial rows
     for (int k = 0; k < nb; ++k) {
         gb[k].batch = c.batch; gb[k].tile_gptr = e->ntiles > 0 ? e->tile_gptr : nullptr;
-        gb[k].slab = slab_take(c, b, (size_t)B * H * H, dst[k], H * H, B);
-        if (!gb[k].slab) return no_slabs();
+        RCP(gb[k].slab = b.slabs(c, B, H * H, dst[k]));
         RC(bn_bwd_sums(c, gb[k], B * nsl * np2, dsum[k], dprod[k], st));
     }
     const GconvBwdBranch2 b2{{gb[0], gb[nb - 1]}};
@@ -879,14 +876,10 @@ int gconv_bwd(Ctx& c, Bwd& b, GconvBwdBranch* gb, int nb, float** dst, double** 
     }
     // lean: the 80 KB instantiation, two workgroups per CU -- the two-branch launch at 128 graphs is twice the CUs, packed batches
     // and batches of > 128 graphs more (its two-branch gn goes out in slot order: only when k_att_bwd_graph consumes it)
-    if (co && lean && e->ntiles > 0) PROF_LAUNCH((k_gconv_bwd<true, 2, true, true>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, e->status);
-    else if (co && lean) PROF_LAUNCH((k_gconv_bwd<true, 2, false, true>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, e->status);
-    else if (co && e->ntiles > 0) PROF_LAUNCH((k_gconv_bwd<true, 2, true>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, e->status);
-    else if (co) PROF_LAUNCH((k_gconv_bwd<true, 2>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, e->status);
-    else if (gb[0].dout && lean) PROF_LAUNCH((k_gconv_bwd<false, 0, false, true>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, e->status);
-    else if (gb[0].dout) PROF_LAUNCH((k_gconv_bwd<false, 0>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, e->status);
-    else if (lean) PROF_LAUNCH((k_gconv_bwd<false, 1, false, true>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, e->status);
-    else PROF_LAUNCH((k_gconv_bwd<false, 1>), grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, e->status);
+    const bool tiles = e->ntiles > 0;
+    auto kern = co ? (lean ? (tiles ? k_gconv_bwd<true, 2, true, true> : k_gconv_bwd<true, 2, false, true>) : tiles ? k_gconv_bwd<true, 2, true> : k_gconv_bwd<true, 2>)
+              : gb[0].dout ? (lean ? k_gconv_bwd<false, 0, false, true> : k_gconv_bwd<false, 0>) : lean ? k_gconv_bwd<false, 1, false, true> : k_gconv_bwd<false, 1>;
+    PROF_LAUNCH(kern, grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, e->status);
     CAL_CHECK_LAUNCH("k_gconv_bwd");
     return 0;
 }
@@ -1061,7 +1054,7 @@ Route make_route(const Ctx& c, bool want_grad) {
     const bool ro = !e->cat && (size_t)B4 * (H + 4) <= (size_t)RO_LDS && B * H <= 16384 && H % RO_CW == 0 && B4 <= 256 && H <= 256 &&
                     B * C <= 2048 && C <= 64;
     const bool ro_rows = e->ro_rows && e->ro_step && !e->cat && B > RS_B && B <= RBK_MAXRB * RS_B && H <= RS_K && H % RO_CW == 0 &&
-                         RS_B * C <= 2048 && C <= 64 && (size_t)3 * cdiv(B, RS_B) * ((size_t)H * H + (size_t)C * H) <= e->slab_floats;
+                         RS_B * C <= 2048 && C <= 64 && ro_slabs(H, C, B).total() <= e->slab_floats;
     const bool step = want_grad && c.training;
     r.ro = ro && step && B <= RS_B && H <= RS_K && e->ro_step ? Readout::OneLaunch : ro_rows && step ? Readout::Rows
          : ro ? Readout::FourKernel : Readout::Gemm;
@@ -1160,6 +1153,23 @@ int fwd_feat(Ctx& c, const float* x0) {
     }
     RC(flush_finals(c)); STAGE();
     return 0;
+}
+
+// GCNConv forward per graph, k_gconv_fwd / k_gw_fwd: one backbone layer (NB = 1) or the two causal convolutions with the add-pool
+// (NB = 2; tiles: packed batch) -- kind: Graph64 / Graph128 / Wide, cols: the wide kernels' slice width.  NB is a template
+// parameter so that each caller names its own kernels only, where it always has: their place in the code object stays (DESIGN
+// section 7, "What decided the form")
+template <int NB>
+void launch_gconv_fwd(Ctx& c, Conv kind, int cols, bool tiles, const GconvBranch2& b2) {
+    Engine* e = c.e;
+    const int H = e->H;
+    const bool wide = kind == Conv::Wide, g64 = kind == Conv::Graph64;
+    void (*kern)(CSR, const int*, const int*, GconvBranch2, int, float, int, int, int*);
+    if constexpr (NB == 1) kern = wide ? (cols == 32 ? k_gw_fwd<false, 32> : k_gw_fwd<false, 64>) : g64 ? k_gconv_fwd<false, 64, 512> : k_gconv_fwd<false, GC_T>;
+    else kern = tiles ? k_gconv_fwd<true, 64, 512, true> : g64 ? k_gconv_fwd<true, 64, 512> : !wide ? k_gconv_fwd<true, GC_T>
+              : cols == 32 ? k_gw_fwd<true, 32> : k_gw_fwd<true, 64>;
+    const int ncol = wide ? cols : GC_N, nt = wide ? GW_NT : tiles || g64 ? 512 : 256;      // (a packed batch runs the 64-node form)
+    PROF_LAUNCH(kern, dim3(c.T, H / ncol, NB), dim3(nt), 0, c.st, csr_dst(c), e->gptr, e->eptr, b2, 1, e->loop_w, H, H, e->status);
 }
 
 // 4. backbone: h_i = relu(A_hat (BN_i(h_{i-1}) @ W_i) + b_i)   (model.py:93-95)
@@ -1275,10 +1285,7 @@ int fwd_backbone(Ctx& c) {
             const GconvBranch2 b2{{gb, gb}};
             {
                 ProfScope ps(st, 2, 2.0 * N * H * H + 2.0 * (double)(E + N) * H, true);
-                if (r.bb_fwd == Conv::Wide && r.gw_cols_bb == 32) PROF_LAUNCH((k_gw_fwd<false, 32>), dim3(T, H / 32, 1), dim3(GW_NT), 0, st, gd, e->gptr, e->eptr, b2, 1, e->loop_w, H, H, e->status);
-                else if (r.bb_fwd == Conv::Wide) PROF_LAUNCH((k_gw_fwd<false, 64>), dim3(T, H / GC_N, 1), dim3(GW_NT), 0, st, gd, e->gptr, e->eptr, b2, 1, e->loop_w, H, H, e->status);
-                else if (r.bb_fwd == Conv::Graph64) PROF_LAUNCH((k_gconv_fwd<false, 64, 512>), dim3(T, H / GC_N, 1), dim3(512), 0, st, gd, e->gptr, e->eptr, b2, 1, e->loop_w, H, H, e->status);
-                else PROF_LAUNCH((k_gconv_fwd<false, GC_T>), dim3(T, H / GC_N, 1), dim3(256), 0, st, gd, e->gptr, e->eptr, b2, 1, e->loop_w, H, H, e->status);
+                launch_gconv_fwd<1>(c, r.bb_fwd, r.gw_cols_bb, false, b2);
             }
             CAL_CHECK_LAUNCH(r.bb_fwd == Conv::Wide ? "k_gw_fwd" : "k_gconv_fwd"); STAGE();
             RC(flush_finals(c)); STAGE();
@@ -1353,7 +1360,7 @@ int fwd_att(Ctx& c) {
 int fwd_co(Ctx& c) {
     Engine* e = c.e;
     const Route& r = c.r;
-    const int N = c.N, B = c.B, T = c.T, H = e->H, L = e->L;
+    const int N = c.N, B = c.B, H = e->H, L = e->L;
     const int64_t E = c.E;
     hipStream_t st = c.st;
     const size_t NH = (size_t)N * H;
@@ -1375,11 +1382,7 @@ int fwd_co(Ctx& c) {
             gb[k].batch = c.batch; gb[k].tile_gptr = tgp;          // packed batch: the add-pool is per GRAPH inside the tile
         }
         const GconvBranch2 b2{{gb[0], gb[1]}};
-        if (tgp) hipLaunchKernelGGL((k_gconv_fwd<true, 64, 512, true>), dim3(T, H / GC_N, 2), dim3(512), 0, st, gd, e->gptr, e->eptr, b2, 1, e->loop_w, H, H, e->status);
-        else if (r.co_fwd == Conv::Graph64) hipLaunchKernelGGL((k_gconv_fwd<true, 64, 512>), dim3(T, H / GC_N, 2), dim3(512), 0, st, gd, e->gptr, e->eptr, b2, 1, e->loop_w, H, H, e->status);
-        else if (r.co_fwd == Conv::Graph128) hipLaunchKernelGGL((k_gconv_fwd<true, GC_T>), dim3(T, H / GC_N, 2), dim3(256), 0, st, gd, e->gptr, e->eptr, b2, 1, e->loop_w, H, H, e->status);
-        else if (r.gw_cols_co == 32) hipLaunchKernelGGL((k_gw_fwd<true, 32>), dim3(T, H / 32, 2), dim3(GW_NT), 0, st, gd, e->gptr, e->eptr, b2, 1, e->loop_w, H, H, e->status);
-        else hipLaunchKernelGGL((k_gw_fwd<true, 64>), dim3(T, H / GC_N, 2), dim3(GW_NT), 0, st, gd, e->gptr, e->eptr, b2, 1, e->loop_w, H, H, e->status);
+        launch_gconv_fwd<2>(c, r.co_fwd, r.gw_cols_co, tgp != nullptr, b2);
         CAL_CHECK_LAUNCH(wide ? "k_gw_fwd(co)" : "k_gconv_fwd(co)"); STAGE();
         return 0;
     }
@@ -1417,7 +1420,8 @@ int fwd_readout(Ctx& c) {
             sa.nrb = nrb;
             sa.xch = parts_alloc(c, (size_t)3 * nch * RBK_XCH);
             if (!sa.xch) return no_parts();
-            sa.gw1_slab = e->slabs; sa.gw2_slab = e->slabs + (size_t)3 * nrb * H * H;
+            const RoSlabs rs = ro_slabs(H, C, B);
+            sa.gw1_slab = e->slabs + rs.w1(0); sa.gw2_slab = e->slabs + rs.w2(0);
             hipLaunchKernelGGL(k_ro_step<true>, dim3(3, nch, nrb), dim3(256), 0, st, sa);
         }
         CAL_CHECK_LAUNCH("k_ro_step"); STAGE();
@@ -1496,13 +1500,11 @@ int bwd_readout(Ctx& c, Bwd& b) {
     hipStream_t st = c.st;
     FinishArgs& fa = b.fa;
     if (c.r.ro == Readout::Rows) {                     // the row-blocked readout left one weight-gradient slab per row block
-        const int nrb = cdiv(B, RS_B);
+        const RoSlabs rs = ro_slabs(H, C, B);
         for (int hd = 0; hd < 3; ++hd) {
-            fa.st[fa.nst++] = SlabTask{e->slabs + (size_t)hd * nrb * H * H, e->G + e->o_fc1_w[hd], H * H, nrb};
-            fa.st[fa.nst++] = SlabTask{e->slabs + (size_t)3 * nrb * H * H + (size_t)hd * nrb * C * H, e->G + e->o_fc2_w[hd], C * H, nrb};
+            RCP(b.slabs_at(c, rs.w1(hd), (int)rs.nrb, H * H, e->G + e->o_fc1_w[hd]));
+            RCP(b.slabs_at(c, rs.w2(hd), (int)rs.nrb, C * H, e->G + e->o_fc2_w[hd]));
         }
-        b.slab_off = (size_t)3 * nrb * ((size_t)H * H + (size_t)C * H);
-        b.slab_off = (b.slab_off + 63) & ~(size_t)63;
     }
     if (c.r.ro != Readout::Gemm) {
         if (c.r.ro == Readout::FourKernel) {
@@ -1634,9 +1636,7 @@ int bwd_co(Ctx& c, Bwd& b) {
             else gb[k].gp0 = e->dpool + (size_t)k * B * H;
             gb[k].gn = e->gn + (size_t)k * E; gb[k].gself = e->gself + (size_t)k * N;
             gb[k].gn_stride = 2 * (size_t)E; gb[k].gself_stride = 2 * (size_t)N;
-            Deferred& db = k ? b.d_ob : b.d_cb;
-            if (!defer(c, db, T, H).on()) return no_parts();
-            gb[k].bias_parts = db.p;
+            RCP(gb[k].bias_parts = b.defer(c, k ? b.d_ob : b.d_cb, T, H));
             gb[k].ew = e->att + (size_t)k * E; gb[k].dis = e->dis_co + (size_t)k * N;
             gb[k].rs = e->anode + k; gb[k].rs_stride = 2; gb[k].bn = bnref(c, L + 1 + k, N, 0);
             gb[k].dxp0 = e->dXhco + (size_t)k * NH; gb[k].dxp1 = e->dzco + (size_t)k * NH;
@@ -1659,9 +1659,7 @@ int bwd_co(Ctx& c, Bwd& b) {
     // gradients are count x pooled-row gradient per graph (k_pool2 counted the positive rows).  Rounds 1-3 wrote and re-read the
     // two [N, H] matrices (656 MB and 155 us per step at config 5).
     if (r.co_fwd != Conv::Node) { RC(launch_pool_cnt(c)); STAGE(); }          // the forward pooled inside k_gconv_fwd: no counts yet
-    b.d_cb.p = parts_alloc(c, (size_t)B * H); b.d_cb.P = B; b.d_cb.stride = H;
-    b.d_ob.p = parts_alloc(c, (size_t)B * H); b.d_ob.P = B; b.d_ob.stride = H;
-    if (!b.d_cb.p || !b.d_ob.p) return no_parts();
+    RCP(b.defer(c, b.d_cb, B, H)); RCP(b.defer(c, b.d_ob, B, H));
     // (fused readout: d pooled is still two addends per row -- combined here into dpool, which that path leaves unused)
     hipLaunchKernelGGL(k_pool_bias_grad, dim3(B, 2), dim3(256), 0, st, e->pcnt, ro ? e->dxh : e->dpool, ro ? e->dxh + 2 * (size_t)B * H : nullptr,
                        e->iperm, e->dpool, b.d_cb.p, b.d_ob.p, B, H);
@@ -1756,9 +1754,9 @@ int bwd_att(Ctx& c, Bwd& b) {
     // one partial row per workgroup: r.ag_split per graph (k_att_bwd_graph / k_att_bwd_wide), or one per row block (k_att_bwd)
     // (folded into the last backbone layer's launch: one per unit, the column slices write disjoint columns)
     const int P = r.att_bwd == Att::Node ? cdiv(N, c.rpb_n) : r.att_fold ? T : r.ag_split * T;
-    aa.dbias = L > 0 ? defer(c, b.d_convb[L - 1], P, H) : Acc();
-    aa.dWn = defer(c, b.d_dwn, P, H + 4); aa.dWe = defer(c, b.d_dwe, P, 2 * H + 4);
-    if (!aa.dWn.on() || !aa.dWe.on()) return no_parts();
+    if (L > 0) { RCP(b.defer(c, b.d_convb[L - 1], P, H)); aa.dbias = b.d_convb[L - 1].acc(); }
+    RCP(b.defer(c, b.d_dwn, P, H + 4)); RCP(b.defer(c, b.d_dwe, P, 2 * H + 4));
+    aa.dWn = b.d_dwn.acc(); aa.dWe = b.d_dwe.acc();
     if (r.att_bwd == Att::Wide) {       // per graph of up to 256 nodes: with a sparse edge phase (engine_attwide.hpp); inputs in edge-id order
         AttBwdWideArgs ag;
         ag.a = aa; ag.gptr = e->gptr; ag.eptr = e->eptr; ag.row32 = e->row32; ag.col32 = e->col32; ag.att = e->att; ag.dis = e->dis_co;
@@ -1818,11 +1816,8 @@ int bwd_feat_units(Ctx& c, Bwd& b, const float* x0, const float* p0, const float
     // of FB_T rows: the layer is row-wise, the chunks need not be graphs (k_feat_bwd with a null unit table)
     const bool chunks = c.r.feat_chunks;
     const int U = chunks ? cdiv(N, FB_T) : c.T;
-    fb.slab = slab_take(c, b, (size_t)U * F * H, e->G + e->o_feat_w, F * H, U);
-    if (!fb.slab) return no_slabs();
-    b.d_bn0.p = parts_alloc(c, (size_t)U * 2 * F); b.d_bn0.P = U; b.d_bn0.stride = 2 * F;
-    if (!b.d_bn0.p) return no_parts();
-    fb.parts = b.d_bn0.p;
+    RCP(fb.slab = b.slabs(c, U, F * H, e->G + e->o_feat_w));
+    RCP(fb.parts = b.defer(c, b.d_bn0, U, 2 * F));
     const dim3 grid(U), blk(GB_NT);
     if (F <= FB_F && !nobn) {
         // few features (SPMotif: F = 10): the FMA-loop kernel is 1.7 us shorter than one MFMA tile behind three barriers
@@ -1850,7 +1845,7 @@ int bwd_backbone(Ctx& c, Bwd& b, const float* x0) {
     const int PN = cdiv(N, c.rpb_n);
     const bool units = r.feat_bwd == FeatBwd::Units, two = H > GC_N;
     for (int i = L; i >= 1; --i) {
-        float* dzi = e->dzi + (size_t)(i - 1) * NH;     // per layer: the side-stream dW GEMM reads it later
+        float* dzi = e->dzi + (size_t)(i - 1) * NH;     // per layer: dz_i of the node-level chain, slice-1 partial dX' of the per-graph kernels
         const float* hin = e->h + (size_t)(i - 1) * NH;
         const bool st_i = bb_striped(r, i);
         if (e->gin && r.bb_bwd == Conv::Graph64) {
@@ -1862,19 +1857,17 @@ int bwd_backbone(Ctx& c, Bwd& b, const float* x0) {
             float* c0 = e->dXh; float* c1 = e->gy + (size_t)(i - 1) * NH;
             float* d0 = e->z; float* d1 = e->gagg + (size_t)(i - 1) * NH;
             const float* t1 = e->gt1 + (size_t)(i - 1) * NH;
-            if (b.slab_off + 2 * (size_t)T * H * H > e->slab_floats || b.fa.nst + 2 > MAX_SLABS) return no_slabs();
             GginBwdArgs ga;
             memset(&ga, 0, sizeof(ga));
             if (i == L) ga.dout = e->dZ;
             else {
                 ga.dy0 = e->z; ga.dy1 = two ? e->gagg + (size_t)i * NH : nullptr; ga.hmask = e->h + (size_t)i * NH;
                 // d b2 of this layer: column sums of the masked d h_i, one partial row per unit
-                if (!defer(c, b.d_convb[i - 1], T, H).on()) return no_parts();
-                ga.bias_parts = b.d_convb[i - 1].p;
+                RCP(ga.bias_parts = b.defer(c, b.d_convb[i - 1], T, H));
             }
             ga.x = t1; ga.W = e->P + e->o_gin_w2[i - 1]; ga.bn = bnref(c, i, N, 0);
             ga.dxp0 = c0; ga.dxp1 = c1;
-            ga.slab = slab_take(c, b, (size_t)T * H * H, e->G + e->o_gin_w2[i - 1], H * H, T);
+            RCP(ga.slab = b.slabs(c, T, H * H, e->G + e->o_gin_w2[i - 1]));
             RC(bn_bwd_sums(c, ga, T * nsl, bn_dsum(c, i), bn_dprod(c, i), st_i));
             hipLaunchKernelGGL((k_ggin_bwd<2>), dim3(T, nsl), dim3(GB_NT), 0, st, gd, e->gptr, e->eptr, ga, N, H, H, e->status);
             CAL_CHECK_LAUNCH("k_ggin_bwd<2>"); STAGE();
@@ -1882,11 +1875,10 @@ int bwd_backbone(Ctx& c, Bwd& b, const float* x0) {
             memset(&ga, 0, sizeof(ga));
             ga.dy0 = c0; ga.dy1 = two ? c1 : nullptr; ga.t1 = t1;
             ga.dot_sum = bn_dsum(c, i); ga.dot_prod = bn_dprod(c, i);
-            if (!defer(c, b.d_gin_b1[i - 1], T, H).on()) return no_parts();       // d b1: column sums of dt1
-            ga.bias_parts = b.d_gin_b1[i - 1].p;
+            RCP(ga.bias_parts = b.defer(c, b.d_gin_b1[i - 1], T, H));             // d b1: column sums of dt1
             ga.x = hin; ga.W = e->P + e->o_conv_w[i - 1]; ga.bn = bnref(c, i, N, 0);
             ga.dxp0 = d0; ga.dxp1 = d1;
-            ga.slab = slab_take(c, b, (size_t)T * H * H, e->G + e->o_conv_w[i - 1], H * H, T);
+            RCP(ga.slab = b.slabs(c, T, H * H, e->G + e->o_conv_w[i - 1]));
             {
                 ProfScope ps(st, 10, 4.0 * N * H * H + 2.0 * (double)(E + N) * H, true);
                 PROF_LAUNCH((k_ggin_bwd<1>), dim3(T, nsl), dim3(GB_NT), 0, st, gd, e->gptr, e->eptr, ga, N, H, H, e->status);
@@ -1935,8 +1927,8 @@ int bwd_backbone(Ctx& c, Bwd& b, const float* x0) {
                 memset(&ga, 0, sizeof(ga));
                 ga.a = e->dXh; ga.y = yy; ga.t1 = t1; ga.out = dzi; ga.bn = bnref(c, i, N, 0);       // dt1
                 ga.dot_sum = bn_dsum(c, i); ga.dot_prod = bn_dprod(c, i);
-                ga.acc0 = defer(c, b.d_gin_b1[i - 1], PN, H);
-                if (!ga.acc0.on()) return no_parts();
+                RCP(b.defer(c, b.d_gin_b1[i - 1], PN, H));
+                ga.acc0 = b.d_gin_b1[i - 1].acc();
                 RC(gin_rows(c, 2, ga));
                 CAL_CHECK_LAUNCH("k_gin_bn_bwd"); STAGE();
             }
@@ -1960,7 +1952,7 @@ int bwd_backbone(Ctx& c, Bwd& b, const float* x0) {
                 GinRowArgs ga;
                 memset(&ga, 0, sizeof(ga));
                 ga.a = e->z; ga.y = hin; ga.out = e->dZ;                                                // masked by h_{i-1} > 0
-                ga.acc0 = i >= 2 ? defer(c, b.d_convb[i - 2], PN, H) : Acc();                           // d b2 of the layer below
+                if (i >= 2) { RCP(b.defer(c, b.d_convb[i - 2], PN, H)); ga.acc0 = b.d_convb[i - 2].acc(); }   // d b2 of the layer below
                 RC(gin_rows(c, 3, ga));
                 CAL_CHECK_LAUNCH("k_gin_mask"); STAGE();
             }
@@ -1969,7 +1961,7 @@ int bwd_backbone(Ctx& c, Bwd& b, const float* x0) {
         // Per graph: slice-0 partials of dX' ping-pong between dXh and z (idle in the fused forward), slice-1 partials are per layer
         // (bb_gconv_bwd for the GCN layers).
         float* p0 = bb_dxp0(e, i);
-        if (r.bb_bwd != Conv::Node && i < L && !defer(c, b.d_convb[i - 1], T, H).on()) return no_parts();   // bias of conv i: one partial row per graph
+        if (r.bb_bwd != Conv::Node && i < L) RCP(b.defer(c, b.d_convb[i - 1], T, H));   // bias of conv i: one partial row per graph
         if (e->K > 0 && r.bb_bwd == Conv::Graph64) {
             // GATConv layer backward per graph (engine_ggat.hpp): attention backward + dX' (two slice partials) + dW / d att slabs
             const int K = e->K, D = H / K, nsl = H / GC_N;
@@ -1990,10 +1982,8 @@ int bwd_backbone(Ctx& c, Bwd& b, const float* x0) {
                 ga.ubn = bnref(c, i + 1, N, 0); ga.udot_sum = bn_dsum(c, i + 1); ga.udot_prod = bn_dprod(c, i + 1);
                 ga.bias_parts = b.d_convb[i - 1].p;
             }
-            const size_t need_w = (size_t)T * H * H, need_a = (size_t)T * 2 * H;
-            if (b.slab_off + need_w + need_a > e->slab_floats || b.fa.nst + 2 > MAX_SLABS) return no_slabs();
-            ga.slab = slab_take(c, b, need_w, e->G + e->o_conv_w[i - 1], H * H, T);
-            ga.att_slab = slab_take(c, b, need_a, e->G + e->o_conv_att[i - 1], 2 * H, T);
+            RCP(ga.slab = b.slabs(c, T, H * H, e->G + e->o_conv_w[i - 1]));
+            RCP(ga.att_slab = b.slabs(c, T, 2 * H, e->G + e->o_conv_att[i - 1]));
             RC(bn_bwd_sums(c, ga, T * nsl, bn_dsum(c, i), bn_dprod(c, i), st_i));
             {
                 ProfScope ps(st, 8, 4.0 * N * H * H + 4.0 * (double)(E + N) * H, true);
@@ -2036,16 +2026,12 @@ int bwd_backbone(Ctx& c, Bwd& b, const float* x0) {
             const float* sc = e->gsc + (size_t)(i - 1) * 4 * nk;
             ProfScope ps(st, 6, 4.0 * N * H * 4 + (double)(E + N) * (16 + 24.0 * K));
             // d att: per-block partial rows parked in the slab area, summed by the final k_finish (no finishing launch)
-            const size_t need = (size_t)gat_datt_parts(N) * 2 * H;
-            if (b.slab_off + need > e->slab_floats || b.fa.nst >= MAX_SLABS) return no_slabs();
-            float* part = e->slabs + b.slab_off;
-            int nparts = 0;
+            float* part = b.slabs(c, gat_datt_parts(N), 2 * H, e->G + e->o_conv_att[i - 1]);
+            RCP(part);
             RC(gat_backward(e->rowptr_dst, e->nbr_dst, e->eid_dst, e->rowptr_src, e->nbr_src, e->eid_src,
                             e->gz + (size_t)(i - 1) * NH, e->P + e->o_conv_att[i - 1], sc, sc + nk, sc + 2 * nk, sc + 3 * nk, e->dZ,
                             e->gat_slope, c.training ? e->gat_p : 0.f, e->gat_seed[i - 1], (const uint64_t*)e->gat_ctr, dzi,
-                            e->G + e->o_conv_att[i - 1], e->gws, N, E, K, D, st, part, &nparts));
-            b.fa.st[b.fa.nst++] = SlabTask{part, e->G + e->o_conv_att[i - 1], 2 * H, nparts};
-            b.slab_off += need;
+                            e->G + e->o_conv_att[i - 1], e->gws, N, E, K, D, st, part, nullptr));
         } else {
             SpmmBranch br{e->dZ, dzi, nullptr, nullptr, e->dis_unit, Acc(), Acc(), nullptr, nullptr, nullptr};
             ProfScope ps(st, 1, 2.0 * N * H * 4 + (double)(E + N) * 8 + (N + 1) * 4.0, true);
@@ -2070,10 +2056,10 @@ int bwd_backbone(Ctx& c, Bwd& b, const float* x0) {
             const int cols = (F + 1) * H;
             FeatBwdRowsArgs fb{e->dXh, hin, bnref(c, 1, N, 0), bn_dsum(c, 1), bn_dprod(c, 1), x0, bnref(c, 0, N, 0), parts_alloc(c, (size_t)PN * cols)};
             double* sums = parts_alloc(c, cols);
-            b.d_bn0.p = parts_alloc(c, 2 * (size_t)F); b.d_bn0.P = 1; b.d_bn0.stride = 2 * F;
-            if (!fb.parts || !sums || !b.d_bn0.p) return no_parts();
-            float* dw = slab_take(c, b, (size_t)F * H, e->G + e->o_feat_w, F * H, 1);
-            if (!dw) return no_slabs();
+            if (!fb.parts || !sums) return no_parts();
+            RCP(b.defer(c, b.d_bn0, 1, 2 * F));
+            float* dw = b.slabs(c, 1, F * H, e->G + e->o_feat_w);
+            RCP(dw);
             RC(with_g_fp(H, F, [&](auto g, auto fp) {
                 hipLaunchKernelGGL((k_bn_bwd_feat<decltype(g)::value, decltype(fp)::value>), dim3(PN), dim3(256), 0, st, fb, N, H, F, c.rpb_n);
                 return 0;
@@ -2084,7 +2070,8 @@ int bwd_backbone(Ctx& c, Bwd& b, const float* x0) {
             hipLaunchKernelGGL(k_feat_bwd_final, dim3(F), dim3(256), 0, st, sums, e->P + e->o_feat_w, bnref(c, 0, N, 0), dw, b.d_bn0.p, H, F);
             CAL_CHECK_LAUNCH("k_feat_bwd_final"); STAGE();
         } else {
-            RC(bn_bwd_dz(e->dXh, nullptr, i >= 2 ? defer(c, b.d_convb[i - 2], PN, H) : Acc(), r.st_node));
+            if (i >= 2) RCP(b.defer(c, b.d_convb[i - 2], PN, H));       // the bias sums of the layer below
+            RC(bn_bwd_dz(e->dXh, nullptr, i >= 2 ? b.d_convb[i - 2].acc() : Acc(), r.st_node));
         }
     }
     return 0;
@@ -2106,8 +2093,8 @@ int bwd_feat(Ctx& c, Bwd& b, const float* x0) {
     {   // bn_feat's sums are only needed by the commit: keep the partial rows, no finalise launch
         const int P0 = use_ks(N) ? gemm_ks_row_tiles(N) : gemm_row_tiles(N, F, H, false);
         if ((size_t)P0 * F * 2 > 4096) {
-            b.d_bn0.p = parts_alloc(c, (size_t)P0 * 2 * F); b.d_bn0.P = P0; b.d_bn0.stride = 2 * F;
-            a.p[0].parts = b.d_bn0.p;
+            // (no rows left is no error here: the epilogue then adds into the arena, which bwd_commit reads while d_bn0 is empty)
+            a.p[0].parts = b.defer(c, b.d_bn0, P0, 2 * F);
         }
     }
     RC(dual_gemm(c, b, a, 1, aw, 1, dst)); STAGE();
@@ -2123,7 +2110,11 @@ int bwd_commit(Ctx& c, Bwd& b) {
         if (fa.nct < MAX_COMMITS) fa.ct[fa.nct] = CommitTask{src, P, stride, dst, n, scale};
         fa.nct++;
     };
-    auto commit_d = [&](const Deferred& d, int col, int dst, int n, float scale) { commit_p(d.p + col, d.P, d.stride, dst, n, scale); };
+    // (a Deferred its route never filled is refused below, with the conv biases')
+    bool missing = false;
+    auto commit_d = [&](const Deferred& d, int col, int dst, int n, float scale) {
+        if (d.p) commit_p(d.p + col, d.P, d.stride, dst, n, scale); else missing = true;
+    };
     for (int k = 0; k < e->nbn; ++k) {
         const BNSlot& s = e->bn[k];
         const int wp = (s.width + 3) / 4 * 4;
@@ -2137,13 +2128,9 @@ int bwd_commit(Ctx& c, Bwd& b) {
         commit_p(e->arena + s.arena + 2 * wp, NSTRIPE, e->bn_plane, s.beta, s.width, 1.f);    // d beta  = sum dyh
     }
     for (int i = 0; i < L; ++i) {
-        if (!b.d_convb[i].p) { set_error("engine: missing bias-gradient partials"); return 2; }
         // GCNConv / GATConv: the layer's bias; GINConv: the bias of its second Linear (the first one's has its own sums)
         commit_d(b.d_convb[i], 0, e->gin ? e->o_gin_b2[i] : e->o_conv_b[i], H, 1.f);
-        if (e->gin) {
-            if (!b.d_gin_b1[i].p) { set_error("engine: missing bias-gradient partials"); return 2; }
-            commit_d(b.d_gin_b1[i], 0, e->o_conv_b[i], H, 1.f);
-        }
+        if (e->gin) commit_d(b.d_gin_b1[i], 0, e->o_conv_b[i], H, 1.f);
     }
     commit_d(b.d_cb, 0, e->o_cb, H, 1.f);
     commit_d(b.d_ob, 0, e->o_ob, H, 1.f);
@@ -2159,8 +2146,8 @@ int bwd_commit(Ctx& c, Bwd& b) {
         commit_p(e->arena + e->a_db1 + hd * H, 1, 0, e->o_fc1_b[hd], H, 1.f);
         commit_p(e->arena + e->a_db2 + hd * C, 1, 0, e->o_fc2_b[hd], C, 1.f);
     }
+    if (missing) { set_error("engine: missing bias-gradient partials"); return 2; }
     if (fa.nct > MAX_COMMITS) { set_error("engine: too many commit tasks"); return 2; }
-    join_side(c);
     if (c.adam_in_finish) {
         // Adam rides in this kernel: parameter ranges no task writes (gradients stored directly by the readout /
         // single-slab GEMMs) become update-only tasks
@@ -2230,6 +2217,14 @@ void ctx_init(Ctx& c, Engine* e, void* stream, int64_t N, int64_t E, int64_t B, 
     c.r = make_route(c, c.want_grad);
 }
 
+// Adam as one kernel over the flat parameter buffer; ticked: the step counter has already been advanced (by the step's k_finish)
+int launch_adam(Engine* e, hipStream_t st, int ticked) {
+    hipLaunchKernelGGL(k_adam, dim3(cdiv(e->nparam, 256)), dim3(256), 0, st, e->P, e->G, e->M1, e->M2, e->step, e->lr, e->beta1,
+                       e->beta2, e->eps, e->wd, e->nparam, ticked, e->grad_scale, e->status);
+    CAL_CHECK_LAUNCH("k_adam");
+    return 0;
+}
+
 }  // namespace
 
 // One training step (or, with mode bits cleared, parts of it) for a device-resident batch.
@@ -2270,16 +2265,11 @@ CAL_EXPORT int cal_engine_step(void* h, const float* x0, const int64_t* edge_ind
         if (rc) return rc;
         if (want_grad) {
             rc = engine_backward(c, x0);
-            if (rc) join_side(c);
             if (rc == -12345) return 0;
             if (rc) return rc;
         }
     }
-    if ((mode & 4) && c.adam_in_finish != 1) {          // k_finish has already advanced the step counter (c.tick_in_finish)
-        hipLaunchKernelGGL(k_adam, dim3(cdiv(e->nparam, 256)), dim3(256), 0, c.st, e->P, e->G, e->M1, e->M2, e->step, e->lr, e->beta1,
-                           e->beta2, e->eps, e->wd, e->nparam, 1, e->grad_scale, e->status);
-        CAL_CHECK_LAUNCH("k_adam");
-    }
+    if ((mode & 4) && c.adam_in_finish != 1) return launch_adam(e, c.st, 1);      // k_finish has already advanced the step counter (c.tick_in_finish)
     return 0;
 }
 
@@ -2300,7 +2290,6 @@ CAL_EXPORT int cal_engine_backward_from(void* h, const float* x0, const int64_t*
     CAL_CHECK_LAUNCH("k_logsoftmax_bwd");
     g_stage = 0;
     int rc = engine_backward(c, x0);
-    if (rc) join_side(c);
     return rc == -12345 ? 0 : rc;
 }
 
@@ -2467,9 +2456,7 @@ CAL_EXPORT int64_t cal_engine_profile_read(double* out, int64_t cap) {
 CAL_EXPORT int cal_engine_adam(void* h, void* stream_) {
     Engine* e = (Engine*)h;
     hipStream_t st = (hipStream_t)stream_;
-    hipLaunchKernelGGL(k_adam, dim3(cdiv(e->nparam, 256)), dim3(256), 0, st, e->P, e->G, e->M1, e->M2, e->step, e->lr, e->beta1,
-                       e->beta2, e->eps, e->wd, e->nparam, 0, e->grad_scale, e->status);
-    CAL_CHECK_LAUNCH("k_adam");
+    RC(launch_adam(e, st, 0));
     hipLaunchKernelGGL(k_adam_tick, dim3(1), dim3(1), 0, st, e->step);
     CAL_CHECK_LAUNCH("k_adam_tick");
     return 0;
@@ -2477,12 +2464,7 @@ CAL_EXPORT int cal_engine_adam(void* h, void* stream_) {
 // Adam after a gradient exchange when the step ran with mode bit 8 (its k_finish already advanced the step counter):
 // ONE launch -- [graph: forward + backward] -> all-reduce(sum) -> this, with the 1/world mean folded into grad_scale
 CAL_EXPORT int cal_engine_adam_ticked(void* h, void* stream_) {
-    Engine* e = (Engine*)h;
-    hipStream_t st = (hipStream_t)stream_;
-    hipLaunchKernelGGL(k_adam, dim3(cdiv(e->nparam, 256)), dim3(256), 0, st, e->P, e->G, e->M1, e->M2, e->step, e->lr, e->beta1,
-                       e->beta2, e->eps, e->wd, e->nparam, 1, e->grad_scale, e->status);
-    CAL_CHECK_LAUNCH("k_adam");
-    return 0;
+    return launch_adam((Engine*)h, (hipStream_t)stream_, 1);
 }
 // ---- one-shot gradient exchange over peer-mapped memory (k_p2p_adam, engine_kernels.hpp) ------------------------------
 // The regions must be FINE-GRAINED device memory: a kernel that polls a flag a peer GPU writes and then reads the peer's bucket

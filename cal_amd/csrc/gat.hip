@@ -241,101 +241,14 @@ __global__ void __launch_bounds__(256) k_gat_fwd_fused(const int* __restrict__ r
     }
 }
 
-// Backward pass 1+2 over the by-destination CSR.  Lanes of one head (LH = D/VEC of them, a power
-// of two) reduce their partial dots with shuffles.  draw[id*K + k] (id = edge id, or E + i for the
-// loop of node i) receives d(raw logit); dadst[i,k] the row sum.
-template <int VEC, int G>
-__global__ void __launch_bounds__(256) k_gat_bwd_dst(const int* __restrict__ rowptr, const int* __restrict__ nbr,
-                                                     const int* __restrict__ eid, const float* __restrict__ z,
-                                                     const float* __restrict__ adst, const float* __restrict__ asrc,
-                                                     const float* __restrict__ mx, const float* __restrict__ den,
-                                                     const float* __restrict__ gout, float slope, float p,
-                                                     uint64_t seed, int64_t E, float* __restrict__ draw,
-                                                     float* __restrict__ dadst, int N, int K, int D,
-                                                     const uint64_t* __restrict__ ctr) {
-    constexpr int RPB = 256 / G;
-    seed = step_seed(seed, ctr);
-    const int g = threadIdx.x / G, l = threadIdx.x % G;
-    const int i = xcd_block() * RPB + g;
-    if (i >= N) return;
-    const int H = K * D;
-    const int LH = D / VEC;
-    const int s0 = rowptr[i], s1 = rowptr[i + 1];
-    const float inv_keep = p > 0.f ? 1.f / (1.f - p) : 1.f;
-    using V = Vec<VEC>;
-    for (int c = l * VEC; c < H; c += G * VEC) {
-        const int k = c / D;
-        const bool head_lead = (c % D) == 0;
-        const float ad = adst[(size_t)i * K + k];
-        const float m = mx[(size_t)i * K + k], dn = den[(size_t)i * K + k];
-        const V gi = V::ld(gout + (size_t)i * H + c);
-        // slots s0..s1 (s1 = the node's own loop), four at a time with every load of a batch requested together
-        float S = 0.f;
-        for (int s = s0; s <= s1; s += 4) {
-            int j[4];
-            int64_t id[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int sq = min(s + q, s1);
-                j[q] = sq < s1 ? nbr[min(sq, max(s1 - 1, 0))] : i;
-                id[q] = sq < s1 ? (int64_t)eid[min(sq, max(s1 - 1, 0))] : E + i;
-            }
-            V zv[4];
-            float as[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { zv[q] = V::ld(z + (size_t)j[q] * H + c); as[q] = asrc[(size_t)j[q] * K + k]; }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) zv[q].pin();
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float dot = gi.dot(zv[q]);
-                if (LH == 16) dot = row16_sum(dot);
-                else for (int o = LH / 2; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
-                const float alpha = expf(lrelu(ad + as[q], slope) - m) / dn;
-                const float dalpha = dot * keep_scale(seed, id[q], k, K, p, inv_keep);
-                if (s + q <= s1) {
-                    S = fmaf(alpha, dalpha, S);
-                    if (head_lead) draw[id[q] * K + k] = dalpha;
-                }
-            }
-        }
-        float rowsum = 0.f;
-        for (int s = s0; s <= s1; s += 4) {
-            int j[4];
-            int64_t id[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int sq = min(s + q, s1);
-                j[q] = sq < s1 ? nbr[min(sq, max(s1 - 1, 0))] : i;
-                id[q] = sq < s1 ? (int64_t)eid[min(sq, max(s1 - 1, 0))] : E + i;
-            }
-            float as[4], da[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { as[q] = asrc[(size_t)j[q] * K + k]; da[q] = draw[id[q] * K + k]; }   // written by this head's lead lane above
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float raw = ad + as[q];
-                const float alpha = expf(lrelu(raw, slope) - m) / dn;
-                const float dalpha = __shfl(da[q], (threadIdx.x & 63) & ~(LH - 1), 64);
-                const float de = alpha * (dalpha - S);
-                const float dr = de * (raw > 0.f ? 1.f : slope);
-                if (s + q <= s1) {
-                    rowsum += dr;
-                    if (head_lead) draw[id[q] * K + k] = dr;
-                }
-            }
-        }
-        if (head_lead) dadst[(size_t)i * K + k] = rowsum;
-    }
-}
-
-// The same with the first NC slots of a row kept in registers between the two passes.  The softmax backward needs
-// S = sum_s alpha_s dalpha_s over the whole row before any d(raw logit) can be formed, so k_gat_bwd_dst walks the row twice
-// and parks dalpha in `draw` in between: rowptr -> nbr/eid -> z rows + a_src -> (write dalpha) -> nbr/eid -> a_src + dalpha
-// read-back -> write: six dependent rounds per row, 459 us per layer at config 5 (12 % of the HBM roofline with the
-// source-side kernel).  BA(m = 2) rows have ~5 slots: with (raw logit, dalpha, slot id) of the first NC = 8 slots held in
-// registers a typical row is rowptr -> nbr/eid -> z rows + a_src -> write, and only a hub's slots beyond the eighth take the
-// read-back path.
+// Backward pass 1+2 over the by-destination CSR.  Lanes of one head (LH = D/VEC of them, a power of two) reduce their
+// partial dots with shuffles.  draw[id*K + k] (id = edge id, or E + i for the loop of node i) receives d(raw logit);
+// dadst[i,k] the row sum.  The softmax backward needs S = sum_s alpha_s dalpha_s over the whole row before any d(raw logit)
+// can be formed.  A kernel that walks the row twice and parks dalpha in `draw` in between goes rowptr -> nbr/eid -> z rows +
+// a_src -> (write dalpha) -> nbr/eid -> a_src + dalpha read-back -> write: six dependent rounds per row, 459 us per layer at
+// config 5 (12 % of the HBM roofline with the source-side kernel).  BA(m = 2) rows have ~5 slots: with (raw logit, dalpha,
+// slot id) of the first NC = 8 slots held in registers between the two passes a typical row is rowptr -> nbr/eid -> z rows +
+// a_src -> write, and only a hub's slots beyond the eighth take the read-back path.
 template <int VEC, int G>
 __global__ void __launch_bounds__(256) k_gat_bwd_dst_c(const int* __restrict__ rowptr, const int* __restrict__ nbr,
                                                        const int* __restrict__ eid, const float* __restrict__ z,
@@ -415,7 +328,7 @@ __global__ void __launch_bounds__(256) k_gat_bwd_dst_c(const int* __restrict__ r
                 }
             }
         }
-        // ---- slots beyond the cache (hub rows): dalpha parked in `draw`, as in k_gat_bwd_dst -------------------------------
+        // ---- slots beyond the cache (hub rows): dalpha parked in `draw` between the two passes ---------------------------
         for (int s = s0 + NC; s <= s1; s += 4) {
             int j[4];
             int64_t id[4];
