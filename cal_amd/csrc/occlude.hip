@@ -1,0 +1,558 @@
+// Occlusion replicas and rank agreement: the two device operators behind cal_amd/occlude.py.
+//
+// (1) cal_occlude_count / cal_occlude_write: replica r is graph g = rep_graph[r] of the batch with one element removed.  Graph g
+// owns the nodes [ptr[g], ptr[g+1]) and the edge_index columns [edge_ptr[g], edge_ptr[g+1]); rep_elem[r] is a global column id
+// (mode 0: that column goes, and its twin column when a twin map is given) or a global node id (mode 1: the node's row goes, later
+// nodes move down by one, every column incident to it goes, the remaining endpoints are rewritten).  An element that is not one
+// of g's removes nothing (the control replica); a graph id outside the batch gives a replica with nothing in it.  A source
+// column with an endpoint outside its graph's node range is dropped, as in splice.hip.  Every integer output is uniquely
+// determined (the host twin and a plain-torch restatement agree bit for bit); the feature rows are copies.
+//
+// Two launches with the caller's one read-back of totals between them, the shape of splice.hip:
+//  * k_occlude_count, one workgroup per replica: the columns that stay (any size: the graph is walked in chunks of one
+//    workgroup's threads) and the replica's node count into ws.  The workgroup that finishes last scans the R counts into
+//    ptr_out / edge_ptr_out and writes totals; it is found with the completion ticket of twin.hip / splice.hip (one atomicInc per
+//    workgroup on a wrapping counter, nothing else): no output value is accumulated atomically.
+//  * k_occlude_write: node workgroups take kNodeChunk result nodes (the replica by binary search in ptr_out, batch_out /
+//    node_src, then the feature rows: 16 bytes per lane when F % 4 == 0 and both bases are 16-byte aligned, else element by
+//    element); after them one column workgroup per replica walks the source graph's columns in chunks and writes the ones that
+//    stay, in order, at edge_ptr_out[r] on (a replica drops a different set of columns each, so there is no per-graph list of
+//    kept columns to share as the splice has; the replicas of an occlusion run are small graphs, one chunk each).
+//
+// (2) cal_rank_agreement: per segment the ten integer counts two score vectors' rank correlations are made of (Spearman's rho
+// from the doubled mid-ranks, Kendall's tau-b from the concordant / discordant / tied pairs, the top-k overlap).  Each lane owns
+// an element i and loops over the segment's (a, b) pairs staged in LDS as broadcast reads, the counting of twin.hip.  Segments
+// within kSegCap: one launch (the geometry of segment.hpp: G = 64 .. 1024 threads per segment).  Longer ones: workgroup
+// (g, c) owns the rows [c S, (c + 1) S) of segment g and stages the segment tile by tile; its partial sums go to ws and
+// k_agree_finish adds them per segment in chunk order.  Integers only: the same bits in any order.
+#include <atomic>
+
+#include "segment.hpp"
+
+namespace cal {
+namespace {
+
+constexpr int kNodeChunk = 256;            // result nodes of one node workgroup (one per thread in the index phase)
+constexpr int kTickets = 64;               // concurrent count launches (on different streams) that may be in flight
+constexpr int kAgIt = kSegCap / kSegWide;  // elements per lane at the widest group
+constexpr int kAgPart = 9;                 // a row chunk's partial: the eight sums (pair counts doubled) and n
+
+__device__ unsigned int g_occlude_ticket[kTickets];   // zero at load; atomicInc wraps each back to zero
+
+struct OccArgs {
+    const int64_t* ei;         // [2, E]
+    int64_t E, N;
+    const int64_t* ptr;        // [B + 1]
+    const int64_t* eptr;       // [B + 1]
+    int64_t B;
+    const int64_t* rg;         // [R] graph of every replica (outside [0, B): none)
+    const int64_t* re;         // [R] the element removed (global column / node id; not one of the graph's: nothing)
+    int64_t R;
+    int mode;                  // 0 edges, 1 nodes
+    const int32_t* twin;       // [E] or null (mode 0)
+    int64_t* ptr_out;          // [R + 1]
+    int64_t* eptr_out;         // [R + 1]
+    int64_t* totals;           // [5]
+    int64_t* cnt;              // ws [2 R]: nodes, columns of every replica
+    const float* x;            // (write) [N, F] or null
+    int64_t F, Nout, Eout;     // (write) totals[0], totals[1] as the caller read them
+    int64_t* batch_out;        // [Nout]
+    float* x_out;              // [Nout, F] or null
+    int64_t* ei_out;           // [2, Eout]
+    int64_t* node_src;         // [Nout]
+    int64_t* edge_src;         // [Eout]
+    int ticket, nblk;
+    int vec;                   // (write) the 16-byte row copy applies
+};
+
+// replica r: its graph's node range [nlo, nlo + nn) and column range [elo, elo + em) (all zero without a graph), the node
+// removed (rn) and the columns removed (c0, c1); -1 = none, which equals no id
+struct Rep {
+    int64_t nlo, nn, elo, em, rn, c0, c1;
+};
+
+__device__ __forceinline__ Rep replica(const OccArgs& a, int64_t r) {
+    Rep q{0, 0, 0, 0, -1, -1, -1};
+    const int64_t g = a.rg[r];
+    if (g < 0 || g >= a.B) return q;
+    seg_clamp(a.ptr, g, a.N, q.nlo, q.nn);
+    seg_clamp(a.eptr, g, a.E, q.elo, q.em);
+    const int64_t e = a.re[r];
+    if (a.mode == 0) {
+        if (e >= q.elo && e < q.elo + q.em) {
+            q.c0 = e;
+            if (a.twin) q.c1 = a.twin[e];                         // (a negative twin or one outside the graph meets no column)
+        }
+    } else if (e >= q.nlo && e < q.nlo + q.nn) {
+        q.rn = e;
+    }
+    return q;
+}
+
+// column e of the replica's graph stays
+__device__ __forceinline__ bool col_stays(const OccArgs& a, const Rep& q, int64_t e) {
+    const int64_t u = a.ei[e], v = a.ei[a.E + e];
+    return u >= q.nlo && u < q.nlo + q.nn && v >= q.nlo && v < q.nlo + q.nn && e != q.c0 && e != q.c1 && u != q.rn && v != q.rn;
+}
+
+// exclusive prefix of v over the workgroup's NT threads in thread order, the workgroup's sum in tot (two barriers); as in
+// splice.hip
+template <int NT>
+__device__ __forceinline__ long long wg_excl_sum(long long v, long long* red, long long& tot) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    long long inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const long long u = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += u;
+    }
+    __syncthreads();
+    if (lane == 63) red[w] = inc;
+    __syncthreads();
+    long long base = 0, t = 0;
+#pragma unroll
+    for (int i = 0; i < NT / 64; ++i) {
+        const long long r = red[i];
+        base += i < w ? r : 0;
+        t += r;
+    }
+    tot = t;
+    return base + inc - v;
+}
+
+// grid R, NT threads
+template <int NT>
+__global__ void __launch_bounds__(NT) k_occlude_count(OccArgs a) {
+    __shared__ long long red[NT / 64];
+    __shared__ int last;
+    const int64_t r = blockIdx.x, R = a.R;
+    const Rep q = replica(a, r);
+    long long c = 0;
+    for (int64_t t = threadIdx.x; t < q.em; t += NT) c += col_stays(a, q, q.elo + t);
+    const int64_t kept = wg_sum<NT>(c, red);
+    if (threadIdx.x == 0) {
+        a.cnt[r] = q.nn - (q.rn >= 0 ? 1 : 0);
+        a.cnt[R + r] = kept;
+        __threadfence();
+        last = atomicInc(&g_occlude_ticket[a.ticket], (unsigned)(a.nblk - 1)) == (unsigned)(a.nblk - 1);
+    }
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    // the scan over the R replicas: thread t owns the run [t L, (t + 1) L) of replicas
+    const int64_t L = (R + NT - 1) / NT, lo = (int64_t)threadIdx.x * L, hi = lo + L < R ? lo + L : R;
+    long long sn = 0, se = 0, mn = 0, me = 0, empty = 0;
+    for (int64_t p = lo; p < hi; ++p) {
+        const long long n = __hip_atomic_load(a.cnt + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const long long e = __hip_atomic_load(a.cnt + R + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        sn += n;
+        se += e;
+        mn = n > mn ? n : mn;
+        me = e > me ? e : me;
+        empty += n == 0;
+    }
+    long long tn, te;
+    long long on = wg_excl_sum<NT>(sn, red, tn), oe = wg_excl_sum<NT>(se, red, te);
+    for (int64_t p = lo; p < hi; ++p) {
+        a.ptr_out[p] = on;
+        a.eptr_out[p] = oe;
+        on += __hip_atomic_load(a.cnt + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        oe += __hip_atomic_load(a.cnt + R + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    mn = wg_max<NT>(mn, red);
+    me = wg_max<NT>(me, red);
+    empty = wg_sum<NT>(empty, red);
+    if (threadIdx.x == 0) {
+        a.ptr_out[R] = tn;
+        a.eptr_out[R] = te;
+        a.totals[0] = tn;
+        a.totals[1] = te;
+        a.totals[2] = mn;
+        a.totals[3] = me;
+        a.totals[4] = empty;
+    }
+}
+
+// last index q in [0, n) with p[q] <= i; p ascending with p[0] = 0 <= i (the replica that owns node i; empty ones are skipped)
+__device__ __forceinline__ int64_t owner(const int64_t* p, int64_t n, int64_t i) {
+    int64_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (p[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// grid ceil(Nout / kNodeChunk) node workgroups, then R column workgroups; 256 threads
+__global__ void __launch_bounds__(256) k_occlude_write(OccArgs a, int node_blocks) {
+    __shared__ int64_t src[kNodeChunk];
+    __shared__ int wcnt[4];
+    const int64_t R = a.R;
+    if ((int)blockIdx.x < node_blocks) {
+        const int64_t i0 = (int64_t)blockIdx.x * kNodeChunk, i = i0 + threadIdx.x;
+        int64_t s = -1;                                           // (no row)
+        if (i < a.Nout) {
+            const int64_t r = owner(a.ptr_out, R + 1, i);
+            if (r < R) {
+                const Rep q = replica(a, r);
+                int64_t c = q.nlo + (i - a.ptr_out[r]);
+                c += q.rn >= 0 && c >= q.rn;
+                if (c < q.nlo + q.nn) {
+                    s = c;
+                    a.batch_out[i] = r;
+                    a.node_src[i] = c;
+                }
+            }
+        }
+        if (!a.x_out) return;
+        src[threadIdx.x] = s;
+        __syncthreads();
+        const int64_t left = a.Nout - i0;
+        const unsigned rows = (unsigned)(left < kNodeChunk ? left : kNodeChunk);
+        if (a.vec) {
+            const unsigned F4 = (unsigned)(a.F >> 2), n = rows * F4;
+            float4* out = reinterpret_cast<float4*>(a.x_out) + i0 * F4;
+            for (unsigned t = threadIdx.x; t < n; t += 256) {
+                const unsigned rr = t / F4, c = t - rr * F4;
+                const int64_t sr = src[rr];
+                if (sr < 0) continue;
+                out[t] = reinterpret_cast<const float4*>(a.x + sr * a.F)[c];
+            }
+        } else {
+            const unsigned F = (unsigned)a.F, n = rows * F;
+            float* out = a.x_out + i0 * a.F;
+            for (unsigned t = threadIdx.x; t < n; t += 256) {
+                const unsigned rr = t / F, c = t - rr * F;
+                const int64_t sr = src[rr];
+                if (sr < 0) continue;
+                out[t] = a.x[sr * a.F + c];
+            }
+        }
+        return;
+    }
+    const int64_t r = (int64_t)((int)blockIdx.x - node_blocks);
+    const Rep q = replica(a, r);
+    const int64_t n0 = a.ptr_out[r], j0 = a.eptr_out[r], j1 = a.eptr_out[r + 1] < a.Eout ? a.eptr_out[r + 1] : a.Eout;
+    int64_t carry = 0;
+    for (int64_t base = 0; base < q.em; base += 256) {            // (q.em is uniform over the workgroup)
+        const int64_t e = q.elo + base + threadIdx.x;
+        const bool f = base + threadIdx.x < q.em && col_stays(a, q, e);
+        int t;
+        const int pos = wg_excl<256>(f, wcnt, t);
+        const int64_t j = j0 + carry + pos;
+        if (f && j < j1) {
+            const int64_t u = a.ei[e], v = a.ei[a.E + e];
+            a.ei_out[j] = n0 + (u - q.nlo) - (q.rn >= 0 && u > q.rn);
+            a.ei_out[a.Eout + j] = n0 + (v - q.nlo) - (q.rn >= 0 && v > q.rn);
+            a.edge_src[j] = e;
+        }
+        carry += t;
+    }
+}
+
+std::atomic<unsigned> g_occlude_calls{0};
+
+int64_t occ_ws_need(int64_t R) { return 16 * (R > 0 ? R : 0) + 256; }
+
+// the checks both entry points share (CAL_REQUIRE names the entry point)
+#define OCCLUDE_REQUIRE_INPUTS()                                                                                                 \
+    CAL_REQUIRE(E >= 0 && N >= 0 && B >= 0 && R >= 0, "sizes must be >= 0");                                                     \
+    CAL_REQUIRE(R <= 0x7FFFFFFF, "too many replicas");                                                             \
+    CAL_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (edges) or 1 (nodes)");                                                  \
+    CAL_REQUIRE(R == 0 || (rep_graph && rep_elem), "rep_graph / rep_elem are null");                                             \
+    CAL_REQUIRE(B == 0 || (ptr && edge_ptr), "ptr / edge_ptr are null");                                                         \
+    CAL_REQUIRE(E == 0 || edge_index, "edge_index is null");                                                                     \
+    CAL_REQUIRE(R == 0 || (ws && ws_bytes >= occ_ws_need(R) && (reinterpret_cast<uintptr_t>(ws) & 7) == 0),                      \
+                "ws must be 8-byte aligned and hold cal_occlude_ws(E, R) bytes")
+
+OccArgs occ_args(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr, int64_t B,
+                 const int64_t* rep_graph, const int64_t* rep_elem, int64_t R, int mode, const int32_t* twin, void* ws) {
+    OccArgs a{};
+    a.ei = edge_index;
+    a.E = E;
+    a.N = N;
+    a.ptr = ptr;
+    a.eptr = edge_ptr;
+    a.B = B;
+    a.rg = rep_graph;
+    a.re = rep_elem;
+    a.R = R;
+    a.mode = mode;
+    a.twin = mode == 0 ? twin : nullptr;
+    a.cnt = (int64_t*)ws;
+    return a;
+}
+
+// ---- rank agreement ------------------------------------------------------------------------------------------------------------
+struct AgArgs {
+    const float* a;            // [M]
+    const float* b;            // [M]
+    int64_t M;
+    const int64_t* seg;        // [B + 1]
+    int64_t B, max_seg;
+    const uint8_t* sel;        // [M] or null
+    int64_t k;                 // >= 0 top k, -1 ceil(ratio n)
+    double ratio;
+    int64_t* counts;           // [B, 10]
+    int64_t* part;             // ws [slots, kAgPart] (large launches)
+    int large;
+};
+
+__device__ __forceinline__ int64_t ag_sel_count(int64_t n, double ratio, int64_t k) {
+    if (k >= 0) return k < n ? k : n;
+    const double c = ceil(ratio * (double)n);
+    return c < (double)n ? (int64_t)c : n;
+}
+
+// the (a, b) of element i of the batch, NaN twice when it does not take part
+__device__ __forceinline__ float2 ag_load(const AgArgs& a, int64_t i, bool& part) {
+    float2 v = make_float2(a.a[i], a.b[i]);
+    part = (!a.sel || a.sel[i] != 0) && v.x == v.x && v.y == v.y;
+    if (!part) v.x = v.y = __builtin_nanf("");
+    return v;
+}
+
+// slot of row chunk c of segment g (at lo) in part[]: chunks of earlier segments number at most floor(lo / S) + g
+__device__ __forceinline__ int64_t ag_slot(int64_t lo, int64_t g, int64_t c) { return lo / kSegCap + g + c; }
+
+__device__ __forceinline__ void ag_write(int64_t* row, int64_t n, const long long* s, int64_t kg) {
+    row[0] = n;
+    row[1] = s[0] / 2;
+    row[2] = s[1] / 2;
+    row[3] = s[2] / 2;
+    row[4] = s[3] / 2;
+    row[5] = s[4];
+    row[6] = s[5];
+    row[7] = s[6];
+    row[8] = kg;
+    row[9] = s[7];
+}
+
+// grid (ceil(B / (NT / G)), row chunks), NT threads; dynamic LDS: (a, b) [NT/G][cap] float2, then [NT/64] i64.
+// cap = G x (elements per lane) >= min(max_seg, S).  A launch whose max_seg is within S finishes every segment here (one tile);
+// otherwise G = NT = 1024, cap = S, one segment per workgroup, and the workgroup owns the rows [c S, (c + 1) S) of it.
+template <int NT>
+__global__ void __launch_bounds__(NT) k_agree(AgArgs a, int G, int cap) {
+    extern __shared__ __align__(16) float2 alds[];
+    const int spb = NT / G, grp = threadIdx.x / G, lt = threadIdx.x % G;
+    float2* sv = alds + (size_t)grp * cap;
+    long long* red = reinterpret_cast<long long*>(alds + (size_t)spb * cap);
+    const int64_t g = (int64_t)blockIdx.x * spb + grp, c = blockIdx.y;
+    int64_t lo = 0, m = 0;
+    if (g < a.B) seg_clamp(a.seg, g, a.M, lo, m);
+    const bool work = g < a.B && m <= a.max_seg, bad = g < a.B && m > a.max_seg;
+    const int64_t rlo = c * kSegCap;
+    const int rn = work && rlo < m ? (int)(m - rlo < cap ? m - rlo : cap) : 0;       // rows of this group
+    // tiles of j: one in a launch without large segments; else (one segment per workgroup: uniform) the segment's, none when
+    // this workgroup has no row
+    const int nt = a.large ? (rn > 0 ? (int)((m + kSegCap - 1) / kSegCap) : 0) : 1;
+    const int nit = cap / G;
+
+    float ai[kAgIt], bi[kAgIt];
+    bool pi[kAgIt];
+    int64_t gi[kAgIt];
+    int la[kAgIt], ea[kAgIt], ga[kAgIt], fa[kAgIt], lb[kAgIt], eb[kAgIt], gb[kAgIt], fb[kAgIt], cc[kAgIt], dd[kAgIt];
+#pragma unroll
+    for (int it = 0; it < kAgIt; ++it) {
+        const int q = lt + it * G;
+        pi[it] = false;
+        gi[it] = rlo + q;
+        ai[it] = bi[it] = __builtin_nanf("");
+        if (it < nit && q < rn) {
+            const float2 v = ag_load(a, lo + gi[it], pi[it]);
+            ai[it] = v.x;
+            bi[it] = v.y;
+        }
+        la[it] = ea[it] = ga[it] = fa[it] = lb[it] = eb[it] = gb[it] = fb[it] = cc[it] = dd[it] = 0;
+    }
+    long long pc = 0;
+    for (int t = 0; t < nt; ++t) {
+        const int64_t tlo = (int64_t)t * kSegCap;
+        const int tn = work && tlo < m ? (int)(m - tlo < cap ? m - tlo : cap) : 0;
+        for (int s = lt; s < tn; s += G) {
+            bool p;
+            sv[s] = ag_load(a, lo + tlo + s, p);
+            pc += p;
+        }
+        __syncthreads();
+        for (int j = 0; j < tn; ++j) {
+            const float2 v = sv[j];                                // (every lane of the group the same address: a broadcast)
+#pragma unroll
+            for (int it = 0; it < kAgIt; ++it) {
+                if (it < nit) {
+                    const int before = tlo + j < gi[it];
+                    const int lta = v.x < ai[it], gta = v.x > ai[it], eqa = v.x == ai[it];
+                    const int ltb = v.y < bi[it], gtb = v.y > bi[it], eqb = v.y == bi[it];
+                    la[it] += lta;
+                    ga[it] += gta;
+                    ea[it] += eqa;
+                    fa[it] += eqa & before;
+                    lb[it] += ltb;
+                    gb[it] += gtb;
+                    eb[it] += eqb;
+                    fb[it] += eqb & before;
+                    cc[it] += (lta & ltb) | (gta & gtb);
+                    dd[it] += (lta & gtb) | (gta & ltb);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    const int64_t n = group_total(pc, G, red);
+    const int64_t kg = ag_sel_count(n, a.ratio, a.k);
+    long long s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int it = 0; it < kAgIt; ++it) {
+        if (pi[it]) {
+            const long long ra = 2ll * la[it] + ea[it] + 1, rb = 2ll * lb[it] + eb[it] + 1;
+            s[0] += cc[it];
+            s[1] += dd[it];
+            s[2] += ea[it] - 1;
+            s[3] += eb[it] - 1;
+            s[4] += ra * ra;
+            s[5] += rb * rb;
+            s[6] += ra * rb;
+            s[7] += (ga[it] + fa[it] < kg) && (gb[it] + fb[it] < kg);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) s[i] = group_total(s[i], G, red);
+    if (lt != 0 || g >= a.B) return;
+    if (!a.large) {
+        if (bad) {
+            for (int i = 0; i < 8; ++i) s[i] = 0;
+        }
+        ag_write(a.counts + 10 * g, bad ? -1 : n, s, bad ? 0 : kg);
+    } else if (rn > 0) {
+        int64_t* p = a.part + ag_slot(lo, g, c) * kAgPart;
+        for (int i = 0; i < 8; ++i) p[i] = s[i];
+        p[8] = n;
+    }
+}
+
+// one thread per segment: the row chunks' partials added in chunk order (a launch with large segments)
+__global__ void __launch_bounds__(256) k_agree_finish(AgArgs a) {
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= a.B) return;
+    int64_t lo, m;
+    seg_clamp(a.seg, g, a.M, lo, m);
+    long long s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t n = 0;
+    if (m > a.max_seg) {
+        ag_write(a.counts + 10 * g, -1, s, 0);
+        return;
+    }
+    const int64_t nch = (m + kSegCap - 1) / kSegCap;
+    for (int64_t c = 0; c < nch; ++c) {
+        const int64_t* p = a.part + ag_slot(lo, g, c) * kAgPart;
+        for (int i = 0; i < 8; ++i) s[i] += p[i];
+        n = p[8];
+    }
+    ag_write(a.counts + 10 * g, n, s, ag_sel_count(n, a.ratio, a.k));
+}
+
+int64_t ag_ws_need(int64_t M, int64_t B, int64_t max_seg) {
+    if (max_seg <= kSegCap) return 0;
+    return 8 * kAgPart * ((M > 0 ? M : 0) / kSegCap + (B > 0 ? B : 0) + 1) + 256;
+}
+
+}  // namespace
+}  // namespace cal
+
+using namespace cal;
+
+CAL_EXPORT int64_t cal_occlude_ws(int64_t, int64_t R) { return occ_ws_need(R); }
+
+CAL_EXPORT int cal_occlude_count(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                                 int64_t B, const int64_t* rep_graph, const int64_t* rep_elem, int64_t R, int mode,
+                                 const int32_t* twin, int64_t* ptr_out, int64_t* edge_ptr_out, int64_t* totals, void* ws,
+                                 int64_t ws_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    OCCLUDE_REQUIRE_INPUTS();
+    CAL_REQUIRE(totals && ptr_out && edge_ptr_out, "totals / ptr_out / edge_ptr_out are null");
+    if (R == 0) {
+        if (hipMemsetAsync(totals, 0, 5 * sizeof(int64_t), stream) != hipSuccess ||
+            hipMemsetAsync(ptr_out, 0, sizeof(int64_t), stream) != hipSuccess ||
+            hipMemsetAsync(edge_ptr_out, 0, sizeof(int64_t), stream) != hipSuccess) {
+            cal::set_error("cal_occlude_count: hipMemsetAsync failed");
+            return 1;
+        }
+        return 0;
+    }
+    OccArgs a = occ_args(edge_index, E, N, ptr, edge_ptr, B, rep_graph, rep_elem, R, mode, twin, ws);
+    a.ptr_out = ptr_out;
+    a.eptr_out = edge_ptr_out;
+    a.totals = totals;
+    a.ticket = (int)(g_occlude_calls.fetch_add(1) % kTickets);
+    a.nblk = (int)R;
+    // wide workgroups once the average source graph has more columns than a 256-thread workgroup walks in a few chunks
+    if (E / (B > 0 ? B : 1) > 2048)
+        hipLaunchKernelGGL(k_occlude_count<1024>, dim3((unsigned)R), dim3(1024), 0, stream, a);
+    else
+        hipLaunchKernelGGL(k_occlude_count<256>, dim3((unsigned)R), dim3(256), 0, stream, a);
+    CAL_CHECK_LAUNCH("k_occlude_count");
+    return 0;
+}
+
+CAL_EXPORT int cal_occlude_write(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                                 int64_t B, const int64_t* rep_graph, const int64_t* rep_elem, int64_t R, int mode,
+                                 const int32_t* twin, const float* x, int64_t F, const int64_t* ptr_out,
+                                 const int64_t* edge_ptr_out, int64_t Nout, int64_t Eout, int64_t* batch_out, float* x_out,
+                                 int64_t* edge_index_out, int64_t* node_src, int64_t* edge_src, void* ws, int64_t ws_bytes,
+                                 void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    OCCLUDE_REQUIRE_INPUTS();
+    CAL_REQUIRE(Nout >= 0 && Eout >= 0 && F >= 0 && F < (1 << 22), "Nout, Eout must be >= 0 and 0 <= F < 2^22");
+    CAL_REQUIRE(R == 0 || (ptr_out && edge_ptr_out), "ptr_out / edge_ptr_out are null");
+    CAL_REQUIRE(Nout == 0 || (batch_out && node_src), "batch_out / node_src are null");
+    CAL_REQUIRE(Eout == 0 || (edge_index_out && edge_src), "edge_index_out / edge_src are null");
+    CAL_REQUIRE(!x_out || (F > 0 && (N == 0 || x)), "x_out needs F > 0 and x");
+    const int64_t nb = (Nout + kNodeChunk - 1) / kNodeChunk, eb = Eout > 0 ? R : 0;
+    CAL_REQUIRE(nb + eb <= 0x7FFFFFFF, "too many elements");
+    if (R == 0 || nb + eb == 0) return 0;
+    OccArgs a = occ_args(edge_index, E, N, ptr, edge_ptr, B, rep_graph, rep_elem, R, mode, twin, ws);
+    a.x = x;
+    a.F = F;
+    a.ptr_out = const_cast<int64_t*>(ptr_out);
+    a.eptr_out = const_cast<int64_t*>(edge_ptr_out);
+    a.Nout = Nout;
+    a.Eout = Eout;
+    a.batch_out = batch_out;
+    a.x_out = x_out;
+    a.ei_out = edge_index_out;
+    a.node_src = node_src;
+    a.edge_src = edge_src;
+    a.vec = x_out && F % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(x_out)) & 15) == 0;
+    hipLaunchKernelGGL(k_occlude_write, dim3((unsigned)(nb + eb)), dim3(256), 0, stream, a, (int)nb);
+    CAL_CHECK_LAUNCH("k_occlude_write");
+    return 0;
+}
+
+CAL_EXPORT int64_t cal_rank_agreement_ws(int64_t M, int64_t B, int64_t max_seg) { return ag_ws_need(M, B, max_seg); }
+
+CAL_EXPORT int cal_rank_agreement(const float* a_, const float* b_, int64_t M, const int64_t* seg_ptr, int64_t B, int64_t max_seg,
+                                  const uint8_t* sel, int64_t k_code, double k_val, int64_t* counts, void* ws, int64_t ws_bytes,
+                                  void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    CAL_REQUIRE(M >= 0 && B >= 0 && max_seg >= 0, "M, B, max_seg must be >= 0");
+    CAL_REQUIRE(max_seg < ((int64_t)1 << 20), "segments of 2^20 elements or more are not supported (the sums would leave int64)");
+    CAL_REQUIRE(k_code >= -1, "k_code must be >= 0 or -1 (ratio)");
+    CAL_REQUIRE(k_code != -1 || k_val >= 0.0, "k_code = -1 needs a ratio >= 0");
+    if (B == 0) return 0;
+    CAL_REQUIRE(seg_ptr && counts, "seg_ptr / counts are null");
+    CAL_REQUIRE(M == 0 || (a_ && b_), "a / b are null");
+    const SegGeom q = seg_geom(max_seg, B);
+    CAL_REQUIRE(q.chunks_ok(), "max_seg too large");
+    CAL_REQUIRE(q.grid_ok(), "too many segments");
+    CAL_REQUIRE(!q.large || (ws && ws_bytes >= ag_ws_need(M, B, max_seg) && (reinterpret_cast<uintptr_t>(ws) & 7) == 0),
+                "ws must be 8-byte aligned and hold cal_rank_agreement_ws(M, B, max_seg) bytes");
+    AgArgs a{a_, b_, M, seg_ptr, B, max_seg, sel, k_code, k_val, counts, (int64_t*)ws, q.large ? 1 : 0};
+    const size_t lds = (size_t)8 * q.spb * q.cap + (size_t)(q.NT / 64) * 8;
+    CAL_SEG_LAUNCH(k_agree, q, lds, stream, a);
+    CAL_CHECK_LAUNCH("k_agree");
+    if (q.large) {
+        hipLaunchKernelGGL(k_agree_finish, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, stream, a);
+        CAL_CHECK_LAUNCH("k_agree_finish");
+    }
+    return 0;
+}

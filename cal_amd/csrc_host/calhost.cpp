@@ -925,6 +925,172 @@ HOST_EXPORT int cal_graph_splice_write(const int64_t* eia, int64_t Ea, int64_t N
 }
 #undef SPLICE_REQUIRE_INPUTS
 
+// ---- occlusion replicas (cal_amd/csrc/occlude.hip; cal_amd/occlude.py occlude_batch): the same nodes and columns in the same
+// order, so every integer output agrees bit for bit.
+namespace {
+struct OccludeSrc {
+    const int64_t* ei; int64_t E, N; const int64_t* ptr; const int64_t* eptr; int64_t B; const int64_t* rg; const int64_t* re;
+    int mode; const int32_t* twin;
+    // replica r: node range, column range, the node removed, the two columns removed (-1: none)
+    void ranges(int64_t r, int64_t& nlo, int64_t& nhi, int64_t& elo, int64_t& ehi, int64_t& rn, int64_t& c0, int64_t& c1) const {
+        const int64_t g = rg[r], e = re[r];
+        nlo = nhi = elo = ehi = 0;
+        rn = c0 = c1 = -1;
+        if (g < 0 || g >= B) return;
+        seg_clamp(ptr, g, N, nlo, nhi);
+        seg_clamp(eptr, g, E, elo, ehi);
+        if (mode == 0) {
+            if (e >= elo && e < ehi) { c0 = e; if (twin) c1 = twin[e]; }
+        } else if (e >= nlo && e < nhi) {
+            rn = e;
+        }
+    }
+    bool stays(int64_t e, int64_t nlo, int64_t nhi, int64_t rn, int64_t c0, int64_t c1) const {
+        const int64_t u = ei[e], v = ei[E + e];
+        return u >= nlo && u < nhi && v >= nlo && v < nhi && e != c0 && e != c1 && u != rn && v != rn;
+    }
+};
+}  // namespace
+
+HOST_EXPORT int64_t cal_occlude_ws(int64_t, int64_t R) { return 16 * (R > 0 ? R : 0) + 256; }
+
+#define OCCLUDE_REQUIRE_INPUTS()                                                                                                 \
+    HOST_REQUIRE(E >= 0 && N >= 0 && B >= 0 && R >= 0, "sizes must be >= 0");                                                    \
+    HOST_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (edges) or 1 (nodes)");                                                 \
+    HOST_REQUIRE(R == 0 || (rep_graph && rep_elem), "rep_graph / rep_elem are null");                                            \
+    HOST_REQUIRE(B == 0 || (ptr && edge_ptr), "ptr / edge_ptr are null");                                                        \
+    HOST_REQUIRE(E == 0 || edge_index, "edge_index is null")
+
+HOST_EXPORT int cal_occlude_count(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                                  int64_t B, const int64_t* rep_graph, const int64_t* rep_elem, int64_t R, int mode,
+                                  const int32_t* twin, int64_t* ptr_out, int64_t* edge_ptr_out, int64_t* totals, void*, int64_t,
+                                  void*) {
+    OCCLUDE_REQUIRE_INPUTS();
+    HOST_REQUIRE(totals && ptr_out && edge_ptr_out, "totals / ptr_out / edge_ptr_out are null");
+    const OccludeSrc S{edge_index, E, N, ptr, edge_ptr, B, rep_graph, rep_elem, mode, mode == 0 ? twin : nullptr};
+    int64_t nt = 0, et = 0, mn = 0, me = 0, empty = 0;
+    for (int64_t r = 0; r < R; ++r) {
+        int64_t nlo, nhi, elo, ehi, rn, c0, c1, m = 0;
+        S.ranges(r, nlo, nhi, elo, ehi, rn, c0, c1);
+        for (int64_t e = elo; e < ehi; ++e) m += S.stays(e, nlo, nhi, rn, c0, c1);
+        const int64_t n = (nhi - nlo) - (rn >= 0 ? 1 : 0);
+        ptr_out[r] = nt;
+        edge_ptr_out[r] = et;
+        nt += n;
+        et += m;
+        mn = std::max(mn, n);
+        me = std::max(me, m);
+        empty += n == 0;
+    }
+    ptr_out[R] = nt;
+    edge_ptr_out[R] = et;
+    totals[0] = nt; totals[1] = et; totals[2] = mn; totals[3] = me; totals[4] = empty;
+    return 0;
+}
+
+HOST_EXPORT int cal_occlude_write(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                                  int64_t B, const int64_t* rep_graph, const int64_t* rep_elem, int64_t R, int mode,
+                                  const int32_t* twin, const float* x, int64_t F, const int64_t* ptr_out,
+                                  const int64_t* edge_ptr_out, int64_t Nout, int64_t Eout, int64_t* batch_out, float* x_out,
+                                  int64_t* edge_index_out, int64_t* node_src, int64_t* edge_src, void*, int64_t, void*) {
+    OCCLUDE_REQUIRE_INPUTS();
+    HOST_REQUIRE(Nout >= 0 && Eout >= 0 && F >= 0 && F < (1 << 22), "Nout, Eout must be >= 0 and 0 <= F < 2^22");
+    HOST_REQUIRE(R == 0 || (ptr_out && edge_ptr_out), "ptr_out / edge_ptr_out are null");
+    HOST_REQUIRE(Nout == 0 || (batch_out && node_src), "batch_out / node_src are null");
+    HOST_REQUIRE(Eout == 0 || (edge_index_out && edge_src), "edge_index_out / edge_src are null");
+    HOST_REQUIRE(!x_out || (F > 0 && (N == 0 || x)), "x_out needs F > 0 and x");
+    const OccludeSrc S{edge_index, E, N, ptr, edge_ptr, B, rep_graph, rep_elem, mode, mode == 0 ? twin : nullptr};
+    for (int64_t r = 0; r < R; ++r) {
+        int64_t nlo, nhi, elo, ehi, rn, c0, c1;
+        S.ranges(r, nlo, nhi, elo, ehi, rn, c0, c1);
+        const int64_t n0 = ptr_out[r];
+        int64_t i = n0, j = edge_ptr_out[r];
+        for (int64_t s = nlo; s < nhi; ++s) {
+            if (s == rn || i >= Nout) continue;
+            batch_out[i] = r;
+            node_src[i] = s;
+            if (x_out) memcpy(x_out + i * F, x + s * F, sizeof(float) * (size_t)F);
+            ++i;
+        }
+        for (int64_t e = elo; e < ehi; ++e) {
+            if (!S.stays(e, nlo, nhi, rn, c0, c1) || j >= Eout) continue;
+            const int64_t u = edge_index[e], v = edge_index[E + e];
+            edge_index_out[j] = n0 + (u - nlo) - (rn >= 0 && u > rn ? 1 : 0);
+            edge_index_out[Eout + j] = n0 + (v - nlo) - (rn >= 0 && v > rn ? 1 : 0);
+            edge_src[j] = e;
+            ++j;
+        }
+    }
+    return 0;
+}
+#undef OCCLUDE_REQUIRE_INPUTS
+
+// ---- rank agreement (cal_amd/csrc/occlude.hip; cal_amd/occlude.py rank_agreement): the same ten integers per segment, here from
+// two sorts per segment where the device counts all pairs.
+HOST_EXPORT int64_t cal_rank_agreement_ws(int64_t, int64_t, int64_t) { return 0; }
+
+HOST_EXPORT int cal_rank_agreement(const float* a, const float* b, int64_t M, const int64_t* seg_ptr, int64_t B, int64_t max_seg,
+                                   const uint8_t* sel, int64_t k_code, double k_val, int64_t* counts, void*, int64_t, void*) {
+    HOST_REQUIRE(M >= 0 && B >= 0 && max_seg >= 0, "M, B, max_seg must be >= 0");
+    HOST_REQUIRE(max_seg < ((int64_t)1 << 20), "segments of 2^20 elements or more are not supported (the sums would leave int64)");
+    HOST_REQUIRE(k_code >= -1, "k_code must be >= 0 or -1 (ratio)");
+    HOST_REQUIRE(k_code != -1 || k_val >= 0.0, "k_code = -1 needs a ratio >= 0");
+    if (B == 0) return 0;
+    HOST_REQUIRE(seg_ptr && counts, "seg_ptr / counts are null");
+    HOST_REQUIRE(M == 0 || (a && b), "a / b are null");
+#pragma omp parallel for schedule(dynamic, 16)
+    for (int64_t g = 0; g < B; ++g) {
+        int64_t lo, hi;
+        seg_clamp(seg_ptr, g, M, lo, hi);
+        int64_t* row = counts + 10 * g;
+        for (int t = 0; t < 10; ++t) row[t] = 0;
+        if (hi - lo > max_seg) { row[0] = -1; continue; }
+        std::vector<int64_t> id;                               // the elements taking part, ascending
+        for (int64_t i = lo; i < hi; ++i)
+            if ((!sel || sel[i]) && a[i] == a[i] && b[i] == b[i]) id.push_back(i);
+        const int64_t n = (int64_t)id.size();
+        int64_t kg = k_code >= 0 ? std::min(k_code, n) : 0;
+        if (k_code == -1) { const double c = ceil(k_val * (double)n); kg = c < (double)n ? (int64_t)c : n; }
+        // doubled mid-ranks and top-k membership of one vector: positions in the order value descending, then index
+        std::vector<int64_t> r2[2];
+        std::vector<uint8_t> top[2];
+        int64_t tied[2] = {0, 0};
+        for (int s = 0; s < 2; ++s) {
+            const float* v = s ? b : a;
+            std::vector<int64_t> ord(n);
+            for (int64_t q = 0; q < n; ++q) ord[q] = q;
+            std::sort(ord.begin(), ord.end(), [&](int64_t p, int64_t q) { return v[id[p]] != v[id[q]] ? v[id[p]] > v[id[q]] : p < q; });
+            r2[s].assign(n, 0);
+            top[s].assign(n, 0);
+            for (int64_t p = 0; p < n;) {                      // runs of equal values: [p, e)
+                int64_t e = p + 1;
+                while (e < n && v[id[ord[e]]] == v[id[ord[p]]]) ++e;
+                const int64_t eq = e - p, less = n - e;
+                tied[s] += eq * (eq - 1) / 2;
+                for (int64_t t = p; t < e; ++t) { r2[s][ord[t]] = 2 * less + eq + 1; top[s][ord[t]] = t < kg; }
+                p = e;
+            }
+        }
+        int64_t C = 0, D = 0, saa = 0, sbb = 0, sab = 0, inter = 0;
+        for (int64_t p = 0; p < n; ++p) {
+            saa += r2[0][p] * r2[0][p];
+            sbb += r2[1][p] * r2[1][p];
+            sab += r2[0][p] * r2[1][p];
+            inter += top[0][p] && top[1][p];
+            const float ap = a[id[p]], bp = b[id[p]];
+            for (int64_t q = p + 1; q < n; ++q) {
+                const float aq = a[id[q]], bq = b[id[q]];
+                const int sa = (aq > ap) - (aq < ap), sb = (bq > bp) - (bq < bp);
+                C += sa * sb > 0;
+                D += sa * sb < 0;
+            }
+        }
+        row[0] = n; row[1] = C; row[2] = D; row[3] = tied[0]; row[4] = tied[1];
+        row[5] = saa; row[6] = sbb; row[7] = sab; row[8] = kg; row[9] = inter;
+    }
+    return 0;
+}
+
 // ---- all-pairs intervention readout (cal_amd/csrc/intervene.hip): the same folded form, dot products accumulated in fp64 ----
 HOST_EXPORT int64_t cal_intervene_ws(int64_t, int64_t, int64_t, int64_t) { return 0; }
 

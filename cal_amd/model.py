@@ -194,6 +194,16 @@ class _CausalBase(torch.nn.Module):
         from .splice import structure_intervention
         return structure_intervention(self, data, **kw)
 
+    def occlusion(self, data, **kw):
+        """``cal_amd.occlude.occlusion(self, data, **kw)``: leave-one-out scores of every edge column or node."""
+        from .occlude import occlusion
+        return occlusion(self, data, **kw)
+
+    def faithfulness(self, data, **kw):
+        """``cal_amd.occlude.faithfulness(self, data, **kw)``: the causal scores against the occlusion scores."""
+        from .occlude import faithfulness
+        return faithfulness(self, data, **kw)
+
     def explain(self, data, **kw):
         """``cal_amd.explain.explain(self, data, **kw)``: per-graph top-k causal subgraphs of ``data``."""
         from .explain import explain

@@ -409,6 +409,54 @@ CAL_API int cal_graph_splice_write(const int64_t* eia, int64_t Ea, int64_t Na, c
                                    int64_t* batch_out, float* x_out, int64_t* edge_index_out, int64_t* node_src,
                                    int64_t* edge_src, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- occlusion replicas: R copies of graphs of one batch, each with one element removed (cal_amd/occlude.py occlude_batch) ----
+ * The batch is x [N, F] fp32 (or null, F = 0), edge_index [2, E] int64, ptr / edge_ptr [B+1] int64 as in cal_subgraph_extract.
+ * Replica r (of R) is graph g = rep_graph[r]; an id outside [0, B) gives a replica with no node and no column.  rep_elem[r] is a
+ * GLOBAL id of the batch.  mode 0 (edges): a column of g; all nodes of g stay in order, all columns of g stay in order except
+ * rep_elem[r] and -- when twin (int32 [E], as cal_edge_twin writes it; or null) is given and twin[rep_elem[r]] >= 0 -- that twin
+ * column (a self loop is its own twin: one column goes).  mode 1 (nodes): a node of g; its row is left out, later nodes move
+ * down by one, every column incident to it is dropped and the remaining endpoints are rewritten.  In both modes a rep_elem[r]
+ * that is no column / node of g (-1, say) removes nothing: the control replica.  A source column with an endpoint outside its
+ * graph's node range is dropped, as in the splice.  Every integer output is uniquely determined.
+ *   cal_occlude_count: ONE launch.  ptr_out / edge_ptr_out [R+1] and totals [5] int64 on the device: N', E', max_nodes',
+ *     max_edges', replicas with no node.  The per-replica counts stay in ws.  The caller reads totals back once.
+ *   cal_occlude_write: ONE launch with the same inputs, the same ws and Nout = totals[0], Eout = totals[1].  batch_out [N'],
+ *     x_out [N', F] (row copies; null with F = 0), edge_index_out (a contiguous [2, E']), node_src [N'] / edge_src [E'] (the
+ *     source node / column of every new one).  The rows are copied 16 bytes per lane when F % 4 == 0 and x, x_out are 16-byte
+ *     aligned, else element by element (0 <= F < 2^22).
+ * ws: 8-byte aligned, cal_occlude_ws bytes.  Everything on `stream`, no synchronisation inside; no value that reaches an output
+ * is accumulated atomically (the completion ticket and the ordered scan of cal_graph_splice_count).  R = 0: nothing is launched
+ * (the count zeroes totals and the two offsets with memsets). */
+CAL_API int64_t cal_occlude_ws(int64_t E, int64_t R);
+CAL_API int cal_occlude_count(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                              int64_t B, const int64_t* rep_graph, const int64_t* rep_elem, int64_t R, int mode,
+                              const int32_t* twin, int64_t* ptr_out, int64_t* edge_ptr_out, int64_t* totals, void* ws,
+                              int64_t ws_bytes, void* stream);
+CAL_API int cal_occlude_write(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                              int64_t B, const int64_t* rep_graph, const int64_t* rep_elem, int64_t R, int mode,
+                              const int32_t* twin, const float* x, int64_t F, const int64_t* ptr_out,
+                              const int64_t* edge_ptr_out, int64_t Nout, int64_t Eout, int64_t* batch_out, float* x_out,
+                              int64_t* edge_index_out, int64_t* node_src, int64_t* edge_src, void* ws, int64_t ws_bytes,
+                              void* stream);
+
+/* ---- rank agreement of two score vectors, per segment, in integers (cal_amd/occlude.py rank_agreement) ----------------------
+ * a, b fp32 [M]; segment g is [seg_ptr[g], seg_ptr[g+1]).  An element takes part iff sel (uint8 [M] or null) marks it and
+ * neither a nor b is NaN there; values compare as floats (-0 == +0).  k_code / k_val are cal_explain_rank's k / ratio
+ * (k_code >= 0: top k; -1: ceil(k_val n)); there is no ground truth here.  counts [B, 10] int64 per segment:
+ *   n (elements taking part), C (concordant pairs), D (discordant pairs), Ta (pairs with equal a, whatever b), Tb (pairs with
+ *   equal b, whatever a: a pair tied in both counts in Ta and in Tb), Saa = sum (2ra)^2, Sbb = sum (2rb)^2, Sab = sum (2ra)(2rb)
+ *   with 2r_i = 2 #{j: v_j < v_i} + #{j: v_j = v_i} + 1 the doubled mid-rank, k_g = min(k, n) or min(n, ceil(k_val n)), and
+ *   inter = |top-k_g(a) & top-k_g(b)|, each top-k in cal_explain_rank's order (value descending, then element index).
+ * A segment longer than max_seg gets n = -1 and zeros.  max_seg < 2^20, so every sum fits int64.  All sums are integers: the
+ * result has the same bits on the GPU, in the host library and in any order of summation.  Segments within
+ * cal_explain_lds_cap(): one launch, no ws.  Above it the j loop runs in LDS-sized tiles over a grid of row chunks whose
+ * partial sums go through ws (8-byte aligned, cal_rank_agreement_ws bytes) and are added in order by a second small launch.
+ * No atomics, no synchronisation, no read-back.  B = 0: nothing is launched. */
+CAL_API int64_t cal_rank_agreement_ws(int64_t M, int64_t B, int64_t max_seg);
+CAL_API int cal_rank_agreement(const float* a, const float* b, int64_t M, const int64_t* seg_ptr, int64_t B, int64_t max_seg,
+                               const uint8_t* sel, int64_t k_code, double k_val, int64_t* counts, void* ws, int64_t ws_bytes,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif
