@@ -282,6 +282,30 @@ CAL_API int cal_sparse_probe_edge_att(const int* ptr, const int* nbr, const int*
 CAL_API int cal_sparse_probe_pool(int sel, const float* hc, const float* ho, const int* gptr, const int64_t* batch, float* pooled,
                                   float* cnt, float* slices, int64_t N, int64_t B, int64_t H, int64_t rpb_n, int64_t* S_out,
                                   void* stream);
+/* test hooks (end of csrc/gat.hip, GPU only) of the GATConv kernels.  0 launched, 2 refused with a message.
+ * cal_gat_probe_fwd / _bwd: cal_gat_fwd / cal_gat_bwd with the arguments those pin to null -- ctr (DEVICE; the step engine's
+ * per-step counter: the mask seed becomes seed + *ctr * 0x9E3779B97F4A7C15 mod 2^64), and part_out (DEVICE,
+ * [cal_gat_datt_parts(N)][2 K D] floats: the d att partial rows go there and datt is not written) + nparts (HOST, receives that
+ * row count).
+ * cal_gat_probe_ws_layout: out[4] (host) = float offsets of draw [(E + N) K], dadst [N K], dasrc [N K] and the d att partial
+ * rows inside a cal_gat_bwd workspace.
+ * cal_gat_probe_last_launch: name of the latest launch site this library passed ("k_gat_fwd_w", "k_gat_fwd_fused", ...).
+ * cal_gat_probe_exp2: out[t] = exp2f(in[t]) (raw = 0), the bare v_exp_f32 (raw = 1) or expf(in[t]) (raw = 2, the two-pass
+ * forward), the forms the kernels use. */
+CAL_API int cal_gat_probe_fwd(const int32_t* rowptr_dst, const int32_t* nbr_dst, const int32_t* eid_dst,
+                              const float* z, const float* att, const float* bias, int relu, float slope,
+                              float p, uint64_t seed, const uint64_t* ctr, float* out, float* adst, float* asrc,
+                              float* mx, float* den, int64_t N, int64_t E, int64_t K, int64_t D, void* stream);
+CAL_API int cal_gat_probe_bwd(const int32_t* rowptr_dst, const int32_t* nbr_dst, const int32_t* eid_dst,
+                              const int32_t* rowptr_src, const int32_t* nbr_src, const int32_t* eid_src,
+                              const float* z, const float* att, const float* adst, const float* asrc,
+                              const float* mx, const float* den, const float* gout, float slope, float p,
+                              uint64_t seed, const uint64_t* ctr, float* dz, float* datt, float* ws, int64_t N,
+                              int64_t E, int64_t K, int64_t D, float* part_out, int* nparts, void* stream);
+CAL_API int cal_gat_probe_ws_layout(int64_t N, int64_t E, int64_t K, int64_t D, int64_t* out);
+CAL_API int cal_gat_datt_parts(int64_t N);
+CAL_API const char* cal_gat_probe_last_launch(void);
+CAL_API int cal_gat_probe_exp2(const float* in, float* out, int64_t n, int raw, void* stream);
 /* name of launch site k (1-based) of the latest untruncated cal_engine_step; "" past the end */
 CAL_API const char* cal_engine_stage_name(int k);
 /* live HIP-event timing of the node-level GEMMs (class 0, work = flops) and aggregations (class 1,

@@ -11,13 +11,15 @@ NCAN = 256
 
 
 class Buf:
-    """n elements on the GPU with a canary block of NCAN elements behind them (the contract tests: every operand and output)"""
+    """n elements on the GPU with a canary block of NCAN elements behind them (the contract tests: every operand and output).
+    off > 0: the elements start `off` elements past the (256 B aligned) allocation, the elements in front are canaries too --
+    what a torch view with a storage offset hands a kernel (off = 1: a float operand that is not 16 B aligned)"""
 
-    def __init__(self, pool, n, dtype=torch.float32, fill=None, data=None):
-        self.n = int(n)
-        self.full = torch.empty(self.n + NCAN, dtype=dtype, device="cuda")
-        self.full[self.n:] = CANARY
-        self.t = self.full[:self.n]
+    def __init__(self, pool, n, dtype=torch.float32, fill=None, data=None, off=0):
+        self.n, self.off = int(n), int(off)
+        self.full = torch.empty(self.off + self.n + NCAN, dtype=dtype, device="cuda")
+        self.full.fill_(CANARY)
+        self.t = self.full[self.off:self.off + self.n]
         if data is not None:
             self.t.copy_(data.reshape(-1).to(dtype))
         elif fill is not None:
@@ -25,10 +27,10 @@ class Buf:
         pool.append(self)
 
     def ptr(self):
-        return self.full.data_ptr()
+        return self.t.data_ptr() if self.n else self.full.data_ptr() + self.off * self.full.element_size()
 
     def intact(self):
-        return bool((self.full[self.n:] == CANARY).all().item())
+        return bool((self.full[self.off + self.n:] == CANARY).all().item() and (self.full[:self.off] == CANARY).all().item())
 
 
 def pool_intact(pool):
