@@ -41,6 +41,10 @@
 extern "C" int cal_launch_gconv_bwd_att(unsigned gx, unsigned gy, hipStream_t st, hipEvent_t e0, hipEvent_t e1, const void* csr, size_t csr_bytes,
                                         const int* gptr, const int* eptr, const void* branches, size_t branches_bytes, float loop_w, int N, int H,
                                         int K, int* status, const void* att, size_t att_bytes);
+// gconv_bwd_seq.hip: launches the k_gconv_bwd instantiations that run the dX' and dW products one after the other (CAL_GCB_ORDER)
+extern "C" int cal_launch_gconv_bwd_seq(int sel, unsigned gx, unsigned gy, unsigned gz, hipStream_t st, hipEvent_t e0, hipEvent_t e1, const void* csr,
+                                        size_t csr_bytes, const int* gptr, const int* eptr, const void* branches, size_t branches_bytes, float loop_w,
+                                        int N, int H, int K, int* status);
 
 namespace cal {
 
@@ -879,6 +883,17 @@ int gconv_bwd(Ctx& c, Bwd& b, GconvBwdBranch* gb, int nb, float** dst, double** 
     const bool tiles = e->ntiles > 0;
     auto kern = co ? (lean ? (tiles ? k_gconv_bwd<true, 2, true, true> : k_gconv_bwd<true, 2, false, true>) : tiles ? k_gconv_bwd<true, 2, true> : k_gconv_bwd<true, 2>)
               : gb[0].dout ? (lean ? k_gconv_bwd<false, 0, false, true> : k_gconv_bwd<false, 0>) : lean ? k_gconv_bwd<false, 1, false, true> : k_gconv_bwd<false, 1>;
+    // order 1 of the two products (engine_gconv_bwd.hpp: the non-LEAN instantiations; 2: all): those kernels are in
+    // gconv_bwd_seq.hip, a code object of their own -- the instantiations named above keep this file's device code what it was
+    if (CAL_GCB_ORDER != 0 && (!lean || CAL_GCB_ORDER == 2)) {
+        const int sel = (co ? 1 : 0) | (co && tiles ? 2 : 0) | (!co && gb[0].dout ? 4 : 0) | (lean ? 8 : 0);
+        const int rc = cal_launch_gconv_bwd_seq(sel, grid.x, grid.y, grid.z, c.st, g_prof_cur ? g_prof_cur->r.e0 : nullptr, g_prof_cur ? g_prof_cur->r.e1 : nullptr,
+                                                &gd, sizeof(gd), e->gptr, e->eptr, &b2, sizeof(b2), e->loop_w, c.N, H, H, e->status);
+        if (rc) { set_error(rc == 2 ? "k_gconv_bwd: argument structures differ between engine.hip and gconv_bwd_seq.hip" : "k_gconv_bwd: instantiation missing from gconv_bwd_seq.hip"); return 2; }
+        if (g_prof_cur) g_prof_cur->used = true;
+        CAL_CHECK_LAUNCH("k_gconv_bwd");
+        return 0;
+    }
     PROF_LAUNCH(kern, grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, e->status);
     CAL_CHECK_LAUNCH("k_gconv_bwd");
     return 0;
@@ -2421,6 +2436,10 @@ CAL_EXPORT int cal_sparse_probe_pool(int sel, const float* hc, const float* ho, 
 #ifdef CAL_BLK_CLOCKS
 CAL_EXPORT int cal_debug_blk_clocks(long long* out) {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(cal::g_blk_clk), sizeof(long long) * 8192);
+}
+// marks 4 .. 7 (BLK_CLK_X); the ATT entry's copies of both buffers: cal_debug_blk_clocks_att (gconv_bwd_att.hip)
+CAL_EXPORT int cal_debug_blk_clocks_x(long long* out) {
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(cal::g_blk_clk_x), sizeof(long long) * 8192);
 }
 #endif
 #ifdef CAL_RO_CLOCKS

@@ -13,13 +13,35 @@
 //
 //   grid (B graphs, H / 64 slices, branches), 512 threads; graphs of at most 64 nodes / 1024 stored edges
 //   (cal_engine_set_graph_bounds), K = H in {64, 128}.  LDS ~115-135 KB: one workgroup per CU, so it brings its
-//   own latency hiding: 8 waves -- waves 0-3 run the dX' product and its epilogue while waves 4-7 run the
-//   dW product (both only need dz), and twice as many loads are in flight while staging.
+//   own latency hiding: 8 waves, and twice as many loads are in flight while staging.  Behind dz both products only
+//   need dz.  Order 1 (CAL_GCB_ORDER below, the non-LEAN instantiations): all eight waves run the dX' product, one
+//   32 x 32 tile each, then all eight the dW product -- what other workgroups and the next kernel wait for (the dX'
+//   tiles, the column-sum fold, the striped atomics) leaves under dW's MFMAs, and dW's slab has no reader before
+//   k_finish.  Order 0 (LEAN): waves 0-3 run dX' and its epilogue while waves 4-7 run dW.
 #pragma once
 #include "engine_gconv.hpp"
 #include "engine_attphases.hpp"
 
 namespace cal {
+
+// Order of the two products behind P1, chosen at build time (-DCAL_GCB_ORDER=0|1 through CAL_HIPCC_EXTRA of build.py).
+// 0: waves 0-3 run dX' and its epilogue while waves 4-7 run dW.  1: all eight waves run dX' (one 32 x 32 tile each), then all
+// eight run dW, so that the dX' tiles, the column-sum fold and the striped atomics leave under dW's MFMAs instead of behind
+// them.  Same results bit for bit.  The LEAN instantiations keep order 0 (their W rows are L2 reads in the dX' product, which
+// order 1 doubles); 2 = order 1 in the LEAN instantiations too, a measuring build only.  The default is what the A/B of
+// profiles/r10/ab_bwd_order.txt decided.
+// Order 1 lives in the translation units that define CAL_GCB_UNIT in front of this header (gconv_bwd_seq.hip: the non-LEAN
+// instantiations of k_gconv_bwd; gconv_bwd_att.hip: the ATT entry).  engine.hip always compiles order 0, the text it has always
+// had: its k_gconv_bwd instantiations serve the LEAN launches (and every launch of an order-0 build), and its code object does
+// not move when the order changes (steps that never launch these kernels lost 0.1-0.45 % when it did).
+#ifndef CAL_GCB_ORDER
+#define CAL_GCB_ORDER 1
+#endif
+#ifdef CAL_GCB_UNIT
+constexpr bool GCB_SEQ = CAL_GCB_ORDER != 0, GCB_SEQ_LEAN = CAL_GCB_ORDER == 2;
+#else
+constexpr bool GCB_SEQ = false, GCB_SEQ_LEAN = false;
+#endif
 
 constexpr int GB_NT = 512;                // threads per workgroup
 constexpr int GB_T = 64;                  // nodes per graph

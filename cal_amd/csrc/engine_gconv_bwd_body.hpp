@@ -1,5 +1,6 @@
 // The body of the per-graph GCNConv backward kernels (engine_gconv_bwd.hpp has the description), included as TEXT by its two
-// entries: k_gconv_bwd<RS, MODE, TILED, LEAN> (engine_gconv_bwd.hpp; MODE 0-2) and k_gconv_bwd_att (gconv_bwd_att.hip; MODE 3 = ATT,
+// entries: k_gconv_bwd<RS, MODE, TILED, LEAN> (engine_gconv_bwd.hpp; MODE 0-2; instantiated in engine.hip with the products in
+// order 0 and in gconv_bwd_seq.hip in the build's order) and k_gconv_bwd_att (gconv_bwd_att.hip; MODE 3 = ATT,
 // RS / TILED / LEAN false).  Text and not a __device__ function: as a function the instantiations of k_gconv_bwd came out a few
 // scalar instructions different from what they were, and every kernel behind them in the code object moved.
 // In scope at the point of inclusion: RS, MODE, TILED, LEAN (compile-time), the kernel arguments g, gptr, eptr, bb, loop_w, N, H, K,
@@ -423,6 +424,78 @@
         }
         __syncthreads();
     }
+    // The two products behind P1, in the order CAL_GCB_ORDER chooses at build time (engine_gconv_bwd.hpp; LEAN keeps order 0
+    // unless the build says 2).
+    constexpr bool SEQ = GCB_SEQ && (!LEAN || GCB_SEQ_LEAN);
+    if constexpr (SEQ) {
+    // ---- order 1, stage A: partial dX' on all eight waves -- wave (rt = w >> 2, kq = w & 3) owns row tile rt x input columns
+    // kq * 32 .. + 31 (H = 64: kq 0, 1).  Every element keeps the reduction order of P2 below (mma_rowk, the same k walk).
+    {
+        const int rt = w >> 2, kq = w & 3, k = kq * 32 + li;
+        const bool on = kq * 32 < K;
+        // the column sums keep P2's operation sequence: four fp32 chains per sum over the lane's 16 terms of row tile 0, then over
+        // its 16 of row tile 1 -- the tile-0 wave parks its 4 + 4 floats per lane (in the adjacency block, dead behind P1), the
+        // tile-1 wave picks them up behind ONE barrier and goes on (a graph of <= 32 rows: with zero terms, as P2 adds zero
+        // accumulators), folds and adds.  The tile-0 waves enter stage B straight from the barrier: what the consumers wait for
+        // -- the dX' tiles, the fold, the striped atomics -- drains under stage B's MFMAs.
+        float4* const park = reinterpret_cast<float4*>(Ab);
+        float xh[16];
+        float f1[4] = {0.f, 0.f, 0.f, 0.f}, f2[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[0][i] = 0.f;
+        if (on) {
+            // (LEAN: the lane's W row straight from global memory / L2, as in P2 -- read by the waves of both row tiles)
+            const float* wrow = LEAN ? br.W + (size_t)k * H + ns0 : Ws + k * GB_LDD;
+            if (rt < R) mma_rowk(Ds + (rt * 32 + li) * GB_LDD, wrow, GC_N, lk, acc[0]);
+            BLK_CLK_X(4, 4, acc[0][15]);                 // (clocks build: the dX' accumulator of wave 4 is done)
+            // x_hat of the tile's rows as ONE batch of unconditional LDS reads, masked after the read (see P2)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) xh[r] = Xs[(mma_row(r, lk, rt * 32)) * LDX + k];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { asm volatile("" : "+v"(xh[r])); if (rt >= R) xh[r] = 0.f; }
+            float* dxp = sl ? br.dxp1 : br.dxp0;
+            if (rt < R) gc_store_tile<gc_site(WT_DXP)>(acc[0], dxp + (size_t)(g0 + rt * 32) * K + kq * 32, K, rows - rt * 32, li, lk, MmaIdent(),
+                                                       ((rows - rt * 32) * K - kq * 32) * 4);
+            if (rt == 0) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { const float v = acc[0][r]; f1[r & 3] += v; f2[r & 3] = fmaf(v, xh[r], f2[r & 3]); }
+                park[(2 * kq) * 64 + lane] = make_float4(f1[0], f1[1], f1[2], f1[3]);
+                park[(2 * kq + 1) * 64 + lane] = make_float4(f2[0], f2[1], f2[2], f2[3]);
+            }
+        }
+        __syncthreads();
+        if (!ATT) BLK_CLK(3);
+        if (on && rt == 1) {
+            const float4 p1 = park[(2 * kq) * 64 + lane], p2 = park[(2 * kq + 1) * 64 + lane];
+            f1[0] = p1.x; f1[1] = p1.y; f1[2] = p1.z; f1[3] = p1.w;
+            f2[0] = p2.x; f2[1] = p2.y; f2[2] = p2.z; f2[3] = p2.w;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { const float v = acc[0][r]; f1[r & 3] += v; f2[r & 3] = fmaf(v, xh[r], f2[r & 3]); }
+            double s1, s2;
+            colsum_fold(f1, f2, s1, s2);
+            if (lk == 0) {
+                if (br.dacc_sum) {
+                    const size_t po = (size_t)stripe_of_block() * br.dacc_ss + k;
+                    atomicAdd(br.dacc_sum + po, s1); atomicAdd(br.dacc_prod + po, s2);
+                } else { parts[k] = s1; parts[K + k] = s2; }
+            }
+        }
+        BLK_CLK_X(5, 4, f1[0]);                          // (clocks build: the tile and the atomics of wave 4 have left)
+    }
+    // ---- order 1, stage B: dW[:, ns] (this graph) on all eight waves -- the (K / 32) x 2 tiles of the slab slice one per wave
+    // (wave w: input-column tile w % (K / 32), slice half w / (K / 32); H = 64: waves 0-3).  Per element the reduction order of P3.
+    if (w < (K >> 4)) {
+        const int ct = w >= (K >> 5) ? 1 : 0, kt = w - ct * (K >> 5), k = kt * 32 + li;
+        const float gam = gam_s[k], bet = bet_s[k];
+        auto affine = [&](float v) { return fmaf(v, gam, bet); };
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[0][i] = 0.f;
+        mma_kmajor_ptrs<1, 1, LDX, GB_LDD>(Xs + kt * 32 + li, nullptr, Ds + ct * 32 + li, nullptr, rowsP, lk, affine, MmaIdent(), acc);
+        const int off = kt * 32 * H + ns0 + ct * 32;         // (the extent: to the end of this graph's slab)
+        gc_store_tile<gc_site(WT_DW)>(acc[0], slab + off, H, 32, li, lk, MmaIdent(), (K * H - off) * 4);
+    }
+    BLK_CLK_X(6, 4, acc[0][15]);                         // (clocks build: the slab tile of wave 4, the last to enter stage B, has left)
+    } else {
     // ---- P2: partial dX'[:, :] = dz[:, ns] W[:, ns]^T   (rows i x K columns, reduction over the 64 columns of ns) ------
     if (w < 4 && w * 32 < K) {
 #pragma unroll
@@ -433,6 +506,7 @@
         const float* wrow = LEAN ? br.W + (size_t)min(w * 32 + li, K - 1) * H + ns0 : Ws + (w * 32 + li) * GB_LDD;
         if (R == 2) mma_rowk<true>(Ds + li * GB_LDD, Ds + (32 + li) * GB_LDD, wrow, GC_N, lk, acc[0], acc[1]);
         else mma_rowk<false>(Ds + li * GB_LDD, nullptr, wrow, GC_N, lk, acc[0], acc[1]);
+        BLK_CLK_X(4, 0, acc[0][15]);                     // (clocks build: the dX' accumulators of wave 0 are done)
         const int k = w * 32 + li;
         float* dxp = sl ? br.dxp1 : br.dxp0;
         // x_hat of all rows first, as ONE batch of unconditional LDS reads (rows rows .. rowsP are zero, as are their dz;
@@ -473,6 +547,7 @@
                 atomicAdd(br.dacc_sum + po, s1); atomicAdd(br.dacc_prod + po, s2);
             } else { parts[k] = s1; parts[K + k] = s2; }
         }
+        BLK_CLK_X(5, 0, f1[0]);                          // (clocks build: the tiles and the atomics of wave 0 have left)
     }
     if (!ATT) BLK_CLK(3);
     // ---- P3: dW[:, ns] (this graph) = x'^T dz[:, ns]   (K rows x 64 columns, reduction over the graph's nodes) ---------
@@ -488,5 +563,7 @@
             const int off = wq * 32 * H + ns0 + q * 32;      // (the extent: to the end of this graph's slab)
             gc_store_tile<gc_site(WT_DW)>(acc[q], slab + off, H, 32, li, lk, MmaIdent(), (K * H - off) * 4);
         }
+        BLK_CLK_X(6, 4, acc[1][15]);                     // (clocks build: the slab tiles of wave 4 have left)
+    }
     }
     BLK_CLK(1);

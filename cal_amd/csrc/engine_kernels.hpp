@@ -19,9 +19,17 @@ __device__ long long g_blk_clk[4 * 2048];     // 4 timestamps per workgroup: ent
 #define BLK_CLK_W(which, wv, dep) do { const int b_ = blockIdx.x + gridDim.x * blockIdx.y; int d_; \
                             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\tv_readfirstlane_b32 %0, %1" : "=s"(d_) : "v"(dep)); \
                             if ((int)threadIdx.x == 64 * (wv) && b_ < 2048) g_blk_clk[4 * b_ + ((which) == 1 ? 3 : (which) == 0 ? 0 : (which) - 1)] = wall_clock64() + (d_ & 0); } while (0)
+// four more marks per workgroup (which = 4 .. 7) in a buffer of their own, taken like BLK_CLK_W but with the wait on wave `wv`
+// alone (the other waves of the workgroup run on undisturbed): the products of k_gconv_bwd
+__device__ long long g_blk_clk_x[4 * 2048];
+#define BLK_CLK_X(which, wv, dep) do { if (__builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) == (wv)) { \
+                            const int b_ = blockIdx.x + gridDim.x * blockIdx.y; int d_; \
+                            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\tv_readfirstlane_b32 %0, %1" : "=s"(d_) : "v"(dep)); \
+                            if ((int)threadIdx.x == 64 * (wv) && b_ < 2048) g_blk_clk_x[4 * b_ + (which) - 4] = wall_clock64() + (d_ & 0); } } while (0)
 #else
 #define BLK_CLK(which) do {} while (0)
 #define BLK_CLK_W(which, wv, dep) do {} while (0)
+#define BLK_CLK_X(which, wv, dep) do {} while (0)
 #endif
 
 struct CSR {

@@ -15,6 +15,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#define CAL_GCB_UNIT              // this unit takes the build's order of the two products (engine_gconv_bwd.hpp)
 namespace {
 #include "engine_kernels.hpp"
 #include "engine_readout.hpp"
@@ -47,3 +48,11 @@ extern "C" int cal_launch_gconv_bwd_att(unsigned gx, unsigned gy, hipStream_t st
     else hipLaunchKernelGGL(k_gconv_bwd_att, grid, dim3(GB_NT), 0, st, g, gptr, eptr, bb, loop_w, N, H, K, status, ga);
     return 0;
 }
+
+#ifdef CAL_BLK_CLOCKS
+// this translation unit's copies of the clock buffers (engine_kernels.hpp): marks 0 .. 3 to out, 4 .. 7 to outx, 8192 values each
+extern "C" __attribute__((visibility("default"))) int cal_debug_blk_clocks_att(long long* out, long long* outx) {
+    const int rc = (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(cal::g_blk_clk), sizeof(long long) * 8192);
+    return rc ? rc : (int)hipMemcpyFromSymbol(outx, HIP_SYMBOL(cal::g_blk_clk_x), sizeof(long long) * 8192);
+}
+#endif
