@@ -36,7 +36,12 @@
 #include "engine_feat.hpp"
 #include "engine_gwide.hpp"
 #include "engine_attwide.hpp"
+#include "engine_attfwd_fold.hpp"     // AttFwdFoldArgs (the kernel that takes them is in gconv_fwd_att.hip)
 
+// gconv_fwd_att.hip: launches k_gconv_fwd_att (the last backbone layer's per-graph forward with the attention forward as its tail)
+extern "C" int cal_launch_gconv_fwd_att(unsigned gx, hipStream_t st, hipEvent_t e0, hipEvent_t e1, const void* csr, size_t csr_bytes,
+                                        const int* gptr, const int* eptr, const void* branches, size_t branches_bytes, int relu, float loop_w,
+                                        int H, int K, int* status, const void* att, size_t att_bytes);
 // gconv_bwd_att.hip: launches k_gconv_bwd_att (the per-graph GCNConv backward's ATT mode); structures as untyped pointers + sizes
 extern "C" int cal_launch_gconv_bwd_att(unsigned gx, unsigned gy, hipStream_t st, hipEvent_t e0, hipEvent_t e1, const void* csr, size_t csr_bytes,
                                         const int* gptr, const int* eptr, const void* branches, size_t branches_bytes, float loop_w, int N, int H,
@@ -204,7 +209,7 @@ struct Engine {
     BNSlot bn[MAX_LAYERS + 9];
     int nbn;
     // arena offsets (doubles)
-    int a_convb[MAX_LAYERS], a_cb, a_ob, a_dwn, a_dwe, a_db1, a_db2, a_sync, arena_n, bn_plane;
+    int a_convb[MAX_LAYERS], a_cb, a_ob, a_dwn, a_dwe, a_db1, a_db2, a_sync, a_aff, arena_n, bn_plane;
     // workspace
     char* ws; size_t ws_bytes;
     int64_t capN, capE, capB;
@@ -218,7 +223,10 @@ struct Engine {
     int bn0_dirty_host;      // host twin of the device word status[3]: a training forward has been enqueued since the last k_finish
     int att_fold;            // 1: the per-graph attention backward runs inside the last backbone layer's k_gconv_bwd launch (its ATT mode);
                              // CAL_AMD_ATT_FOLD=0 keeps the two launches
-    int gwide;               // 1: graphs of 129 .. 256 nodes run the wide per-graph convolutions (engine_gwide.hpp); CAL_AMD_GWIDE=0: the node-level chain
+    int att_fwd_fold;        // 1: the per-graph attention forward runs as the tail of the last backbone layer's forward launch (k_gconv_fwd_att);
+                             // CAL_AMD_ATT_FWD_FOLD=0 / cal_engine_set_att_fwd_fold(h, 0) keep the two launches
+    float* att_xch;          // [AFF_MAXT][2][AFF_XCH] partial attention dots the two slice workgroups of a graph exchange in that launch
+    int gwide;              // 1: graphs of 129 .. 256 nodes run the wide per-graph convolutions (engine_gwide.hpp); CAL_AMD_GWIDE=0: the node-level chain
     int ro_step;             // 1: training steps run the readout as one launch (k_ro_step); CAL_AMD_RO_STEP=0 keeps the four kernels
     float *dzl, *dyh1, *dy1, *dxh, *dpool, *dZco, *gn, *gself, *ddeg, *dl, *dzco, *dXhco, *dZ, *dzi, *dXh, *slabs;
     size_t slab_floats;
@@ -282,6 +290,7 @@ CAL_EXPORT void* cal_engine_create(int64_t F, int64_t H, int64_t C, int64_t L) {
     else { (void)hipGetLastError(); e->host_status = nullptr; }       // (no mirror: cal_engine_peek_status reports 0, check_status still works)
     e->ro_step = env_on("CAL_AMD_RO_STEP"); e->ro_rows = env_on("CAL_AMD_RO_ROWS"); e->striped = env_on("CAL_AMD_STRIPED");
     e->gwide = env_on("CAL_AMD_GWIDE"); e->fold_zero = env_on("CAL_AMD_FOLD_ZERO"); e->att_fold = env_on("CAL_AMD_ATT_FOLD");
+    e->att_fwd_fold = env_on("CAL_AMD_ATT_FWD_FOLD");
     e->adam_fused = env_on("CAL_AMD_ADAM_FUSED");
     e->bn0_dirty_host = 1;
     {
@@ -311,6 +320,14 @@ CAL_EXPORT void cal_engine_destroy(void* h) {
 
 CAL_EXPORT int64_t cal_engine_num_param_slots(void* h) { Engine* e = (Engine*)h; return 3 + (e->gin ? 6 : 4) * e->L + 12 + 24; }
 CAL_EXPORT int64_t cal_engine_num_bn(void* h) { return ((Engine*)h)->nbn; }
+// Where BatchNorm k's batch sums live in the fp64 arena (tests read them back): out = {offset of the column sums (plane 0), padded
+// width -- the sums of squares follow that many doubles later --, distance of the NSTRIPE accumulator planes}, all in doubles
+CAL_EXPORT int cal_engine_bn_arena(void* h, int64_t k, int64_t* out) {
+    Engine* e = (Engine*)h;
+    CAL_REQUIRE(e != nullptr && out != nullptr && k >= 0 && k < e->nbn, "bad arguments");
+    out[0] = e->bn[k].arena; out[1] = (e->bn[k].width + 3) / 4 * 4; out[2] = e->bn_plane;
+    return 0;
+}
 
 // Bind the flat parameter / gradient / Adam-state buffers.
 //   offs[slot]: float offset of every parameter inside P (and G, M1, M2), slots in the order
@@ -361,6 +378,7 @@ CAL_EXPORT int cal_engine_bind(void* h, float* P, float* G, float* M1, float* M2
     e->a_db1 = a; a += 3 * H;
     e->a_db2 = a; a += (3 * C + 3) / 4 * 4;
     e->a_sync = a; a += (RBK_SYNC_INTS + 1) / 2 + 2;  // barrier counters of k_ro_step (ints: 6, or RBK_SYNC_INTS row-blocked), zeroed with the arena
+    e->a_aff = a; a += AFF_MAXT;                      // k_gconv_fwd_att's flags (ints: two per graph), zeroed with the arena
     // the BatchNorm sums last: NSTRIPE planes of them, bn_plane doubles apart (engine.hpp: stripe_sum); BNSlot::arena is plane 0
     a = (a + 3) / 4 * 4;
     const int a_bn = a;
@@ -432,6 +450,7 @@ static size_t engine_layout(Engine* e, int64_t N, int64_t E, int64_t B, bool ass
         F32(e->gz, (L > 0 ? L : 1) * N * H); F32(e->gsc, (L > 0 ? L : 1) * 4 * al(N * K));
         F32(e->gws, (size_t)cal_gat_bwd_ws(N, E, K, H / K));
     }
+    F32(e->att_xch, (size_t)std::min<size_t>(B, AFF_MAXT) * 2 * AFF_XCH);
     return off * 4;
 }
 
@@ -521,6 +540,10 @@ struct Route {
     // the per-graph attention backward and the last backbone layer's backward are ONE launch (k_gconv_bwd's ATT mode builds dOut
     // from the attention backward instead of reading e->dZ): GCN layers on the one-workgroup-per-CU k_gconv_bwd only
     bool att_fold;
+    // the per-graph attention forward is the tail of the last backbone layer's forward launch (k_gconv_fwd_att, gconv_fwd_att.hip):
+    // GCN, H = 128 (the graph's two slice workgroups exchange their partial attention dots inside the launch), striped sums, and
+    // a launch of ONE round -- both workgroups of a graph are resident together (2 T <= CUs, one workgroup per CU)
+    bool att_fwd_fold;
     // causal convolutions: forward per graph up to 128 nodes, backward only for 64-node graphs of <= 512 units; where the
     // forward pooled per graph and the backward is node-level, the backward counts the positive rows itself (launch_pool_cnt)
     Conv co_fwd, co_bwd;
@@ -1064,6 +1087,8 @@ Route make_route(const Ctx& c, bool want_grad) {
     r.st_node = st && gcn && !gc && N > 0 && N < 16384;
     r.st_feat = (r.st_bb && !gin && !gw && r.feat_bwd == FeatBwd::Units) || r.st_node;
     r.st_co = gw ? st : st && ag && gcb && T <= 256;
+    r.att_fwd_fold = e->att_fwd_fold && gcn && r.bb_fwd == Conv::Graph64 && r.att_fwd == Att::Graph && H == 2 * GC_N && L >= 1 &&
+                     e->ntiles == 0 && r.st_co && 2 * T <= e->num_cus && T <= AFF_MAXT;
     // readout (the 2H-wide co head of cat takes the GEMM chain); row blocks: training steps of 129 .. 512 graphs
     const int B4 = (B + 15) & ~15;
     const bool ro = !e->cat && (size_t)B4 * (H + 4) <= (size_t)RO_LDS && B * H <= 16384 && H % RO_CW == 0 && B4 <= 256 && H <= 256 &&
@@ -1298,6 +1323,30 @@ int fwd_backbone(Ctx& c) {
             if (i == 1 && !r.plan_coef) gb.coef_out = e->coef; else gb.coef_in = e->coef;
             if (c.training && i < L) { gb.st_sum = graph_acc(c, bn_stsum(c, i + 1), H, r.st_bb); gb.st_sq = graph_acc(c, bn_stsq(c, i + 1), H, r.st_bb); }
             const GconvBranch2 b2{{gb, gb}};
+            if (i == L && r.att_fwd_fold) {
+                // the attention forward (fwd_att's per-graph kernel) as this launch's tail: k_gconv_fwd_att in gconv_fwd_att.hip, a code
+                // object of its own; inside a single-kernel ProfScope the dispatch carries its events
+                AttFwdFoldArgs fa;
+                memset(&fa, 0, sizeof(fa));
+                fa.gs = csr_src(c);
+                fa.Wn = e->P + e->o_natt_w; fa.bn = e->P + e->o_natt_b; fa.We = e->P + e->o_eatt_w; fa.be = e->P + e->o_eatt_b;
+                fa.anode = e->anode; fa.pq = e->pq; fa.att = e->att; fa.dis_c = e->dis_co; fa.dis_o = e->dis_co + N;
+                fa.stc_sum = graph_acc(c, bn_stsum(c, L + 1), H, true); fa.stc_sq = graph_acc(c, bn_stsq(c, L + 1), H, true);
+                fa.sto_sum = graph_acc(c, bn_stsum(c, L + 2), H, true); fa.sto_sq = graph_acc(c, bn_stsq(c, L + 2), H, true);
+                fa.E = E; fa.fnode = e->no_node_att ? 0.f : 1.f; fa.fedge = e->no_edge_att ? 0.f : 1.f;
+                fa.xch = e->att_xch; fa.flags = (int*)(e->arena + e->a_aff);
+                {
+                    ProfScope ps(st, 2, 2.0 * N * H * H + 2.0 * (double)(E + N) * H, true);
+                    if (cal_launch_gconv_fwd_att((unsigned)T, st, g_prof_cur ? g_prof_cur->r.e0 : nullptr, g_prof_cur ? g_prof_cur->r.e1 : nullptr, &gd, sizeof(gd),
+                                                 e->gptr, e->eptr, &b2, sizeof(b2), 1, e->loop_w, H, H, e->status, &fa, sizeof(fa))) {
+                        set_error("k_gconv_fwd_att: argument structures differ between engine.hip and gconv_fwd_att.hip"); return 2;
+                    }
+                    if (g_prof_cur) g_prof_cur->used = true;
+                }
+                CAL_CHECK_LAUNCH("k_gconv_fwd_att"); STAGE();
+                RC(flush_finals(c)); STAGE();
+                continue;
+            }
             {
                 ProfScope ps(st, 2, 2.0 * N * H * H + 2.0 * (double)(E + N) * H, true);
                 launch_gconv_fwd<1>(c, r.bb_fwd, r.gw_cols_bb, false, b2);
@@ -1333,6 +1382,7 @@ int fwd_att(Ctx& c) {
     hipStream_t st = c.st;
     const float* x = e->h + (size_t)L * N * H;
     const CSR gs = csr_src(c);
+    if (r.att_fwd_fold) return 0;         // done by the last backbone layer's launch (fwd_backbone: k_gconv_fwd_att)
     if (r.att_fwd != Att::Node) {
         // per graph: all of it in one kernel (4 rows per lane group); graphs of 129-256 nodes: the same kernel in four row passes,
         // four slots per lane (engine_attwide.hpp)
@@ -2360,6 +2410,14 @@ CAL_EXPORT int cal_engine_set_deterministic(void* h, int on) {
     Engine* e = (Engine*)h;
     CAL_REQUIRE(e != nullptr, "bad arguments");
     e->striped = on ? 0 : 1;
+    return 0;
+}
+// on = 0: the per-graph attention forward stays a launch of its own (k_att_fwd_graph) instead of the tail of the last backbone layer's
+// forward (Route::att_fwd_fold; what CAL_AMD_ATT_FWD_FOLD=0 selects process-wide).  Call before the first step is captured.
+CAL_EXPORT int cal_engine_set_att_fwd_fold(void* h, int on) {
+    Engine* e = (Engine*)h;
+    CAL_REQUIRE(e != nullptr, "bad arguments");
+    e->att_fwd_fold = on ? 1 : 0;
     return 0;
 }
 CAL_EXPORT int cal_engine_debug_stop(int k) { g_stop_after = k; return 0; }

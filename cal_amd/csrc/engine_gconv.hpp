@@ -22,6 +22,18 @@
 #include "engine_readout.hpp"     // RO_CLK profiling aid
 #include "engine_mma.hpp"         // 32 x 32 tile products, row mapping, tile stores
 #include "engine_gunit.hpp"       // unit extents, slot batch, operand tiles, BatchNorm tables, z tile / adjacency block, column sums
+// CAL_GCF_ATT_UNIT (gconv_fwd_att.hip alone defines it): the kernel below is compiled as k_gconv_fwd_att -- one more argument, the
+// attention forward's operands, and that forward as its tail (engine_attfwd_fold.hpp).  The additions are preprocessor blocks and
+// not `if constexpr`: without the macro the compiler sees the tokens it has always seen, and engine.hip's device code stays what
+// it was ("What decided the form").
+#ifdef CAL_GCF_ATT_UNIT
+#include "engine_attfwd_fold.hpp"
+#define GCF_KERNEL k_gconv_fwd_att
+#define GCF_ATT_PARAM , const AttFwdFoldArgs fa
+#else
+#define GCF_KERNEL k_gconv_fwd
+#define GCF_ATT_PARAM
+#endif
 
 namespace cal {
 
@@ -66,9 +78,9 @@ struct GconvBranch2 { GconvBranch b[2]; };
 constexpr int GC_LDX = GC_K + 4;            // x' rows as loaded: Xr[row * GC_LDX + k], stride 132 = 4 mod 32 (conflict-free 16 B reads)
 
 template <bool RS, int T, int NT = 256, bool TILED = false>
-__global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g, const int* __restrict__ gptr, const int* __restrict__ eptr,
+__global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) GCF_KERNEL(const CSR g, const int* __restrict__ gptr, const int* __restrict__ eptr,
                                                    const GconvBranch2 bb, int relu, float loop_w, int H,
-                                                   int K, int* __restrict__ status) {
+                                                   int K, int* __restrict__ status GCF_ATT_PARAM) {
     // NT = 256: one 32 x 32 tile pair per wave.  NT = 512 (T = 64): eight waves -- the first product's reduction range is
     // split over two waves per tile (partial z tiles combined through LDS), twice the lanes stage the operands, and waves
     // 4-7 are free for the adjacency block while waves 0-3 finish the z tile
@@ -86,8 +98,18 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
     __shared__ double red[4][2][32];
     __shared__ float pool_s[4][32];
     __shared__ unsigned char bg_s[TILED ? T : 4];        // TILED: graph (inside the tile) of every row
+#ifdef CAL_GCF_ATT_UNIT
+    static_assert(!RS && T == AFF_T && NT == 512 && !TILED && ECAP == AFF_E && GC_N == AFF_N, "the attention tail: the backbone's 64-node form");
+    __shared__ float Ot_att[AFF_T * AFF_LDO];           // the output tile, parked for the tail (an array of its own: with it the kernel's LDS is over half a CU's, ONE workgroup per CU)
+    __shared__ float4 wsl[AFF_ND * 16];                  // the six 64-float weight slices of the attention dots
+    AttFwdFoldLoads fr;
+#endif
     BLK_CLK(0);
+#ifdef CAL_GCF_ATT_UNIT
+    warm_kernargs<sizeof(CSR) + 2 * sizeof(void*) + sizeof(GconvBranch2) + 32 + sizeof(AttFwdFoldArgs)>();
+#else
     warm_kernargs<sizeof(CSR) + 2 * sizeof(void*) + sizeof(GconvBranch2) + 32>();
+#endif
     const GconvBranch& br = bb.b[blockIdx.z];           // indexed in the kernel-argument segment: one set of scalar loads (b0 / b1 as two parameters were loaded both and selected field by field)
     const int b = blockIdx.x, n0 = blockIdx.y * GC_N, t = threadIdx.x;
     // the W slice does not depend on the graph: requested before the graph's extents (a scalar round trip) are known
@@ -137,6 +159,9 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
     float bias = biasp[n0 + ct * 32 + li];
     BNRawS braws = bn_raws_load(br.bn, min(t, K - 1));       // (striped reader: the producer may be a per-graph kernel)
     slots.template load_coef<NT>(g, un, t, br.coef_in, br.dis);
+#ifdef CAL_GCF_ATT_UNIT
+    aff_issue(fr, fa, un, n0, H, t);                     // the tail's weight slices and (slice 0) by-source CSR rows, in the same round
+#endif
     // all of the above stay in flight together (engine_gunit.hpp)
 #pragma unroll
     for (int u = 0; u < UA; ++u) ro_pin(va[u]);
@@ -144,6 +169,9 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
     for (int u = 0; u < WU; ++u) ro_pin(vb[u]);
     bn_raws_pin(braws);
     slots.pin();
+#ifdef CAL_GCF_ATT_UNIT
+    aff_pin(fr);
+#endif
     asm volatile("" : "+v"(bias));
     if (!br.bias) bias = 0.f;
     slots.repair_empty(un);
@@ -235,6 +263,9 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
         else mma_rowk_tile<false, LDT>(At, Zt, rowsP, r0, ct, li, lk, acc0, acc1);
     }
     RO_CLK(38);
+#ifdef CAL_GCF_ATT_UNIT
+    BLK_CLK_X(4, 0, acc0[0]);
+#endif
     // ---- epilogue: bias, ReLU, store, column sums of this graph ---------------------------------------------------
     float f1[4] = {0.f, 0.f, 0.f, 0.f}, f2[4] = {0.f, 0.f, 0.f, 0.f};
     float psum = 0.f;
@@ -254,6 +285,9 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
             acc0[r] = v;                                 // (stored below, four columns per lane)
             const float vm = row < rows ? v : 0.f;
             if (TILED) Ot[row * LDO + ct * 32 + li] = vm;
+#ifdef CAL_GCF_ATT_UNIT
+            Ot_att[row * AFF_LDO + ct * 32 + li] = vm;   // (T = 64: two row tiles at most, this loop holds every row)
+#endif
             f1[r & 3] += vm; f2[r & 3] = fmaf(vm, vm, f2[r & 3]);
         }
         if (r0 + 2 < R) {
@@ -279,6 +313,9 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
     psum += __shfl_xor(psum, 32, 64);
     // (colsum_commit written out: the add-pool's fp32 sums share its store, barrier and lanes)
     if (own && lk == 0) { red[w & 3][0][li] = s1; red[w & 3][1][li] = s2; pool_s[w & 3][li] = psum; }
+#ifdef CAL_GCF_ATT_UNIT
+    if (t < AFF_ND * 16) wsl[t] = fr.wq;                 // (published, with the parked tile, by the barrier below)
+#endif
     __syncthreads();
     if (w < 2 && lk == 0) {
         if (want) {
@@ -301,6 +338,10 @@ __global__ void __launch_bounds__(NT, (T == 64 ? 2 : 1)) k_gconv_fwd(const CSR g
         }
         pp[(size_t)cur * H] = sum;
     }
+#ifdef CAL_GCF_ATT_UNIT
+    // every wave is past the second product and the barrier above: the z tile's stage is free for the tail's fp64 partials
+    aff_tail(fa, fr, un, Ot_att, wsl, reinterpret_cast<double*>(Bs), n0, loop_w, status);
+#endif
     RO_CLK(39);
     BLK_CLK(1);
 }

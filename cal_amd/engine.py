@@ -211,6 +211,12 @@ class StepEngine:
         from .optim import register_engine
         register_engine(self)
 
+    def set_att_fwd_fold(self, on: bool):
+        """False keeps the per-graph attention forward a launch of its own (k_att_fwd_graph) instead of the tail of the last GCN
+        layer's forward launch (k_gconv_fwd_att, ``Route::att_fwd_fold``); the environment variable CAL_AMD_ATT_FWD_FOLD=0
+        selects the same process-wide.  Call before a step is captured."""
+        _lib.call("cal_engine_set_att_fwd_fold", self._h, int(bool(on)))
+
     def set_adam(self, beta1: float, beta2: float, eps: float, weight_decay: float):
         """Adam hyper-parameters of an attached optimizer object (cal_amd/optim.py); the learning rate is ``self.lr``."""
         _lib.call("cal_engine_set_adam", self._h, float(beta1), float(beta2), float(eps), float(weight_decay))
@@ -275,7 +281,10 @@ class StepEngine:
                     (256, "the one-launch readout timed out at an in-kernel barrier (its workgroups were not co-resident: "
                           "another process is holding CUs; CAL_AMD_RO_STEP=0 runs the readout as separate launches)"),
                     (512, "a captured train step was replayed behind a training-mode forward that had no backward (the step's "
-                          "BatchNorm accumulators were not clean: nothing was updated; the next step runs normally)"))
+                          "BatchNorm accumulators were not clean: nothing was updated; the next step runs normally)"),
+                    (1024, "the folded attention forward timed out waiting for its partner workgroup (the two workgroups of a graph "
+                           "were not co-resident: another process is holding CUs; CAL_AMD_ATT_FWD_FOLD=0 keeps the attention "
+                           "forward a launch of its own)"))
 
     def peek_status(self) -> int:
         """The status words as the latest COMPLETED training step left them (host-mapped mirror written by the step's last

@@ -252,6 +252,13 @@ CAL_API int cal_engine_set_graph_ptrs(void* engine, const int64_t* node_ptr, con
 /* Deterministic mode of one engine: every BatchNorm sum as fixed-order partial rows (no fp64 atomics): bit-reproducible steps.
  * No reference counterpart (torch.use_deterministic_algorithms is the closest notion); SURVEY.md section 7 "determinism". */
 CAL_API int cal_engine_set_deterministic(void* engine, int on);
+/* on = 0: the per-graph attention forward stays a launch of its own instead of the tail of the last GCN layer's forward launch
+ * (k_gconv_fwd_att; the environment variable CAL_AMD_ATT_FWD_FOLD=0 selects the same process-wide).  No reference counterpart. */
+CAL_API int cal_engine_set_att_fwd_fold(void* engine, int on);
+/* test aid: where BatchNorm k's batch sums live in the engine's fp64 arena (buffer "arena"), in doubles: out[0] offset of the column
+ * sums (plane 0 of the four accumulator planes), out[1] padded width (the sums of squares follow that far behind), out[2] distance
+ * of the planes.  BatchNorms in the order 0 bn_feat, 1..L bns_conv, L+1 bnc, L+2 bno, then the readout's. */
+CAL_API int cal_engine_bn_arena(void* engine, int64_t k, int64_t* out);
 CAL_API int cal_engine_debug_stop(int k);
 /* test hook (csrc/gemm_probe.hip, GPU only): a flat description of a batched GEMM -- sizes and flags iv, device pointers pv,
  * doubles dv, all three HOST arrays laid out as the file's header comment says -- becomes a GemmArgs and goes to launcher
