@@ -37,19 +37,7 @@
 #include "engine_gwide.hpp"
 #include "engine_attwide.hpp"
 #include "engine_attfwd_fold.hpp"     // AttFwdFoldArgs (the kernel that takes them is in gconv_fwd_att.hip)
-
-// gconv_fwd_att.hip: launches k_gconv_fwd_att (the last backbone layer's per-graph forward with the attention forward as its tail)
-extern "C" int cal_launch_gconv_fwd_att(unsigned gx, hipStream_t st, hipEvent_t e0, hipEvent_t e1, const void* csr, size_t csr_bytes,
-                                        const int* gptr, const int* eptr, const void* branches, size_t branches_bytes, int relu, float loop_w,
-                                        int H, int K, int* status, const void* att, size_t att_bytes);
-// gconv_bwd_att.hip: launches k_gconv_bwd_att (the per-graph GCNConv backward's ATT mode); structures as untyped pointers + sizes
-extern "C" int cal_launch_gconv_bwd_att(unsigned gx, unsigned gy, hipStream_t st, hipEvent_t e0, hipEvent_t e1, const void* csr, size_t csr_bytes,
-                                        const int* gptr, const int* eptr, const void* branches, size_t branches_bytes, float loop_w, int N, int H,
-                                        int K, int* status, const void* att, size_t att_bytes);
-// gconv_bwd_seq.hip: launches the k_gconv_bwd instantiations that run the dX' and dW products one after the other (CAL_GCB_ORDER)
-extern "C" int cal_launch_gconv_bwd_seq(int sel, unsigned gx, unsigned gy, unsigned gz, hipStream_t st, hipEvent_t e0, hipEvent_t e1, const void* csr,
-                                        size_t csr_bytes, const int* gptr, const int* eptr, const void* branches, size_t branches_bytes, float loop_w,
-                                        int N, int H, int K, int* status);
+#include "engine_unit.hpp"            // the entries of the side units (gconv_fwd_att.hip, gconv_bwd_att.hip, gconv_bwd_seq.hip)
 
 namespace cal {
 
@@ -256,6 +244,7 @@ static int env_on(const char* name) { const char* v = getenv(name); return !(v &
 }  // namespace cal
 
 using namespace cal;
+#include "engine_order.hpp"           // pins the order of this file's kernels in its code object: nothing that names a kernel goes in front of it
 
 namespace cal {
 int gat_forward(const int32_t* rowptr_dst, const int32_t* nbr_dst, const int32_t* eid_dst, const float* z,
@@ -805,9 +794,22 @@ struct ProfScope {
     }
 };
 // launch inside a single-kernel ProfScope: the dispatch carries the scope's events when profiling is on
-#define PROF_LAUNCH(kernel, grid, block, shmem, stream, ...) do { \
-        if (g_prof_cur) { hipExtLaunchKernelGGL(kernel, grid, block, shmem, stream, g_prof_cur->r.e0, g_prof_cur->r.e1, 0, __VA_ARGS__); g_prof_cur->used = true; } \
-        else hipLaunchKernelGGL(kernel, grid, block, shmem, stream, __VA_ARGS__); } while (0)
+static calunit::LaunchSite prof_site(dim3 grid, hipStream_t st) {
+    return {grid, st, g_prof_cur ? g_prof_cur->r.e0 : nullptr, g_prof_cur ? g_prof_cur->r.e1 : nullptr};
+}
+template <typename K, typename... A>
+void prof_launch(K kern, dim3 grid, dim3 block, hipStream_t st, const A&... a) {
+    calunit::launch(kern, prof_site(grid, st), block, a...);
+    if (g_prof_cur) g_prof_cur->used = true;
+}
+// the same for a kernel of a side unit (engine_unit.hpp), through the unit's entry; its refusals become the step's error
+template <typename... P, typename... A>
+int side_launch(int (*entry)(const calunit::LaunchSite&, P...), const char* kernel, const char* file, dim3 grid, hipStream_t st, const A&... a) {
+    const int rc = entry(prof_site(grid, st), static_cast<P>(a)...);
+    if (rc) { set_error(rc == 2 ? "%s: argument structures differ between engine.hip and %s" : "%s: instantiation missing from %s", kernel, file); return 2; }
+    if (g_prof_cur) g_prof_cur->used = true;
+    return 0;
+}
 
 int launch_espmm(hipStream_t st, const CSR& csr, const SpmmBranch2& bb, int nbranch, int relu, float loop_w, int N, int H, int rpb) {
     const bool wt = bb.b[0].w != nullptr, stt = bb.b[0].st_sum.on(), sd = bb.b[0].sd_z != nullptr;
@@ -821,17 +823,17 @@ int launch_espmm(hipStream_t st, const CSR& csr, const SpmmBranch2& bb, int nbra
         if (pb != (bb.b[nbranch - 1].pb_g != nullptr)) { set_error("k_espmm: branches differ in kind"); return 2; }
         return with_g(H, [&](auto g) {
             constexpr int G = decltype(g)::value;
-            if (pb) PROF_LAUNCH((k_espmm<4, G, true, false, true, true>), grid, dim3(256), 0, st, csr, bb, relu, loop_w, N, H, rpb);
-            else PROF_LAUNCH((k_espmm<4, G, true, false, true>), grid, dim3(256), 0, st, csr, bb, relu, loop_w, N, H, rpb);
+            if (pb) prof_launch(k_espmm<4, G, true, false, true, true>, grid, dim3(256), st, csr, bb, relu, loop_w, N, H, rpb);
+            else prof_launch(k_espmm<4, G, true, false, true>, grid, dim3(256), st, csr, bb, relu, loop_w, N, H, rpb);
             return 0;
         });
     }
     return with_g(H, [&](auto g) {
         constexpr int G = decltype(g)::value;
-        if (wt && stt) PROF_LAUNCH((k_espmm<4, G, true, true>), grid, dim3(256), 0, st, csr, bb, relu, loop_w, N, H, rpb);
-        else if (wt) PROF_LAUNCH((k_espmm<4, G, true, false>), grid, dim3(256), 0, st, csr, bb, relu, loop_w, N, H, rpb);
-        else if (stt) PROF_LAUNCH((k_espmm<4, G, false, true>), grid, dim3(256), 0, st, csr, bb, relu, loop_w, N, H, rpb);
-        else PROF_LAUNCH((k_espmm<4, G, false, false>), grid, dim3(256), 0, st, csr, bb, relu, loop_w, N, H, rpb);
+        if (wt && stt) prof_launch(k_espmm<4, G, true, true>, grid, dim3(256), st, csr, bb, relu, loop_w, N, H, rpb);
+        else if (wt) prof_launch(k_espmm<4, G, true, false>, grid, dim3(256), st, csr, bb, relu, loop_w, N, H, rpb);
+        else if (stt) prof_launch(k_espmm<4, G, false, true>, grid, dim3(256), st, csr, bb, relu, loop_w, N, H, rpb);
+        else prof_launch(k_espmm<4, G, false, false>, grid, dim3(256), st, csr, bb, relu, loop_w, N, H, rpb);
         return 0;
     });
 }
@@ -882,9 +884,9 @@ int gconv_bwd(Ctx& c, Bwd& b, GconvBwdBranch* gb, int nb, float** dst, double** 
         // four workgroups when one each would leave CUs without one
         const CSR gs = csr_src(c);
         const dim3 gridw(B, nsl * nsplit, nb);
-        if (co) PROF_LAUNCH((k_gw_bwd<true, 2>), gridw, dim3(GW_NT), 0, c.st, gs, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, nsplit, e->status);
-        else if (gb[0].dout) PROF_LAUNCH((k_gw_bwd<false, 0>), gridw, dim3(GW_NT), 0, c.st, gs, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, nsplit, e->status);
-        else PROF_LAUNCH((k_gw_bwd<false, 1>), gridw, dim3(GW_NT), 0, c.st, gs, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, nsplit, e->status);
+        if (co) prof_launch(k_gw_bwd<true, 2>, gridw, dim3(GW_NT), c.st, gs, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, nsplit, e->status);
+        else if (gb[0].dout) prof_launch(k_gw_bwd<false, 0>, gridw, dim3(GW_NT), c.st, gs, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, nsplit, e->status);
+        else prof_launch(k_gw_bwd<false, 1>, gridw, dim3(GW_NT), c.st, gs, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, nsplit, e->status);
         CAL_CHECK_LAUNCH("k_gw_bwd");
         return 0;
     }
@@ -892,12 +894,8 @@ int gconv_bwd(Ctx& c, Bwd& b, GconvBwdBranch* gb, int nb, float** dst, double** 
     const dim3 grid(B, nsl, nb);
     if (att) {      // ATT: dOut comes from the attention backward inside the launch (bwd_att)
         if (co || lean || gb[0].dout) { set_error("k_gconv_bwd: the ATT mode is a one-branch, one-workgroup-per-CU launch"); return 2; }
-        // (the kernel is in gconv_bwd_att.hip, a code object of its own; inside a single-kernel ProfScope the dispatch carries its events)
-        if (cal_launch_gconv_bwd_att(grid.x, grid.y, c.st, g_prof_cur ? g_prof_cur->r.e0 : nullptr, g_prof_cur ? g_prof_cur->r.e1 : nullptr, &gd, sizeof(gd),
-                                     e->gptr, e->eptr, &b2, sizeof(b2), e->loop_w, c.N, H, H, e->status, att, sizeof(*att))) {
-            set_error("k_gconv_bwd_att: argument structures differ between engine.hip and gconv_bwd_att.hip"); return 2;
-        }
-        if (g_prof_cur) g_prof_cur->used = true;
+        RC(side_launch(cal_launch_gconv_bwd_att, "k_gconv_bwd_att", "gconv_bwd_att.hip", grid, c.st, &gd, sizeof(gd), e->gptr, e->eptr,
+                       &b2, sizeof(b2), e->loop_w, c.N, H, H, e->status, att, sizeof(*att)));
         CAL_CHECK_LAUNCH("k_att_bwd_graph");
         return 0;
     }
@@ -907,17 +905,15 @@ int gconv_bwd(Ctx& c, Bwd& b, GconvBwdBranch* gb, int nb, float** dst, double** 
     auto kern = co ? (lean ? (tiles ? k_gconv_bwd<true, 2, true, true> : k_gconv_bwd<true, 2, false, true>) : tiles ? k_gconv_bwd<true, 2, true> : k_gconv_bwd<true, 2>)
               : gb[0].dout ? (lean ? k_gconv_bwd<false, 0, false, true> : k_gconv_bwd<false, 0>) : lean ? k_gconv_bwd<false, 1, false, true> : k_gconv_bwd<false, 1>;
     // order 1 of the two products (engine_gconv_bwd.hpp: the non-LEAN instantiations; 2: all): those kernels are in
-    // gconv_bwd_seq.hip, a code object of their own -- the instantiations named above keep this file's device code what it was
+    // gconv_bwd_seq.hip, a code object of their own; this file's instantiations serve the LEAN launches and the order-0 builds
     if (CAL_GCB_ORDER != 0 && (!lean || CAL_GCB_ORDER == 2)) {
         const int sel = (co ? 1 : 0) | (co && tiles ? 2 : 0) | (!co && gb[0].dout ? 4 : 0) | (lean ? 8 : 0);
-        const int rc = cal_launch_gconv_bwd_seq(sel, grid.x, grid.y, grid.z, c.st, g_prof_cur ? g_prof_cur->r.e0 : nullptr, g_prof_cur ? g_prof_cur->r.e1 : nullptr,
-                                                &gd, sizeof(gd), e->gptr, e->eptr, &b2, sizeof(b2), e->loop_w, c.N, H, H, e->status);
-        if (rc) { set_error(rc == 2 ? "k_gconv_bwd: argument structures differ between engine.hip and gconv_bwd_seq.hip" : "k_gconv_bwd: instantiation missing from gconv_bwd_seq.hip"); return 2; }
-        if (g_prof_cur) g_prof_cur->used = true;
+        RC(side_launch(cal_launch_gconv_bwd_seq, "k_gconv_bwd", "gconv_bwd_seq.hip", grid, c.st, sel, &gd, sizeof(gd), e->gptr, e->eptr,
+                       &b2, sizeof(b2), e->loop_w, c.N, H, H, e->status));
         CAL_CHECK_LAUNCH("k_gconv_bwd");
         return 0;
     }
-    PROF_LAUNCH(kern, grid, dim3(GB_NT), 0, c.st, gd, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, e->status);
+    prof_launch(kern, grid, dim3(GB_NT), c.st, gd, e->gptr, e->eptr, b2, e->loop_w, c.N, H, H, e->status);
     CAL_CHECK_LAUNCH("k_gconv_bwd");
     return 0;
 }
@@ -1195,21 +1191,17 @@ int fwd_feat(Ctx& c, const float* x0) {
     return 0;
 }
 
-// GCNConv forward per graph, k_gconv_fwd / k_gw_fwd: one backbone layer (NB = 1) or the two causal convolutions with the add-pool
-// (NB = 2; tiles: packed batch) -- kind: Graph64 / Graph128 / Wide, cols: the wide kernels' slice width.  NB is a template
-// parameter so that each caller names its own kernels only, where it always has: their place in the code object stays (DESIGN
-// section 7, "What decided the form")
-template <int NB>
-void launch_gconv_fwd(Ctx& c, Conv kind, int cols, bool tiles, const GconvBranch2& b2) {
+// GCNConv forward per graph, k_gconv_fwd / k_gw_fwd: one backbone layer (nb = 1) or the two causal convolutions with the add-pool
+// (nb = 2; tiles: packed batch) -- kind: Graph64 / Graph128 / Wide, cols: the wide kernels' slice width
+void launch_gconv_fwd(Ctx& c, int nb, Conv kind, int cols, bool tiles, const GconvBranch2& b2) {
     Engine* e = c.e;
     const int H = e->H;
     const bool wide = kind == Conv::Wide, g64 = kind == Conv::Graph64;
-    void (*kern)(CSR, const int*, const int*, GconvBranch2, int, float, int, int, int*);
-    if constexpr (NB == 1) kern = wide ? (cols == 32 ? k_gw_fwd<false, 32> : k_gw_fwd<false, 64>) : g64 ? k_gconv_fwd<false, 64, 512> : k_gconv_fwd<false, GC_T>;
-    else kern = tiles ? k_gconv_fwd<true, 64, 512, true> : g64 ? k_gconv_fwd<true, 64, 512> : !wide ? k_gconv_fwd<true, GC_T>
+    auto kern = nb == 1 ? (wide ? (cols == 32 ? k_gw_fwd<false, 32> : k_gw_fwd<false, 64>) : g64 ? k_gconv_fwd<false, 64, 512> : k_gconv_fwd<false, GC_T>)
+              : tiles ? k_gconv_fwd<true, 64, 512, true> : g64 ? k_gconv_fwd<true, 64, 512> : !wide ? k_gconv_fwd<true, GC_T>
               : cols == 32 ? k_gw_fwd<true, 32> : k_gw_fwd<true, 64>;
     const int ncol = wide ? cols : GC_N, nt = wide ? GW_NT : tiles || g64 ? 512 : 256;      // (a packed batch runs the 64-node form)
-    PROF_LAUNCH(kern, dim3(c.T, H / ncol, NB), dim3(nt), 0, c.st, csr_dst(c), e->gptr, e->eptr, b2, 1, e->loop_w, H, H, e->status);
+    prof_launch(kern, dim3(c.T, H / ncol, nb), dim3(nt), c.st, csr_dst(c), e->gptr, e->eptr, b2, 1, e->loop_w, H, H, e->status);
 }
 
 // 4. backbone: h_i = relu(A_hat (BN_i(h_{i-1}) @ W_i) + b_i)   (model.py:93-95)
@@ -1233,7 +1225,7 @@ int fwd_backbone(Ctx& c) {
             if (c.training) { ga.st_sum = graph_acc(c, bn_stsum(c, i), H, r.st_bb); ga.st_sq = graph_acc(c, bn_stsq(c, i), H, r.st_bb); }
             {
                 ProfScope ps(st, 9, 2.0 * N * H * H + 2.0 * (double)(E + N) * H, true);
-                PROF_LAUNCH((k_ggin_fwd<1>), dim3(T, H / GC_N), dim3(512), 0, st, gd, e->gptr, e->eptr, ga, H, H, e->status);
+                prof_launch(k_ggin_fwd<1>, dim3(T, H / GC_N), dim3(512), st, gd, e->gptr, e->eptr, ga, H, H, e->status);
             }
             CAL_CHECK_LAUNCH("k_ggin_fwd<1>"); STAGE();
             RC(flush_finals(c)); STAGE();
@@ -1286,7 +1278,7 @@ int fwd_backbone(Ctx& c) {
                 ga.seed = e->gat_seed[i - 1]; ga.ctr = (const uint64_t*)e->gat_ctr; ga.E = E;
                 {
                     ProfScope ps(st, 7, 2.0 * N * H * H + 2.0 * (double)(E + N) * H, true);
-                    PROF_LAUNCH(k_ggat_fwd, dim3(T, H / GC_N), dim3(256), 0, st, gd, e->gptr, e->eptr, ga, H, H, e->status);
+                    prof_launch(k_ggat_fwd, dim3(T, H / GC_N), dim3(256), st, gd, e->gptr, e->eptr, ga, H, H, e->status);
                 }
                 CAL_CHECK_LAUNCH("k_ggat_fwd"); STAGE();
                 RC(flush_finals(c)); STAGE();
@@ -1325,7 +1317,7 @@ int fwd_backbone(Ctx& c) {
             const GconvBranch2 b2{{gb, gb}};
             if (i == L && r.att_fwd_fold) {
                 // the attention forward (fwd_att's per-graph kernel) as this launch's tail: k_gconv_fwd_att in gconv_fwd_att.hip, a code
-                // object of its own; inside a single-kernel ProfScope the dispatch carries its events
+                // object of its own
                 AttFwdFoldArgs fa;
                 memset(&fa, 0, sizeof(fa));
                 fa.gs = csr_src(c);
@@ -1337,11 +1329,8 @@ int fwd_backbone(Ctx& c) {
                 fa.xch = e->att_xch; fa.flags = (int*)(e->arena + e->a_aff);
                 {
                     ProfScope ps(st, 2, 2.0 * N * H * H + 2.0 * (double)(E + N) * H, true);
-                    if (cal_launch_gconv_fwd_att((unsigned)T, st, g_prof_cur ? g_prof_cur->r.e0 : nullptr, g_prof_cur ? g_prof_cur->r.e1 : nullptr, &gd, sizeof(gd),
-                                                 e->gptr, e->eptr, &b2, sizeof(b2), 1, e->loop_w, H, H, e->status, &fa, sizeof(fa))) {
-                        set_error("k_gconv_fwd_att: argument structures differ between engine.hip and gconv_fwd_att.hip"); return 2;
-                    }
-                    if (g_prof_cur) g_prof_cur->used = true;
+                    RC(side_launch(cal_launch_gconv_fwd_att, "k_gconv_fwd_att", "gconv_fwd_att.hip", dim3(T, 2), st, &gd, sizeof(gd), e->gptr, e->eptr,
+                                   &b2, sizeof(b2), 1, e->loop_w, H, H, e->status, &fa, sizeof(fa)));
                 }
                 CAL_CHECK_LAUNCH("k_gconv_fwd_att"); STAGE();
                 RC(flush_finals(c)); STAGE();
@@ -1349,7 +1338,7 @@ int fwd_backbone(Ctx& c) {
             }
             {
                 ProfScope ps(st, 2, 2.0 * N * H * H + 2.0 * (double)(E + N) * H, true);
-                launch_gconv_fwd<1>(c, r.bb_fwd, r.gw_cols_bb, false, b2);
+                launch_gconv_fwd(c, 1, r.bb_fwd, r.gw_cols_bb, false, b2);
             }
             CAL_CHECK_LAUNCH(r.bb_fwd == Conv::Wide ? "k_gw_fwd" : "k_gconv_fwd"); STAGE();
             RC(flush_finals(c)); STAGE();
@@ -1447,7 +1436,7 @@ int fwd_co(Ctx& c) {
             gb[k].batch = c.batch; gb[k].tile_gptr = tgp;          // packed batch: the add-pool is per GRAPH inside the tile
         }
         const GconvBranch2 b2{{gb[0], gb[1]}};
-        launch_gconv_fwd<2>(c, r.co_fwd, r.gw_cols_co, tgp != nullptr, b2);
+        launch_gconv_fwd(c, 2, r.co_fwd, r.gw_cols_co, tgp != nullptr, b2);
         CAL_CHECK_LAUNCH(wide ? "k_gw_fwd(co)" : "k_gconv_fwd(co)"); STAGE();
         return 0;
     }
@@ -1946,7 +1935,7 @@ int bwd_backbone(Ctx& c, Bwd& b, const float* x0) {
             RCP(ga.slab = b.slabs(c, T, H * H, e->G + e->o_conv_w[i - 1]));
             {
                 ProfScope ps(st, 10, 4.0 * N * H * H + 2.0 * (double)(E + N) * H, true);
-                PROF_LAUNCH((k_ggin_bwd<1>), dim3(T, nsl), dim3(GB_NT), 0, st, gd, e->gptr, e->eptr, ga, N, H, H, e->status);
+                prof_launch(k_ggin_bwd<1>, dim3(T, nsl), dim3(GB_NT), st, gd, e->gptr, e->eptr, ga, N, H, H, e->status);
             }
             CAL_CHECK_LAUNCH("k_ggin_bwd<1>"); STAGE();
             if (i == 1 && units) {
@@ -2052,8 +2041,8 @@ int bwd_backbone(Ctx& c, Bwd& b, const float* x0) {
             RC(bn_bwd_sums(c, ga, T * nsl, bn_dsum(c, i), bn_dprod(c, i), st_i));
             {
                 ProfScope ps(st, 8, 4.0 * N * H * H + 4.0 * (double)(E + N) * H, true);
-                if (i == L) PROF_LAUNCH((k_ggat_bwd<false>), dim3(T, nsl), dim3(GB_NT), 0, st, gd, e->gptr, e->eptr, ga, N, H, H, e->status);
-                else PROF_LAUNCH((k_ggat_bwd<true>), dim3(T, nsl), dim3(GB_NT), 0, st, gd, e->gptr, e->eptr, ga, N, H, H, e->status);
+                if (i == L) prof_launch(k_ggat_bwd<false>, dim3(T, nsl), dim3(GB_NT), st, gd, e->gptr, e->eptr, ga, N, H, H, e->status);
+                else prof_launch(k_ggat_bwd<true>, dim3(T, nsl), dim3(GB_NT), st, gd, e->gptr, e->eptr, ga, N, H, H, e->status);
             }
             CAL_CHECK_LAUNCH("k_ggat_bwd"); STAGE();
             RC(flush_finals(c)); STAGE();
