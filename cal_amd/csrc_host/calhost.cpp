@@ -1025,6 +1025,120 @@ HOST_EXPORT int cal_occlude_write(const int64_t* edge_index, int64_t E, int64_t 
 }
 #undef OCCLUDE_REQUIRE_INPUTS
 
+// ---- coalition replicas (cal_amd/csrc/coalition.hip; cal_amd/coalition.py coalition_batch): the same nodes and columns in the
+// same order, so every integer output agrees bit for bit.
+namespace {
+struct CoalitionSrc {
+    const int64_t* ei; int64_t E, N; const int64_t* ptr; const int64_t* eptr; int64_t B; const int32_t* key; int64_t K, M;
+    const int64_t* rg; const int64_t* rrow; const int64_t* rth; int mode, invert; int64_t mx;
+    // replica r: node range, column range, its key row (null: everything stays) and threshold
+    void ranges(int64_t r, int64_t& nlo, int64_t& nhi, int64_t& elo, int64_t& ehi, const int32_t*& row, int64_t& th) const {
+        const int64_t g = rg[r];
+        nlo = nhi = elo = ehi = th = 0;
+        row = nullptr;
+        if (g < 0 || g >= B) return;
+        seg_clamp(ptr, g, N, nlo, nhi);
+        seg_clamp(eptr, g, E, elo, ehi);
+        if (mode == 1 && nhi - nlo > mx) { nlo = nhi = elo = ehi = 0; return; }
+        const int64_t k = rrow[r];
+        if (k >= 0 && k < K) row = key + k * M;
+        th = rth[r];
+    }
+    bool elem(const int32_t* row, int64_t th, int64_t e) const { return !row || (invert ? row[e] >= th : row[e] < th); }
+    bool stays(int64_t e, int64_t nlo, int64_t nhi, const int32_t* row, int64_t th) const {
+        const int64_t u = ei[e], v = ei[E + e];
+        if (!(u >= nlo && u < nhi && v >= nlo && v < nhi)) return false;
+        return mode == 0 ? elem(row, th, e) : elem(row, th, u) && elem(row, th, v);
+    }
+};
+}  // namespace
+
+HOST_EXPORT int64_t cal_coalition_ws(int64_t, int64_t R, int64_t max_nodes, int mode) {
+    R = R > 0 ? R : 0;
+    return 16 * R + (mode == 1 ? 4 * R * (max_nodes > 0 ? max_nodes : 0) : 0) + 256;
+}
+
+#define COALITION_REQUIRE_INPUTS()                                                                                               \
+    HOST_REQUIRE(E >= 0 && N >= 0 && B >= 0 && R >= 0 && K >= 0, "sizes must be >= 0");                                          \
+    HOST_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (edges) or 1 (nodes)");                                                 \
+    HOST_REQUIRE(invert == 0 || invert == 1, "invert must be 0 or 1");                                                           \
+    HOST_REQUIRE(max_nodes >= 0 && max_nodes <= 0x7FFFFFFF, "max_nodes must be in [0, 2^31)");                                   \
+    HOST_REQUIRE(R == 0 || (rep_graph && rep_row && rep_thresh), "rep_graph / rep_row / rep_thresh are null");                   \
+    HOST_REQUIRE(K == 0 || (mode == 0 ? E : N) == 0 || key, "key is null");                                                      \
+    HOST_REQUIRE(B == 0 || (ptr && edge_ptr), "ptr / edge_ptr are null");                                                        \
+    HOST_REQUIRE(E == 0 || edge_index, "edge_index is null");                                                                    \
+    const int64_t M = mode == 0 ? E : N;                                                                                         \
+    const CoalitionSrc S{edge_index, E, N, ptr, edge_ptr, B, key, key && M > 0 ? K : 0, M, rep_graph, rep_row, rep_thresh, mode, \
+                         invert, max_nodes}
+
+HOST_EXPORT int cal_coalition_count(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                                    int64_t B, const int32_t* key, int64_t K, const int64_t* rep_graph, const int64_t* rep_row,
+                                    const int64_t* rep_thresh, int64_t R, int mode, int invert, int64_t max_nodes,
+                                    int64_t* ptr_out, int64_t* edge_ptr_out, int64_t* totals, void*, int64_t, void*) {
+    COALITION_REQUIRE_INPUTS();
+    HOST_REQUIRE(totals && ptr_out && edge_ptr_out, "totals / ptr_out / edge_ptr_out are null");
+    int64_t nt = 0, et = 0, mn = 0, me = 0, empty = 0;
+    for (int64_t r = 0; r < R; ++r) {
+        int64_t nlo, nhi, elo, ehi, th, n = 0, m = 0;
+        const int32_t* row;
+        S.ranges(r, nlo, nhi, elo, ehi, row, th);
+        if (mode == 0) n = nhi - nlo;
+        else for (int64_t s = nlo; s < nhi; ++s) n += S.elem(row, th, s);
+        for (int64_t e = elo; e < ehi; ++e) m += S.stays(e, nlo, nhi, row, th);
+        ptr_out[r] = nt;
+        edge_ptr_out[r] = et;
+        nt += n;
+        et += m;
+        mn = std::max(mn, n);
+        me = std::max(me, m);
+        empty += n == 0;
+    }
+    ptr_out[R] = nt;
+    edge_ptr_out[R] = et;
+    totals[0] = nt; totals[1] = et; totals[2] = mn; totals[3] = me; totals[4] = empty;
+    return 0;
+}
+
+HOST_EXPORT int cal_coalition_write(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                                    int64_t B, const int32_t* key, int64_t K, const int64_t* rep_graph, const int64_t* rep_row,
+                                    const int64_t* rep_thresh, int64_t R, int mode, int invert, int64_t max_nodes, const float* x,
+                                    int64_t F, const int64_t* ptr_out, const int64_t* edge_ptr_out, int64_t Nout, int64_t Eout,
+                                    int64_t* batch_out, float* x_out, int64_t* edge_index_out, int64_t* node_src,
+                                    int64_t* edge_src, void*, int64_t, void*) {
+    COALITION_REQUIRE_INPUTS();
+    HOST_REQUIRE(Nout >= 0 && Eout >= 0 && F >= 0 && F < (1 << 22), "Nout, Eout must be >= 0 and 0 <= F < 2^22");
+    HOST_REQUIRE(R == 0 || (ptr_out && edge_ptr_out), "ptr_out / edge_ptr_out are null");
+    HOST_REQUIRE(Nout == 0 || (batch_out && node_src), "batch_out / node_src are null");
+    HOST_REQUIRE(Eout == 0 || (edge_index_out && edge_src), "edge_index_out / edge_src are null");
+    HOST_REQUIRE(!x_out || (F > 0 && (N == 0 || x)), "x_out needs F > 0 and x");
+    std::vector<int64_t> local;                            // (mode 1) new local id of every node of the replica's graph
+    for (int64_t r = 0; r < R; ++r) {
+        int64_t nlo, nhi, elo, ehi, th;
+        const int32_t* row;
+        S.ranges(r, nlo, nhi, elo, ehi, row, th);
+        const int64_t n0 = ptr_out[r];
+        int64_t i = n0, j = edge_ptr_out[r];
+        local.assign((size_t)(nhi - nlo), 0);
+        for (int64_t s = nlo; s < nhi; ++s) {
+            local[(size_t)(s - nlo)] = i - n0;
+            if ((mode == 1 && !S.elem(row, th, s)) || i >= Nout) continue;
+            batch_out[i] = r;
+            node_src[i] = s;
+            if (x_out) memcpy(x_out + i * F, x + s * F, sizeof(float) * (size_t)F);
+            ++i;
+        }
+        for (int64_t e = elo; e < ehi; ++e) {
+            if (!S.stays(e, nlo, nhi, row, th) || j >= Eout) continue;
+            edge_index_out[j] = n0 + local[(size_t)(edge_index[e] - nlo)];
+            edge_index_out[Eout + j] = n0 + local[(size_t)(edge_index[E + e] - nlo)];
+            edge_src[j] = e;
+            ++j;
+        }
+    }
+    return 0;
+}
+#undef COALITION_REQUIRE_INPUTS
+
 // ---- rank agreement (cal_amd/csrc/occlude.hip; cal_amd/occlude.py rank_agreement): the same ten integers per segment, here from
 // two sorts per segment where the device counts all pairs.
 HOST_EXPORT int64_t cal_rank_agreement_ws(int64_t, int64_t, int64_t) { return 0; }

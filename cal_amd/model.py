@@ -204,6 +204,16 @@ class _CausalBase(torch.nn.Module):
         from .occlude import faithfulness
         return faithfulness(self, data, **kw)
 
+    def shapley(self, data, **kw):
+        """``cal_amd.coalition.shapley(self, data, **kw)``: permutation-sampled Shapley values of every edge or node."""
+        from .coalition import shapley
+        return shapley(self, data, **kw)
+
+    def perturbation_curve(self, data, **kw):
+        """``cal_amd.coalition.perturbation_curve(self, data, **kw)``: insertion and deletion curves under a ranking."""
+        from .coalition import perturbation_curve
+        return perturbation_curve(self, data, **kw)
+
     def explain(self, data, **kw):
         """``cal_amd.explain.explain(self, data, **kw)``: per-graph top-k causal subgraphs of ``data``."""
         from .explain import explain

@@ -488,6 +488,42 @@ CAL_API int cal_rank_agreement(const float* a, const float* b, int64_t M, const 
                                const uint8_t* sel, int64_t k_code, double k_val, int64_t* counts, void* ws, int64_t ws_bytes,
                                void* stream);
 
+/* ---- coalition replicas: R copies of graphs of one batch, each restricted to a subset of its elements (cal_amd/coalition.py
+ * coalition_batch; sampled Shapley values, deletion / insertion curves) ----
+ * The batch is x [N, F] fp32 (or null, F = 0), edge_index [2, E] int64, ptr / edge_ptr [B+1] int64 as in cal_occlude_*.  key is
+ * int32 [K, M], row-major, one entry per edge column (mode 0, M = E) or per node (mode 1, M = N).  Replica r (of R) is graph
+ * g = rep_graph[r]; an id outside [0, B) gives a replica with no node and no column.  Element e of g STAYS iff rep_row[r] is
+ * outside [0, K) (the control replica: everything stays), or key[rep_row[r], e] < rep_thresh[r] with invert = 0, or
+ * key[rep_row[r], e] >= rep_thresh[r] with invert = 1.  A plain integer compare: ties, negative keys and keys that are no
+ * permutation all have a defined result.  mode 0 (edges): all nodes of g stay in order, the columns that stay keep their order.
+ * mode 1 (nodes): the nodes that stay are renumbered densely in their order and their rows copied; a column stays iff both
+ * endpoints stay, and its endpoints are rewritten.  In both modes a source column with an endpoint outside its graph's node
+ * range is dropped, as in the splice and the occlusion.  max_nodes (< 2^31) must bound every graph's node count: in mode 1 it is
+ * the row length of the per-replica node map in ws, and a graph with more nodes gives a replica with nothing in it.  Every
+ * integer output is uniquely determined.
+ *   cal_coalition_count: ONE launch.  ptr_out / edge_ptr_out [R+1] and totals [5] int64 on the device: N', E', max_nodes',
+ *     max_edges', replicas with no node.  The per-replica counts and (mode 1) the node maps stay in ws.  The caller reads totals
+ *     back once.
+ *   cal_coalition_write: ONE launch with the same inputs, the same ws and Nout = totals[0], Eout = totals[1].  batch_out [N'],
+ *     x_out [N', F] (row copies; null with F = 0), edge_index_out (a contiguous [2, E']), node_src [N'] / edge_src [E'] (the
+ *     source node / column of every new one).  The rows are copied 16 bytes per lane when F % 4 == 0 and x, x_out are 16-byte
+ *     aligned, else element by element (0 <= F < 2^22).
+ * ws: 8-byte aligned, cal_coalition_ws bytes (16 R + 256, and 4 R max_nodes more in mode 1).  Everything on `stream`, no
+ * synchronisation inside; no value that reaches an output is accumulated atomically (the completion ticket and the ordered scan
+ * of cal_occlude_count).  R = 0: nothing is launched (the count zeroes totals and the two offsets with memsets). */
+CAL_API int64_t cal_coalition_ws(int64_t E, int64_t R, int64_t max_nodes, int mode);
+CAL_API int cal_coalition_count(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                                int64_t B, const int32_t* key, int64_t K, const int64_t* rep_graph, const int64_t* rep_row,
+                                const int64_t* rep_thresh, int64_t R, int mode, int invert, int64_t max_nodes,
+                                int64_t* ptr_out, int64_t* edge_ptr_out, int64_t* totals, void* ws, int64_t ws_bytes,
+                                void* stream);
+CAL_API int cal_coalition_write(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                                int64_t B, const int32_t* key, int64_t K, const int64_t* rep_graph, const int64_t* rep_row,
+                                const int64_t* rep_thresh, int64_t R, int mode, int invert, int64_t max_nodes, const float* x,
+                                int64_t F, const int64_t* ptr_out, const int64_t* edge_ptr_out, int64_t Nout, int64_t Eout,
+                                int64_t* batch_out, float* x_out, int64_t* edge_index_out, int64_t* node_src,
+                                int64_t* edge_src, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
