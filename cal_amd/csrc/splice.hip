@@ -7,32 +7,21 @@
 // range is dropped, as in subgraph.hip.  Every integer output is uniquely determined (the host twin and a plain-torch
 // restatement agree bit for bit); the feature rows are copies.
 //
-// Two launches with the caller's one read-back of totals between them:
-//  * k_splice_count, one workgroup per pair: the valid columns of the two parts (any size: the part is walked in chunks of one
-//    workgroup's threads) and the pair's node / column counts into ws.  A part that drops a column also gets sel[] in ws, the
-//    position of its k-th valid column (a property of the source graph: pairs that share it write the same values).  The
-//    workgroup that finishes last scans the P counts into ptr_out / edge_ptr_out and writes totals; the only way to know it is
-//    last is the completion ticket of twin.hip (one atomicInc per workgroup on a wrapping counter, nothing else): the integer
-//    result does not depend on which workgroup that is, and no output value is accumulated atomically.
-//  * k_splice_write, fixed chunks of the OUTPUT, so that a 5000-node part and a 3-node part cost what their elements cost:
-//    node workgroups take kNodeChunk result nodes (the pair by binary search in ptr_out, batch_out / node_src, then the feature
-//    rows of the chunk: 16 bytes per lane when F % 4 == 0 and the three bases are 16-byte aligned, else element by element),
-//    column workgroups take kColChunk result columns (the pair by binary search in edge_ptr_out, the source column directly or
-//    through sel[], the endpoints rewritten).
-#include <atomic>
-
-#include "segment.hpp"
+// The two launches follow the protocol of rebatch.hpp.  What is particular here:
+//  * k_splice_count: a part that drops a column also gets sel[] in ws, the position of its k-th valid column (a property of the
+//    source graph: pairs that share it write the same values); totals[5] counts the bridges asked for and not written.
+//  * k_splice_write works on fixed chunks of the OUTPUT, so that a 5000-node part and a 3-node part cost what their elements
+//    cost: after the node workgroups (two sources: node_src holds A's row id as it is, B's as -1 - id) the column workgroups
+//    take kColChunk result columns each (the pair by binary search in edge_ptr_out, the source column directly or through
+//    sel[], the endpoints rewritten).
+#include "rebatch.hpp"
 
 namespace cal {
 namespace {
 
-constexpr int kNodeChunk = 256;            // result nodes of one node workgroup (one per thread in the index phase)
 constexpr int kColPerLane = 4;             // result columns per thread of a column workgroup
 constexpr int kColChunk = 256 * kColPerLane;
-constexpr int kTickets = 64;               // concurrent count launches (on different streams) that may be in flight
-constexpr int64_t kBridge = INT64_MIN;     // edge_src of a bridge column (CAL_SPLICE_BRIDGE)
-
-__device__ unsigned int g_splice_ticket[kTickets];   // zero at load; atomicInc wraps each back to zero
+constexpr int64_t kBridge = INT64_MIN;     // edge_src of a bridge column (CAL_SPLICE_BRIDGE); as a row code: no row
 
 struct Side {
     const int64_t* ei;         // [2, E]
@@ -48,19 +37,13 @@ struct Side {
 
 struct SpliceArgs {
     Side a, b;
-    int64_t P, F;
+    int64_t P;
     int64_t* ptr_out;          // [P + 1]
     int64_t* eptr_out;         // [P + 1]
     int64_t* totals;           // [6]
     int64_t* cnt;              // ws [5 P]: valid columns of A, of B, nodes, columns, bridges asked for and not written
-    int64_t Nout, Eout;        // (write) totals[0], totals[1] as the caller read them
-    int64_t* batch_out;        // [Nout]
-    float* x_out;              // [Nout, F] or null
-    int64_t* ei_out;           // [2, Eout]
-    int64_t* node_src;         // [Nout]
-    int64_t* edge_src;         // [Eout]
+    WriteOut out;              // (write)
     int ticket, nblk;
-    int vec;                   // (write) the 16-byte row copy applies
 };
 
 // the part of pair p on side s: node range [nlo, nlo + nn), column range [elo, elo + em); all zero when absent
@@ -98,30 +81,6 @@ __device__ __forceinline__ int64_t count_side(const Side& s, int64_t nlo, int64_
     return tot;
 }
 
-// exclusive prefix of v over the workgroup's NT threads in thread order, the workgroup's sum in tot (two barriers)
-template <int NT>
-__device__ __forceinline__ long long wg_excl_sum(long long v, long long* red, long long& tot) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    long long inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long u = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += u;
-    }
-    __syncthreads();
-    if (lane == 63) red[w] = inc;
-    __syncthreads();
-    long long base = 0, t = 0;
-#pragma unroll
-    for (int i = 0; i < NT / 64; ++i) {
-        const long long r = red[i];
-        base += i < w ? r : 0;
-        t += r;
-    }
-    tot = t;
-    return base + inc - v;
-}
-
 // grid P, NT threads
 template <int NT>
 __global__ void __launch_bounds__(NT) k_splice_count(SpliceArgs a) {
@@ -143,57 +102,14 @@ __global__ void __launch_bounds__(NT) k_splice_count(SpliceArgs a) {
         a.cnt[2 * P + p] = an + bn;
         a.cnt[3 * P + p] = ea + eb + (put ? 2 : 0);
         a.cnt[4 * P + p] = asked && !put;
-        __threadfence();
-        last = atomicInc(&g_splice_ticket[a.ticket], (unsigned)(a.nblk - 1)) == (unsigned)(a.nblk - 1);
     }
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
-    // the scan over the P pairs: thread t owns the run [t R, (t + 1) R) of pairs
-    const int64_t R = (P + NT - 1) / NT, lo = (int64_t)threadIdx.x * R, hi = lo + R < P ? lo + R : P;
-    long long sn = 0, se = 0, mn = 0, me = 0, empty = 0, unput = 0;
-    for (int64_t q = lo; q < hi; ++q) {
-        const long long n = __hip_atomic_load(a.cnt + 2 * P + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const long long e = __hip_atomic_load(a.cnt + 3 * P + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!last_workgroup(a.ticket, a.nblk, &last)) return;
+    long long unput = 0;                                          // (read before the scan: its loads' latency hides under it)
+    for (int64_t q = threadIdx.x; q < P; q += NT)
         unput += __hip_atomic_load(a.cnt + 4 * P + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        sn += n;
-        se += e;
-        mn = n > mn ? n : mn;
-        me = e > me ? e : me;
-        empty += n == 0;
-    }
-    long long tn, te;
-    long long on = wg_excl_sum<NT>(sn, red, tn), oe = wg_excl_sum<NT>(se, red, te);
-    for (int64_t q = lo; q < hi; ++q) {
-        a.ptr_out[q] = on;
-        a.eptr_out[q] = oe;
-        on += __hip_atomic_load(a.cnt + 2 * P + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        oe += __hip_atomic_load(a.cnt + 3 * P + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    mn = wg_max<NT>(mn, red);
-    me = wg_max<NT>(me, red);
-    empty = wg_sum<NT>(empty, red);
+    scan_counts<NT>(a.cnt + 2 * P, a.cnt + 3 * P, P, a.ptr_out, a.eptr_out, a.totals, red);
     unput = wg_sum<NT>(unput, red);
-    if (threadIdx.x == 0) {
-        a.ptr_out[P] = tn;
-        a.eptr_out[P] = te;
-        a.totals[0] = tn;
-        a.totals[1] = te;
-        a.totals[2] = mn;
-        a.totals[3] = me;
-        a.totals[4] = empty;
-        a.totals[5] = unput;
-    }
-}
-
-// last index q in [0, n) with p[q] <= i; p ascending with p[0] = 0 <= i (the graph that owns element i; empty ones are skipped)
-__device__ __forceinline__ int64_t owner(const int64_t* p, int64_t n, int64_t i) {
-    int64_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (p[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
+    if (threadIdx.x == 0) a.totals[5] = unput;
 }
 
 // grid ceil(Nout / kNodeChunk) node workgroups, then ceil(Eout / kColChunk) column workgroups; 256 threads
@@ -201,58 +117,23 @@ __global__ void __launch_bounds__(256) k_splice_write(SpliceArgs a, int node_blo
     __shared__ int64_t src[kNodeChunk];
     const int64_t P = a.P;
     if ((int)blockIdx.x < node_blocks) {
-        const int64_t i0 = (int64_t)blockIdx.x * kNodeChunk, i = i0 + threadIdx.x;
-        int64_t code = kBridge;                                   // (no row)
-        if (i < a.Nout) {
-            const int64_t p = owner(a.ptr_out, P + 1, i);
-            if (p < P) {
+        write_nodes(
+            a.out, a.ptr_out, P, kBridge, src,
+            [&](int64_t p, int64_t l) -> int64_t {
                 int64_t alo, an, blo, bn, e0, e1;
                 side_ranges(a.a, p, alo, an, e0, e1);
-                const int64_t l = i - a.ptr_out[p];
-                if (l < an) {
-                    code = alo + l;
-                } else {
-                    side_ranges(a.b, p, blo, bn, e0, e1);
-                    if (l - an < bn) code = -1 - (blo + l - an);
-                }
-                if (code != kBridge) {
-                    a.batch_out[i] = p;
-                    a.node_src[i] = code;
-                }
-            }
-        }
-        if (!a.x_out) return;
-        src[threadIdx.x] = code;
-        __syncthreads();
-        const int64_t left = a.Nout - i0;
-        const unsigned rows = (unsigned)(left < kNodeChunk ? left : kNodeChunk);
-        if (a.vec) {
-            const unsigned F4 = (unsigned)(a.F >> 2), n = rows * F4;
-            float4* out = reinterpret_cast<float4*>(a.x_out) + i0 * F4;
-            for (unsigned t = threadIdx.x; t < n; t += 256) {
-                const unsigned r = t / F4, c = t - r * F4;
-                const int64_t s = src[r];
-                if (s == kBridge) continue;
-                const float* row = s >= 0 ? a.a.x + s * a.F : a.b.x + (-1 - s) * a.F;
-                out[t] = reinterpret_cast<const float4*>(row)[c];
-            }
-        } else {
-            const unsigned F = (unsigned)a.F, n = rows * F;
-            float* out = a.x_out + i0 * a.F;
-            for (unsigned t = threadIdx.x; t < n; t += 256) {
-                const unsigned r = t / F, c = t - r * F;
-                const int64_t s = src[r];
-                if (s == kBridge) continue;
-                out[t] = s >= 0 ? a.a.x[s * a.F + c] : a.b.x[(-1 - s) * a.F + c];
-            }
-        }
+                if (l < an) return alo + l;
+                side_ranges(a.b, p, blo, bn, e0, e1);
+                return l - an < bn ? -1 - (blo + l - an) : kBridge;
+            },
+            [&](int64_t s) { return s >= 0 ? a.a.x + s * a.out.F : a.b.x + (-1 - s) * a.out.F; });
         return;
     }
     const int64_t j0 = (int64_t)((int)blockIdx.x - node_blocks) * kColChunk;
 #pragma unroll
     for (int k = 0; k < kColPerLane; ++k) {
         const int64_t j = j0 + k * 256 + threadIdx.x;
-        if (j >= a.Eout) continue;
+        if (j >= a.out.Eout) continue;
         const int64_t p = owner(a.eptr_out, P + 1, j);
         if (p >= P) continue;
         const int64_t l = j - a.eptr_out[p], ea = a.cnt[p], eb = a.cnt[P + p], n0 = a.ptr_out[p];
@@ -282,13 +163,11 @@ __global__ void __launch_bounds__(256) k_splice_write(SpliceArgs a, int node_blo
                 code = kBridge;
             }
         }
-        a.ei_out[j] = u;
-        a.ei_out[a.Eout + j] = v;
-        a.edge_src[j] = code;
+        a.out.ei_out[j] = u;
+        a.out.ei_out[a.out.Eout + j] = v;
+        a.out.edge_src[j] = code;
     }
 }
-
-std::atomic<unsigned> g_splice_calls{0};
 
 int64_t ws_need(int64_t Ea, int64_t Eb, int64_t P) {            // cnt [5 P], sel of A [Ea], sel of B [Eb]
     return 40 * (P > 0 ? P : 0) + 8 * (Ea > 0 ? Ea : 0) + 8 * (Eb > 0 ? Eb : 0) + 256;
@@ -334,26 +213,14 @@ CAL_EXPORT int cal_graph_splice_count(const int64_t* eia, int64_t Ea, int64_t Na
     hipStream_t stream = (hipStream_t)stream_;
     SPLICE_REQUIRE_INPUTS();
     CAL_REQUIRE(totals && ptr_out && edge_ptr_out, "totals / ptr_out / edge_ptr_out are null");
-    if (P == 0) {
-        if (hipMemsetAsync(totals, 0, 6 * sizeof(int64_t), stream) != hipSuccess ||
-            hipMemsetAsync(ptr_out, 0, sizeof(int64_t), stream) != hipSuccess ||
-            hipMemsetAsync(edge_ptr_out, 0, sizeof(int64_t), stream) != hipSuccess) {
-            cal::set_error("cal_graph_splice_count: hipMemsetAsync failed");
-            return 1;
-        }
-        return 0;
-    }
+    if (P == 0) return zero_counts(__func__, totals, 6, ptr_out, edge_ptr_out, stream);
     SpliceArgs a = make_args(eia, Ea, Na, ptr_a, eptr_a, Ba, eib, Eb, Nb, ptr_b, eptr_b, Bb, ga, gb, P, bridge_a, bridge_b, ws);
     a.ptr_out = ptr_out;
     a.eptr_out = edge_ptr_out;
     a.totals = totals;
-    a.ticket = (int)(g_splice_calls.fetch_add(1) % kTickets);
+    a.ticket = next_ticket();
     a.nblk = (int)P;
-    // wide workgroups once the average source graph has more columns than a 256-thread workgroup walks in a few chunks
-    if ((Ea + Eb) / (Ba + Bb > 0 ? Ba + Bb : 1) > 2048)
-        hipLaunchKernelGGL(k_splice_count<1024>, dim3((unsigned)P), dim3(1024), 0, stream, a);
-    else
-        hipLaunchKernelGGL(k_splice_count<256>, dim3((unsigned)P), dim3(256), 0, stream, a);
+    CAL_REBATCH_COUNT(k_splice_count, (Ea + Eb) / (Ba + Bb > 0 ? Ba + Bb : 1), P, stream, a);
     CAL_CHECK_LAUNCH("k_splice_count");
     return 0;
 }
@@ -367,29 +234,15 @@ CAL_EXPORT int cal_graph_splice_write(const int64_t* eia, int64_t Ea, int64_t Na
                                       int64_t* edge_src, void* ws, int64_t ws_bytes, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     SPLICE_REQUIRE_INPUTS();
-    CAL_REQUIRE(Nout >= 0 && Eout >= 0 && F >= 0 && F < (1 << 22), "Nout, Eout must be >= 0 and 0 <= F < 2^22");
-    CAL_REQUIRE(P == 0 || (ptr_out && edge_ptr_out), "ptr_out / edge_ptr_out are null");
-    CAL_REQUIRE(Nout == 0 || (batch_out && node_src), "batch_out / node_src are null");
-    CAL_REQUIRE(Eout == 0 || (edge_index_out && edge_src), "edge_index_out / edge_src are null");
-    CAL_REQUIRE(!x_out || (F > 0 && (Na == 0 || xa) && (Nb == 0 || xb)), "x_out needs F > 0, xa and xb");
-    const int64_t nb = (Nout + kNodeChunk - 1) / kNodeChunk, eb = (Eout + kColChunk - 1) / kColChunk;
-    CAL_REQUIRE(nb + eb <= 0x7FFFFFFF, "too many elements");
+    CAL_REBATCH_REQUIRE_WRITE(P, !x_out || (F > 0 && (Na == 0 || xa) && (Nb == 0 || xb)), "x_out needs F > 0, xa and xb",
+                              (Eout + kColChunk - 1) / kColChunk);
     if (P == 0 || nb + eb == 0) return 0;
     SpliceArgs a = make_args(eia, Ea, Na, ptr_a, eptr_a, Ba, eib, Eb, Nb, ptr_b, eptr_b, Bb, ga, gb, P, bridge_a, bridge_b, ws);
     a.a.x = xa;
     a.b.x = xb;
-    a.F = F;
     a.ptr_out = const_cast<int64_t*>(ptr_out);
     a.eptr_out = const_cast<int64_t*>(edge_ptr_out);
-    a.Nout = Nout;
-    a.Eout = Eout;
-    a.batch_out = batch_out;
-    a.x_out = x_out;
-    a.ei_out = edge_index_out;
-    a.node_src = node_src;
-    a.edge_src = edge_src;
-    a.vec = x_out && F % 4 == 0 &&
-            ((reinterpret_cast<uintptr_t>(xa) | reinterpret_cast<uintptr_t>(xb) | reinterpret_cast<uintptr_t>(x_out)) & 15) == 0;
+    a.out = write_out(Nout, Eout, batch_out, x_out, edge_index_out, node_src, edge_src, F, xa, xb);
     hipLaunchKernelGGL(k_splice_write, dim3((unsigned)(nb + eb)), dim3(256), 0, stream, a, (int)nb);
     CAL_CHECK_LAUNCH("k_splice_write");
     return 0;

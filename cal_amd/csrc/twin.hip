@@ -22,20 +22,15 @@
 //
 // No value is accumulated atomically.  Every workgroup writes its two counts to ws; the totals are their sum in workgroup
 // order.  In the one-launch path the workgroup that finishes last does that sum, and the only way to know it is last is a
-// completion ticket (one atomicInc per workgroup on a wrapping counter, nothing else): the integer result does not depend on
-// which workgroup that is.  The large path needs no ticket.
-#include <atomic>
-
-#include "segment.hpp"
+// completion ticket (last_workgroup of rebatch.hpp): the integer result does not depend on which workgroup that is.  The large
+// path needs no ticket.
+#include "rebatch.hpp"
 
 namespace cal {
 namespace {
 
 constexpr int kIt = kSegCap / kSegWide;   // columns per lane at the widest group
 constexpr uint64_t kPad = ~0ull;   // key of a column that pairs with nothing, and of the LDS rows' padding
-constexpr int kTickets = 64;   // concurrent one-launch calls (on different streams) that may be in flight
-
-__device__ unsigned int g_twin_ticket[kTickets];   // zero at load; atomicInc wraps each back to zero
 
 struct TwinArgs {
     const int64_t* ei;         // [2, E]
@@ -48,7 +43,7 @@ struct TwinArgs {
     int64_t* part;             // ws: [2 x workgroups] columns with twin < 0, self loops
     uint64_t* skey;            // ws: chunk keys in sorted order [E]          (large segments only)
     int32_t* sidx;             // ws: their column indices inside the segment (large segments only)
-    int ticket;                // slot of g_twin_ticket, -1: no ticket (the large path)
+    int ticket;                // completion ticket slot, -1: no ticket (the large path)
     int nblk;                  // workgroups of the first launch (grid.x)
 };
 
@@ -174,14 +169,7 @@ __global__ void __launch_bounds__(NT) k_twin_lds(TwinArgs a, int G, int cap) {
         a.part[2 * blockIdx.x] = unp;
         a.part[2 * blockIdx.x + 1] = nself;
     }
-    if (a.ticket < 0) return;
-    if (threadIdx.x == 0) {
-        __threadfence();
-        last = atomicInc(&g_twin_ticket[a.ticket], (unsigned)(a.nblk - 1)) == (unsigned)(a.nblk - 1);
-    }
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
+    if (a.ticket < 0 || !last_workgroup(a.ticket, a.nblk, &last)) return;
     long long s0 = 0, s1 = 0;
     for (int i = threadIdx.x; i < a.nblk; i += NT) {
         s0 += __hip_atomic_load(a.part + 2 * i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -299,8 +287,6 @@ __global__ void __launch_bounds__(kSegWide) k_twin_totals(TwinArgs a, int64_t np
     }
 }
 
-std::atomic<unsigned> g_twin_calls{0};
-
 }  // namespace
 }  // namespace cal
 
@@ -335,7 +321,7 @@ CAL_EXPORT int cal_edge_twin(const int64_t* edge_index, int64_t E, const int64_t
     const int64_t nblk = q.nblk;
     char* w = (char*)ws;
     TwinArgs a{edge_index, E, ptr, edge_ptr, B, max_edges, twin, totals, (int64_t*)w, (uint64_t*)(w + 32 * B),
-               (int32_t*)(w + 32 * B + 8 * E), q.large ? -1 : (int)(g_twin_calls.fetch_add(1) % kTickets), (int)nblk};
+               (int32_t*)(w + 32 * B + 8 * E), q.large ? -1 : next_ticket(), (int)nblk};
     const size_t lds = (size_t)12 * q.spb * q.cap + (size_t)(q.NT / 64) * 8;
     CAL_SEG_LAUNCH(k_twin_lds, q, lds, stream, a);
     CAL_CHECK_LAUNCH("k_twin_lds");

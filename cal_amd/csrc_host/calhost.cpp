@@ -801,6 +801,61 @@ HOST_EXPORT int cal_explain_rank_pairs(const float* score, int64_t stride, const
     return 0;
 }
 
+// ---- the batch builders (cal_amd/csrc/rebatch.hpp: splice, occlusion replicas, coalition replicas): what their count and write
+// entry points share.
+namespace {
+// the count side: result graph r has n nodes and m columns; finish(R) after the last one
+struct BatchScan {
+    int64_t* ptr_out; int64_t* edge_ptr_out; int64_t* totals;
+    int64_t nt = 0, et = 0, mn = 0, me = 0, empty = 0;
+    void add(int64_t r, int64_t n, int64_t m) {
+        ptr_out[r] = nt;
+        edge_ptr_out[r] = et;
+        nt += n;
+        et += m;
+        mn = std::max(mn, n);
+        me = std::max(me, m);
+        empty += n == 0;
+    }
+    void finish(int64_t R) {
+        ptr_out[R] = nt;
+        edge_ptr_out[R] = et;
+        totals[0] = nt; totals[1] = et; totals[2] = mn; totals[3] = me; totals[4] = empty;
+    }
+};
+// the write side: the next node / column of result graph r, after begin(r); nothing is written at or beyond Nout / Eout
+struct OutWriter {
+    int64_t Nout, Eout, F; const int64_t* ptr_out; const int64_t* edge_ptr_out;
+    int64_t* batch_out; float* x_out; int64_t* edge_index_out; int64_t* node_src; int64_t* edge_src;
+    int64_t r = 0, n0 = 0, i = 0, j = 0;
+    void begin(int64_t r_) { r = r_; i = n0 = ptr_out[r]; j = edge_ptr_out[r]; }
+    void node(int64_t code, const float* x, int64_t s) {      // (row s of x)
+        if (i >= Nout) return;
+        batch_out[i] = r;
+        node_src[i] = code;
+        if (x_out) memcpy(x_out + i * F, x + s * F, sizeof(float) * (size_t)F);
+        ++i;
+    }
+    void col(int64_t u, int64_t v, int64_t code) {
+        if (j >= Eout) return;
+        edge_index_out[j] = u;
+        edge_index_out[Eout + j] = v;
+        edge_src[j] = code;
+        ++j;
+    }
+};
+}  // namespace
+
+// the checks of a write entry point on what it fills (HOST_REQUIRE names the entry point), x_ok / x_msg its own on the features;
+// then W, the writer
+#define HOST_REQUIRE_WRITE(R, x_ok, x_msg)                                                                                       \
+    HOST_REQUIRE(Nout >= 0 && Eout >= 0 && F >= 0 && F < (1 << 22), "Nout, Eout must be >= 0 and 0 <= F < 2^22");                \
+    HOST_REQUIRE(R == 0 || (ptr_out && edge_ptr_out), "ptr_out / edge_ptr_out are null");                                        \
+    HOST_REQUIRE(Nout == 0 || (batch_out && node_src), "batch_out / node_src are null");                                         \
+    HOST_REQUIRE(Eout == 0 || (edge_index_out && edge_src), "edge_index_out / edge_src are null");                               \
+    HOST_REQUIRE(x_ok, x_msg);                                                                                                   \
+    OutWriter W{Nout, Eout, F, ptr_out, edge_ptr_out, batch_out, x_out, edge_index_out, node_src, edge_src}
+
 // ---- batch splice (cal_amd/csrc/splice.hip): the same order of nodes and columns, the same dropped columns and bridge rules, so
 // every integer output agrees bit for bit.  The count leaves each pair's valid-column counts in ws, as the device does.
 namespace {
@@ -847,7 +902,8 @@ HOST_EXPORT int cal_graph_splice_count(const int64_t* eia, int64_t Ea, int64_t N
     HOST_REQUIRE(totals && ptr_out && edge_ptr_out, "totals / ptr_out / edge_ptr_out are null");
     const SpliceSide A{eia, Ea, Na, ptr_a, eptr_a, Ba, ga, bridge_a}, B{eib, Eb, Nb, ptr_b, eptr_b, Bb, gb, bridge_b};
     int64_t* cnt = (int64_t*)ws;
-    int64_t nt = 0, et = 0, mn = 0, me = 0, empty = 0, unput = 0;
+    BatchScan scan{ptr_out, edge_ptr_out, totals};
+    int64_t unput = 0;
     for (int64_t p = 0; p < P; ++p) {
         int64_t alo, ahi, aelo, aehi, blo, bhi, belo, behi, ea = 0, eb = 0;
         A.ranges(p, alo, ahi, aelo, aehi);
@@ -856,21 +912,13 @@ HOST_EXPORT int cal_graph_splice_count(const int64_t* eia, int64_t Ea, int64_t N
         for (int64_t e = belo; e < behi; ++e) eb += B.valid(e, blo, bhi);
         bool asked;
         const bool put = splice_bridge(A, B, p, alo, ahi, blo, bhi, asked);
-        const int64_t n = (ahi - alo) + (bhi - blo), m = ea + eb + (put ? 2 : 0);
         cnt[p] = ea;
         cnt[P + p] = eb;
-        ptr_out[p] = nt;
-        edge_ptr_out[p] = et;
-        nt += n;
-        et += m;
-        mn = std::max(mn, n);
-        me = std::max(me, m);
-        empty += n == 0;
+        scan.add(p, (ahi - alo) + (bhi - blo), ea + eb + (put ? 2 : 0));
         unput += asked && !put;
     }
-    ptr_out[P] = nt;
-    edge_ptr_out[P] = et;
-    totals[0] = nt; totals[1] = et; totals[2] = mn; totals[3] = me; totals[4] = empty; totals[5] = unput;
+    scan.finish(P);
+    totals[5] = unput;
     return 0;
 }
 
@@ -882,43 +930,25 @@ HOST_EXPORT int cal_graph_splice_write(const int64_t* eia, int64_t Ea, int64_t N
                                        int64_t* batch_out, float* x_out, int64_t* edge_index_out, int64_t* node_src,
                                        int64_t* edge_src, void* ws, int64_t ws_bytes, void*) {
     SPLICE_REQUIRE_INPUTS();
-    HOST_REQUIRE(Nout >= 0 && Eout >= 0 && F >= 0 && F < (1 << 22), "Nout, Eout must be >= 0 and 0 <= F < 2^22");
-    HOST_REQUIRE(P == 0 || (ptr_out && edge_ptr_out), "ptr_out / edge_ptr_out are null");
-    HOST_REQUIRE(Nout == 0 || (batch_out && node_src), "batch_out / node_src are null");
-    HOST_REQUIRE(Eout == 0 || (edge_index_out && edge_src), "edge_index_out / edge_src are null");
-    HOST_REQUIRE(!x_out || (F > 0 && (Na == 0 || xa) && (Nb == 0 || xb)), "x_out needs F > 0, xa and xb");
+    HOST_REQUIRE_WRITE(P, !x_out || (F > 0 && (Na == 0 || xa) && (Nb == 0 || xb)), "x_out needs F > 0, xa and xb");
     const SpliceSide A{eia, Ea, Na, ptr_a, eptr_a, Ba, ga, bridge_a}, B{eib, Eb, Nb, ptr_b, eptr_b, Bb, gb, bridge_b};
     for (int64_t p = 0; p < P; ++p) {
         int64_t alo, ahi, aelo, aehi, blo, bhi, belo, behi;
         A.ranges(p, alo, ahi, aelo, aehi);
         B.ranges(p, blo, bhi, belo, behi);
-        const int64_t n0 = ptr_out[p], an = ahi - alo;
-        int64_t i = n0, j = edge_ptr_out[p];
-        auto node = [&](const float* x, int64_t s, int64_t code) {
-            if (i >= Nout) return;
-            batch_out[i] = p;
-            node_src[i] = code;
-            if (x_out) memcpy(x_out + i * F, x + s * F, sizeof(float) * (size_t)F);
-            ++i;
-        };
-        auto col = [&](int64_t u, int64_t v, int64_t code) {
-            if (j >= Eout) return;
-            edge_index_out[j] = u;
-            edge_index_out[Eout + j] = v;
-            edge_src[j] = code;
-            ++j;
-        };
-        for (int64_t s = alo; s < ahi; ++s) node(xa, s, s);
-        for (int64_t s = blo; s < bhi; ++s) node(xb, s, -1 - s);
+        W.begin(p);
+        const int64_t n0 = W.n0, an = ahi - alo;
+        for (int64_t s = alo; s < ahi; ++s) W.node(s, xa, s);
+        for (int64_t s = blo; s < bhi; ++s) W.node(-1 - s, xb, s);
         for (int64_t e = aelo; e < aehi; ++e)
-            if (A.valid(e, alo, ahi)) col(n0 + (eia[e] - alo), n0 + (eia[Ea + e] - alo), e);
+            if (A.valid(e, alo, ahi)) W.col(n0 + (eia[e] - alo), n0 + (eia[Ea + e] - alo), e);
         for (int64_t e = belo; e < behi; ++e)
-            if (B.valid(e, blo, bhi)) col(n0 + an + (eib[e] - blo), n0 + an + (eib[Eb + e] - blo), -1 - e);
+            if (B.valid(e, blo, bhi)) W.col(n0 + an + (eib[e] - blo), n0 + an + (eib[Eb + e] - blo), -1 - e);
         bool asked;
         if (splice_bridge(A, B, p, alo, ahi, blo, bhi, asked)) {
             const int64_t u = n0 + (bridge_a[p] - alo), v = n0 + an + (bridge_b[p] - blo);
-            col(u, v, CAL_SPLICE_BRIDGE);
-            col(v, u, CAL_SPLICE_BRIDGE);
+            W.col(u, v, CAL_SPLICE_BRIDGE);
+            W.col(v, u, CAL_SPLICE_BRIDGE);
         }
     }
     return 0;
@@ -968,23 +998,14 @@ HOST_EXPORT int cal_occlude_count(const int64_t* edge_index, int64_t E, int64_t 
     OCCLUDE_REQUIRE_INPUTS();
     HOST_REQUIRE(totals && ptr_out && edge_ptr_out, "totals / ptr_out / edge_ptr_out are null");
     const OccludeSrc S{edge_index, E, N, ptr, edge_ptr, B, rep_graph, rep_elem, mode, mode == 0 ? twin : nullptr};
-    int64_t nt = 0, et = 0, mn = 0, me = 0, empty = 0;
+    BatchScan scan{ptr_out, edge_ptr_out, totals};
     for (int64_t r = 0; r < R; ++r) {
         int64_t nlo, nhi, elo, ehi, rn, c0, c1, m = 0;
         S.ranges(r, nlo, nhi, elo, ehi, rn, c0, c1);
         for (int64_t e = elo; e < ehi; ++e) m += S.stays(e, nlo, nhi, rn, c0, c1);
-        const int64_t n = (nhi - nlo) - (rn >= 0 ? 1 : 0);
-        ptr_out[r] = nt;
-        edge_ptr_out[r] = et;
-        nt += n;
-        et += m;
-        mn = std::max(mn, n);
-        me = std::max(me, m);
-        empty += n == 0;
+        scan.add(r, (nhi - nlo) - (rn >= 0 ? 1 : 0), m);
     }
-    ptr_out[R] = nt;
-    edge_ptr_out[R] = et;
-    totals[0] = nt; totals[1] = et; totals[2] = mn; totals[3] = me; totals[4] = empty;
+    scan.finish(R);
     return 0;
 }
 
@@ -994,31 +1015,18 @@ HOST_EXPORT int cal_occlude_write(const int64_t* edge_index, int64_t E, int64_t 
                                   const int64_t* edge_ptr_out, int64_t Nout, int64_t Eout, int64_t* batch_out, float* x_out,
                                   int64_t* edge_index_out, int64_t* node_src, int64_t* edge_src, void*, int64_t, void*) {
     OCCLUDE_REQUIRE_INPUTS();
-    HOST_REQUIRE(Nout >= 0 && Eout >= 0 && F >= 0 && F < (1 << 22), "Nout, Eout must be >= 0 and 0 <= F < 2^22");
-    HOST_REQUIRE(R == 0 || (ptr_out && edge_ptr_out), "ptr_out / edge_ptr_out are null");
-    HOST_REQUIRE(Nout == 0 || (batch_out && node_src), "batch_out / node_src are null");
-    HOST_REQUIRE(Eout == 0 || (edge_index_out && edge_src), "edge_index_out / edge_src are null");
-    HOST_REQUIRE(!x_out || (F > 0 && (N == 0 || x)), "x_out needs F > 0 and x");
+    HOST_REQUIRE_WRITE(R, !x_out || (F > 0 && (N == 0 || x)), "x_out needs F > 0 and x");
     const OccludeSrc S{edge_index, E, N, ptr, edge_ptr, B, rep_graph, rep_elem, mode, mode == 0 ? twin : nullptr};
     for (int64_t r = 0; r < R; ++r) {
         int64_t nlo, nhi, elo, ehi, rn, c0, c1;
         S.ranges(r, nlo, nhi, elo, ehi, rn, c0, c1);
-        const int64_t n0 = ptr_out[r];
-        int64_t i = n0, j = edge_ptr_out[r];
-        for (int64_t s = nlo; s < nhi; ++s) {
-            if (s == rn || i >= Nout) continue;
-            batch_out[i] = r;
-            node_src[i] = s;
-            if (x_out) memcpy(x_out + i * F, x + s * F, sizeof(float) * (size_t)F);
-            ++i;
-        }
+        W.begin(r);
+        for (int64_t s = nlo; s < nhi; ++s)
+            if (s != rn) W.node(s, x, s);
         for (int64_t e = elo; e < ehi; ++e) {
-            if (!S.stays(e, nlo, nhi, rn, c0, c1) || j >= Eout) continue;
+            if (!S.stays(e, nlo, nhi, rn, c0, c1)) continue;
             const int64_t u = edge_index[e], v = edge_index[E + e];
-            edge_index_out[j] = n0 + (u - nlo) - (rn >= 0 && u > rn ? 1 : 0);
-            edge_index_out[Eout + j] = n0 + (v - nlo) - (rn >= 0 && v > rn ? 1 : 0);
-            edge_src[j] = e;
-            ++j;
+            W.col(W.n0 + (u - nlo) - (rn >= 0 && u > rn ? 1 : 0), W.n0 + (v - nlo) - (rn >= 0 && v > rn ? 1 : 0), e);
         }
     }
     return 0;
@@ -1077,7 +1085,7 @@ HOST_EXPORT int cal_coalition_count(const int64_t* edge_index, int64_t E, int64_
                                     int64_t* ptr_out, int64_t* edge_ptr_out, int64_t* totals, void*, int64_t, void*) {
     COALITION_REQUIRE_INPUTS();
     HOST_REQUIRE(totals && ptr_out && edge_ptr_out, "totals / ptr_out / edge_ptr_out are null");
-    int64_t nt = 0, et = 0, mn = 0, me = 0, empty = 0;
+    BatchScan scan{ptr_out, edge_ptr_out, totals};
     for (int64_t r = 0; r < R; ++r) {
         int64_t nlo, nhi, elo, ehi, th, n = 0, m = 0;
         const int32_t* row;
@@ -1085,17 +1093,9 @@ HOST_EXPORT int cal_coalition_count(const int64_t* edge_index, int64_t E, int64_
         if (mode == 0) n = nhi - nlo;
         else for (int64_t s = nlo; s < nhi; ++s) n += S.elem(row, th, s);
         for (int64_t e = elo; e < ehi; ++e) m += S.stays(e, nlo, nhi, row, th);
-        ptr_out[r] = nt;
-        edge_ptr_out[r] = et;
-        nt += n;
-        et += m;
-        mn = std::max(mn, n);
-        me = std::max(me, m);
-        empty += n == 0;
+        scan.add(r, n, m);
     }
-    ptr_out[R] = nt;
-    edge_ptr_out[R] = et;
-    totals[0] = nt; totals[1] = et; totals[2] = mn; totals[3] = me; totals[4] = empty;
+    scan.finish(R);
     return 0;
 }
 
@@ -1106,34 +1106,21 @@ HOST_EXPORT int cal_coalition_write(const int64_t* edge_index, int64_t E, int64_
                                     int64_t* batch_out, float* x_out, int64_t* edge_index_out, int64_t* node_src,
                                     int64_t* edge_src, void*, int64_t, void*) {
     COALITION_REQUIRE_INPUTS();
-    HOST_REQUIRE(Nout >= 0 && Eout >= 0 && F >= 0 && F < (1 << 22), "Nout, Eout must be >= 0 and 0 <= F < 2^22");
-    HOST_REQUIRE(R == 0 || (ptr_out && edge_ptr_out), "ptr_out / edge_ptr_out are null");
-    HOST_REQUIRE(Nout == 0 || (batch_out && node_src), "batch_out / node_src are null");
-    HOST_REQUIRE(Eout == 0 || (edge_index_out && edge_src), "edge_index_out / edge_src are null");
-    HOST_REQUIRE(!x_out || (F > 0 && (N == 0 || x)), "x_out needs F > 0 and x");
+    HOST_REQUIRE_WRITE(R, !x_out || (F > 0 && (N == 0 || x)), "x_out needs F > 0 and x");
     std::vector<int64_t> local;                            // (mode 1) new local id of every node of the replica's graph
     for (int64_t r = 0; r < R; ++r) {
         int64_t nlo, nhi, elo, ehi, th;
         const int32_t* row;
         S.ranges(r, nlo, nhi, elo, ehi, row, th);
-        const int64_t n0 = ptr_out[r];
-        int64_t i = n0, j = edge_ptr_out[r];
+        W.begin(r);
         local.assign((size_t)(nhi - nlo), 0);
         for (int64_t s = nlo; s < nhi; ++s) {
-            local[(size_t)(s - nlo)] = i - n0;
-            if ((mode == 1 && !S.elem(row, th, s)) || i >= Nout) continue;
-            batch_out[i] = r;
-            node_src[i] = s;
-            if (x_out) memcpy(x_out + i * F, x + s * F, sizeof(float) * (size_t)F);
-            ++i;
+            local[(size_t)(s - nlo)] = W.i - W.n0;
+            if (mode == 0 || S.elem(row, th, s)) W.node(s, x, s);
         }
-        for (int64_t e = elo; e < ehi; ++e) {
-            if (!S.stays(e, nlo, nhi, row, th) || j >= Eout) continue;
-            edge_index_out[j] = n0 + local[(size_t)(edge_index[e] - nlo)];
-            edge_index_out[Eout + j] = n0 + local[(size_t)(edge_index[E + e] - nlo)];
-            edge_src[j] = e;
-            ++j;
-        }
+        for (int64_t e = elo; e < ehi; ++e)
+            if (S.stays(e, nlo, nhi, row, th))
+                W.col(W.n0 + local[(size_t)(edge_index[e] - nlo)], W.n0 + local[(size_t)(edge_index[E + e] - nlo)], e);
     }
     return 0;
 }

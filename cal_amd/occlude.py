@@ -25,7 +25,7 @@ import torch
 from . import _lib
 from .explain import _HEADS, _Layout, _k_code, _keep8, _log_probs, _reduce_code, _scores, rank_segment_pairs, rank_segments
 from .plan import _p, _stream
-from .splice import _Source, _check_use, _pairs
+from .splice import _Source, _built_batch, _check_use, _feature_width, _pairs, _rebatch
 
 __all__ = ["Occlusion", "occlude_batch", "occlusion", "rank_agreement", "faithfulness", "eval_faithfulness"]
 
@@ -49,18 +49,10 @@ def occlude_batch(data, rep_graph, rep_elem, *, use: str = "edges", twin=None):
     CUDA tensors: ``cal_occlude_count`` and ``cal_occlude_write`` on the current stream with one read-back of the totals between
     them; CPU tensors: libcalhost.  Inputs other than ``Batch`` objects get their layout derived as in ``splice_batches``; edge
     columns that are not grouped by graph are put in stable graph order first and ``edge_src`` is mapped back to the caller's."""
-    from .data import Batch
     _check_use(use)
     mode = 0 if use == "edges" else 1
     S = _Source(data)
-    dev, host = S.dev, not S.ei.is_cuda
-    F = 0
-    if S.x is not None:
-        if S.x.dtype != torch.float32:
-            raise TypeError("occlude_batch copies float32 features")
-        if S.x.dim() != 2:
-            raise ValueError("the features must be [N, F]")
-        F = int(S.x.size(1))
+    dev, F = S.dev, _feature_width(S, "occlude_batch")
     if rep_graph is None or rep_elem is None:
         raise TypeError("rep_graph and rep_elem are required")
     rg, re = _pairs(rep_graph, 0, dev, "rep_graph"), _pairs(rep_elem, 0, dev, "rep_elem")
@@ -79,33 +71,12 @@ def occlude_batch(data, rep_graph, rep_elem, *, use: str = "edges", twin=None):
         if tw is not None:
             tw = tw[S.order]
             tw = torch.where(tw >= 0, inv[tw.clamp(min=0).long()].to(torch.int32), tw).contiguous()
-    wsb = _lib.query("cal_occlude_ws", S.E, R, host=host)
-    sizes = (R + 1, R + 1, 5, (wsb + 7) // 8)
-    ptr_o, eptr_o, totals, ws = torch.split(torch.empty(sum(sizes), dtype=torch.long, device=dev), sizes)
-    st = None if host else _stream()
     inputs = S.args() + [_p(rg) if R else None, _p(re) if R else None, R, mode, _p(tw) if S.E else None]
-    _lib.call("cal_occlude_count", *inputs, _p(ptr_o), _p(eptr_o), _p(totals), _p(ws), 8 * sizes[-1], st, host=host)
-    # the one read-back: the Batch needs the totals as host ints (and y whether every replica has a graph)
-    n2, e2, mn, me, empty, bad = torch.cat([totals, ((rg < 0) | (rg >= S.B)).sum().view(1)]).tolist()
-    ints = torch.empty(2 * n2 + 3 * e2, dtype=torch.long, device=dev)
-    batch_o, nsrc, ei_o, esrc = torch.split(ints, (n2, n2, 2 * e2, e2))
-    x_o = torch.empty(n2, F, dtype=torch.float32, device=dev) if F else None
-    xin = S.x.contiguous() if F else None
-    _lib.call("cal_occlude_write", *inputs, _p(xin) if F and S.N else None, F, _p(ptr_o), _p(eptr_o), n2, e2,
-              _p(batch_o) if n2 else None, _p(x_o) if F and n2 else None, _p(ei_o) if e2 else None, _p(nsrc) if n2 else None,
-              _p(esrc) if e2 else None, _p(ws), 8 * sizes[-1], st, host=host)
-    if S.order is not None and e2:                         # columns that were reordered: back to the caller's numbering
+    built = _rebatch("cal_occlude", (S.E, R), inputs, R, 5, (S,), F, lambda: (rg < 0) | (rg >= S.B))
+    esrc = built.edge_src
+    if S.order is not None and built.tot[1]:               # columns that were reordered: back to the caller's numbering
         esrc = S.order[esrc]
-    out = Batch()
-    out.x, out.feat = (x_o, None) if S.is_x or S.x is None else (None, x_o)
-    out.edge_index, out.batch = ei_o.view(2, e2), batch_o
-    out.y = S.y.view(-1)[rg] if S.y is not None and not bad else None
-    out.ptr, out.edge_ptr, out.num_graphs = ptr_o, eptr_o, R
-    out.max_nodes, out.max_edges = int(mn), int(me)
-    out.no_self_loops = S.no_self_loops
-    out.node_src, out.edge_src = nsrc, esrc
-    out.empty_graphs = int(empty)
-    return out
+    return _built_batch(S, built, rg, S.no_self_loops, esrc)
 
 
 # ---- leave-one-out scores -----------------------------------------------------------------------------------------------------

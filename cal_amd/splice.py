@@ -14,6 +14,8 @@ that has already mixed trivial structure into ``xo`` passes ``intervene`` untouc
 """
 from __future__ import annotations
 
+from collections import namedtuple
+
 import torch
 
 from . import _lib
@@ -64,6 +66,63 @@ def _pairs(t, n: int, dev, what: str):
     return t.to(device=dev, dtype=torch.long).contiguous()
 
 
+def _feature_width(S, name: str) -> int:
+    """F of a replica builder's one source (0: no features); ``name`` is the builder's, for the message."""
+    if S.x is None:
+        return 0
+    if S.x.dtype != torch.float32:
+        raise TypeError("%s copies float32 features" % name)
+    if S.x.dim() != 2:
+        raise ValueError("the features must be [N, F]")
+    return int(S.x.size(1))
+
+
+#: what ``_rebatch`` returns: the offsets, ``tot`` (the totals and the bad count as host ints: nodes, columns, largest node count,
+#: largest column count, result graphs without a node, ..., bad), the outputs (``edge_index`` flat [2 Eout], ``x`` or ``None``)
+_Built = namedtuple("_Built", "ptr edge_ptr tot batch node_src edge_index edge_src x")
+
+
+def _rebatch(stem: str, ws_args, inputs, R: int, ntot: int, srcs, F: int, bad):
+    """The calls of one batch builder, ``stem`` + ``_ws`` / ``_count`` / ``_write``: the workspace query, one allocation for the
+    offsets, ``totals`` [ntot] and the workspace, the count, the one read-back, the outputs' allocation, the write.  ``inputs``:
+    the arguments both entry points start with; ``srcs``: the ``_Source`` objects whose rows (F columns) are copied; ``bad()``: a
+    bool tensor whose count is read back with the totals -- a callable, so that its torch launches are issued while the count
+    kernel runs, not in front of it.  -> ``_Built``."""
+    dev, host = srcs[0].dev, not srcs[0].ei.is_cuda
+    wsb = _lib.query(stem + "_ws", *ws_args, host=host)
+    sizes = (R + 1, R + 1, ntot, (wsb + 7) // 8)
+    ptr_o, eptr_o, totals, ws = torch.split(torch.empty(sum(sizes), dtype=torch.long, device=dev), sizes)
+    st = None if host else _stream()
+    _lib.call(stem + "_count", *inputs, _p(ptr_o), _p(eptr_o), _p(totals), _p(ws), 8 * sizes[-1], st, host=host)
+    # the one read-back: the Batch needs the totals as host ints (and y whether every result graph has its source of y)
+    tot = torch.cat([totals, bad().sum().view(1)]).tolist()
+    n2, e2 = tot[:2]
+    ints = torch.empty(2 * n2 + 3 * e2, dtype=torch.long, device=dev)
+    batch_o, nsrc, ei_o, esrc = torch.split(ints, (n2, n2, 2 * e2, e2))
+    x_o = torch.empty(n2, F, dtype=torch.float32, device=dev) if F else None
+    xs = [s.x.contiguous() if F and s.N else None for s in srcs]
+    _lib.call(stem + "_write", *inputs, *map(_p, xs), F, _p(ptr_o), _p(eptr_o), n2, e2,
+              _p(batch_o) if n2 else None, _p(x_o) if F and n2 else None, _p(ei_o) if e2 else None, _p(nsrc) if n2 else None,
+              _p(esrc) if e2 else None, _p(ws), 8 * sizes[-1], st, host=host)
+    return _Built(ptr_o, eptr_o, tot, batch_o, nsrc, ei_o, esrc, x_o)
+
+
+def _built_batch(S, b, picks, no_self_loops: bool, edge_src):
+    """The ``Batch`` of ``b`` (``_Built``): features as ``S`` carries them, ``y = S.y[picks]`` unless a pick was bad; ``edge_src``
+    in the caller's column numbering."""
+    from .data import Batch
+    out = Batch()
+    out.x, out.feat = (b.x, None) if S.is_x or S.x is None else (None, b.x)
+    out.edge_index, out.batch = b.edge_index.view(2, b.tot[1]), b.batch
+    out.y = S.y.view(-1)[picks] if S.y is not None and not b.tot[-1] else None
+    out.ptr, out.edge_ptr, out.num_graphs = b.ptr, b.edge_ptr, int(picks.numel())
+    out.max_nodes, out.max_edges = int(b.tot[2]), int(b.tot[3])
+    out.no_self_loops = no_self_loops
+    out.node_src, out.edge_src = b.node_src, edge_src
+    out.empty_graphs = int(b.tot[4])
+    return out
+
+
 def splice_batches(a, b, pairs_a=None, pairs_b=None, *, bridge=None):
     """Per pair the disjoint union of one graph of ``a`` and one graph of ``b``, as a ``cal_amd.data.Batch`` the engine can run.
 
@@ -82,9 +141,8 @@ def splice_batches(a, b, pairs_a=None, pairs_b=None, *, bridge=None):
     CUDA tensors: ``cal_graph_splice_count`` and ``cal_graph_splice_write`` on the current stream with one read-back of the
     totals between them; CPU tensors: libcalhost.  Inputs other than ``Batch`` objects get their layout derived as in
     ``extract_subgraph``; edge columns that are not grouped by graph are put in stable graph order first."""
-    from .data import Batch
     A, Bs = _Source(a), _Source(b)
-    dev, host = A.dev, not A.ei.is_cuda
+    dev = A.dev
     if Bs.dev != dev:
         raise ValueError("a and b must be on one device")
     if (A.x is None) != (Bs.x is None):
@@ -115,35 +173,16 @@ def splice_batches(a, b, pairs_a=None, pairs_b=None, *, bridge=None):
         ba, bb = _pairs(bridge[0], P, dev, "bridge[0]"), _pairs(bridge[1], P, dev, "bridge[1]")
         if int(ba.numel()) != P or int(bb.numel()) != P:
             raise ValueError("the bridge tensors must have one entry per result graph")
-    wsb = _lib.query("cal_graph_splice_ws", A.E, Bs.E, P, host=host)
-    sizes = (P + 1, P + 1, 6, (wsb + 7) // 8)
-    ptr_o, eptr_o, totals, ws = torch.split(torch.empty(sum(sizes), dtype=torch.long, device=dev), sizes)
-    st = None if host else _stream()
     inputs = A.args() + Bs.args() + [_p(ga) if P else None, _p(gb) if P else None, P, _p(ba), _p(bb)]
-    _lib.call("cal_graph_splice_count", *inputs, _p(ptr_o), _p(eptr_o), _p(totals), _p(ws), 8 * sizes[-1], st, host=host)
-    # the one read-back: the Batch needs the totals as host ints (and y whether every pair has a part of a)
-    n2, e2, mn, me, empty, unput, bad = torch.cat([totals, (~a_ok).sum().view(1)]).tolist()
-    ints = torch.empty(2 * n2 + 3 * e2, dtype=torch.long, device=dev)
-    batch_o, nsrc, ei_o, esrc = torch.split(ints, (n2, n2, 2 * e2, e2))
-    x_o = torch.empty(n2, F, dtype=torch.float32, device=dev) if F else None
-    xa, xb = (A.x.contiguous(), Bs.x.contiguous()) if F else (None, None)
-    _lib.call("cal_graph_splice_write", *inputs, _p(xa) if F and A.N else None, _p(xb) if F and Bs.N else None, F, _p(ptr_o),
-              _p(eptr_o), n2, e2, _p(batch_o) if n2 else None, _p(x_o) if F and n2 else None, _p(ei_o) if e2 else None,
-              _p(nsrc) if n2 else None, _p(esrc) if e2 else None, _p(ws), 8 * sizes[-1], st, host=host)
+    built = _rebatch("cal_graph_splice", (A.E, Bs.E, P), inputs, P, 6, (A, Bs), F, lambda: ~a_ok)
+    e2, esrc = built.tot[1], built.edge_src
     for s, neg in ((A, False), (Bs, True)):                # columns that were reordered: back to the caller's numbering
         if s.order is not None and e2:
             m = (esrc < 0) & (esrc != BRIDGE) if neg else esrc >= 0
             idx = (-1 - esrc if neg else esrc).clamp(0, max(s.E - 1, 0))
             esrc = torch.where(m, -1 - s.order[idx] if neg else s.order[idx], esrc)
-    out = Batch()
-    out.x, out.feat = (x_o, None) if A.is_x or A.x is None else (None, x_o)
-    out.edge_index, out.batch = ei_o.view(2, e2), batch_o
-    out.y = A.y.view(-1)[ga] if A.y is not None and not bad else None
-    out.ptr, out.edge_ptr, out.num_graphs = ptr_o, eptr_o, P
-    out.max_nodes, out.max_edges = int(mn), int(me)
-    out.no_self_loops = A.no_self_loops and Bs.no_self_loops
-    out.node_src, out.edge_src = nsrc, esrc
-    out.empty_graphs, out.bridges_unwritten = int(empty), int(unput)
+    out = _built_batch(A, built, ga, A.no_self_loops and Bs.no_self_loops, esrc)
+    out.bridges_unwritten = int(built.tot[5])
     return out
 
 

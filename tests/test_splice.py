@@ -234,3 +234,33 @@ def test_cpu_structure_intervention_leaves_state_untouched():
     m.eval()
     structure_intervention(m, b, k=2, partners=1)
     assert not m.training
+
+
+def test_every_builder_makes_one_query_and_two_calls(monkeypatch):
+    """splice_batches, occlude_batch and coalition_batch go through one driver: per call one workspace query, the count, the
+    write, nothing else; without a result graph they return the empty Batch."""
+    from cal_amd.coalition import coalition_batch
+    from cal_amd.occlude import occlude_batch
+    a, b, _, _, _ = CASES["identity"]
+    seen = []
+    call, query = _lib.call, _lib.query
+    monkeypatch.setattr(_lib, "call", lambda name, *args, **kw: (seen.append(name), call(name, *args, **kw))[1])
+    monkeypatch.setattr(_lib, "query", lambda name, *args, **kw: (seen.append(name), query(name, *args, **kw))[1])
+    E, N = int(a.edge_index.size(1)), int(a.batch.numel())
+    for R in (3, 0):
+        rg, none = torch.arange(R), torch.zeros(0, dtype=torch.long)
+        runs = [("cal_graph_splice", lambda: splice_batches(a, b, rg, rg, bridge="first"))]
+        for use, M in (("edges", E), ("nodes", N)):
+            runs.append(("cal_occlude", lambda use=use: occlude_batch(a, rg, a.ptr[:R] if R else none, use=use)))
+            runs.append(("cal_coalition", lambda use=use, M=M: coalition_batch(a, rg, torch.full((R,), 1), torch.arange(M) % 3, use=use)))
+        for stem, run in runs:
+            del seen[:]
+            res = run()
+            assert seen == [stem + "_ws", stem + "_count", stem + "_write"], stem
+            assert res.num_graphs == R and res.ptr.numel() == R + 1 and res.edge_ptr.numel() == R + 1
+            if R == 0:
+                assert res.edge_index.shape == (2, 0) and res.x.shape == (0, 5) and res.feat is None and res.batch.numel() == 0
+                assert res.ptr.tolist() == [0] and res.edge_ptr.tolist() == [0] and res.y.numel() == 0
+                assert res.node_src.numel() == 0 and res.edge_src.numel() == 0 and res.no_self_loops == a.no_self_loops
+                assert (res.max_nodes, res.max_edges, res.empty_graphs) == (0, 0, 0)
+                assert getattr(res, "bridges_unwritten", 0) == 0
