@@ -482,6 +482,143 @@ HOST_EXPORT int cal_gat_dropout_mask(uint64_t seed, int64_t E, int64_t N, int64_
     return 0;
 }
 
+// ---- soft edge masks (cal_amd/csrc/softmask.hip; cal_amd/gradient.py): the same formulas, sums in slot order.
+// out[e] = <a[col[e]], b[row[e]]>, exactly 0 for a self-loop column: d/dw_e of GINConv's weighted sum
+HOST_EXPORT int cal_edge_dot(const int32_t* row32, const int32_t* col32, const float* a, const float* b, float* out, int64_t N,
+                             int64_t E, int64_t H, void*) {
+    HOST_REQUIRE(N >= 0 && E >= 0 && H >= 0, "bad sizes");
+#pragma omp parallel for schedule(static)
+    for (int64_t e = 0; e < E; ++e) {
+        const int r = row32[e], c = col32[e];
+        float p = 0.f;
+        if (r != c) for (int64_t h = 0; h < H; ++h) p = fmaf(a[(int64_t)c * H + h], b[(int64_t)r * H + h], p);
+        out[e] = p;
+    }
+    return 0;
+}
+
+// GATConv with a mask m >= 0 by column inside the edge softmax (no dropout): alpha = m exp(e - max) / (sum m exp(e - max) + 1e-16),
+// the added loop at weight 1, max over the loop and the columns with m > 0
+HOST_EXPORT int cal_gat_mask_fwd(const int32_t* rowptr, const int32_t* nbr, const int32_t* eid, const float* z, const float* att,
+                                 const float* bias, int relu, float slope, const float* m, float* out, float* adst, float* asrc,
+                                 float* mx, float* den, int64_t N, int64_t E, int64_t K, int64_t D, void*) {
+    HOST_REQUIRE(N >= 0 && E >= 0 && K > 0 && K <= 64 && D > 0, "bad shape (1 <= K <= 64, D >= 1)");
+    const int64_t H = K * D;
+#pragma omp parallel for schedule(static)
+    for (int64_t t = 0; t < N * K; ++t) {
+        const int64_t k = t % K;
+        const float* zp = z + t * D;
+        float sd = 0.f, ss = 0.f;
+        for (int64_t d = 0; d < D; ++d) { sd = fmaf(zp[d], att[k * 2 * D + d], sd); ss = fmaf(zp[d], att[k * 2 * D + D + d], ss); }
+        adst[t] = sd; asrc[t] = ss;
+    }
+#pragma omp parallel for schedule(dynamic, 64)
+    for (int64_t i = 0; i < N; ++i)
+        for (int64_t k = 0; k < K; ++k) {
+            const float ad = adst[i * K + k];
+            const float eself = lrelu(ad + asrc[i * K + k], slope);
+            float mv = eself;
+            for (int s = rowptr[i]; s < rowptr[i + 1]; ++s)
+                if (m[eid[s]] > 0.f) mv = fmaxf(mv, lrelu(ad + asrc[(int64_t)nbr[s] * K + k], slope));
+            float* o = out + i * H + k * D;
+            for (int64_t d = 0; d < D; ++d) o[d] = 0.f;
+            float lsum = 0.f;
+            for (int s = rowptr[i]; s <= rowptr[i + 1]; ++s) {
+                const bool self = s == rowptr[i + 1];
+                const int64_t j = self ? i : nbr[s];
+                const float ms = self ? 1.f : m[eid[s]];
+                if (!(ms > 0.f)) continue;
+                const float wgt = ms * expf((self ? eself : lrelu(ad + asrc[j * K + k], slope)) - mv);
+                lsum += wgt;
+                const float* zj = z + j * H + k * D;
+                for (int64_t d = 0; d < D; ++d) o[d] = fmaf(wgt, zj[d], o[d]);
+            }
+            const float dn = lsum + 1e-16f;
+            for (int64_t d = 0; d < D; ++d) {
+                const float v = o[d] / dn + (bias ? bias[k * D + d] : 0.f);
+                o[d] = relu ? (v > 0.f ? v : 0.f) : v;
+            }
+            mx[i * K + k] = mv; den[i * K + k] = dn;
+        }
+    return 0;
+}
+HOST_EXPORT int64_t cal_gat_mask_bwd_ws(int64_t, int64_t, int64_t, int64_t) { return 4; }
+// gout: gradient at the layer output (already masked by the ReLU if one was fused).  dz [N, K*D]; dm [E], 0 for a column
+// outside the CSR (an input self loop).  max is a constant.
+HOST_EXPORT int cal_gat_mask_bwd(const int32_t* rowptr_dst, const int32_t* nbr_dst, const int32_t* eid_dst, const int32_t* rowptr_src,
+                                 const int32_t* nbr_src, const int32_t* eid_src, const float* z, const float* att, const float* adst,
+                                 const float* asrc, const float* mx, const float* den, const float* gout, float slope, const float* m,
+                                 float* dz, float* dm, float* ws, int64_t N, int64_t E, int64_t K, int64_t D, void*) {
+    (void)ws;
+    HOST_REQUIRE(N >= 0 && E >= 0 && K > 0 && K <= 64 && D > 0, "bad shape (1 <= K <= 64, D >= 1)");
+    const int64_t H = K * D;
+    std::vector<float> draw((size_t)(E + N) * K, 0.f);
+    for (int64_t e = 0; e < E; ++e) dm[e] = 0.f;
+#pragma omp parallel for schedule(dynamic, 64)
+    for (int64_t i = 0; i < N; ++i) {
+        const int s0 = rowptr_dst[i], s1 = rowptr_dst[i + 1];
+        std::vector<float> S((size_t)K, 0.f);
+        for (int64_t k = 0; k < K; ++k) {
+            const float ad = adst[i * K + k], mk = mx[i * K + k], dn = den[i * K + k];
+            const float* gi = gout + i * H + k * D;
+            float acc = 0.f;
+            for (int s = s0; s <= s1; ++s) {
+                const bool self = s == s1;
+                const int64_t j = self ? i : nbr_dst[s];
+                const float ms = self ? 1.f : m[eid_dst[s]];
+                if (!(ms > 0.f)) continue;
+                const float* zj = z + j * H + k * D;
+                float dot = 0.f;
+                for (int64_t d = 0; d < D; ++d) dot = fmaf(gi[d], zj[d], dot);
+                acc = fmaf(ms * expf(lrelu(ad + asrc[j * K + k], slope) - mk) / dn, dot, acc);
+            }
+            S[k] = acc;
+        }
+        for (int s = s0; s <= s1; ++s) {
+            const bool self = s == s1;
+            const int64_t j = self ? i : nbr_dst[s], id = self ? E + i : (int64_t)eid_dst[s];
+            const float ms = self ? 1.f : m[id];
+            float dmacc = 0.f;
+            for (int64_t k = 0; k < K; ++k) {
+                const float* gi = gout + i * H + k * D;
+                const float* zj = z + j * H + k * D;
+                float dot = 0.f;
+                for (int64_t d = 0; d < D; ++d) dot = fmaf(gi[d], zj[d], dot);
+                const float raw = adst[i * K + k] + asrc[j * K + k];
+                const float q = expf(lrelu(raw, slope) - mx[i * K + k]) / den[i * K + k];
+                const float alpha = ms > 0.f ? ms * q : 0.f;
+                draw[id * K + k] = alpha * (dot - S[k]) * (raw > 0.f ? 1.f : slope);
+                dmacc += q * (dot - S[k]);
+            }
+            if (!self) dm[id] = dmacc;
+        }
+    }
+#pragma omp parallel for schedule(dynamic, 64)
+    for (int64_t j = 0; j < N; ++j)
+        for (int64_t k = 0; k < K; ++k) {
+            const float as = asrc[j * K + k];
+            float* o = dz + j * H + k * D;
+            for (int64_t d = 0; d < D; ++d) o[d] = 0.f;
+            float das = 0.f, dad = 0.f;
+            const int s0 = rowptr_src[j], s1 = rowptr_src[j + 1];
+            for (int s = s0; s <= s1; ++s) {
+                const bool self = s == s1;
+                const int64_t i = self ? j : nbr_src[s], id = self ? E + j : (int64_t)eid_src[s];
+                const float ms = self ? 1.f : m[id];
+                if (ms > 0.f) {
+                    const float alpha = ms * expf(lrelu(adst[i * K + k] + as, slope) - mx[i * K + k]) / den[i * K + k];
+                    const float* gi = gout + i * H + k * D;
+                    for (int64_t d = 0; d < D; ++d) o[d] = fmaf(alpha, gi[d], o[d]);
+                }
+                das += draw[id * K + k];
+            }
+            for (int s = rowptr_dst[j]; s < rowptr_dst[j + 1]; ++s) dad += draw[(int64_t)eid_dst[s] * K + k];
+            dad += draw[(E + j) * K + k];
+            for (int64_t d = 0; d < D; ++d) o[d] = fmaf(das, att[k * 2 * D + D + d], fmaf(dad, att[k * 2 * D + d], o[d]));
+        }
+    return 0;
+}
+
 // Batch.from_data_list for graphs that live in ONE host-side concatenation (train_causal.py:13-15; cal_amd/data.py::_HostConcat):
 // features copied, edge_index rebased by the running node offset, batch vector and labels written.  Same entry point as
 // libcalhip.so (collate.hip) -- it only ever sees host pointers, so a machine with the host library alone serves DataLoader too.

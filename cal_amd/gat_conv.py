@@ -47,10 +47,16 @@ class GATConv(torch.nn.Module):
         self._calls += 1
         return int(torch.initial_seed() * 1000003 + id(self) % 65521 * 7919 + self._calls) & ((1 << 63) - 1)
 
-    def forward(self, x, edge_index, *, plan: Optional[GraphPlan] = None, relu: bool = False):
+    def forward(self, x, edge_index, *, plan: Optional[GraphPlan] = None, relu: bool = False, edge_mask=None):
+        """``edge_mask`` ([E] >= 0, by edge column): the soft mask of ``cal_amd.gradient`` inside the edge softmax (eval mode,
+        or training without attention dropout; ``att`` and ``bias`` frozen)."""
         z = ops.matmul(x, self.weight)
         if plan is None:
             plan = GraphPlan(edge_index, x.size(0))
+        if edge_mask is not None:
+            if self.training and self.dropout > 0:
+                raise ValueError("GATConv takes an edge mask in eval mode only: the mask does not go through attention dropout")
+            return ops.gat_aggregate(z, self.att, self.bias, plan, self.heads, self.negative_slope, relu=relu, edge_mask=edge_mask)
         p = float(self.dropout) if self.training else 0.0
         seed = self._next_seed() if p > 0 else 0
         self.last_seed = seed

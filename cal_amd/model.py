@@ -70,7 +70,7 @@ class _CausalBase(torch.nn.Module):
                 torch.nn.init.constant_(m.bias, 0.0001)
 
     # -- hooks -----------------------------------------------------------------
-    def _backbone(self, x, edge_index, plan):
+    def _backbone(self, x, edge_index, plan, edge_mask=None):
         raise NotImplementedError
 
     #: CausalGCN / CausalGAT: run forward/backward on the native step engine (cal_amd/csrc/engine.hip)
@@ -183,6 +183,63 @@ class _CausalBase(torch.nn.Module):
         xo = self.objects_convs(self.bno(xo), edge_index, edge_att[1], plan=plan, relu=True)
         return ops.add_pool(xc, plan), ops.add_pool(xo, plan)
 
+    def _masked_forward(self, data, edge_mask=None, node_mask=None):
+        """Operator-level soft-mask forward with the identity intervention permutation -> the three
+        log-prob heads ``(c, o, co)`` [B, C], differentiable in the masks.  ``edge_mask`` float32 [E] >= 0 weighs every edge
+        column through every convolution, backbone included: the GCNConvs take it as (a factor of) ``edge_weight``, GINConv as
+        the weight of its sum, GATConv inside its edge softmax; ``conv_feat`` (no propagation), the attention MLPs, the pooling
+        and the readouts are as in ``forward``.  ``node_mask`` float32 [N] >= 0 puts ``n_u n_v`` on column (u, v) and scales the
+        node's rows just before the add-pool.  A column at 0 is the graph without it, a node at 0 the graph without that node,
+        all ones the model as it is.  Meant for eval mode (``cal_amd.gradient`` sets it); a GATConv refuses a mask in training
+        mode with dropout."""
+        x = data.x if data.x is not None else data.feat
+        edge_index = data.edge_index
+        plan = plan_of(data)
+        m = None
+        if edge_mask is not None:
+            m = edge_mask.view(-1)
+            if m.numel() != plan.E:
+                raise ValueError("edge_mask must have one entry per edge column (%d, got %d)" % (plan.E, m.numel()))
+        if node_mask is not None:
+            node_mask = node_mask.view(-1)
+            nm = ops.node_mask_columns(node_mask, plan)
+            m = nm if m is None else m * nm
+        if m is None:
+            m = plan.ones()[1][:plan.E]
+        x = self.bn_feat(x)
+        x = self.conv_feat(x, edge_index, relu=True)
+        x = self._backbone(x, edge_index, plan, m)
+        if getattr(self, "without_edge_attention", False):
+            edge_weight_c = edge_weight_o = 0.5 * m                                         # model.py:100
+        else:
+            edge_att = ops.edge_attention(x, self.edge_att_mlp.weight, self.edge_att_mlp.bias, plan)
+            edge_weight_c, edge_weight_o = edge_att[0] * m, edge_att[1] * m
+        if getattr(self, "without_node_attention", False):
+            xc = 0.5 * x
+            xo = 0.5 * x
+        else:
+            xc, xo, _ = ops.node_attention_split(x, self.node_att_mlp.weight, self.node_att_mlp.bias)
+        xc = self.context_convs(self.bnc(xc), edge_index, edge_weight_c, plan=plan, relu=True)
+        xo = self.objects_convs(self.bno(xo), edge_index, edge_weight_o, plan=plan, relu=True)
+        if node_mask is not None:
+            xc = xc * node_mask.view(-1, 1)
+            xo = xo * node_mask.view(-1, 1)
+        xc = ops.add_pool(xc, plan)
+        xo = ops.add_pool(xo, plan)
+        perm = torch.arange(xc.size(0), device=xc.device)
+        return (self.context_readout_layer(xc), self.objects_readout_layer(xo),
+                self.random_readout_layer(xc, xo, eval_random=False, perm=perm))
+
+    def saliency(self, data, **kw):
+        """``cal_amd.gradient.saliency(self, data, **kw)``: the gradient of ``p(ŷ)`` w.r.t. a soft mask of every edge or node."""
+        from .gradient import saliency
+        return saliency(self, data, **kw)
+
+    def integrated_gradients(self, data, **kw):
+        """``cal_amd.gradient.integrated_gradients(self, data, **kw)``: that gradient integrated from the empty to the full graph."""
+        from .gradient import integrated_gradients
+        return integrated_gradients(self, data, **kw)
+
     def intervene(self, data, **kw):
         """``cal_amd.intervene.intervene(self, data, **kw)``: the ``co`` head over every (graph, trivial partner) pair."""
         from .intervene import intervene
@@ -289,10 +346,10 @@ class CausalGCN(_CausalBase):
         self._build_head(hidden, num_classes, GConv)
         self._init_bn()
 
-    def _backbone(self, x, edge_index, plan):
+    def _backbone(self, x, edge_index, plan, edge_mask=None):
         for i, conv in enumerate(self.convs):                     # model.py:93-95
             x = self.bns_conv[i](x)
-            x = conv(x, edge_index, plan=plan, relu=True)
+            x = conv(x, edge_index, edge_mask, plan=plan, relu=True)
         return x
 
 
@@ -319,10 +376,10 @@ class CausalGAT(_CausalBase):
         self._build_head(hidden, num_classes, GConv)
         self._init_bn()
 
-    def _backbone(self, x, edge_index, plan):
+    def _backbone(self, x, edge_index, plan, edge_mask=None):
         for i, conv in enumerate(self.convs):                     # model.py:388-390
             x = self.bns_conv[i](x)
-            x = conv(x, edge_index, plan=plan, relu=True)
+            x = conv(x, edge_index, plan=plan, relu=True, edge_mask=edge_mask)
         return x
 
 
@@ -335,11 +392,11 @@ class GINConv(torch.nn.Module):
         self.initial_eps = float(eps)
         self.register_buffer("eps", torch.tensor([float(eps)]))     # PyG keeps eps in the state dict
 
-    def forward(self, x, edge_index, *, plan=None):
+    def forward(self, x, edge_index, *, plan=None, edge_mask=None):
         from .plan import GraphPlan
         if plan is None:
             plan = GraphPlan(edge_index, x.size(0))
-        out = ops.gin_aggregate(x, plan, self.initial_eps)
+        out = ops.gin_aggregate(x, plan, self.initial_eps, edge_weight=edge_mask)
         lin1, bn, _, lin2, _ = self.nn                               # model.py:189-194
         out = ops.linear(out, lin1.weight, lin1.bias)
         out = torch.relu(bn(out))
@@ -367,9 +424,9 @@ class CausalGIN(_CausalBase):
         self._build_head(hidden, num_classes, GConv)
         self._init_bn()
 
-    def _backbone(self, x, edge_index, plan):
+    def _backbone(self, x, edge_index, plan, edge_mask=None):
         for conv in self.convs:                                   # model.py:244-245
-            x = conv(x, edge_index, plan=plan)
+            x = conv(x, edge_index, plan=plan, edge_mask=edge_mask)
         return x
 
     def forward(self, data, eval_random=True, train_type="base", perm=None):

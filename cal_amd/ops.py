@@ -235,8 +235,62 @@ class _GATAggregate(Function):
         return dz, datt.view(ctx.att_shape), dbias, None, None, None, None, None, None
 
 
+class _GATMaskAggregate(Function):
+    """GATConv after z = x @ W with a mask ``m`` [E] >= 0 by edge column inside the edge softmax (no dropout):
+    ``alpha_ij = m_ij exp(s_ij - max_i) / (sum_k m_ik exp(s_ik - max_i) + 1e-16)``, the added loop at weight 1, ``max_i`` over the
+    loop and the columns with ``m > 0`` and a constant in the backward.  Differentiable in ``z`` and ``m``; ``att`` and ``bias``
+    are frozen on this path (``cal_amd.gradient``): a backward with either requiring grad raises."""
+
+    @staticmethod
+    def forward(ctx, z, att, bias, m, plan: GraphPlan, heads: int, slope: float, relu: bool):
+        z, att, m = _f32(z, "z"), _f32(att, "att"), _f32(m, "edge_mask").view(-1)
+        N, H = z.shape
+        K = int(heads)
+        D = H // K
+        if att.numel() != K * 2 * D:
+            raise ValueError("att must have heads * 2 * out_channels elements")
+        if N != plan.N:
+            raise ValueError("feature rows (%d) != plan nodes (%d)" % (N, plan.N))
+        if m.numel() != plan.E:
+            raise ValueError("edge_mask must have one entry per edge column (%d, got %d)" % (plan.E, m.numel()))
+        if bias is not None:
+            bias = _f32(bias, "bias")
+        dev = z.device
+        out = torch.empty_like(z)
+        adst, asrc, mx, den = (_empty(N * K, dev) for _ in range(4))
+        _c("cal_gat_mask_fwd", plan.rowptr_dst, plan.nbr_dst, plan.eid_dst, z, att, bias, int(relu), slope, m,
+                  out, adst, asrc, mx, den, N, plan.E, K, D)
+        ctx.plan, ctx.K, ctx.D, ctx.slope, ctx.relu = plan, K, D, slope, relu
+        ctx.save_for_backward(z, att, m, adst, asrc, mx, den, out if relu else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            raise RuntimeError("the masked GATConv has no gradient for att / bias: freeze the parameters (cal_amd.gradient does)")
+        z, att, m, adst, asrc, mx, den, out = ctx.saved_tensors
+        plan, K, D = ctx.plan, ctx.K, ctx.D
+        gout = _f32(gout, "grad")
+        N, H = gout.shape
+        dev = gout.device
+        g = gout
+        if ctx.relu:
+            g = torch.empty_like(gout)
+            _c("cal_relu_bwd_colsum", gout, out, g, None, None, N, H)
+        dz = torch.empty_like(gout)
+        dm = _empty(plan.E, dev)[:plan.E]
+        ws = _empty(_q(gout, "cal_gat_mask_bwd_ws", N, plan.E, K, D), dev)
+        _c("cal_gat_mask_bwd", plan.rowptr_dst, plan.nbr_dst, plan.eid_dst, plan.rowptr_src, plan.nbr_src, plan.eid_src,
+                  z, att, adst, asrc, mx, den, g, ctx.slope, m, dz, dm, ws, N, plan.E, K, D)
+        return dz, None, None, dm, None, None, None, None
+
+
 def gat_aggregate(z, att, bias, plan: GraphPlan, heads: int, negative_slope: float = 0.2,
-                  dropout: float = 0.0, seed: int = 0, relu: bool = False):
+                  dropout: float = 0.0, seed: int = 0, relu: bool = False, edge_mask=None):
+    if edge_mask is not None:
+        if dropout > 0:
+            raise ValueError("a GAT edge mask does not go through attention dropout")
+        return _GATMaskAggregate.apply(z, att, bias, edge_mask, plan, heads, negative_slope, relu)
     return _GATAggregate.apply(z, att, bias, plan, heads, negative_slope, dropout, seed, relu)
 
 
@@ -334,5 +388,79 @@ class _GINAggregate(Function):
         return dx, None, None
 
 
-def gin_aggregate(x, plan: GraphPlan, eps: float = 0.0):
+class _GINWeightedAggregate(Function):
+    """(1 + eps) * x_i + sum_{j -> i} w_ji x_j with a weight per edge column (self loops of the input dropped): forward and dx on the
+    CSR aggregation kernel with norm = w, dis = 1, loop_w = 1 + eps; d w_e = <g[col_e], x[row_e]> by ``cal_edge_dot``."""
+
+    @staticmethod
+    def forward(ctx, x, w, plan: GraphPlan, eps: float):
+        x, w = _f32(x, "x"), _f32(w, "edge_weight").view(-1)
+        N, H = x.shape
+        if N != plan.N:
+            raise ValueError("feature rows (%d) != plan nodes (%d)" % (N, plan.N))
+        if w.numel() != plan.E:
+            raise ValueError("edge_weight must have one entry per edge column (%d, got %d)" % (plan.E, w.numel()))
+        ones_n = plan.ones()[0]
+        wk = w if plan.E else plan.ones()[1]
+        out = torch.empty_like(x)
+        _c("cal_spmm_fwd", plan.rowptr_dst, plan.nbr_dst, plan.eid_dst, wk, ones_n, 1.0 + eps, x, None, 0, out, N, H)
+        ctx.plan, ctx.eps = plan, eps
+        ctx.save_for_backward(x if ctx.needs_input_grad[1] else None, wk)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, wk = ctx.saved_tensors
+        g = _f32(g, "grad")
+        N, H = g.shape
+        plan = ctx.plan
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(g)
+            _c("cal_spmm_fwd", plan.rowptr_src, plan.nbr_src, plan.eid_src, wk, plan.ones()[0], 1.0 + ctx.eps, g, None, 0, dx, N, H)
+        if ctx.needs_input_grad[1]:
+            dw = _empty(plan.E, g.device)[:plan.E]
+            _c("cal_edge_dot", plan.row32, plan.col32, g, x, dw, N, plan.E, H)
+        return dx, dw, None, None
+
+
+def gin_aggregate(x, plan: GraphPlan, eps: float = 0.0, edge_weight=None):
+    if edge_weight is not None:
+        return _GINWeightedAggregate.apply(x, edge_weight, plan, eps)
     return _GINAggregate.apply(x, plan, eps)
+
+
+class _NodeMaskColumns(Function):
+    """n [N] -> n[row_e] * n[col_e] per edge column: what a node mask puts on the columns.  The backward gathers over the plan's two
+    CSR views (the aggregation kernel at width 1), so it has a fixed summation order; a self-loop column, which no convolution
+    reads, sends nothing back."""
+
+    @staticmethod
+    def forward(ctx, n, plan: GraphPlan):
+        n = _f32(n, "node_mask").view(-1)
+        if n.numel() != plan.N:
+            raise ValueError("node_mask must have one entry per node (%d, got %d)" % (plan.N, n.numel()))
+        ctx.plan = plan
+        ctx.save_for_backward(n)
+        if plan.E == 0:
+            return n.new_empty(0)
+        return n[plan.row32.long()] * n[plan.col32.long()]
+
+    @staticmethod
+    def backward(ctx, g):
+        (n,) = ctx.saved_tensors
+        plan = ctx.plan
+        N = plan.N
+        if plan.E == 0 or N == 0:
+            return torch.zeros_like(n), None
+        g = _f32(g, "grad")
+        h = n.view(N, 1)
+        ones_n = plan.ones()[0]
+        a, b = torch.empty_like(h), torch.empty_like(h)
+        _c("cal_spmm_fwd", plan.rowptr_src, plan.nbr_src, plan.eid_src, g, ones_n, 0.0, h, None, 0, a, N, 1)
+        _c("cal_spmm_fwd", plan.rowptr_dst, plan.nbr_dst, plan.eid_dst, g, ones_n, 0.0, h, None, 0, b, N, 1)
+        return (a + b).view(-1), None
+
+
+def node_mask_columns(n, plan: GraphPlan):
+    return _NodeMaskColumns.apply(n, plan)

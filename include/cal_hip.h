@@ -124,6 +124,30 @@ CAL_API int cal_gat_bwd(const int32_t* rowptr_dst, const int32_t* nbr_dst, const
 CAL_API int cal_gat_dropout_mask(uint64_t seed, int64_t E, int64_t N, int64_t K, float p,
                                  float* mask, void* stream);
 
+/* ---- soft edge masks (cal_amd/gradient.py; csrc/softmask.hip, host twins in csrc_host/calhost.cpp) ------------------------
+ * cal_edge_dot: out[e] = <a[col32[e], :], b[row32[e], :]> over H floats, exactly 0 for a self-loop column; a, b [N, H].  With
+ * a = the upstream gradient and b = the input it is d/dw_e of GINConv's weighted sum (1 + eps) x_i + sum_{j -> i} w_ji x_j, whose
+ * forward and dx are cal_spmm_fwd with norm_e = w, dis = 1, loop_w = 1 + eps (call site cal_amd/ops.py _GINWeightedAggregate).
+ * E = 0 launches nothing.
+ * cal_gat_mask_fwd / _bwd: cal_gat_fwd / cal_gat_bwd without dropout and with a mask m [E] >= 0 by column inside the edge softmax,
+ * alpha_ij = m_ij exp(s_ij - max_i) / (sum_k m_ik exp(s_ik - max_i) + 1e-16), the added loop at weight 1, max_i over the loop and
+ * the columns with m > 0 and a constant in the backward (call site cal_amd/ops.py _GATMaskAggregate).  The backward returns dz and
+ * dm [E] (0 for a column outside the plan's CSR, i.e. an input self loop) and no d att: parameters are frozen on this path.
+ * One general path: 1 <= K <= 64, any D >= 1, no alignment demand.  ws: cal_gat_mask_bwd_ws floats. */
+CAL_API int cal_edge_dot(const int32_t* row32, const int32_t* col32, const float* a, const float* b, float* out,
+                         int64_t N, int64_t E, int64_t H, void* stream);
+CAL_API int cal_gat_mask_fwd(const int32_t* rowptr_dst, const int32_t* nbr_dst, const int32_t* eid_dst,
+                             const float* z, const float* att, const float* bias, int relu, float slope,
+                             const float* m, float* out, float* adst, float* asrc, float* mx, float* den,
+                             int64_t N, int64_t E, int64_t K, int64_t D, void* stream);
+CAL_API int64_t cal_gat_mask_bwd_ws(int64_t N, int64_t E, int64_t K, int64_t D);
+CAL_API int cal_gat_mask_bwd(const int32_t* rowptr_dst, const int32_t* nbr_dst, const int32_t* eid_dst,
+                             const int32_t* rowptr_src, const int32_t* nbr_src, const int32_t* eid_src,
+                             const float* z, const float* att, const float* adst, const float* asrc,
+                             const float* mx, const float* den, const float* gout, float slope,
+                             const float* m, float* dz, float* dm, float* ws, int64_t N, int64_t E,
+                             int64_t K, int64_t D, void* stream);
+
 /* ---- on-device mini-batch assembly (PyG DataLoader / Batch collate, train_causal.py:13-15,171-174)
  * over a device-resident concatenated dataset; offsets of the selected graphs computed by the host */
 CAL_API int cal_collate(const float* X, const int64_t* EI, int64_t sumE, int64_t F,
