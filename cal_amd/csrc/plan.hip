@@ -191,7 +191,8 @@ __global__ void k_graph_ptr(const int64_t* __restrict__ batch, int N, int B, int
     int64_t prev = i == 0 ? -1 : batch[i - 1];
     int64_t cur = i == N ? (int64_t)B : batch[i];
     if (i < N && (cur < prev || cur >= B || cur < 0)) { atomicOr(status, 2); return; }
-    for (int64_t b = prev + 1; b <= cur && b <= B; ++b) gptr[b] = i;
+    // prev < 0 is an invalid entry that its own thread has flagged: never index gptr below 0 for it
+    for (int64_t b = prev < 0 ? 0 : prev + 1; b <= cur && b <= B; ++b) gptr[b] = i;
 }
 
 }  // namespace cal
