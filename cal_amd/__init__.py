@@ -5,3 +5,14 @@ train_causal.py).  Hand-written HIP kernels behind a C ABI
 reference's nn.Module surface.  There is no CPU fallback: compute entry points
 raise if libcalhip.so or a GPU is missing."""
 __version__ = "0.1.0"
+
+_MASKOPT = ("LearnedMask", "MaskOptimizer", "learn_mask", "mask_agreement")
+
+
+def __getattr__(name):
+    # the learned-mask explanations (cal_amd/maskopt.py), imported on first use: importing the package loads neither torch nor a
+    # library
+    if name in _MASKOPT:
+        from . import maskopt
+        return getattr(maskopt, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

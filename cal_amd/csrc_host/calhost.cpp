@@ -619,6 +619,76 @@ HOST_EXPORT int cal_gat_mask_bwd(const int32_t* rowptr_dst, const int32_t* nbr_d
     return 0;
 }
 
+// ---- learned masks (cal_amd/csrc/maskopt.hip; cal_amd/maskopt.py): the same formulas in fp32, the per-graph sums in double in the
+// kernel's order -- 256 strided lane partials, a butterfly per 64 of them, the four wave partials in order
+namespace {
+struct Logit { float m, dm, ent; };
+inline Logit logit_terms(float th) {
+    const float a = fabsf(th), z = expf(-a), r = 1.f / (1.f + z);
+    Logit o;
+    o.m = th >= 0.f ? r : z * r;
+    o.dm = z * r * r;
+    o.ent = log1pf(z) + a * (z * r);
+    return o;
+}
+inline double lanes_total(double* v) {                        // [256], destroyed
+    for (int w = 0; w < 4; ++w)
+        for (int o = 32; o > 0; o >>= 1)
+            for (int l = 0; l < o; ++l) v[64 * w + l] += v[64 * w + l + o];
+    return ((v[0] + v[64]) + v[128]) + v[192];
+}
+}  // namespace
+
+HOST_EXPORT int cal_mask_step(const int64_t* pptr, const int32_t* rep, const int32_t* mate, const float* grad, float* theta,
+                              float* exp_avg, float* exp_avg_sq, float* mask, double* terms, int64_t B, int64_t P, int64_t M,
+                              int32_t step, float lr, float beta1, float beta2, float eps, float l_size, float l_ent, void*) {
+    HOST_REQUIRE(B >= 0 && P >= 0 && M >= 0 && step >= 0, "bad sizes");
+    if (B == 0 || P == 0) return 0;
+    HOST_REQUIRE(pptr && rep && mate && theta && (M == 0 || mask), "null operand");
+    HOST_REQUIRE(step == 0 || (grad && exp_avg && exp_avg_sq), "a step >= 1 needs grad and both moments");
+    HOST_REQUIRE(step == 0 || (beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f), "betas must be in [0, 1)");
+    float step_size = 0.f, rsq2 = 1.f;
+    if (step > 0) {
+        step_size = (float)((double)lr / (1.0 - pow((double)beta1, (double)step)));
+        rsq2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, (double)step)));
+    }
+    for (int64_t g = 0; g < B; ++g) {
+        int64_t lo = pptr[g], hi = pptr[g + 1];
+        lo = lo < 0 ? 0 : (lo > P ? P : lo);
+        hi = hi < lo ? lo : (hi > P ? P : hi);
+        const int64_t n = hi - lo;
+        const float ent_w = n > 0 ? l_ent / (float)n : 0.f;
+        double s_size[256] = {0.0}, s_ent[256] = {0.0};
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t p = lo + i;
+            const int64_t r = rep[p], t = mate[p];
+            const bool r_ok = r >= 0 && r < M, t_ok = t >= 0 && t < M;
+            float th = theta[p];
+            Logit q = logit_terms(th);
+            s_size[i & 255] += (double)q.m;
+            s_ent[i & 255] += (double)q.ent;
+            if (step > 0) {
+                // dL/dtheta = (dL_pred/dm of the player's elements + d size/dm + d entropy/dm) dm/dtheta
+                const float gr = ((r_ok ? grad[r] : 0.f) + (t_ok ? grad[t] : 0.f) + (l_size - ent_w * th)) * q.dm;
+                const float m1 = beta1 * exp_avg[p] + (1.f - beta1) * gr;
+                const float m2 = beta2 * exp_avg_sq[p] + (1.f - beta2) * gr * gr;
+                th -= step_size * (m1 / (sqrtf(m2) * rsq2 + eps));
+                exp_avg[p] = m1;
+                exp_avg_sq[p] = m2;
+                theta[p] = th;
+                q = logit_terms(th);
+            }
+            if (r_ok) mask[r] = q.m;
+            if (t_ok) mask[t] = q.m;
+        }
+        if (terms) {
+            terms[2 * g] = lanes_total(s_size);
+            terms[2 * g + 1] = lanes_total(s_ent);
+        }
+    }
+    return 0;
+}
+
 // Batch.from_data_list for graphs that live in ONE host-side concatenation (train_causal.py:13-15; cal_amd/data.py::_HostConcat):
 // features copied, edge_index rebased by the running node offset, batch vector and labels written.  Same entry point as
 // libcalhip.so (collate.hip) -- it only ever sees host pointers, so a machine with the host library alone serves DataLoader too.

@@ -242,6 +242,11 @@ def gradient_agreement(model, data, *, method: str = "ig", steps: int = 32, use:
         res = integrated_gradients(model, data, use=use, undirected=undirected, head=head, elements=elements, steps=steps)
     else:
         res = saliency(model, data, use=use, undirected=undirected, head=head, elements=elements)
+    return _agreement(model, data, res.score, res.forwards, use, undirected, ratio, k)
+
+
+def _agreement(model, data, score, forwards, use, undirected, ratio, k) -> dict:
+    """The causal score against ``score`` ([M], the caller's order) by one ``rank_agreement`` call -> the agreement dict."""
     was_training = model.training
     model.eval()
     try:
@@ -249,7 +254,7 @@ def gradient_agreement(model, data, *, method: str = "ig", steps: int = 32, use:
             edge, node = _scores(model, data)
             causal = (edge if use == "edges" else node).clone()
             lay = _Layout(data)
-            score = res.score.float()
+            score = score.float()
             sel = None
             if use == "edges":
                 if lay.order is not None:
@@ -271,5 +276,5 @@ def gradient_agreement(model, data, *, method: str = "ig", steps: int = 32, use:
     for j, key in enumerate(_AGREE):
         out[key] = row[j] / row[3 + j] if row[3 + j] else float("nan")
         out[key + "_undefined"] = int(lay.B - row[3 + j])
-    out["graphs"], out["elements"], out["forwards"] = lay.B, int(row[6]), res.forwards + 1
+    out["graphs"], out["elements"], out["forwards"] = lay.B, int(row[6]), forwards + 1
     return out

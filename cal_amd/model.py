@@ -240,6 +240,11 @@ class _CausalBase(torch.nn.Module):
         from .gradient import integrated_gradients
         return integrated_gradients(self, data, **kw)
 
+    def learn_mask(self, data, **kw):
+        """``cal_amd.maskopt.learn_mask(self, data, **kw)``: a soft mask per graph trained to keep ``p(ŷ)`` while small and binary."""
+        from .maskopt import learn_mask
+        return learn_mask(self, data, **kw)
+
     def intervene(self, data, **kw):
         """``cal_amd.intervene.intervene(self, data, **kw)``: the ``co`` head over every (graph, trivial partner) pair."""
         from .intervene import intervene

@@ -148,6 +148,25 @@ CAL_API int cal_gat_mask_bwd(const int32_t* rowptr_dst, const int32_t* nbr_dst, 
                              const float* m, float* dz, float* dm, float* ws, int64_t N, int64_t E,
                              int64_t K, int64_t D, void* stream);
 
+/* ---- learned masks (cal_amd/maskopt.py; csrc/maskopt.hip, host twin in csrc_host/calhost.cpp) ---------------------------------
+ * cal_mask_step: one optimiser step over the mask logits of a batch in one launch.  The P players
+ * are grouped by graph, pptr [B + 1]; player p owns mask element rep[p] and, for a twin pair, mate[p] (else -1), both indices
+ * into the M elements in the caller's order.  With m = sigma(theta), P_g the graph's player count and step >= 1:
+ *   g      = (grad[rep] + (mate >= 0 ? grad[mate] : 0) + l_size - (l_ent / P_g) theta) m (1 - m)       [= dL / dtheta]
+ *   exp_avg    = beta1 exp_avg + (1 - beta1) g,   exp_avg_sq = beta2 exp_avg_sq + (1 - beta2) g^2
+ *   theta -= lr / (1 - beta1^step) * exp_avg / (sqrt(exp_avg_sq) / sqrt(1 - beta2^step) + eps)
+ * and sigma(theta_new) is written to mask[rep] and mask[mate]; every other mask entry is left alone.  terms [B, 2] (or null)
+ * receives per graph sum_p m_p and sum_p H(m_p), H(m) = softplus(theta) - theta m, of the mask BEFORE the update, summed in
+ * double in a fixed order; a graph without players gets 0, 0.  step == 0 updates nothing and does not read grad (may be null) or
+ * the moments: mask and terms are written from the current theta (the initial scatter, the closing evaluation).
+ * One workgroup per graph; no atomics, one writer per output element: equal inputs give equal bits.  Finite for any finite
+ * theta.  pptr is clamped into [0, P], a rep / mate outside [0, M) is neither read nor written, B = 0 or P = 0 launches nothing.
+ * No alignment demand beyond the elements' own. */
+CAL_API int cal_mask_step(const int64_t* pptr, const int32_t* rep, const int32_t* mate, const float* grad,
+                          float* theta, float* exp_avg, float* exp_avg_sq, float* mask, double* terms,
+                          int64_t B, int64_t P, int64_t M, int32_t step, float lr, float beta1, float beta2,
+                          float eps, float l_size, float l_ent, void* stream);
+
 /* ---- on-device mini-batch assembly (PyG DataLoader / Batch collate, train_causal.py:13-15,171-174)
  * over a device-resident concatenated dataset; offsets of the selected graphs computed by the host */
 CAL_API int cal_collate(const float* X, const int64_t* EI, int64_t sumE, int64_t F,
