@@ -37,7 +37,8 @@ HOST_SYMBOLS = ("cal_last_error", "cal_version", "cal_plan_build", "cal_graph_pt
                 "cal_occlude_ws", "cal_occlude_count", "cal_occlude_write", "cal_rank_agreement_ws", "cal_rank_agreement",
                 "cal_coalition_ws", "cal_coalition_count", "cal_coalition_write",
                 "cal_edge_dot", "cal_gat_mask_fwd", "cal_gat_mask_bwd_ws", "cal_gat_mask_bwd",
-                "cal_mask_step")
+                "cal_mask_step",
+                "cal_noise_ws", "cal_noise_count", "cal_noise_write", "cal_degree_onehot")
 
 _SCALARS = {
     "int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,

@@ -1,4 +1,4 @@
-// The count / scan / write toolkit of the batch builders (splice.hip, occlude.hip, coalition.hip): operators that make a new
+// The count / scan / write toolkit of the batch builders (splice.hip, occlude.hip, coalition.hip, noise.hip): operators that make a new
 // batch of R result graphs out of the graphs of an old one.  Device helpers are __device__ __forceinline__, host helpers plain
 // inline or macros: no kernel and no translation unit of their own.
 //

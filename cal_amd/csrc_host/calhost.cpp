@@ -1333,6 +1333,143 @@ HOST_EXPORT int cal_coalition_write(const int64_t* edge_index, int64_t E, int64_
 }
 #undef COALITION_REQUIRE_INPUTS
 
+// ---- structural-noise replicas (cal_amd/csrc/noise.hip; cal_amd/noise.py noise_batch): the same hash, the same deletions and the
+// same accepted candidates in the same order, so every integer output agrees bit for bit.  Nothing is kept between the two
+// calls: the write decides the insertions again.
+namespace {
+inline uint64_t splitmix64(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+inline uint64_t noise_hash(uint64_t s, uint64_t i) { return splitmix64(splitmix64(s) + i); }
+
+struct NoiseSrc {
+    const int64_t* ei; int64_t E, N; const int64_t* ptr; const int64_t* eptr; int64_t B; const int32_t* twin;
+    const int64_t* rg; const int64_t* rseed; const int64_t* rdel; const int64_t* radd; int64_t tries;
+    void ranges(int64_t r, int64_t& nlo, int64_t& nhi, int64_t& elo, int64_t& ehi) const {
+        const int64_t g = rg[r];
+        nlo = nhi = elo = ehi = 0;
+        if (g < 0 || g >= B) return;
+        seg_clamp(ptr, g, N, nlo, nhi);
+        seg_clamp(eptr, g, E, elo, ehi);
+    }
+    bool inside(int64_t e, int64_t nlo, int64_t nhi) const {
+        const int64_t u = ei[e], v = ei[E + e];
+        return u >= nlo && u < nhi && v >= nlo && v < nhi;
+    }
+    bool stays(int64_t r, int64_t e, int64_t nlo, int64_t nhi, int64_t elo) const {
+        if (!inside(e, nlo, nhi)) return false;
+        if (ei[e] == ei[E + e] || rdel[r] <= 0) return true;
+        int64_t rep = e;
+        if (twin && twin[e] >= elo && twin[e] < e) rep = twin[e];
+        return !((int64_t)(noise_hash((uint64_t)rseed[r] ^ CAL_NOISE_C_DEL, (uint64_t)(rep - elo)) >> 1) < rdel[r]);
+    }
+    uint64_t key(uint64_t u, uint64_t v, uint64_t n) const { return twin ? (u < v ? u * n + v : v * n + u) : u * n + v; }
+    // the accepted pairs of replica r, in candidate order
+    void insertions(int64_t r, int64_t nlo, int64_t nhi, int64_t elo, int64_t ehi, std::vector<std::pair<int64_t, int64_t>>& out) const {
+        out.clear();
+        const int64_t a = radd[r] > 0 ? radd[r] : 0;
+        const uint64_t n = (uint64_t)(nhi - nlo);
+        if (a == 0 || n <= 1) return;
+        std::vector<uint64_t> taken;                           // the source pairs, sorted; then the accepted ones, unsorted
+        for (int64_t e = elo; e < ehi; ++e)
+            if (inside(e, nlo, nhi) && ei[e] != ei[E + e]) taken.push_back(key((uint64_t)(ei[e] - nlo), (uint64_t)(ei[E + e] - nlo), n));
+        std::sort(taken.begin(), taken.end());
+        const size_t ns = taken.size();
+        const uint64_t total = (uint64_t)tries * (uint64_t)a;
+        for (uint64_t c = 0; c < total && (int64_t)out.size() < a; ++c) {
+            const uint64_t h = noise_hash((uint64_t)rseed[r] ^ CAL_NOISE_C_ADD, c);
+            const uint64_t u = (h >> 32) % n, v = (h & 0xffffffffull) % n;
+            if (u == v) continue;
+            const uint64_t k = key(u, v, n);
+            if (std::binary_search(taken.begin(), taken.begin() + (long)ns, k)) continue;
+            if (std::find(taken.begin() + (long)ns, taken.end(), k) != taken.end()) continue;
+            taken.push_back(k);
+            out.emplace_back((int64_t)u, (int64_t)v);
+        }
+    }
+};
+}  // namespace
+
+HOST_EXPORT int64_t cal_noise_ws(int64_t, int64_t, int64_t, int64_t) { return 0; }
+
+#define NOISE_REQUIRE_INPUTS()                                                                                                   \
+    HOST_REQUIRE(E >= 0 && N >= 0 && B >= 0 && R >= 0, "sizes must be >= 0");                                                    \
+    HOST_REQUIRE(tries >= 1 && tries <= (1 << 20), "tries must be in [1, 2^20]");                                                \
+    HOST_REQUIRE(R == 0 || (rep_graph && rep_seed && rep_del && rep_add && added), "rep_graph / rep_seed / rep_del / rep_add / added are null"); \
+    HOST_REQUIRE(B == 0 || (ptr && edge_ptr), "ptr / edge_ptr are null");                                                        \
+    HOST_REQUIRE(E == 0 || edge_index, "edge_index is null");                                                                    \
+    const NoiseSrc S{edge_index, E, N, ptr, edge_ptr, B, E > 0 ? twin : nullptr, rep_graph, rep_seed, rep_del, rep_add, tries}
+
+HOST_EXPORT int cal_noise_count(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                                int64_t B, const int32_t* twin, const int64_t* rep_graph, const int64_t* rep_seed,
+                                const int64_t* rep_del, const int64_t* rep_add, int64_t R, int64_t tries, int64_t* added,
+                                int64_t* ptr_out, int64_t* edge_ptr_out, int64_t* totals, void*, int64_t, void*) {
+    NOISE_REQUIRE_INPUTS();
+    HOST_REQUIRE(totals && ptr_out && edge_ptr_out, "totals / ptr_out / edge_ptr_out are null");
+    BatchScan scan{ptr_out, edge_ptr_out, totals};
+    std::vector<std::pair<int64_t, int64_t>> ins;
+    int64_t sum = 0, fell = 0;
+    for (int64_t r = 0; r < R; ++r) {
+        int64_t nlo, nhi, elo, ehi, m = 0;
+        S.ranges(r, nlo, nhi, elo, ehi);
+        for (int64_t e = elo; e < ehi; ++e) m += S.stays(r, e, nlo, nhi, elo);
+        S.insertions(r, nlo, nhi, elo, ehi, ins);
+        added[r] = (int64_t)ins.size();
+        sum += added[r];
+        fell += added[r] < (rep_add[r] > 0 ? rep_add[r] : 0);
+        scan.add(r, nhi - nlo, m + added[r] * (S.twin ? 2 : 1));
+    }
+    scan.finish(R);
+    totals[5] = sum;
+    totals[6] = fell;
+    return 0;
+}
+
+HOST_EXPORT int cal_noise_write(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                                int64_t B, const int32_t* twin, const int64_t* rep_graph, const int64_t* rep_seed,
+                                const int64_t* rep_del, const int64_t* rep_add, int64_t R, int64_t tries, int64_t* added,
+                                const float* x, int64_t F, const int64_t* ptr_out, const int64_t* edge_ptr_out, int64_t Nout,
+                                int64_t Eout, int64_t* batch_out, float* x_out, int64_t* edge_index_out, int64_t* node_src,
+                                int64_t* edge_src, void*, int64_t, void*) {
+    NOISE_REQUIRE_INPUTS();
+    HOST_REQUIRE_WRITE(R, !x_out || (F > 0 && (N == 0 || x)), "x_out needs F > 0 and x");
+    std::vector<std::pair<int64_t, int64_t>> ins;
+    for (int64_t r = 0; r < R; ++r) {
+        int64_t nlo, nhi, elo, ehi;
+        S.ranges(r, nlo, nhi, elo, ehi);
+        W.begin(r);
+        for (int64_t s = nlo; s < nhi; ++s) W.node(s, x, s);
+        for (int64_t e = elo; e < ehi; ++e)
+            if (S.stays(r, e, nlo, nhi, elo)) W.col(W.n0 + edge_index[e] - nlo, W.n0 + edge_index[E + e] - nlo, e);
+        S.insertions(r, nlo, nhi, elo, ehi, ins);
+        for (const auto& p : ins) {
+            W.col(W.n0 + p.first, W.n0 + p.second, -1);
+            if (S.twin) W.col(W.n0 + p.second, W.n0 + p.first, -1);
+        }
+    }
+    return 0;
+}
+#undef NOISE_REQUIRE_INPUTS
+
+HOST_EXPORT int cal_degree_onehot(const int64_t* edge_index, int64_t E, int64_t N, int64_t F, float* x_out, void*) {
+    HOST_REQUIRE(E >= 0 && N >= 0, "E, N must be >= 0");
+    HOST_REQUIRE(F >= 1 && F < (1 << 22), "F must be in [1, 2^22)");
+    if (N == 0) return 0;
+    HOST_REQUIRE(x_out, "x_out is null");
+    HOST_REQUIRE(E == 0 || edge_index, "edge_index is null");
+    std::vector<int64_t> deg((size_t)N, 0);
+    for (int64_t e = 0; e < E; ++e) {
+        const int64_t u = edge_index[e];
+        if (u >= 0 && u < N && u != edge_index[E + e]) ++deg[(size_t)u];
+    }
+    memset(x_out, 0, sizeof(float) * (size_t)N * (size_t)F);
+    for (int64_t i = 0; i < N; ++i) x_out[i * F + std::min(deg[(size_t)i], F - 1)] = 1.f;
+    return 0;
+}
+
 // ---- rank agreement (cal_amd/csrc/occlude.hip; cal_amd/occlude.py rank_agreement): the same ten integers per segment, here from
 // two sorts per segment where the device counts all pairs.
 HOST_EXPORT int64_t cal_rank_agreement_ws(int64_t, int64_t, int64_t) { return 0; }

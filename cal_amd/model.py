@@ -276,6 +276,16 @@ class _CausalBase(torch.nn.Module):
         from .coalition import perturbation_curve
         return perturbation_curve(self, data, **kw)
 
+    def noise_curve(self, data, **kw):
+        """``cal_amd.noise.noise_curve(self, data, **kw)``: the prediction under growing random edge insertion / deletion."""
+        from .noise import noise_curve
+        return noise_curve(self, data, **kw)
+
+    def stability(self, data, **kw):
+        """``cal_amd.noise.stability(self, data, **kw)``: the causal edge ranking on noisy replicas against the clean graph's."""
+        from .noise import stability
+        return stability(self, data, **kw)
+
     def explain(self, data, **kw):
         """``cal_amd.explain.explain(self, data, **kw)``: per-graph top-k causal subgraphs of ``data``."""
         from .explain import explain

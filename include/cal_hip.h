@@ -567,6 +567,63 @@ CAL_API int cal_coalition_write(const int64_t* edge_index, int64_t E, int64_t N,
                                 int64_t* batch_out, float* x_out, int64_t* edge_index_out, int64_t* node_src,
                                 int64_t* edge_src, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- structural-noise replicas: R copies of graphs of one batch, each with random edges deleted and random edges inserted
+ * (cal_amd/noise.py noise_batch; noise curves, explanation stability) ----
+ * The batch is x [N, F] fp32 (or null, F = 0), edge_index [2, E] int64, ptr / edge_ptr [B+1] int64 as in cal_coalition_*.  Replica
+ * r (of R) is graph g = rep_graph[r]; an id outside [0, B) gives a replica with no node and no column.  Let n be g's node count
+ * and H(s, i) = splitmix64(splitmix64(s) + i), splitmix64(x): x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9;
+ * x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31 (all mod 2^64).  twin is int32 [E] as cal_edge_twin writes it, or null:
+ *   null (directed): every column that is no self loop is its own player, an inserted edge is the one column (u, v);
+ *   given (undirected): the player of column e is the lower column of its pair -- twin[e] when it lies inside g's segment and
+ *   below e, else e itself -- as cal_explain_rank_pairs has it; an inserted edge is the two columns (u, v), (v, u), adjacent.
+ * Deletion: with e_loc the index of a column's player inside g's segment, the column GOES iff it is no self loop and
+ *   (H(rep_seed[r] ^ CAL_NOISE_C_DEL, e_loc) >> 1) < rep_del[r] (signed): both columns of a pair go together, rep_del <= 0 deletes
+ *   nothing, rep_del = 2^63 - 1 all but surely everything, and the deletions at a smaller threshold are a subset of those at a
+ *   larger one.  Self loops always stay; a column with an endpoint outside its graph's node range is dropped, as everywhere.
+ * Insertion: a = max(rep_add[r], 0); candidate c = 0 .. tries a - 1 is the pair of local ids u = (h >> 32) mod n,
+ *   v = (h & 0xffffffff) mod n with h = H(rep_seed[r] ^ CAL_NOISE_C_ADD, c).  It is ACCEPTABLE iff u != v and the source graph g
+ *   has no column (u, v) -- undirected: nor (v, u) -- whether or not this replica deleted it; FRESH iff acceptable and no earlier
+ *   candidate is the same pair (undirected: unordered).  The replica receives the first a fresh candidates in candidate order,
+ *   after its surviving source columns (which keep their order); n <= 1 or a = 0 inserts nothing.  Freshness does not depend on
+ *   a: for one seed the insertions at a smaller a are a prefix of those at a larger one, as long as neither falls short.
+ * Every output is an integer or a row copy and is uniquely determined (the host library and a plain restatement agree bit for bit).
+ *   cal_noise_count: ONE launch.  added [R] (the insertions made), ptr_out / edge_ptr_out [R+1] and totals [7] int64 on the
+ *     device: N', E', max_nodes', max_edges', replicas with no node, the sum of added, replicas that fell short (added < a).  The
+ *     per-replica counts and the accepted pairs stay in ws.  The caller reads totals back once.
+ *   cal_noise_write: ONE launch with the same inputs, the same added and ws (untouched since the count) and Nout = totals[0],
+ *     Eout = totals[1].  batch_out [N'], x_out [N', F] (row copies; null with F = 0), edge_index_out (a contiguous [2, E']),
+ *     node_src [N'] / edge_src [E'] (the source node / column of every new one; edge_src = -1 for an inserted column).  The rows
+ *     are copied 16 bytes per lane when F % 4 == 0 and x, x_out are 16-byte aligned, else element by element (0 <= F < 2^22).
+ * ws: 8-byte aligned, cal_noise_ws(E, R, cand, tries) bytes (24 R + 256 + 8 ceil(cand / tries)) with cand a host-known bound on
+ *   the sum over the replicas of tries a, both entry points given the same ws_bytes.  Every replica takes its run of a pairs
+ *   from a counter in ws (an integer atomic; where a run lies depends on the order of the workgroups, no output does); under a
+ *   bound that does not hold, a replica whose pairs would not fit is treated as asking for fewer, so that nothing is overrun.  1 <= tries <= 2^20, N < 2^31.  One workgroup per replica: source segments
+ *   within cal_explain_lds_cap() columns keep the adjacency test and the de-duplication in an LDS hash set; larger ones (or more
+ *   than 3072 source columns and insertions together) test every candidate against the segment's columns and the accepted pairs
+ *   one by one.  Everything on `stream`, no synchronisation inside; no value that reaches an output is accumulated in an
+ *   order-dependent way (the completion ticket and the ordered scan of cal_occlude_count).  R = 0: nothing is launched (the count
+ *   zeroes totals and the two offsets with memsets). */
+#define CAL_NOISE_C_DEL 0xA0761D6478BD642FULL
+#define CAL_NOISE_C_ADD 0xE7037ED1A0B428DBULL
+CAL_API int64_t cal_noise_ws(int64_t E, int64_t R, int64_t cand, int64_t tries);
+CAL_API int cal_noise_count(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                            int64_t B, const int32_t* twin, const int64_t* rep_graph, const int64_t* rep_seed,
+                            const int64_t* rep_del, const int64_t* rep_add, int64_t R, int64_t tries, int64_t* added,
+                            int64_t* ptr_out, int64_t* edge_ptr_out, int64_t* totals, void* ws, int64_t ws_bytes, void* stream);
+CAL_API int cal_noise_write(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                            int64_t B, const int32_t* twin, const int64_t* rep_graph, const int64_t* rep_seed,
+                            const int64_t* rep_del, const int64_t* rep_add, int64_t R, int64_t tries, int64_t* added,
+                            const float* x, int64_t F, const int64_t* ptr_out, const int64_t* edge_ptr_out, int64_t Nout,
+                            int64_t Eout, int64_t* batch_out, float* x_out, int64_t* edge_index_out, int64_t* node_src,
+                            int64_t* edge_src, void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- capped one-hot degree features (SPMotif's node feature, cal_amd/spmotif.py make_graph) ----
+ * Row i of x_out [N, F] fp32 becomes zero except a 1 at min(d_i, F - 1), d_i the number of columns of edge_index [2, E] with row-0
+ * endpoint i and row-1 endpoint != i (a column whose row-0 endpoint lies outside [0, N) counts for nobody).  The counts are
+ * integers, so the order of accumulation cannot show.  F >= 1; E = 0 gives column 0; N = 0 launches nothing.  A memset and two
+ * launches on `stream`, no ws, no synchronisation. */
+CAL_API int cal_degree_onehot(const int64_t* edge_index, int64_t E, int64_t N, int64_t F, float* x_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
