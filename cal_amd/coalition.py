@@ -24,10 +24,12 @@ from typing import Optional
 
 import torch
 
-from .explain import _Layout, _k_code, _keep8, _log_probs, _reduce_code, _scores, rank_segment_pairs, rank_segments
-from .occlude import _check_occlusion_args, _grouped, rank_agreement
+from .explain import _eval_mode, _Layout, _scores
+from .occlude import rank_agreement
 from .plan import _p
-from .splice import _Source, _built_batch, _check_use, _feature_width, _pairs, _rebatch
+from .replica import (_agree_report, _agree_sums, _built_batch, _caller_columns, _causal_in_order, _check_driver_args, _check_topk,
+                      _check_use, _feature_width, _grouped, _members, _p_at, _pairs, _Players, _rebatch, _replica_log_probs,
+                      _Source, _symmetrised, _whole)
 
 __all__ = ["Shapley", "coalition_batch", "shapley", "perturbation_curve", "eval_perturbation_curve", "shapley_agreement"]
 
@@ -92,54 +94,10 @@ def coalition_batch(data, rep_graph, rep_thresh, key, *, rep_row=None, use: str 
     inputs = S.args() + [_p(key) if K and M else None, K, _p(rg) if R else None, _p(rrow) if R else None, _p(rth) if R else None, R,
                          mode, int(bool(invert)), mx]
     built = _rebatch("cal_coalition", (S.E, R, mx, mode), inputs, R, 5, (S,), F, lambda: (rg < 0) | (rg >= S.B))
-    esrc = built.edge_src
-    if S.order is not None and built.tot[1]:               # columns that were reordered: back to the caller's numbering
-        esrc = S.order[esrc]
-    return _built_batch(S, built, rg, S.no_self_loops, esrc)
+    return _built_batch(S, built, rg, S.no_self_loops, _caller_columns(S, built.edge_src, built.tot[1]))
 
 
 # ---- the pieces the drivers share ---------------------------------------------------------------------------------------------
-class _Players:
-    """The elements of a batch as the drivers see them, over the edge columns in ``lay``'s graph order: ``M`` elements in the
-    segments ``seg`` (bound ``max_seg``) with graph ids ``gid``; ``twin`` (int32 [M], ``undirected`` only) and ``rep`` (bool [M]
-    or ``None``: one representative per undirected edge -- the lower column of a pair, an unpaired column, a self loop);
-    ``nodes`` int64 [B], every graph's node count."""
-
-    def __init__(self, data, lay, src, use, undirected):
-        dev = src.edge_index.device
-        self.nodes = (lay.ptr[1:] - lay.ptr[:-1]).to(dev)
-        self.twin = self.rep = None
-        B = lay.B
-        if use == "edges":
-            self.M, self.seg, self.max_seg = int(src.edge_index.size(1)), lay.edge_ptr.to(dev), lay.max_edges
-            self.gid = torch.repeat_interleave(torch.arange(B, device=dev), self.seg[1:] - self.seg[:-1], output_size=self.M)
-            if undirected is not None:
-                self.twin = lay.twins(data.edge_index)[0]
-                self.rep = ~((self.twin >= 0) & (self.twin < torch.arange(self.M, device=dev)))
-        else:
-            self.M, self.seg, self.max_seg, self.gid = int(src.batch.numel()), lay.ptr.to(dev), lay.max_nodes, src.batch
-        self.B, self.dev, self.undirected = B, dev, undirected
-
-    def count(self, mask):
-        """int64 [B]: the marked elements of every graph."""
-        return torch.zeros(self.B, dtype=torch.long, device=self.dev).index_add_(0, self.gid, mask.long())
-
-    def rank(self, score):
-        """int32 [M]: every element's 0-based position inside its graph under ``score`` (float32 [M], descending, NaN last, then
-        index ascending); with ``undirected`` the position of its undirected edge among the graph's undirected edges."""
-        score = score.contiguous()
-        if self.twin is None:
-            return rank_segments(score, self.seg, self.max_seg, k=0)[1]
-        return rank_segment_pairs(score, self.seg, self.max_seg, self.twin, self.undirected, k=0)[1]
-
-
-def _full(model, src, h):
-    """-> (ŷ int64 [B], p_full [B], C): the whole batch on the route the replicas take."""
-    full = _log_probs(model, src)[h]                                     # [B, C]
-    yhat = full.argmax(-1)
-    return yhat, full.gather(-1, yhat.unsqueeze(-1)).squeeze(-1).exp(), int(full.size(-1))
-
-
 def _run_replicas(model, src, h, yhat, rg, rth, key, rrow, use, invert, chunk, out, slot):
     """The replicas ``(rg, rrow, rth)`` (one entry each per replica; ``rrow`` may be ``None``) in chunks of at most ``chunk``, one
     ``coalition_batch`` and one forward each: ``out[slot[r]] = p(ŷ)`` of replica r (``out`` 1-D).  -> the forwards it took."""
@@ -148,10 +106,7 @@ def _run_replicas(model, src, h, yhat, rg, rth, key, rrow, use, invert, chunk, o
         g = rg[i:i + chunk]
         rb = coalition_batch(src, g, rth[i:i + chunk], key, rep_row=None if rrow is None else rrow[i:i + chunk], use=use,
                              invert=invert)
-        if rb.empty_graphs:
-            raise ValueError("%d replicas have no node (the engine does not run zero-node graphs)" % rb.empty_graphs)
-        lp = _log_probs(model, rb)[h]                                    # [R, C]
-        out[slot[i:i + chunk]] = lp.gather(-1, yhat[g].unsqueeze(-1)).squeeze(-1).exp().to(out.dtype)
+        out[slot[i:i + chunk]] = _p_at(_replica_log_probs(model, rb, h), yhat[g]).to(out.dtype)
         forwards += 1
     return forwards
 
@@ -206,18 +161,14 @@ def _shapley(model, data, lay, use, undirected, h, perms, elements, generator, c
     """-> ``(Shapley, players bool [M], _Players)`` over the edge columns in ``lay``'s graph order (``score``, ``stderr``, ``twin``
     and ``keys`` index that order).  ``players`` marks one representative per player.  Called in eval mode under no_grad."""
     src = _grouped(data, lay)
-    yhat, p_full, C = _full(model, src, h)
+    yhat, p_full, C = _whole(model, src, h)
     P = _Players(data, lay, src, use, undirected)
     dev, B, M = P.dev, P.B, P.M
     pl = torch.ones(M, dtype=torch.bool, device=dev) if P.rep is None else P.rep.clone()
     member = torch.ones(M, dtype=torch.bool, device=dev)
     if elements is not None:
-        want = _keep8(elements, M, dev, "elements").view(torch.bool)
-        if use == "edges" and lay.order is not None:
-            want = want[lay.order]
-        if P.twin is not None:                                           # an undirected edge is asked for by either column
-            want = want | (want[P.twin.clamp(min=0).long()] & (P.twin >= 0))
-        pl, member = pl & want, want
+        member = _members(elements, M, lay, use, P.twin)
+        pl = pl & member
     if torch.is_tensor(perms):
         if perms.dim() != 2 or int(perms.size(1)) != M or int(perms.size(0)) < 1:
             raise ValueError("perms as a tensor must be int32 [S, M] with S >= 1 and M = %d elements" % M)
@@ -262,7 +213,7 @@ def _shapley(model, data, lay, use, undirected, h, perms, elements, generator, c
 
 
 def _check_shapley_args(use, undirected, head, perms, chunk):
-    h, chunk = _check_occlusion_args(use, undirected, head, chunk)
+    h, chunk = _check_driver_args(use, undirected, head, chunk)
     if not torch.is_tensor(perms):
         if isinstance(perms, bool) or not isinstance(perms, int):
             raise TypeError("perms must be an int >= 1 or an int32 [S, M] tensor of keys")
@@ -315,14 +266,9 @@ def shapley(model, data, *, use: str = "edges", undirected=None, head: str = "o"
     and the operator-level ``model(data)``.  Like ``explain``, it runs in eval mode under ``no_grad`` and leaves parameters,
     optimizer state, the engine's step counter, BatchNorm statistics, the RNG states and ``model.training`` as they were."""
     h, chunk = _check_shapley_args(use, undirected, head, perms, chunk)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            lay = _Layout(data)
-            sh = _caller_order(_shapley(model, data, lay, use, undirected, h, perms, elements, generator, chunk)[0], lay, use)
-    finally:
-        model.train(was_training)
+    with _eval_mode(model):
+        lay = _Layout(data)
+        sh = _caller_order(_shapley(model, data, lay, use, undirected, h, perms, elements, generator, chunk)[0], lay, use)
     return sh
 
 
@@ -350,7 +296,7 @@ def _curve(model, data, use, undirected, h, ratios, order, chunk):
         order = (edge if use == "edges" else node).clone()
         forwards = 1
     src = _grouped(data, lay)
-    yhat, p_full, C = _full(model, src, h)
+    yhat, p_full, C = _whole(model, src, h)
     P = _Players(data, lay, src, use, undirected)
     dev, B, M = P.dev, P.B, P.M
     if not torch.is_tensor(order) or order.dim() != 1 or int(order.numel()) != M:
@@ -387,7 +333,7 @@ def _auc(y, ratios):
 
 
 def _check_curve_args(use, undirected, head, ratios, chunk):
-    h, chunk = _check_occlusion_args(use, undirected, head, chunk)
+    h, chunk = _check_driver_args(use, undirected, head, chunk)
     return h, chunk, _check_ratios(ratios)
 
 
@@ -409,17 +355,12 @@ def perturbation_curve(model, data, *, use: str = "edges", undirected=None, head
     included, and the scores' when ``order`` is not given).  The tensors stay on ``data``'s device.  It leaves the model as
     ``explain`` does."""
     h, chunk, ratios = _check_curve_args(use, undirected, head, ratios, chunk)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            ins, dele, p_full, yhat, replicas, forwards = _curve(model, data, use, undirected, h, ratios, order, chunk)
-            ai, ad = _auc(ins, ratios), _auc(dele, ratios)
-            res = {"insertion": ins, "deletion": dele, "insertion_mean": ins.double().mean(0), "deletion_mean": dele.double().mean(0),
-                   "auc_insertion": ai, "auc_deletion": ad, "auc_insertion_mean": ai.mean(), "auc_deletion_mean": ad.mean(),
-                   "p_full": p_full, "yhat": yhat, "ratios": ratios, "replicas": replicas, "forwards": forwards}
-    finally:
-        model.train(was_training)
+    with _eval_mode(model):
+        ins, dele, p_full, yhat, replicas, forwards = _curve(model, data, use, undirected, h, ratios, order, chunk)
+        ai, ad = _auc(ins, ratios), _auc(dele, ratios)
+        res = {"insertion": ins, "deletion": dele, "insertion_mean": ins.double().mean(0), "deletion_mean": dele.double().mean(0),
+               "auc_insertion": ai, "auc_deletion": ad, "auc_insertion_mean": ai.mean(), "auc_deletion_mean": ad.mean(),
+               "p_full": p_full, "yhat": yhat, "ratios": ratios, "replicas": replicas, "forwards": forwards}
     return res
 
 
@@ -431,20 +372,15 @@ def eval_perturbation_curve(model, loader, device, *, use: str = "edges", undire
     the replica builder's)."""
     h, chunk, ratios = _check_curve_args(use, undirected, head, ratios, chunk)
     T = len(ratios)
-    was_training = model.training
-    model.eval()
     sums = torch.zeros(2 * T + 4, dtype=torch.float64, device=device)
     replicas = forwards = 0
-    try:
-        with torch.no_grad():
-            for data in loader:
-                ins, dele, p_full, _, r, f = _curve(model, data.to(device), use, undirected, h, ratios, None, chunk)
-                tail = torch.stack([_auc(ins, ratios).sum(), _auc(dele, ratios).sum(), p_full.double().sum(),
-                                    torch.as_tensor(float(p_full.numel()), dtype=torch.float64, device=p_full.device)])
-                sums += torch.cat([ins.double().sum(0), dele.double().sum(0), tail])
-                replicas, forwards = replicas + r, forwards + f
-    finally:
-        model.train(was_training)
+    with _eval_mode(model):
+        for data in loader:
+            ins, dele, p_full, _, r, f = _curve(model, data.to(device), use, undirected, h, ratios, None, chunk)
+            tail = torch.stack([_auc(ins, ratios).sum(), _auc(dele, ratios).sum(), p_full.double().sum(),
+                                torch.as_tensor(float(p_full.numel()), dtype=torch.float64, device=p_full.device)])
+            sums += torch.cat([ins.double().sum(0), dele.double().sum(0), tail])
+            replicas, forwards = replicas + r, forwards + f
     row = sums.tolist()
     n = row[-1]
     mean = lambda v: v / n if n else float("nan")
@@ -454,9 +390,6 @@ def eval_perturbation_curve(model, loader, device, *, use: str = "edges", undire
 
 
 # ---- causal attention against the Shapley scores ------------------------------------------------------------------------------
-_AGREE = ("rho", "tau", "jaccard")
-
-
 def shapley_agreement(model, data, *, use: str = "edges", undirected=None, head: str = "o", perms=8, elements=None,
                       generator=None, ratio=None, k=None, chunk: int = 512) -> dict:
     """Do ``model``'s causal scores rank the elements of ``data`` as their Shapley values do?
@@ -468,31 +401,15 @@ def shapley_agreement(model, data, *, use: str = "edges", undirected=None, head:
     the graphs where each is defined), ``rho_undefined``, ``tau_undefined``, ``jaccard_undefined`` (the graphs where it is not),
     ``graphs``, ``elements`` (players compared), ``replicas`` and ``forwards`` (``shapley``'s plus one for the scores): the
     shape of ``faithfulness``, which is what to compare it with.  It leaves the model as ``shapley`` does."""
-    _k_code(ratio, k)
-    if k == "gt":
-        raise ValueError('shapley_agreement has no ground truth: k must be an int >= 0')
+    _check_topk(ratio, k, "shapley_agreement")
     h, chunk = _check_shapley_args(use, undirected, head, perms, chunk)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            edge, node = _scores(model, data)
-            causal = (edge if use == "edges" else node).clone()
-            lay = _Layout(data)
-            sh, pl, P = _shapley(model, data, lay, use, undirected, h, perms, elements, generator, chunk)
-            if use == "edges" and lay.order is not None:
-                causal = causal[lay.order].contiguous()
-            if P.twin is not None:                                       # one symmetrised score per undirected edge, as explain
-                causal = rank_segment_pairs(causal, P.seg, P.max_seg, P.twin, undirected, k=0)[3]
-            counts, met = rank_agreement(causal, sh.score.float(), P.seg, P.max_seg, sel=pl, ratio=ratio, k=k)
-            defined = ~torch.isnan(met)
-            row = torch.cat([torch.where(defined, met, torch.zeros_like(met)).sum(0), defined.sum(0).double(),
-                             counts[:, 0].sum().double().view(1)]).tolist()
-    finally:
-        model.train(was_training)
-    res = {}
-    for j, key in enumerate(_AGREE):
-        res[key] = row[j] / row[3 + j] if row[3 + j] else float("nan")
-        res[key + "_undefined"] = int(lay.B - row[3 + j])
+    with _eval_mode(model):
+        causal, lay = _causal_in_order(model, data, use)
+        sh, pl, P = _shapley(model, data, lay, use, undirected, h, perms, elements, generator, chunk)
+        if P.twin is not None:
+            causal = _symmetrised(causal, lay, P.twin, undirected)
+        counts, met = rank_agreement(causal, sh.score.float(), P.seg, P.max_seg, sel=pl, ratio=ratio, k=k)
+        row = torch.cat([_agree_sums(met), counts[:, 0].sum().double().view(1)]).tolist()
+    res = _agree_report(row, lay.B)
     res["graphs"], res["elements"], res["replicas"], res["forwards"] = lay.B, int(row[6]), sh.replicas, sh.forwards + 1
     return res

@@ -24,6 +24,7 @@ column 1**: ``edge_att[:, 1]`` (``edge_weight_o``) per edge and ``node_att[:, 1]
 """
 from __future__ import annotations
 
+import contextlib
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -183,6 +184,19 @@ def _eval_forward(model, data):
     return eng
 
 
+@contextlib.contextmanager
+def _eval_mode(model):
+    """Eval mode under ``no_grad``; ``model.training`` is put back on the way out.  The scope of every driver that "leaves the
+    model as ``explain`` does"."""
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            yield
+    finally:
+        model.train(was_training)
+
+
 def _scores(model, data):
     """Eval-mode causal scores (edge [E], node [N]) of ``data`` with the identity permutation.  Engine-backed models: views
     into the engine's workspace; others: the operator-level backbone + attention (``_CausalBase._attention_scores``)."""
@@ -309,24 +323,19 @@ def explain(model, data, *, ratio=None, k=None, node_ratio=None, node_k=None, ed
         raise ValueError('k="gt" needs edge_gt')
     if node_k == "gt" and node_gt is None:
         raise ValueError('node_k="gt" needs node_gt')
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            edge, node = _scores(model, data)
-            lay = _Layout(data)
-            twin = None
-            if undirected is None:
-                em, er_, emet = lay.rank_edges(edge, ratio=er, k=ek, gt=edge_gt, metrics=edge_gt is not None)
-                edge = edge.clone()
-            else:
-                em, er_, emet, edge = lay.rank_edge_pairs(edge, data.edge_index, undirected, ratio=er, k=ek, gt=edge_gt,
-                                                          metrics=edge_gt is not None)
-                twin = lay.caller_twin(lay.twins(data.edge_index)[0])
-            nm, nr, nmet = lay.rank_nodes(node, ratio=node_ratio, k=node_k, gt=node_gt, metrics=node_gt is not None)
-            node = node.clone()
-    finally:
-        model.train(was_training)
+    with _eval_mode(model):
+        edge, node = _scores(model, data)
+        lay = _Layout(data)
+        twin = None
+        if undirected is None:
+            em, er_, emet = lay.rank_edges(edge, ratio=er, k=ek, gt=edge_gt, metrics=edge_gt is not None)
+            edge = edge.clone()
+        else:
+            em, er_, emet, edge = lay.rank_edge_pairs(edge, data.edge_index, undirected, ratio=er, k=ek, gt=edge_gt,
+                                                      metrics=edge_gt is not None)
+            twin = lay.caller_twin(lay.twins(data.edge_index)[0])
+        nm, nr, nmet = lay.rank_nodes(node, ratio=node_ratio, k=node_k, gt=node_gt, metrics=node_gt is not None)
+        node = node.clone()
     metrics = None
     if emet is not None or nmet is not None:
         metrics = {"edge": emet, "node": nmet}
@@ -361,25 +370,20 @@ def eval_explanation(model, loader, device, *, k="gt", ratio=None, undirected=No
     _reduce_code(undirected)
     if ratio is not None:
         k = None
-    was_training = model.training
-    model.eval()
     sums = torch.zeros(12, dtype=torch.float64, device=device)
-    try:
-        with torch.no_grad():
-            for data in loader:
-                data = data.to(device)
-                edge, node = _scores(model, data)
-                node_gt, edge_gt = ground_truth(data)
-                lay = _Layout(data)
-                if undirected is None:
-                    emet = lay.rank_edges(edge, ratio=ratio, k=k, gt=edge_gt, metrics=True)[2]
-                else:
-                    emet = lay.rank_edge_pairs(edge, data.edge_index, undirected, ratio=ratio, k=k, gt=edge_gt, metrics=True)[2]
-                _, _, nmet = lay.rank_nodes(node, ratio=ratio, k=k, gt=node_gt, metrics=True)
-                _accumulate(sums, emet, 0)
-                _accumulate(sums, nmet, 6)
-    finally:
-        model.train(was_training)
+    with _eval_mode(model):
+        for data in loader:
+            data = data.to(device)
+            edge, node = _scores(model, data)
+            node_gt, edge_gt = ground_truth(data)
+            lay = _Layout(data)
+            if undirected is None:
+                emet = lay.rank_edges(edge, ratio=ratio, k=k, gt=edge_gt, metrics=True)[2]
+            else:
+                emet = lay.rank_edge_pairs(edge, data.edge_index, undirected, ratio=ratio, k=k, gt=edge_gt, metrics=True)[2]
+            _, _, nmet = lay.rank_nodes(node, ratio=ratio, k=k, gt=node_gt, metrics=True)
+            _accumulate(sums, emet, 0)
+            _accumulate(sums, nmet, 6)
     s = sums.tolist()
     out = {}
     for j, part in enumerate(("edge", "node")):
@@ -562,13 +566,8 @@ def fidelity(model, data, *, ratio=None, k=None, use: str = "edges", undirected=
     if k == "gt":
         raise ValueError('fidelity has no ground truth: k must be an int >= 0')
     _use_masks(use, None, None)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            sums = _fidelity_sums(model, data, [(ratio, k)], use, undirected)
-    finally:
-        model.train(was_training)
+    with _eval_mode(model):
+        sums = _fidelity_sums(model, data, [(ratio, k)], use, undirected)
     return _fidelity_report(sums[0].tolist())
 
 
@@ -584,13 +583,8 @@ def eval_fidelity(model, loader, device, *, ratios=(0.1, 0.2, 0.3, 0.5), use: st
     for r, _ in specs:
         _k_code(r, None)
     _use_masks(use, None, None)
-    was_training = model.training
-    model.eval()
     sums = torch.zeros(len(specs), 18, dtype=torch.float64, device=device)
-    try:
-        with torch.no_grad():
-            for data in loader:
-                sums += _fidelity_sums(model, data.to(device), specs, use, undirected)
-    finally:
-        model.train(was_training)
+    with _eval_mode(model):
+        for data in loader:
+            sums += _fidelity_sums(model, data.to(device), specs, use, undirected)
     return {r: _fidelity_report(row) for r, row in zip(ratios, sums.tolist())}

@@ -23,8 +23,10 @@ from typing import Optional
 
 import torch
 
-from .explain import _Layout, _k_code, _scores, rank_segment_pairs
-from .occlude import _check_occlusion_args, rank_agreement
+from .explain import _eval_mode
+from .occlude import rank_agreement
+from .replica import (_agree_report, _agree_sums, _causal_in_order, _check_driver_args, _check_topk, _p_at, _representatives,
+                      _symmetrised)
 
 __all__ = ["Gradients", "masked_log_probs", "saliency", "integrated_gradients", "gradient_agreement"]
 
@@ -129,7 +131,7 @@ class _Setup:
             self.paired = (twin >= 0) & (t != idx)
             member = member | (member[t] & self.paired)             # an undirected edge is asked for by either column
             self.t = t
-            self.rep = member & ~(self.paired & (t < idx))           # one representative per player
+            self.rep = member & _representatives(twin)               # one representative per player
         self.member = member
 
     def mask(self, alpha: float):
@@ -156,7 +158,7 @@ def _p_of(model, data, S, m, h, yhat=None):
     lp = model._masked_forward(data, m if S.use == "edges" else None, m if S.use == "nodes" else None)[h]
     if yhat is None:
         yhat = lp.argmax(-1)
-    return lp.gather(-1, yhat.unsqueeze(-1)).squeeze(-1).exp(), yhat
+    return _p_at(lp, yhat), yhat
 
 
 def _grad(p, m):
@@ -165,7 +167,7 @@ def _grad(p, m):
 
 
 def _check_args(use, undirected, head):
-    return _check_occlusion_args(use, undirected, head, 1)[0]
+    return _check_driver_args(use, undirected, head, 1)[0]
 
 
 def saliency(model, data, *, use: str = "edges", undirected=None, head: str = "o", elements=None) -> Gradients:
@@ -221,9 +223,6 @@ def integrated_gradients(model, data, *, use: str = "edges", undirected=None, he
                      gap=gap, twin=S.twin)
 
 
-_AGREE = ("rho", "tau", "jaccard")
-
-
 def gradient_agreement(model, data, *, method: str = "ig", steps: int = 32, use: str = "edges", undirected=None,
                        head: str = "o", elements=None, ratio=None, k=None) -> dict:
     """Do ``model``'s causal scores rank the elements of ``data`` as their gradient scores do?
@@ -235,9 +234,7 @@ def gradient_agreement(model, data, *, method: str = "ig", steps: int = 32, use:
     ``forwards`` (the method's plus one for the scores): the shape of ``shapley_agreement`` without its ``replicas``."""
     if method not in ("ig", "saliency"):
         raise ValueError('method must be "ig" or "saliency"')
-    _k_code(ratio, k)
-    if k == "gt":
-        raise ValueError('gradient_agreement has no ground truth: k must be an int >= 0')
+    _check_topk(ratio, k, "gradient_agreement")
     if method == "ig":
         res = integrated_gradients(model, data, use=use, undirected=undirected, head=head, elements=elements, steps=steps)
     else:
@@ -247,34 +244,22 @@ def gradient_agreement(model, data, *, method: str = "ig", steps: int = 32, use:
 
 def _agreement(model, data, score, forwards, use, undirected, ratio, k) -> dict:
     """The causal score against ``score`` ([M], the caller's order) by one ``rank_agreement`` call -> the agreement dict."""
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            edge, node = _scores(model, data)
-            causal = (edge if use == "edges" else node).clone()
-            lay = _Layout(data)
-            score = score.float()
-            sel = None
-            if use == "edges":
-                if lay.order is not None:
-                    causal, score = causal[lay.order].contiguous(), score[lay.order].contiguous()
-                seg, max_seg = lay.edge_ptr, lay.max_edges
-                if undirected is not None:
-                    twin = lay.twins(data.edge_index)[0]
-                    causal = rank_segment_pairs(causal, seg, max_seg, twin, undirected, k=0)[3]
-                    sel = ~((twin >= 0) & (twin < torch.arange(twin.numel(), device=twin.device)))
-            else:
-                seg, max_seg = lay.ptr, lay.max_nodes
-            counts, met = rank_agreement(causal.contiguous(), score, seg, max_seg, sel=sel, ratio=ratio, k=k)
-            defined = ~torch.isnan(met)
-            row = torch.cat([torch.where(defined, met, torch.zeros_like(met)).sum(0), defined.sum(0).double(),
-                             counts[:, 0].sum().double().view(1)]).tolist()
-    finally:
-        model.train(was_training)
-    out = {}
-    for j, key in enumerate(_AGREE):
-        out[key] = row[j] / row[3 + j] if row[3 + j] else float("nan")
-        out[key + "_undefined"] = int(lay.B - row[3 + j])
+    with _eval_mode(model):
+        causal, lay = _causal_in_order(model, data, use)
+        score = score.float()
+        sel = None
+        if use == "edges":
+            if lay.order is not None:
+                score = score[lay.order].contiguous()
+            seg, max_seg = lay.edge_ptr, lay.max_edges
+            if undirected is not None:
+                twin = lay.twins(data.edge_index)[0]
+                causal = _symmetrised(causal, lay, twin, undirected)
+                sel = _representatives(twin)
+        else:
+            seg, max_seg = lay.ptr, lay.max_nodes
+        counts, met = rank_agreement(causal.contiguous(), score, seg, max_seg, sel=sel, ratio=ratio, k=k)
+        row = torch.cat([_agree_sums(met), counts[:, 0].sum().double().view(1)]).tolist()
+    out = _agree_report(row, lay.B)
     out["graphs"], out["elements"], out["forwards"] = lay.B, int(row[6]), forwards + 1
     return out

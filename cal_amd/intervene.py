@@ -30,6 +30,7 @@ from typing import Optional
 import torch
 
 from . import _lib
+from .explain import _eval_forward, _eval_mode
 from .plan import _p, _stream
 
 __all__ = ["InterventionResult", "pooled_representations", "intervention_readout", "intervene", "trivial_bank",
@@ -54,18 +55,11 @@ class InterventionResult:
     M: int
 
 
-def _features(data):
-    return data.x if getattr(data, "x", None) is not None else data.feat
-
-
 def _pooled(model, data):
     """(xc, xo) of one forward in the module's current mode; engine-backed models: private copies of the ``pooled`` buffer."""
-    x = _features(data)
-    eng = model._engine_for(x)
+    eng = _eval_forward(model, data)
     if eng is None:
         return model._pooled(data)
-    eng.forward(data, None, training=False)              # identity permutation: no host RNG
-    eng._fwd_token = getattr(eng, "_fwd_token", 0) + 1    # (a pending training-mode backward would now read eval activations)
     B = int(data.num_graphs)
     pooled = eng.buffer("pooled", 2 * B * eng.H).clone().view(2, B, eng.H)
     return pooled[0], pooled[1]
@@ -74,14 +68,9 @@ def _pooled(model, data):
 def pooled_representations(model, data):
     """``(xc [B, H], xo [B, H])``: the pooled trivial and objects rows of ``data`` from one eval-mode forward with the identity
     permutation; private copies that survive later engine calls.  Leaves the model's state as ``explain`` does."""
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            xc, xo = _pooled(model, data)
-            return xc.clone() if xc._base is None else xc, xo.clone() if xo._base is None else xo
-    finally:
-        model.train(was_training)
+    with _eval_mode(model):
+        xc, xo = _pooled(model, data)
+        return xc.clone() if xc._base is None else xc, xo.clone() if xo._base is None else xo
 
 
 def _bn_args(bn):
@@ -153,32 +142,22 @@ def intervene(model, data, *, bank: Optional[torch.Tensor] = None, ref="y", pair
     statistics and both RNG states are left as they were, and ``model.training`` is restored."""
     if not (ref is None or torch.is_tensor(ref) or ref in ("y", "o")):
         raise ValueError('ref must be "y", "o", a tensor or None')
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            xc, xo = _pooled(model, data)
-            return intervention_readout(model, xo, xc if bank is None else bank, _ref_of(model, data, xo, ref), pairs=pairs)
-    finally:
-        model.train(was_training)
+    with _eval_mode(model):
+        xc, xo = _pooled(model, data)
+        return intervention_readout(model, xo, xc if bank is None else bank, _ref_of(model, data, xo, ref), pairs=pairs)
 
 
 def trivial_bank(model, loader, device, max_rows: Optional[int] = None) -> torch.Tensor:
     """The pooled trivial rows ``xc`` of every graph of ``loader`` (eval mode, identity permutation), ``[M, H]`` on ``device``;
     at most ``max_rows`` rows (the first ones) when given."""
-    was_training = model.training
-    model.eval()
     rows, n = [], 0
-    try:
-        with torch.no_grad():
-            for data in loader:
-                xc = _pooled(model, data.to(device))[0]
-                rows.append(xc.clone() if xc._base is None else xc)
-                n += int(xc.size(0))
-                if max_rows is not None and n >= max_rows:
-                    break
-    finally:
-        model.train(was_training)
+    with _eval_mode(model):
+        for data in loader:
+            xc = _pooled(model, data.to(device))[0]
+            rows.append(xc.clone() if xc._base is None else xc)
+            n += int(xc.size(0))
+            if max_rows is not None and n >= max_rows:
+                break
     if not rows:
         raise ValueError("the loader is empty")
     bank = torch.cat(rows)
@@ -199,21 +178,16 @@ def eval_intervention(model, loader, device, *, bank="batch") -> dict:
     Per mini-batch one eval forward and one ``cal_intervene_pairs`` call; the sums stay on the device until one read-back."""
     if not (torch.is_tensor(bank) or bank == "batch"):
         raise ValueError('bank must be "batch" or a [M, H] tensor')
-    was_training = model.training
-    model.eval()
     sums = torch.zeros(5, dtype=torch.float64, device=device)
-    try:
-        with torch.no_grad():
-            for data in loader:
-                data = data.to(device)
-                xc, xo = _pooled(model, data)
-                y = data.y.view(-1)
-                r = intervention_readout(model, xo, xc if not torch.is_tensor(bank) else bank, y)
-                sums += torch.stack([(r.p_do.argmax(-1) == y).sum().double(), r.hits.double().sum() / r.M,
-                                     (r.hits == r.M).sum().double(), r.p_min.double().sum(),
-                                     torch.as_tensor(float(y.numel()), dtype=torch.float64, device=y.device)])
-    finally:
-        model.train(was_training)
+    with _eval_mode(model):
+        for data in loader:
+            data = data.to(device)
+            xc, xo = _pooled(model, data)
+            y = data.y.view(-1)
+            r = intervention_readout(model, xo, xc if not torch.is_tensor(bank) else bank, y)
+            sums += torch.stack([(r.p_do.argmax(-1) == y).sum().double(), r.hits.double().sum() / r.M,
+                                 (r.hits == r.M).sum().double(), r.p_min.double().sum(),
+                                 torch.as_tensor(float(y.numel()), dtype=torch.float64, device=y.device)])
     do, mean, all_, pmin, n = sums.tolist()
     nan = float("nan")
     return {"acc_do": do / n if n else nan, "acc_mean": mean / n if n else nan, "acc_all": all_ / n if n else nan,

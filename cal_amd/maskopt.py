@@ -25,9 +25,10 @@ from typing import Optional
 
 import torch
 
-from .explain import _Layout, _k_code
+from .explain import _Layout
 from .gradient import _Setup, _agreement, _check_args, _frozen
 from .plan import _c
+from .replica import _check_topk, _p_at
 
 __all__ = ["LearnedMask", "MaskOptimizer", "learn_mask", "mask_agreement"]
 
@@ -123,7 +124,7 @@ class MaskOptimizer:
         with _frozen(model), torch.no_grad():
             lp = self._forward(self.mask)
             self.yhat = lp.argmax(-1)
-            self.p_full = lp.gather(-1, self.yhat.unsqueeze(-1)).squeeze(-1).exp()
+            self.p_full = _p_at(lp, self.yhat)
         self._kernel(0, None, None)                            # the initial scatter: mask = sigmoid(theta) on the players
 
     def _forward(self, m):
@@ -206,8 +207,6 @@ def mask_agreement(model, data, *, steps: int = 100, use: str = "edges", undirec
     """Do ``model``'s causal scores rank the elements of ``data`` as their learned mask does?  ``gradient_agreement`` with
     ``learn_mask(steps=steps, **kw)``'s mask in the place of the gradient score: ``rho``, ``tau``, ``jaccard`` and their
     ``_undefined`` counts, ``graphs``, ``elements`` (players compared) and ``forwards`` (``learn_mask``'s plus one)."""
-    _k_code(ratio, k)
-    if k == "gt":
-        raise ValueError('mask_agreement has no ground truth: k must be an int >= 0')
+    _check_topk(ratio, k, "mask_agreement")
     res = learn_mask(model, data, steps=steps, use=use, undirected=undirected, head=head, elements=elements, **kw)
     return _agreement(model, data, res.mask, res.forwards, use, undirected, ratio, k)

@@ -22,10 +22,12 @@ import math
 import torch
 
 from . import _lib
-from .explain import _Layout, _eval_forward, _k_code, _log_probs, _reduce_code, _scores, rank_segment_pairs, rank_segments
-from .occlude import _check_head, _grouped, rank_agreement
+from .explain import (_eval_forward, _eval_mode, _k_code, _Layout, _log_probs, _reduce_code, _scores, rank_segment_pairs,
+                      rank_segments)
+from .occlude import rank_agreement
 from .plan import _p, _stream
-from .splice import _Source, _built_batch, _feature_width, _pairs, _rebatch
+from .replica import (_agree_report, _agree_sums, _built_batch, _caller_columns, _check_head, _check_replicas, _feature_width,
+                      _grouped, _p_at, _pairs, _rebatch, _replica_log_probs, _representatives, _Source, _whole)
 
 __all__ = ["noise_batch", "degree_onehot", "noise_curve", "eval_noise_curve", "stability", "eval_stability", "C_DEL", "C_ADD"]
 
@@ -107,7 +109,7 @@ def _players(S, twin):
     """int64 [B]: every graph's players -- the columns that are no self loop, with ``twin`` one per undirected edge."""
     ok = S.ei[0] != S.ei[1]
     if twin is not None:
-        ok = ok & ~((twin >= 0) & (twin < torch.arange(S.E, device=S.dev)))
+        ok = ok & _representatives(twin)
     gid = torch.repeat_interleave(torch.arange(S.B, device=S.dev), S.edge_ptr[1:] - S.edge_ptr[:-1], output_size=S.E)
     return torch.zeros(S.B, dtype=torch.long, device=S.dev).index_add_(0, gid, ok.long())
 
@@ -138,10 +140,7 @@ def _noise_build(S, F, twin, max_edges, rg, add, delete, seed, tries, features):
     inputs = S.args() + [_p(twin) if twin is not None and S.E else None, _p(rg) if R else None, _p(rseed) if R else None,
                          _p(rdel) if R else None, _p(radd) if R else None, R, tries, _p(added)]
     built = _rebatch("cal_noise", (S.E, R, cand, tries), inputs, R, 7, (S,), F, lambda: ~ok)
-    esrc = built.edge_src
-    if S.order is not None and built.tot[1]:                # columns that were reordered: back to the caller's numbering
-        esrc = torch.where(esrc >= 0, S.order[esrc.clamp(min=0)], esrc)
-    out = _built_batch(S, built, rg, S.no_self_loops, esrc)
+    out = _built_batch(S, built, rg, S.no_self_loops, _caller_columns(S, built.edge_src, built.tot[1]))
     out.added, out.n_added, out.short = added[:R], int(built.tot[5]), int(built.tot[6])
     if features == "degree":
         x = degree_onehot(out.edge_index, int(built.tot[0]), F)
@@ -199,16 +198,11 @@ class _Clean:
         self.S = _Source(self.src)
         self.F = _feature_width(self.S, "noise_batch")
         self.twin = self.lay.twins(data.edge_index)[0] if undirected else None
-        full = _log_probs(model, self.src)[h]                            # [B, C]
-        self.yhat = full.argmax(-1)
-        self.p_full = full.gather(-1, self.yhat.unsqueeze(-1)).squeeze(-1).exp()
+        self.yhat, self.p_full, _ = _whole(model, self.src, h)
         self.B, self.dev = self.lay.B, self.S.dev
 
     def replicas(self, rg, add, delete, seeds, features):
-        nb = _noise_build(self.S, self.F, self.twin, self.lay.max_edges, rg, add, delete, seeds, 8, features)
-        if nb.empty_graphs:
-            raise ValueError("%d replicas have no node (the engine does not run zero-node graphs)" % nb.empty_graphs)
-        return nb
+        return _noise_build(self.S, self.F, self.twin, self.lay.max_edges, rg, add, delete, seeds, 8, features)
 
 
 def _check_noise_args(head, trials, chunk, features):
@@ -249,9 +243,9 @@ def _curve_sums(model, data, h, adds, dels, trials, seed, features, undirected, 
         for i in range(0, trials * B, chunk):
             g = rg[i:i + chunk]
             nb = cl.replicas(g, a, d, seeds[i:i + chunk], features)
-            lp = _log_probs(model, nb)[h]                                # [R, C]
+            lp = _replica_log_probs(model, nb, h)                        # [R, C]
             pred = lp.argmax(-1)
-            p = lp.gather(-1, cl.yhat[g].unsqueeze(-1)).squeeze(-1).exp().double()
+            p = _p_at(lp, cl.yhat[g]).double()
             hit = (pred == y[g]).double() if y is not None else torch.full_like(p, float("nan"))
             tab.index_add_(1, g, torch.stack([hit, (pred == cl.yhat[g]).double(), p]))
             forwards, added, short = forwards + 1, added + nb.n_added, short + nb.short
@@ -299,15 +293,10 @@ def noise_curve(model, data, *, add=(0.0, 0.1, 0.2, 0.4), delete=0.0, trials: in
     and ``model.training`` as they were."""
     h, trials, chunk = _check_noise_args(head, trials, chunk, features)
     adds, dels = _level_list(add, delete)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            sums, stats, cl = _curve_sums(model, data, h, adds, dels, trials, seed, features, bool(undirected), chunk)
-            labels = cl.src.y is not None
-            levels = [_level_report(a, d, t, trials, s, labels, True) for a, d, t, s in zip(adds, dels, sums, stats)]
-    finally:
-        model.train(was_training)
+    with _eval_mode(model):
+        sums, stats, cl = _curve_sums(model, data, h, adds, dels, trials, seed, features, bool(undirected), chunk)
+        labels = cl.src.y is not None
+        levels = [_level_report(a, d, t, trials, s, labels, True) for a, d, t, s in zip(adds, dels, sums, stats)]
     return {"levels": levels, "p_full": cl.p_full, "yhat": cl.yhat, "forwards": 1 + sum(s[1] for s in stats)}
 
 
@@ -319,22 +308,17 @@ def eval_noise_curve(model, loader, device, *, add=(0.0, 0.1, 0.2, 0.4), delete=
     h, trials, chunk = _check_noise_args(head, trials, chunk, features)
     adds, dels = _level_list(add, delete)
     L = len(adds)
-    was_training = model.training
-    model.eval()
     tot = torch.zeros(L, 3, dtype=torch.float64, device=device)
     stat = [[0, 0, 0, 0] for _ in range(L)]
     graphs = batches = 0
-    try:
-        with torch.no_grad():
-            for data in loader:
-                batches += 1
-                sums, stats, cl = _curve_sums(model, data.to(device), h, adds, dels, trials, seed + trials * graphs, features,
-                                              bool(undirected), chunk)
-                tot += torch.stack([t.sum(1) for t in sums])
-                stat = [[u + v for u, v in zip(s, st)] for s, st in zip(stat, stats)]
-                graphs += cl.B
-    finally:
-        model.train(was_training)
+    with _eval_mode(model):
+        for data in loader:
+            batches += 1
+            sums, stats, cl = _curve_sums(model, data.to(device), h, adds, dels, trials, seed + trials * graphs, features,
+                                          bool(undirected), chunk)
+            tot += torch.stack([t.sum(1) for t in sums])
+            stat = [[u + v for u, v in zip(s, st)] for s, st in zip(stat, stats)]
+            graphs += cl.B
     rows = tot.tolist()
     labels = not any(math.isnan(r[0]) for r in rows)
     levels = [_level_report(a, d, r, s[0], tuple(s), labels, False) for a, d, r, s in zip(adds, dels, rows, stat)]
@@ -342,9 +326,9 @@ def eval_noise_curve(model, loader, device, *, add=(0.0, 0.1, 0.2, 0.4), delete=
 
 
 # ---- explanation stability ----------------------------------------------------------------------------------------------------
-_AGREE = ("rho", "tau", "jaccard")
-_SROW = 17          # per figure its sum and the replicas where it is defined; replicas; flips; sum of dp; inserted edges in the
-#                     top-k and inserted edges; precision sums and counts (noisy, clean); elements compared; clean graphs
+_SROW = 17          # the three figures' sums, then the replicas where each is defined (_agree_sums); replicas; flips; sum of dp;
+#                     inserted edges in the top-k and inserted edges; precision sums and counts (clean, noisy); elements compared;
+#                     clean graphs
 
 
 def _scores_and_log_probs(model, data):
@@ -394,6 +378,7 @@ def _stability_sums(model, data, h, add, delete, trials, seed, ratio, k, undirec
     for i in range(0, trials * B, chunk):
         g = rg[i:i + chunk]
         nb = cl.replicas(g, add, delete, seeds[i:i + chunk], features)
+        _check_replicas(nb)
         noisy, lp = _scores_and_log_probs(model, nb)
         E2 = int(nb.edge_index.size(1))
         survivor = nb.edge_src >= 0
@@ -401,17 +386,16 @@ def _stability_sums(model, data, h, add, delete, trials, seed, ratio, k, undirec
         twin2, rep2 = None, torch.ones(E2, dtype=torch.bool, device=dev)
         if cl.twin is not None:
             twin2 = _Layout(nb).twins(nb.edge_index)[0]
-            rep2 = ~((twin2 >= 0) & (twin2 < torch.arange(E2, device=dev)))
+            rep2 = _representatives(twin2)
         gt2 = None if gt is None else gt[src_col] & survivor            # an inserted edge is never ground truth
         top2, met2, noisy = _ranked(noisy, nb.edge_ptr, nb.max_edges, twin2, undirected, ratio, k, gt2)
         a = clean[src_col] if cl.S.E else noisy
         _, met = rank_agreement(a, noisy, nb.edge_ptr, nb.max_edges, sel=survivor & rep2, ratio=ratio, k=k)
-        defined = ~torch.isnan(met)                                      # [R, 3]
         ins = ~survivor & rep2
         lph = lp[h]
         pred = lph.argmax(-1)
-        p = lph.gather(-1, cl.yhat[g].unsqueeze(-1)).squeeze(-1).exp()
-        row[:6] += torch.stack([torch.where(defined, met, torch.zeros_like(met)).sum(0), defined.sum(0).double()], 1).view(-1)
+        p = _p_at(lph, cl.yhat[g])
+        row[:6] += _agree_sums(met)
         row[6:11] += torch.stack([torch.as_tensor(float(g.numel()), dtype=torch.float64, device=dev), (pred != cl.yhat[g]).sum().double(),
                                   (cl.p_full[g] - p).double().sum(), (ins & top2).sum().double(), ins.sum().double()])
         row[13:15] += _precision(met2, dev)
@@ -423,10 +407,7 @@ def _stability_sums(model, data, h, add, delete, trials, seed, ratio, k, undirec
 def _stability_report(row, stat, with_gt) -> dict:
     nan = float("nan")
     n = row[6]
-    res = {}
-    for j, key in enumerate(_AGREE):
-        res[key] = row[2 * j] / row[2 * j + 1] if row[2 * j + 1] else nan
-        res[key + "_undefined"] = int(n - row[2 * j + 1])
+    res = _agree_report(row[:6], n)
     res["flip"], res["dp"] = (row[7] / n, row[8] / n) if n else (nan, nan)
     res["noise_in_top"] = row[9] / row[10] if row[10] else 0.0
     if with_gt:
@@ -472,14 +453,9 @@ def stability(model, data, *, add: float = 0.1, delete: float = 0.0, trials: int
     ``added``, ``short``.  The sums stay on the device: the read-backs are the replica builder's and one at the end.  It leaves
     the model as ``explain`` does."""
     h, trials, chunk = _check_stability_args(ratio, k, undirected, head, trials, chunk, features, add, delete)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            row, stat = _stability_sums(model, data, h, float(add), float(delete), trials, seed, ratio, k, undirected, edge_gt,
-                                        features, chunk)
-    finally:
-        model.train(was_training)
+    with _eval_mode(model):
+        row, stat = _stability_sums(model, data, h, float(add), float(delete), trials, seed, ratio, k, undirected, edge_gt,
+                                    features, chunk)
     return _stability_report(row.tolist(), stat, edge_gt is not None)
 
 
@@ -490,19 +466,14 @@ def eval_stability(model, loader, device, *, add: float = 0.1, delete: float = 0
     until one read-back at the end (besides the replica builder's)."""
     from .spmotif import ground_truth
     h, trials, chunk = _check_stability_args(ratio, k, undirected, head, trials, chunk, features, add, delete)
-    was_training = model.training
-    model.eval()
     sums = torch.zeros(_SROW, dtype=torch.float64, device=device)
     stat, graphs = (0, 0, 0, 0), 0
-    try:
-        with torch.no_grad():
-            for data in loader:
-                data = data.to(device)
-                row, st = _stability_sums(model, data, h, float(add), float(delete), trials, seed + trials * graphs, ratio, k,
-                                          undirected, ground_truth(data)[1], features, chunk)
-                graphs += int(data.num_graphs)
-                sums += row
-                stat = tuple(u + v for u, v in zip(stat, st))
-    finally:
-        model.train(was_training)
+    with _eval_mode(model):
+        for data in loader:
+            data = data.to(device)
+            row, st = _stability_sums(model, data, h, float(add), float(delete), trials, seed + trials * graphs, ratio, k,
+                                      undirected, ground_truth(data)[1], features, chunk)
+            graphs += int(data.num_graphs)
+            sums += row
+            stat = tuple(u + v for u, v in zip(stat, st))
     return _stability_report(sums.tolist(), stat, True)

@@ -23,9 +23,11 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .explain import _HEADS, _Layout, _k_code, _keep8, _log_probs, _reduce_code, _scores, rank_segment_pairs, rank_segments
+from .explain import _eval_mode, _keep8, _Layout, rank_segment_pairs, rank_segments
 from .plan import _p, _stream
-from .splice import _Source, _built_batch, _check_use, _feature_width, _pairs, _rebatch
+from .replica import (_agree_report, _agree_sums, _built_batch, _caller_columns, _causal_in_order, _check_driver_args, _check_topk,
+                      _check_use, _feature_width, _grouped, _members, _p_at, _pairs, _Players, _rebatch, _replica_log_probs,
+                      _Source, _whole)
 
 __all__ = ["Occlusion", "occlude_batch", "occlusion", "rank_agreement", "faithfulness", "eval_faithfulness"]
 
@@ -73,10 +75,7 @@ def occlude_batch(data, rep_graph, rep_elem, *, use: str = "edges", twin=None):
             tw = torch.where(tw >= 0, inv[tw.clamp(min=0).long()].to(torch.int32), tw).contiguous()
     inputs = S.args() + [_p(rg) if R else None, _p(re) if R else None, R, mode, _p(tw) if S.E else None]
     built = _rebatch("cal_occlude", (S.E, R), inputs, R, 5, (S,), F, lambda: (rg < 0) | (rg >= S.B))
-    esrc = built.edge_src
-    if S.order is not None and built.tot[1]:               # columns that were reordered: back to the caller's numbering
-        esrc = S.order[esrc]
-    return _built_batch(S, built, rg, S.no_self_loops, esrc)
+    return _built_batch(S, built, rg, S.no_self_loops, _caller_columns(S, built.edge_src, built.tot[1]))
 
 
 # ---- leave-one-out scores -----------------------------------------------------------------------------------------------------
@@ -95,52 +94,16 @@ class Occlusion:
     twin: Optional[torch.Tensor] = None
 
 
-def _check_head(head):
-    if head not in _HEADS:
-        raise ValueError('head must be "c", "o" or "co"')
-    return _HEADS.index(head)
-
-
-def _grouped(data, lay):
-    """``data`` with its edge columns in graph order and the layout facts of ``lay``, no tile packing: the source of the
-    replicas, and the whole batch on the route the replicas take (``explain._untiled`` for grouped columns)."""
-    from .data import Batch
-    b = Batch()
-    b.x, b.feat, b.batch, b.y = getattr(data, "x", None), getattr(data, "feat", None), data.batch, getattr(data, "y", None)
-    b.edge_index = (data.edge_index if lay.order is None else data.edge_index[:, lay.order]).contiguous()
-    b.ptr, b.edge_ptr, b.num_graphs = lay.ptr, lay.edge_ptr, lay.B
-    b.max_nodes, b.max_edges, b.no_self_loops = lay.max_nodes, lay.max_edges, lay.no_self_loops
-    return b
-
-
 def _occlusion(model, data, lay, use, undirected, h, elements, chunk):
     """-> ``(Occlusion, representatives bool [M] or None)`` over the edge columns in ``lay``'s graph order (``score`` and
     ``twin`` index that order).  Called in eval mode under no_grad."""
     src = _grouped(data, lay)
-    dev = src.edge_index.device
-    full = _log_probs(model, src)[h]                                     # [B, C]
-    yhat = full.argmax(-1)
-    p_full = full.gather(-1, yhat.unsqueeze(-1)).squeeze(-1).exp()
-    nodes = (lay.ptr[1:] - lay.ptr[:-1]).to(dev)
-    twin = rep = None
-    if use == "edges":
-        M = int(src.edge_index.size(1))
-        ep = lay.edge_ptr.to(dev)
-        gid = torch.repeat_interleave(torch.arange(lay.B, device=dev), ep[1:] - ep[:-1], output_size=M)
-        low = 0                                                          # every node stays: a graph with one has a replica
-        if undirected is not None:
-            twin = lay.twins(data.edge_index)[0]
-            rep = ~((twin >= 0) & (twin < torch.arange(M, device=dev)))  # the lower column of a pair; unpaired; self loops
-    else:
-        M, gid, low = int(src.batch.numel()), src.batch, 1
-    want = None
-    if elements is not None:
-        want = _keep8(elements, M, dev, "elements").view(torch.bool)
-        if use == "edges" and lay.order is not None:
-            want = want[lay.order]
-        if twin is not None:                                             # an undirected edge is asked for by either column
-            want = want | (want[twin.clamp(min=0).long()] & (twin >= 0))
-    cand = nodes[gid] > low if M else torch.zeros(0, dtype=torch.bool, device=dev)
+    yhat, p_full, _ = _whole(model, src, h)
+    P = _Players(data, lay, src, use, undirected)
+    dev, M, gid, twin, rep = P.dev, P.M, P.gid, P.twin, P.rep
+    low = 0 if use == "edges" else 1                                     # edges: every node stays, a graph with one has a replica
+    want = None if elements is None else _members(elements, M, lay, use, twin)
+    cand = P.nodes[gid] > low if M else torch.zeros(0, dtype=torch.bool, device=dev)
     for m in (rep, want):
         if m is not None:
             cand = cand & m
@@ -151,27 +114,14 @@ def _occlusion(model, data, lay, use, undirected, h, elements, chunk):
     for i in range(0, n, chunk):
         ids, rg = idx[i:i + chunk], graph[i:i + chunk]
         rb = occlude_batch(src, rg, ids, use=use, twin=twin)
-        if rb.empty_graphs:
-            raise ValueError("%d replicas have no node (the engine does not run zero-node graphs)" % rb.empty_graphs)
-        lp = _log_probs(model, rb)[h]                                    # [R, C]
-        sc = p_full[rg] - lp.gather(-1, yhat[rg].unsqueeze(-1)).squeeze(-1).exp()
+        lp = _replica_log_probs(model, rb, h)                            # [R, C]
+        sc = p_full[rg] - _p_at(lp, yhat[rg])
         score[ids] = sc
         if twin is not None:
             t = twin[ids].long()
             score[torch.where(t >= 0, t, ids)] = sc                      # both columns receive the score
         forwards += 1
     return Occlusion(score=score, p_full=p_full, yhat=yhat, replicas=n, forwards=forwards, twin=twin), rep
-
-
-def _check_occlusion_args(use, undirected, head, chunk):
-    _check_use(use)
-    _reduce_code(undirected)
-    if undirected is not None and use != "edges":
-        raise ValueError('undirected needs use="edges"')
-    chunk = int(chunk)
-    if chunk < 1:
-        raise ValueError("chunk must be >= 1")
-    return _check_head(head), chunk
 
 
 def occlusion(model, data, *, use: str = "edges", undirected=None, head: str = "o", elements=None, chunk: int = 512) -> Occlusion:
@@ -191,20 +141,15 @@ def occlusion(model, data, *, use: str = "edges", undirected=None, head: str = "
     without ``elements``.  CPU-resident models go through libcalhost and the operator-level ``model(data)``.  Like ``explain``,
     it runs in eval mode under ``no_grad`` and leaves parameters, optimizer state, the engine's step counter, BatchNorm
     statistics, the RNG states and ``model.training`` as they were."""
-    h, chunk = _check_occlusion_args(use, undirected, head, chunk)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            lay = _Layout(data)
-            occ, _ = _occlusion(model, data, lay, use, undirected, h, elements, chunk)
-            if use == "edges" and lay.order is not None:                # back to the caller's column order
-                score = torch.empty_like(occ.score)
-                score[lay.order] = occ.score
-                occ.score = score
-                occ.twin = None if occ.twin is None else lay.caller_twin(occ.twin)
-    finally:
-        model.train(was_training)
+    h, chunk = _check_driver_args(use, undirected, head, chunk)
+    with _eval_mode(model):
+        lay = _Layout(data)
+        occ, _ = _occlusion(model, data, lay, use, undirected, h, elements, chunk)
+        if use == "edges" and lay.order is not None:                    # back to the caller's column order
+            score = torch.empty_like(occ.score)
+            score[lay.order] = occ.score
+            occ.score = score
+            occ.twin = None if occ.twin is None else lay.caller_twin(occ.twin)
     return occ
 
 
@@ -239,9 +184,7 @@ def rank_agreement(a: torch.Tensor, b: torch.Tensor, seg_ptr: torch.Tensor, max_
     mid-ranks), Kendall's tau-b ``(C - D) / sqrt((n0 - Ta)(n0 - Tb))`` with ``n0 = n (n - 1) / 2`` and the Jaccard overlap
     ``inter / (2 k_g - inter)``; NaN where the denominator is zero or ``n < 2``.  The counts are integers, so the GPU, the host
     library and any restatement agree bit for bit."""
-    kc, rt = _k_code(ratio, k)
-    if kc == -2:
-        raise ValueError('rank_agreement has no ground truth: k must be an int >= 0')
+    kc, rt = _check_topk(ratio, k, "rank_agreement")
     if a.dim() != 1 or b.dim() != 1 or a.dtype != torch.float32 or b.dtype != torch.float32 or a.numel() != b.numel():
         raise TypeError("a and b must be 1-D float32 tensors of one length")
     if a.device != b.device:
@@ -260,38 +203,28 @@ def rank_agreement(a: torch.Tensor, b: torch.Tensor, seg_ptr: torch.Tensor, max_
 
 
 # ---- causal attention against occlusion ---------------------------------------------------------------------------------------
-_FAITH = ("rho", "tau", "jaccard")
-_ROW = 11          # per figure its sum and the graphs where it is defined; graphs; sum and count of the occlusion score inside
-#                    the causal top-k and outside it
+_ROW = 11          # the three figures' sums, then the graphs where each is defined (_agree_sums); graphs; sum and count of the
+#                    occlusion score inside the causal top-k and outside it
 
 
 def _faith_sums(model, data, use, undirected, h, ratio, k, elements, chunk):
     """One batch's sums [_ROW] fp64 on the device, the replicas and forwards it took (host ints), and the pieces the sums are
     made of ``(causal score, occlusion score, sel, seg_ptr, max_seg, top-k mask)``, all over the columns in graph order.
     Called in eval mode under no_grad."""
-    edge, node = _scores(model, data)
-    causal = (edge if use == "edges" else node).clone()
-    lay = _Layout(data)
+    causal, lay = _causal_in_order(model, data, use)
     occ, rep = _occlusion(model, data, lay, use, undirected, h, elements, chunk)
-    if use == "nodes":
-        seg, max_seg = lay.ptr, lay.max_nodes
+    seg, max_seg = (lay.ptr, lay.max_nodes) if use == "nodes" else (lay.edge_ptr, lay.max_edges)
+    if undirected is None:
         top = rank_segments(causal, seg, max_seg, ratio=ratio, k=k)[0]
-    else:
-        seg, max_seg = lay.edge_ptr, lay.max_edges
-        if lay.order is not None:
-            causal = causal[lay.order].contiguous()
-        if undirected is None:
-            top = rank_segments(causal, seg, max_seg, ratio=ratio, k=k)[0]
-        else:                                                            # one symmetrised score per undirected edge, as explain
-            top, _, _, causal = rank_segment_pairs(causal, seg, max_seg, occ.twin, undirected, ratio=ratio, k=k)
+    else:                        # one symmetrised score per undirected edge, as explain; the top-k mask comes from the same call
+        top, _, _, causal = rank_segment_pairs(causal, seg, max_seg, occ.twin, undirected, ratio=ratio, k=k)
     counts, met = rank_agreement(causal, occ.score, seg, max_seg, sel=rep, ratio=ratio, k=k)
     took = ~torch.isnan(occ.score)
     if rep is not None:
         took = took & rep
-    defined = ~torch.isnan(met)                                          # [B, 3]
     sc = occ.score.double()
     zero = torch.zeros_like(sc)
-    row = torch.cat([torch.stack([torch.where(defined, met, torch.zeros_like(met)).sum(0), defined.sum(0).double()], 1).view(-1),
+    row = torch.cat([_agree_sums(met),
                      torch.stack([torch.as_tensor(float(lay.B), dtype=torch.float64, device=sc.device),
                                   torch.where(took & top, sc, zero).sum(), (took & top).sum().double(),
                                   torch.where(took & ~top, sc, zero).sum(), (took & ~top).sum().double()])])
@@ -301,10 +234,7 @@ def _faith_sums(model, data, use, undirected, h, ratio, k, elements, chunk):
 def _faith_report(row, replicas, forwards) -> dict:
     nan = float("nan")
     n = row[6]
-    res = {}
-    for j, key in enumerate(_FAITH):
-        res[key] = row[2 * j] / row[2 * j + 1] if row[2 * j + 1] else nan
-        res[key + "_undefined"] = int(n - row[2 * j + 1])
+    res = _agree_report(row[:6], n)
     res["occ_top"] = row[7] / row[8] if row[8] else nan
     res["occ_rest"] = row[9] / row[10] if row[10] else nan
     res["graphs"], res["elements"], res["replicas"], res["forwards"] = int(n), int(row[8] + row[10]), int(replicas), int(forwards)
@@ -312,10 +242,8 @@ def _faith_report(row, replicas, forwards) -> dict:
 
 
 def _check_faith_args(use, undirected, head, ratio, k, chunk):
-    _k_code(ratio, k)
-    if k == "gt":
-        raise ValueError('faithfulness has no ground truth: k must be an int >= 0')
-    return _check_occlusion_args(use, undirected, head, chunk)
+    _check_topk(ratio, k, "faithfulness")
+    return _check_driver_args(use, undirected, head, chunk)
 
 
 def faithfulness(model, data, *, use: str = "edges", undirected=None, head: str = "o", ratio=None, k=None, elements=None,
@@ -337,13 +265,8 @@ def faithfulness(model, data, *, use: str = "edges", undirected=None, head: str 
     forward for the scores.  The sums stay on the device: the read-backs are the replica builder's and one at the end.  It
     leaves the model as ``occlusion`` does."""
     h, chunk = _check_faith_args(use, undirected, head, ratio, k, chunk)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            row, replicas, forwards, _ = _faith_sums(model, data, use, undirected, h, ratio, k, elements, chunk)
-    finally:
-        model.train(was_training)
+    with _eval_mode(model):
+        row, replicas, forwards, _ = _faith_sums(model, data, use, undirected, h, ratio, k, elements, chunk)
     return _faith_report(row.tolist(), replicas, forwards)
 
 
@@ -352,16 +275,11 @@ def eval_faithfulness(model, loader, device, *, use: str = "edges", undirected=N
     """``faithfulness`` over a loader: the means taken over all graphs (and all occluded elements) of the loader.  The sums stay
     on the device until one read-back at the end (besides the replica builder's)."""
     h, chunk = _check_faith_args(use, undirected, head, ratio, k, chunk)
-    was_training = model.training
-    model.eval()
     sums = torch.zeros(_ROW, dtype=torch.float64, device=device)
     replicas = forwards = 0
-    try:
-        with torch.no_grad():
-            for data in loader:
-                row, r, f, _ = _faith_sums(model, data.to(device), use, undirected, h, ratio, k, None, chunk)
-                sums += row
-                replicas, forwards = replicas + r, forwards + f
-    finally:
-        model.train(was_training)
+    with _eval_mode(model):
+        for data in loader:
+            row, r, f, _ = _faith_sums(model, data.to(device), use, undirected, h, ratio, k, None, chunk)
+            sums += row
+            replicas, forwards = replicas + r, forwards + f
     return _faith_report(sums.tolist(), replicas, forwards)

@@ -14,113 +14,16 @@ that has already mixed trivial structure into ``xo`` passes ``intervene`` untouc
 """
 from __future__ import annotations
 
-from collections import namedtuple
-
 import torch
 
-from . import _lib
-from .explain import (_HEADS, _Layout, _k_code, _log_probs, _reduce_code, _scores, _untiled, extract_subgraph)
-from .plan import _p, _stream
+from .explain import _HEADS, _eval_mode, _Layout, _log_probs, _reduce_code, _scores, _untiled, extract_subgraph
+from .plan import _p
+from .replica import _Source, _built_batch, _check_topk, _check_use, _p_at, _pairs, _rebatch
 
 __all__ = ["splice_batches", "structure_intervention", "eval_structure_intervention", "BRIDGE"]
 
 #: ``edge_src`` of a bridge column (``CAL_SPLICE_BRIDGE``)
 BRIDGE = -(1 << 63)
-
-
-class _Source:
-    """What the operator reads of one batch: features, grouped edge columns, the two offset arrays."""
-
-    def __init__(self, data):
-        from .data import Batch
-        self.is_x = getattr(data, "x", None) is not None
-        self.x = data.x if self.is_x else getattr(data, "feat", None)
-        ei = data.edge_index
-        self.order = None
-        if isinstance(data, Batch) and data.ptr is not None and data.edge_ptr is not None:
-            self.B, self.ptr, self.edge_ptr = int(data.num_graphs), data.ptr, data.edge_ptr
-            self.no_self_loops = bool(data.no_self_loops)
-        else:
-            lay = _Layout(data)
-            self.B, self.ptr, self.edge_ptr, self.no_self_loops, self.order = lay.B, lay.ptr, lay.edge_ptr, lay.no_self_loops, lay.order
-            if self.order is not None:                     # columns not grouped by graph: stable graph order first
-                ei = ei[:, self.order]
-        self.dev = ei.device
-        self.ei = ei.to(torch.long).contiguous()
-        self.ptr = self.ptr.to(device=self.dev, dtype=torch.long).contiguous()
-        self.edge_ptr = self.edge_ptr.to(device=self.dev, dtype=torch.long).contiguous()
-        self.E = int(ei.size(1))
-        self.N = int(data.batch.numel()) if getattr(data, "batch", None) is not None else int(self.x.size(0))
-        self.y = getattr(data, "y", None)
-
-    def args(self):
-        return [_p(self.ei) if self.E else None, self.E, self.N, _p(self.ptr), _p(self.edge_ptr), self.B]
-
-
-def _pairs(t, n: int, dev, what: str):
-    if t is None:
-        return torch.arange(n, dtype=torch.long, device=dev)
-    t = torch.as_tensor(t)
-    if t.dim() != 1 or t.dtype.is_floating_point or t.dtype == torch.bool:
-        raise TypeError("%s must be a 1-D integer tensor" % what)
-    return t.to(device=dev, dtype=torch.long).contiguous()
-
-
-def _feature_width(S, name: str) -> int:
-    """F of a replica builder's one source (0: no features); ``name`` is the builder's, for the message."""
-    if S.x is None:
-        return 0
-    if S.x.dtype != torch.float32:
-        raise TypeError("%s copies float32 features" % name)
-    if S.x.dim() != 2:
-        raise ValueError("the features must be [N, F]")
-    return int(S.x.size(1))
-
-
-#: what ``_rebatch`` returns: the offsets, ``tot`` (the totals and the bad count as host ints: nodes, columns, largest node count,
-#: largest column count, result graphs without a node, ..., bad), the outputs (``edge_index`` flat [2 Eout], ``x`` or ``None``)
-_Built = namedtuple("_Built", "ptr edge_ptr tot batch node_src edge_index edge_src x")
-
-
-def _rebatch(stem: str, ws_args, inputs, R: int, ntot: int, srcs, F: int, bad):
-    """The calls of one batch builder, ``stem`` + ``_ws`` / ``_count`` / ``_write``: the workspace query, one allocation for the
-    offsets, ``totals`` [ntot] and the workspace, the count, the one read-back, the outputs' allocation, the write.  ``inputs``:
-    the arguments both entry points start with; ``srcs``: the ``_Source`` objects whose rows (F columns) are copied; ``bad()``: a
-    bool tensor whose count is read back with the totals -- a callable, so that its torch launches are issued while the count
-    kernel runs, not in front of it.  -> ``_Built``."""
-    dev, host = srcs[0].dev, not srcs[0].ei.is_cuda
-    wsb = _lib.query(stem + "_ws", *ws_args, host=host)
-    sizes = (R + 1, R + 1, ntot, (wsb + 7) // 8)
-    ptr_o, eptr_o, totals, ws = torch.split(torch.empty(sum(sizes), dtype=torch.long, device=dev), sizes)
-    st = None if host else _stream()
-    _lib.call(stem + "_count", *inputs, _p(ptr_o), _p(eptr_o), _p(totals), _p(ws), 8 * sizes[-1], st, host=host)
-    # the one read-back: the Batch needs the totals as host ints (and y whether every result graph has its source of y)
-    tot = torch.cat([totals, bad().sum().view(1)]).tolist()
-    n2, e2 = tot[:2]
-    ints = torch.empty(2 * n2 + 3 * e2, dtype=torch.long, device=dev)
-    batch_o, nsrc, ei_o, esrc = torch.split(ints, (n2, n2, 2 * e2, e2))
-    x_o = torch.empty(n2, F, dtype=torch.float32, device=dev) if F else None
-    xs = [s.x.contiguous() if F and s.N else None for s in srcs]
-    _lib.call(stem + "_write", *inputs, *map(_p, xs), F, _p(ptr_o), _p(eptr_o), n2, e2,
-              _p(batch_o) if n2 else None, _p(x_o) if F and n2 else None, _p(ei_o) if e2 else None, _p(nsrc) if n2 else None,
-              _p(esrc) if e2 else None, _p(ws), 8 * sizes[-1], st, host=host)
-    return _Built(ptr_o, eptr_o, tot, batch_o, nsrc, ei_o, esrc, x_o)
-
-
-def _built_batch(S, b, picks, no_self_loops: bool, edge_src):
-    """The ``Batch`` of ``b`` (``_Built``): features as ``S`` carries them, ``y = S.y[picks]`` unless a pick was bad; ``edge_src``
-    in the caller's column numbering."""
-    from .data import Batch
-    out = Batch()
-    out.x, out.feat = (b.x, None) if S.is_x or S.x is None else (None, b.x)
-    out.edge_index, out.batch = b.edge_index.view(2, b.tot[1]), b.batch
-    out.y = S.y.view(-1)[picks] if S.y is not None and not b.tot[-1] else None
-    out.ptr, out.edge_ptr, out.num_graphs = b.ptr, b.edge_ptr, int(picks.numel())
-    out.max_nodes, out.max_edges = int(b.tot[2]), int(b.tot[3])
-    out.no_self_loops = no_self_loops
-    out.node_src, out.edge_src = b.node_src, edge_src
-    out.empty_graphs = int(b.tot[4])
-    return out
 
 
 def splice_batches(a, b, pairs_a=None, pairs_b=None, *, bridge=None):
@@ -189,11 +92,6 @@ def splice_batches(a, b, pairs_a=None, pairs_b=None, *, bridge=None):
 # ---- the report ---------------------------------------------------------------------------------------------------------------
 _PER_HEAD = ("acc_full", "acc_self", "acc_swap", "follow", "agree", "p_shift")
 _ROW = 6 * len(_HEADS) + 5          # per head the six sums, then: pairs with y_j != y_g, pairs, graphs, kept, total elements
-
-
-def _check_use(use):
-    if use not in ("nodes", "edges"):
-        raise ValueError('use must be "nodes" or "edges"')
 
 
 def _partner_rows(partners, B: int, dev, generator):
@@ -272,7 +170,7 @@ def _structure_sums(model, data, specs, use, undirected, partners, generator, br
     for ratio, k in specs:
         full, ident, swaps, _, kept, total, _ = _structure_forward(model, data, lay, scores, ratio, k, use, undirected, rows, bridge)
         yhat = full.argmax(-1)                                           # [3, B]
-        pf = full.gather(-1, yhat.unsqueeze(-1)).squeeze(-1).exp()
+        pf = _p_at(full, yhat)
         pred = swaps.argmax(-1).transpose(0, 1)                          # [3, m, B]
         idx = yhat.view(3, 1, B, 1).expand(3, rows.size(0), B, 1)
         ps = swaps.transpose(0, 1).gather(-1, idx).squeeze(-1).exp()     # [3, m, B]: p_swap of the whole graph's argmax
@@ -300,9 +198,7 @@ def _structure_report(row) -> dict:
 
 
 def _check_args(ratio, k, use, undirected, partners, bridge):
-    _k_code(ratio, k)
-    if k == "gt":
-        raise ValueError('structure_intervention has no ground truth: k must be an int >= 0')
+    _check_topk(ratio, k, "structure_intervention")
     _check_use(use)
     _reduce_code(undirected)
     if not (torch.is_tensor(partners) or partners == "all" or (isinstance(partners, int) and partners >= 0)):
@@ -336,13 +232,8 @@ def structure_intervention(model, data, *, ratio=None, k=None, use: str = "nodes
     it leaves parameters, optimizer state, the engine's step counter, BatchNorm statistics, ``model.training`` and the RNG
     states as they were (a given ``generator`` advances; without one the global torch state is restored)."""
     _check_args(ratio, k, use, undirected, partners, bridge)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            sums = _structure_sums(model, data, [(ratio, k)], use, undirected, partners, generator, bridge)
-    finally:
-        model.train(was_training)
+    with _eval_mode(model):
+        sums = _structure_sums(model, data, [(ratio, k)], use, undirected, partners, generator, bridge)
     return _structure_report(sums[0].tolist())
 
 
@@ -355,13 +246,8 @@ def eval_structure_intervention(model, loader, device, *, ratios=(0.3,), use: st
     for r in ratios:
         _check_args(r, None, use, undirected, partners, bridge)
     specs = [(r, None) for r in ratios]
-    was_training = model.training
-    model.eval()
     sums = torch.zeros(len(specs), _ROW, dtype=torch.float64, device=device)
-    try:
-        with torch.no_grad():
-            for data in loader:
-                sums += _structure_sums(model, data.to(device), specs, use, undirected, partners, generator, bridge)
-    finally:
-        model.train(was_training)
+    with _eval_mode(model):
+        for data in loader:
+            sums += _structure_sums(model, data.to(device), specs, use, undirected, partners, generator, bridge)
     return {r: _structure_report(row) for r, row in zip(ratios, sums.tolist())}

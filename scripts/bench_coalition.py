@@ -68,10 +68,10 @@ def main():
     ap.add_argument("--device", default="cuda", help="cpu rehearses the script through libcalhost; its times say nothing")
     a = ap.parse_args()
     from cal_amd import model as M, spmotif
-    from cal_amd.coalition import _Players, coalition_batch, perturbation_curve, shapley
+    from cal_amd.coalition import coalition_batch, perturbation_curve, shapley
     from cal_amd.data import Batch
     from cal_amd.explain import _Layout, _log_probs, _scores
-    from cal_amd.occlude import _grouped
+    from cal_amd.replica import _grouped, _Players
     dev = a.device
     args = argparse.Namespace(layers=3, hidden=128, with_random=True, without_node_attention=False,
                               without_edge_attention=False, fc_num="222", cat_or_add="add", c=0.5, o=1.0, co=0.5)

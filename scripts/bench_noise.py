@@ -59,8 +59,8 @@ def main():
     from cal_amd.coalition import coalition_batch
     from cal_amd.data import Batch
     from cal_amd.explain import _Layout
-    from cal_amd.noise import _Source, _feature_width, _noise_build, noise_batch, noise_curve, stability
-    from cal_amd.occlude import _grouped
+    from cal_amd.noise import _noise_build, noise_batch, noise_curve, stability
+    from cal_amd.replica import _feature_width, _grouped, _Source
     dev = a.device
     args = argparse.Namespace(layers=3, hidden=128, with_random=True, without_node_attention=False,
                               without_edge_attention=False, fc_num="222", cat_or_add="add", c=0.5, o=1.0, co=0.5)

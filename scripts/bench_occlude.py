@@ -95,7 +95,8 @@ def main():
     from cal_amd import model as M, spmotif
     from cal_amd.data import Batch
     from cal_amd.explain import _Layout, _log_probs, edge_twins, explain
-    from cal_amd.occlude import _grouped, occlude_batch, occlusion, rank_agreement
+    from cal_amd.occlude import occlude_batch, occlusion, rank_agreement
+    from cal_amd.replica import _grouped
     dev = "cuda"
     args = argparse.Namespace(layers=3, hidden=128, with_random=True, without_node_attention=False,
                               without_edge_attention=False, fc_num="222", cat_or_add="add", c=0.5, o=1.0, co=0.5)

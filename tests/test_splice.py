@@ -11,9 +11,8 @@ import torch
 
 from cal_amd import _lib
 from cal_amd.data import Batch
-from cal_amd.explain import explain, extract_subgraph
-from cal_amd.splice import (BRIDGE, _Layout, _scores, _structure_forward, eval_structure_intervention, splice_batches,
-                            structure_intervention)
+from cal_amd.explain import _Layout, _scores, explain, extract_subgraph
+from cal_amd.splice import BRIDGE, _structure_forward, eval_structure_intervention, splice_batches, structure_intervention
 from oracle import cal_oracle as O
 from tests.splice_oracle import HEADS, KEYS, check_splice, check_structure, splice_cases, structure_oracle
 
