@@ -7,6 +7,8 @@ raise if libcalhip.so or a GPU is missing."""
 __version__ = "0.1.0"
 
 _MASKOPT = ("LearnedMask", "MaskOptimizer", "learn_mask", "mask_agreement")
+_PGEXPLAIN = ("EdgeExplainer", "ExplainerTrainer", "ParametricMask", "fit_explainer", "explain_edges", "explainer_agreement",
+              "eval_explainer")
 
 
 def __getattr__(name):
@@ -15,4 +17,7 @@ def __getattr__(name):
     if name in _MASKOPT:
         from . import maskopt
         return getattr(maskopt, name)
+    if name in _PGEXPLAIN:                                    # the parametric edge explainer (cal_amd/pgexplain.py), likewise
+        from . import pgexplain
+        return getattr(pgexplain, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

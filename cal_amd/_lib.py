@@ -38,6 +38,7 @@ HOST_SYMBOLS = ("cal_last_error", "cal_version", "cal_plan_build", "cal_graph_pt
                 "cal_coalition_ws", "cal_coalition_count", "cal_coalition_write",
                 "cal_edge_dot", "cal_gat_mask_fwd", "cal_gat_mask_bwd_ws", "cal_gat_mask_bwd",
                 "cal_mask_step",
+                "cal_edge_mlp_fwd", "cal_edge_mlp_bwd_ws", "cal_edge_mlp_bwd",
                 "cal_noise_ws", "cal_noise_count", "cal_noise_write", "cal_degree_onehot")
 
 _SCALARS = {

@@ -689,6 +689,154 @@ HOST_EXPORT int cal_mask_step(const int64_t* pptr, const int32_t* rep, const int
     return 0;
 }
 
+// ---- parametric edge explainer (cal_amd/csrc/edgemlp.hip; cal_amd/pgexplain.py): the same formulas in fp32 -- a column's dot
+// product over the hidden units in order, a node's row sums in slot order, dw2 / db2 through the kernel's per-block, per-wave
+// partials -- the per-graph sums in double
+namespace {
+inline uint64_t splitmix64(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+inline bool column_ok(int64_t e, const int32_t* row32, const int32_t* col32, int64_t E, int64_t N, int64_t& u, int64_t& v) {
+    u = v = 0;
+    if (e < 0 || e >= E) return false;
+    u = row32[e];
+    v = col32[e];
+    return u >= 0 && u < N && v >= 0 && v < N;
+}
+inline float column_omega(const float* pq, const float* w2, float b2, int64_t u, int64_t v, int64_t Hd) {
+    float a = 0.f;
+    for (int64_t k = 0; k < Hd; ++k) a = fmaf(fmaxf(pq[u * 2 * Hd + k] + pq[v * 2 * Hd + Hd + k], 0.f), w2[k], a);
+    return b2 + a;
+}
+inline bool mlp_sizes_ok(int64_t N, int64_t E, int64_t Hd, int64_t B, int64_t P) {
+    return N >= 0 && E >= 0 && B >= 0 && P >= 0 && N < (1ll << 31) && E < (1ll << 31) && B < (1ll << 31) && P < (1ll << 31) &&
+           Hd >= 4 && Hd <= 256 && Hd % 4 == 0;
+}
+inline int mlp_rows_per_block(int64_t N) {
+    const int64_t rpb = (N + 511) / 512;
+    return (int)(rpb < 16 ? 16 : rpb);
+}
+}  // namespace
+
+HOST_EXPORT int cal_edge_mlp_fwd(const float* pq, const float* w2, const float* b2, const int32_t* row32, const int32_t* col32,
+                                 const int64_t* pptr, const int32_t* rep, const int32_t* mate, float* omega, float* z, float* mask,
+                                 double* terms, int64_t N, int64_t E, int64_t Hd, int64_t B, int64_t P, float tau, uint64_t seed,
+                                 int64_t step, void*) {
+    HOST_REQUIRE(mlp_sizes_ok(N, E, Hd, B, P), "bad sizes (Hd: a multiple of 4 in [4, 256])");
+    HOST_REQUIRE(tau > 0.f && step >= 0 && step < (1ll << 31), "tau must be > 0, step in [0, 2^31)");
+    if (B == 0 || P == 0) return 0;
+    HOST_REQUIRE(pq && w2 && b2 && row32 && col32 && pptr && rep && mate && omega && z && mask, "null operand");
+    for (int64_t g = 0; g < B; ++g) {
+        int64_t lo = pptr[g], hi = pptr[g + 1];
+        lo = lo < 0 ? 0 : (lo > P ? P : lo);
+        hi = hi < lo ? lo : (hi > P ? P : hi);
+        double s_size = 0.0, s_ent = 0.0;
+        for (int64_t p = lo; p < hi; ++p) {
+            int64_t ur, vr, ut, vt;
+            float om = 0.f, zz = 0.f;
+            if (column_ok(rep[p], row32, col32, E, N, ur, vr)) {
+                const bool t_ok = column_ok(mate[p], row32, col32, E, N, ut, vt);
+                om = column_omega(pq, w2, b2[0], ur, vr, Hd);
+                if (t_ok) om = 0.5f * (om + column_omega(pq, w2, b2[0], ut, vt, Hd));
+                float noise = 0.f;
+                if (seed != 0) {
+                    const uint64_t h = splitmix64(splitmix64(seed) + (((uint64_t)step << 32) + (uint64_t)p));
+                    const float u = ((float)(h >> 41) + 0.5f) * (1.f / 8388608.f);
+                    noise = logf(u) - logf(1.f - u);
+                }
+                zz = (noise + om) / tau;
+                const Logit q = logit_terms(zz);
+                mask[rep[p]] = q.m;
+                if (t_ok) mask[mate[p]] = q.m;
+                s_size += (double)q.m;
+                s_ent += (double)q.ent;
+            }
+            omega[p] = om;
+            z[p] = zz;
+        }
+        if (terms) { terms[2 * g] = s_size; terms[2 * g + 1] = s_ent; }
+    }
+    return 0;
+}
+
+HOST_EXPORT int64_t cal_edge_mlp_bwd_ws(int64_t, int64_t, int64_t) { return 4; }
+
+HOST_EXPORT int cal_edge_mlp_bwd(const float* pq, const float* w2, const int32_t* row32, const int32_t* col32,
+                                 const int32_t* rowptr_src, const int32_t* eid_src, const int32_t* rowptr_dst, const int32_t* eid_dst,
+                                 const int64_t* pptr, const int32_t* rep, const int32_t* mate, const float* z, const float* gmask,
+                                 float* dpq, float* dw2, float* db2, float* ws, int64_t N, int64_t E, int64_t Hd, int64_t B, int64_t P,
+                                 float tau, float l_size, float l_ent, void*) {
+    (void)ws;
+    HOST_REQUIRE(mlp_sizes_ok(N, E, Hd, B, P), "bad sizes (Hd: a multiple of 4 in [4, 256])");
+    HOST_REQUIRE(tau > 0.f, "tau must be > 0");
+    if (B == 0 || P == 0) return 0;
+    HOST_REQUIRE(pq && w2 && row32 && col32 && rowptr_src && eid_src && rowptr_dst && eid_dst && pptr && rep && mate && z && gmask &&
+                     dpq && dw2 && db2, "null operand");
+    std::vector<float> c((size_t)(E > 0 ? E : 1), 0.f);
+    for (int64_t g = 0; g < B; ++g) {
+        int64_t lo = pptr[g], hi = pptr[g + 1];
+        lo = lo < 0 ? 0 : (lo > P ? P : lo);
+        hi = hi < lo ? lo : (hi > P ? P : hi);
+        const float ent_w = hi > lo ? l_ent / (float)(hi - lo) : 0.f;
+        for (int64_t p = lo; p < hi; ++p) {
+            int64_t u, v;
+            const int64_t r = rep[p], t = mate[p];
+            if (!column_ok(r, row32, col32, E, N, u, v)) continue;
+            const bool t_ok = column_ok(t, row32, col32, E, N, u, v);
+            const Logit q = logit_terms(z[p]);
+            const float gr = ((gmask[r] + (t_ok ? gmask[t] : 0.f) + (l_size - ent_w * z[p])) * q.dm) / tau;
+            if (t_ok) { c[r] = 0.5f * gr; c[t] = 0.5f * gr; }
+            else c[r] = gr;
+        }
+    }
+    // the kernel's partials: workgroup b owns rpb nodes, its wave w every fourth of them; a block's partial is its four waves' in
+    // order, the total the blocks' in order
+    const int rpb = mlp_rows_per_block(N);
+    std::vector<float> tot((size_t)Hd + 1, 0.f), wave(4 * ((size_t)Hd + 1));
+    for (int64_t r0 = 0; r0 < N; r0 += rpb) {
+        std::fill(wave.begin(), wave.end(), 0.f);
+        const int64_t r1 = r0 + rpb < N ? r0 + rpb : N;
+        for (int64_t n = r0; n < r1; ++n) {
+            float* aw = wave.data() + ((n - r0) & 3) * (Hd + 1);
+            float* dp = dpq + n * 2 * Hd;
+            std::fill(dp, dp + 2 * Hd, 0.f);
+            for (int side = 0; side < 2; ++side) {
+                const int32_t* ptr = side == 0 ? rowptr_src : rowptr_dst;
+                const int32_t* eid = side == 0 ? eid_src : eid_dst;
+                const int32_t* other = side == 0 ? col32 : row32;
+                int64_t beg = ptr[n], end = ptr[n + 1];
+                beg = beg < 0 ? 0 : beg;
+                end = end > E ? E : end;
+                const float* own = pq + n * 2 * Hd + (side == 0 ? 0 : Hd);
+                for (int64_t s = beg; s < end; ++s) {
+                    const int64_t e = eid[s];
+                    if (e < 0 || e >= E) continue;
+                    const int64_t o = other[e];
+                    if (o < 0 || o >= N || c[e] == 0.f) continue;
+                    const float ce = c[e];
+                    const float* oth = pq + o * 2 * Hd + (side == 0 ? Hd : 0);
+                    for (int64_t k = 0; k < Hd; ++k) {
+                        const float h = own[k] + oth[k];
+                        if (h > 0.f) {
+                            dp[side * Hd + k] = fmaf(ce, w2[k], dp[side * Hd + k]);
+                            if (side == 0) aw[k] = fmaf(ce, h, aw[k]);
+                        }
+                    }
+                    if (side == 0) aw[Hd] += ce;
+                }
+            }
+        }
+        for (int64_t k = 0; k <= Hd; ++k)
+            tot[k] += ((wave[k] + wave[Hd + 1 + k]) + wave[2 * (Hd + 1) + k]) + wave[3 * (Hd + 1) + k];
+    }
+    for (int64_t k = 0; k < Hd; ++k) dw2[k] = tot[k];
+    db2[0] = tot[Hd];
+    return 0;
+}
+
 // Batch.from_data_list for graphs that live in ONE host-side concatenation (train_causal.py:13-15; cal_amd/data.py::_HostConcat):
 // features copied, edge_index rebased by the running node offset, batch vector and labels written.  Same entry point as
 // libcalhip.so (collate.hip) -- it only ever sees host pointers, so a machine with the host library alone serves DataLoader too.
@@ -1337,12 +1485,7 @@ HOST_EXPORT int cal_coalition_write(const int64_t* edge_index, int64_t E, int64_
 // same accepted candidates in the same order, so every integer output agrees bit for bit.  Nothing is kept between the two
 // calls: the write decides the insertions again.
 namespace {
-inline uint64_t splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
+// (splitmix64: above, with the edge explainer's twins)
 inline uint64_t noise_hash(uint64_t s, uint64_t i) { return splitmix64(splitmix64(s) + i); }
 
 struct NoiseSrc {

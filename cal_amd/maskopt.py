@@ -61,6 +61,24 @@ def _number(v, what, positive=False):
     return float(v)
 
 
+def _player_tables(data, S):
+    """The players of ``S`` (a ``gradient._Setup`` of ``data``) in graph order, the representatives of ``_Setup`` over the segments
+    of ``_Layout`` -> ``(pptr int64 [B + 1], rep int32 [P], mate int32 [P])``: a player's first element and its twin column or
+    -1; columns that are not grouped by graph need no reordering."""
+    dev, M = S.dev, S.M
+    lay = _Layout(data)
+    order, seg = (lay.order, lay.edge_ptr) if S.use == "edges" else (None, lay.ptr)
+    rep_o = S.rep if order is None else S.rep[order]
+    elems = torch.arange(M, device=dev) if order is None else order
+    rep = elems[rep_o]
+    pptr = torch.cat([torch.zeros(1, dtype=torch.long, device=dev), torch.cumsum(rep_o.long(), 0)])[seg.long()].contiguous()
+    if S.twin is not None:
+        mate = torch.where(S.paired[rep], S.t[rep], torch.full_like(rep, -1)).to(torch.int32).contiguous()
+    else:
+        mate = torch.full((int(rep.numel()),), -1, dtype=torch.int32, device=dev)
+    return pptr, rep.to(torch.int32).contiguous(), mate
+
+
 class MaskOptimizer:
     """Adam over the mask logits of ``data``'s players (``use``, ``undirected``, ``elements``, ``head`` as in ``saliency``).
 
@@ -100,21 +118,10 @@ class MaskOptimizer:
             if isinstance(init, bool) or not isinstance(init, (int, float)):
                 raise TypeError("init must be a float or a float32 tensor")
             init = torch.full((M,), float(init), dtype=torch.float32, device=dev)
-        # the players in graph order: the representatives of _Setup over the segments of _Layout
-        lay = _Layout(data)
-        order, seg = (lay.order, lay.edge_ptr) if use == "edges" else (None, lay.ptr)
-        rep_o = S.rep if order is None else S.rep[order]
-        elems = torch.arange(M, device=dev) if order is None else order
-        rep = elems[rep_o]
-        self.P = P = int(rep.numel())
+        self.pptr, self.rep, self.mate = _player_tables(data, S)
+        self.P = P = int(self.rep.numel())
         self.B, self.M = B, M
-        self.pptr = torch.cat([torch.zeros(1, dtype=torch.long, device=dev), torch.cumsum(rep_o.long(), 0)])[seg.long()].contiguous()
-        self.rep = rep.to(torch.int32).contiguous()
-        if S.twin is not None:
-            self.mate = torch.where(S.paired[rep], S.t[rep], torch.full_like(rep, -1)).to(torch.int32).contiguous()
-        else:
-            self.mate = torch.full((P,), -1, dtype=torch.int32, device=dev)
-        self.theta = init[rep].contiguous()
+        self.theta = init[self.rep.long()].contiguous()
         self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.theta), torch.zeros_like(self.theta)
         self.mask = torch.ones(M, dtype=torch.float32, device=dev)
         self.t = 0

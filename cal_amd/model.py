@@ -144,12 +144,7 @@ class _CausalBase(torch.nn.Module):
         """Operator-level causal scores (model.py:85-111 up to the soft masks: backbone and attention, no convolutions or
         readouts): edge ``edge_att[:, 1]`` [E] and node ``node_att[:, 1]`` [N], column 1 being the objects branch.  Runs in
         the module's current mode; ``cal_amd.explain`` calls it in eval mode under ``no_grad``."""
-        x = data.x if data.x is not None else data.feat
-        edge_index = data.edge_index
-        plan = plan_of(data)
-        x = self.bn_feat(x)
-        x = self.conv_feat(x, edge_index, relu=True)
-        x = self._backbone(x, edge_index, plan)
+        x, plan = self._embed(data)
         if getattr(self, "without_edge_attention", False):
             edge = torch.full((plan.E,), 0.5, dtype=x.dtype, device=x.device)
         else:
@@ -159,6 +154,23 @@ class _CausalBase(torch.nn.Module):
         else:
             node = ops.node_attention_split(x, self.node_att_mlp.weight, self.node_att_mlp.bias)[2][:, 1]
         return edge, node
+
+    def _embed(self, data):
+        """Operator-level backbone (model.py:85-95): ``(x [N, H], plan)``, the rows both attention MLPs read.  Runs in the
+        module's current mode and grad mode."""
+        x = data.x if data.x is not None else data.feat
+        edge_index = data.edge_index
+        plan = plan_of(data)
+        x = self.bn_feat(x)
+        x = self.conv_feat(x, edge_index, relu=True)
+        return self._backbone(x, edge_index, plan), plan
+
+    def _node_embeddings(self, data):
+        """The backbone output ``x`` [N, H] that ``_attention_scores`` feeds to ``edge_att_mlp``, in eval mode under ``no_grad``
+        (``model.training`` is put back): the input of ``cal_amd.pgexplain``'s edge MLP."""
+        from .explain import _eval_mode
+        with _eval_mode(self):
+            return self._embed(data)[0]
 
     def _pooled(self, data):
         """Operator-level forward up to the add-pool (model.py:85-116): the pooled trivial rows ``xc`` [B, H] and objects rows
@@ -244,6 +256,16 @@ class _CausalBase(torch.nn.Module):
         """``cal_amd.maskopt.learn_mask(self, data, **kw)``: a soft mask per graph trained to keep ``p(ŷ)`` while small and binary."""
         from .maskopt import learn_mask
         return learn_mask(self, data, **kw)
+
+    def fit_explainer(self, loader, device, **kw):
+        """``cal_amd.pgexplain.fit_explainer(self, loader, device, **kw)``: an edge MLP trained once to explain any graph."""
+        from .pgexplain import fit_explainer
+        return fit_explainer(self, loader, device, **kw)
+
+    def explain_edges(self, explainer, data, **kw):
+        """``cal_amd.pgexplain.explain_edges(self, explainer, data, **kw)``: that MLP's mask of ``data``, two forwards."""
+        from .pgexplain import explain_edges
+        return explain_edges(self, explainer, data, **kw)
 
     def intervene(self, data, **kw):
         """``cal_amd.intervene.intervene(self, data, **kw)``: the ``co`` head over every (graph, trivial partner) pair."""

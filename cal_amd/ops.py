@@ -464,3 +464,59 @@ class _NodeMaskColumns(Function):
 
 def node_mask_columns(n, plan: GraphPlan):
     return _NodeMaskColumns.apply(n, plan)
+
+
+class _EdgeMlpMask(Function):
+    """The parametric explainer's edge MLP on the node projections ``pq`` [N, 2 Hd] (``cal_edge_mlp_fwd`` / ``_bwd``, include/cal_hip.h)
+    -> ``(mask [E], terms [B, 2], omega [P], z [P])``; only ``mask`` carries a gradient.  The backward takes ``dmask``, adds the
+    gradients of ``l_size * sum m + l_ent / P_g * sum H(m)`` in closed form and returns ``dpq, dw2, db2``."""
+
+    @staticmethod
+    def forward(ctx, pq, w2, b2, plan: GraphPlan, players, tau: float, seed: int, step: int, l_size: float, l_ent: float):
+        pq, w2, b2 = _f32(pq, "pq"), _f32(w2, "w2"), _f32(b2, "b2")
+        if pq.dim() != 2 or pq.size(0) != plan.N or pq.size(1) % 2:
+            raise ValueError("pq must be [nodes (%d), 2 * hidden]" % plan.N)
+        N, Hd = plan.N, pq.size(1) // 2
+        if Hd < 4 or Hd > 256 or Hd % 4:
+            raise ValueError("the hidden width must be a multiple of 4 in [4, 256] (got %d)" % Hd)
+        if w2.numel() != Hd or b2.numel() != 1:
+            raise ValueError("w2 must have one entry per hidden unit (%d) and b2 one" % Hd)
+        if players.E != plan.E:
+            raise ValueError("the players belong to another batch (%d columns, the plan has %d)" % (players.E, plan.E))
+        dev, B, P = pq.device, players.B, players.P
+        mask = torch.ones(plan.E, dtype=torch.float32, device=dev)
+        terms = torch.zeros(B, 2, dtype=torch.float64, device=dev)
+        omega, z = torch.zeros(P, dtype=torch.float32, device=dev), torch.zeros(P, dtype=torch.float32, device=dev)
+        _c("cal_edge_mlp_fwd", pq, w2, b2, plan.row32, plan.col32, players.pptr, players.rep, players.mate, omega, z, mask, terms,
+           N, plan.E, Hd, B, P, tau, seed, step)
+        ctx.plan, ctx.players, ctx.tau, ctx.l_size, ctx.l_ent = plan, players, tau, l_size, l_ent
+        ctx.shapes = (w2.shape, b2.shape)
+        ctx.save_for_backward(pq, w2, z)
+        ctx.mark_non_differentiable(terms, omega, z)
+        return mask, terms, omega, z
+
+    @staticmethod
+    def backward(ctx, dmask, _dterms, _domega, _dz):
+        pq, w2, z = ctx.saved_tensors
+        plan, players = ctx.plan, ctx.players
+        dev, N, Hd = pq.device, plan.N, w2.numel()
+        gmask = torch.zeros(plan.E, dtype=torch.float32, device=dev) if dmask is None else _f32(dmask, "grad")
+        if players.B == 0 or players.P == 0:                    # (the entry point launches nothing)
+            return torch.zeros_like(pq), torch.zeros(ctx.shapes[0], device=dev), torch.zeros(ctx.shapes[1], device=dev), \
+                None, None, None, None, None, None, None
+        dpq = torch.empty_like(pq)
+        dw2, db2 = torch.empty(Hd, dtype=torch.float32, device=dev), torch.empty(1, dtype=torch.float32, device=dev)
+        ws = _empty(_q(pq, "cal_edge_mlp_bwd_ws", N, plan.E, Hd), dev)
+        rs, es, rd, ed = players.csr(plan)
+        _c("cal_edge_mlp_bwd", pq, w2, plan.row32, plan.col32, rs, es, rd, ed, players.pptr, players.rep, players.mate, z, gmask,
+           dpq, dw2, db2, ws, N, plan.E, Hd, players.B, players.P, ctx.tau, ctx.l_size, ctx.l_ent)
+        return dpq, dw2.view(ctx.shapes[0]), db2.view(ctx.shapes[1]), None, None, None, None, None, None, None
+
+
+def edge_mlp_mask(pq, w2, b2, plan: GraphPlan, players, tau: float = 1.0, seed: int = 0, step: int = 0, size_coeff: float = 0.0,
+                  ent_coeff: float = 0.0, full: bool = False):
+    """``(mask float32 [E], terms fp64 [B, 2])`` of the edge MLP over ``players`` (``cal_amd.pgexplain.EdgePlayers``: ``pptr`` /
+    ``rep`` / ``mate`` and the two CSRs); ``full``: also ``omega`` and ``z`` [P].  ``mask`` is 1 outside the players.  ``seed = 0``:
+    no noise."""
+    out = _EdgeMlpMask.apply(pq, w2, b2, plan, players, float(tau), int(seed), int(step), float(size_coeff), float(ent_coeff))
+    return out if full else out[:2]

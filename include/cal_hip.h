@@ -167,6 +167,45 @@ CAL_API int cal_mask_step(const int64_t* pptr, const int32_t* rep, const int32_t
                           int64_t B, int64_t P, int64_t M, int32_t step, float lr, float beta1, float beta2,
                           float eps, float l_size, float l_ent, void* stream);
 
+/* ---- parametric edge explainer (cal_amd/pgexplain.py; csrc/edgemlp.hip, host twins in csrc_host/calhost.cpp) ------------------
+ * A two-layer MLP on the embeddings of an edge's end nodes, hidden width Hd (a multiple of 4, 4 to
+ * 256).  pq [N, 2 Hd] holds the node projections P = x W1a^T + b1 (columns [0, Hd)) and Q = x W1b^T (columns [Hd, 2 Hd)), one
+ * cal_gemm; w2 [Hd], b2 [1].  For a column e = (u -> v), u = row32[e], v = col32[e]:
+ *   h_e[k] = pq[u, k] + pq[v, Hd + k],   omega(e) = b2 + sum_k w2[k] relu(h_e[k])
+ * The P players are grouped by graph, pptr [B + 1]; player p owns column rep[p] and, for a twin pair, mate[p] (else -1):
+ *   omega_p = (omega(rep) + omega(mate)) / 2 for a pair, omega(rep) otherwise.
+ * cal_edge_mlp_fwd samples the concrete relaxation: seed == 0 gives z_p = omega_p / tau; otherwise, with splitmix64 as in
+ * csrc/common.hpp and H(s, i) = splitmix64(splitmix64(s) + i),
+ *   u_p = ((H(seed, step 2^32 + p) >> 41) + 0.5) 2^-23   (23 bits: exact in fp32, as 1 - u_p is, and never 0 or 1)
+ *   z_p = (log u_p - log(1 - u_p) + omega_p) / tau
+ * and writes omega [P], z [P] and m_p = sigma(z_p) to mask[rep] and mask[mate]; every other entry of mask [E] keeps its bits.
+ * terms [B, 2] (or null) receives per graph sum_p m_p and sum_p H(m_p), H(m) = softplus(z) - z sigma(z), summed in double in a
+ * fixed order; a graph without players gets 0, 0.  One launch, one workgroup per graph, a group of lanes per player (Hd / 4
+ * lanes with 16-byte loads); no atomics.
+ * cal_edge_mlp_bwd: with gmask [E] the gradient of the prediction loss with respect to mask, P_g the graph's player count,
+ *   domega_p = (gmask[rep] + gmask[mate] + l_size - (l_ent / P_g) z_p) m_p (1 - m_p) / tau
+ * a column's coefficient c_e is domega_p, halved on both columns of a pair, 0 for a column of no player, and
+ *   dpq[u, k]      = sum_{e: row = u} c_e w2[k] [h_e[k] > 0]        dw2[k] = sum_e c_e relu(h_e[k])
+ *   dpq[v, Hd + k] = sum_{e: col = v} c_e w2[k] [h_e[k] > 0]        db2    = sum_e c_e
+ * The node sums run over two CSRs by source and by destination with the columns' ids (the plan's, or any that list every
+ * player column once per view: the plan's leave out input self loops), one wave per row in slot order; h_e is recomputed; dw2
+ * and db2 go through per-block partials and a fixed-order finish.  One memset and three launches; every row of dpq is written
+ * (0 for a node without a player column); equal inputs give equal bits.  ws: cal_edge_mlp_bwd_ws floats.
+ * Both: pptr is clamped into [0, P]; a player whose rep is outside [0, E) (or has an end node outside [0, N)) is skipped --
+ * omega = z = 0 are written for it, it reaches neither mask nor terms nor any gradient, it still counts in P_g -- and such a mate
+ * counts as no mate.  B = 0 or P = 0 launches nothing.  pq / w2 / dpq that are not 16-byte aligned take a scalar path. */
+CAL_API int cal_edge_mlp_fwd(const float* pq, const float* w2, const float* b2, const int32_t* row32, const int32_t* col32,
+                             const int64_t* pptr, const int32_t* rep, const int32_t* mate, float* omega, float* z,
+                             float* mask, double* terms, int64_t N, int64_t E, int64_t Hd, int64_t B, int64_t P,
+                             float tau, uint64_t seed, int64_t step, void* stream);
+CAL_API int64_t cal_edge_mlp_bwd_ws(int64_t N, int64_t E, int64_t Hd);
+CAL_API int cal_edge_mlp_bwd(const float* pq, const float* w2, const int32_t* row32, const int32_t* col32,
+                             const int32_t* rowptr_src, const int32_t* eid_src, const int32_t* rowptr_dst,
+                             const int32_t* eid_dst, const int64_t* pptr, const int32_t* rep, const int32_t* mate,
+                             const float* z, const float* gmask, float* dpq, float* dw2, float* db2, float* ws,
+                             int64_t N, int64_t E, int64_t Hd, int64_t B, int64_t P, float tau, float l_size,
+                             float l_ent, void* stream);
+
 /* ---- on-device mini-batch assembly (PyG DataLoader / Batch collate, train_causal.py:13-15,171-174)
  * over a device-resident concatenated dataset; offsets of the selected graphs computed by the host */
 CAL_API int cal_collate(const float* X, const int64_t* EI, int64_t sumE, int64_t F,
