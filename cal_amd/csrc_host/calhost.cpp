@@ -1763,3 +1763,117 @@ HOST_EXPORT int cal_intervene_pairs(const float* xo, int64_t B, const float* xc,
     }
     return 0;
 }
+
+// ---- Weisfeiler-Lehman refinement and the WL subtree kernel (cal_amd/csrc/wl.hip; cal_amd/wl.py): the same integer formulas,
+// graph by graph; the match counts colours through a sorted copy, as the device does.
+namespace {
+inline uint64_t wl_next(uint64_t c, uint64_t so, uint64_t si) {
+    return splitmix64(splitmix64(splitmix64(c + CAL_WL_C_SELF) + so) + si);
+}
+}  // namespace
+
+HOST_EXPORT int64_t cal_wl_ws(int64_t, int64_t, int64_t) { return 0; }
+
+HOST_EXPORT int cal_wl_refine(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                              int64_t B, const int64_t* init, int64_t T, int64_t max_nodes, int64_t* colors, int64_t* hash,
+                              int64_t* totals, void*, int64_t, void*) {
+    HOST_REQUIRE(E >= 0 && N >= 0 && B >= 0 && max_nodes >= 0, "E, N, B, max_nodes must be >= 0");
+    HOST_REQUIRE(T >= 0 && T <= 4096, "T must be in [0, 4096]");
+    HOST_REQUIRE(totals, "totals is null");
+    totals[0] = 0;
+    if (B == 0) return 0;
+    HOST_REQUIRE(ptr && edge_ptr && hash, "ptr / edge_ptr / hash are null");
+    HOST_REQUIRE(E == 0 || edge_index, "edge_index is null");
+    HOST_REQUIRE(N == 0 || colors, "colors is null");
+    uint64_t* col = reinterpret_cast<uint64_t*>(colors);
+    uint64_t* hs = reinterpret_cast<uint64_t*>(hash);
+    int64_t ignored = 0;
+#pragma omp parallel for schedule(dynamic, 16) reduction(+ : ignored)
+    for (int64_t g = 0; g < B; ++g) {
+        int64_t nlo, nhi, elo, ehi;
+        seg_clamp(ptr, g, N, nlo, nhi);
+        seg_clamp(edge_ptr, g, E, elo, ehi);
+        const int64_t n = nhi - nlo;
+        auto inside = [&](int64_t e) {
+            const int64_t u = edge_index[e], v = edge_index[E + e];
+            return u >= nlo && u < nhi && v >= nlo && v < nhi;
+        };
+        for (int64_t e = elo; e < ehi; ++e) ignored += !inside(e);
+        uint64_t* hrow = hs + g * (T + 1);
+        if (n > max_nodes) {
+            for (int64_t t = 0; t <= T; ++t) {
+                hrow[t] = 0;
+                for (int64_t v = nlo; v < nhi; ++v) col[t * N + v] = 0;
+            }
+            continue;
+        }
+        for (int64_t v = nlo; v < nhi; ++v) col[v] = splitmix64((init ? (uint64_t)init[v] : 0ull) ^ CAL_WL_C_INIT);
+        std::vector<uint64_t> so((size_t)n), si((size_t)n);
+        uint64_t h = splitmix64((uint64_t)n ^ CAL_WL_C_GRAPH);
+        for (int64_t t = 0;; ++t) {
+            const uint64_t* c = col + t * N;
+            uint64_t s = 0;
+            for (int64_t v = nlo; v < nhi; ++v) s += splitmix64(c[v] ^ CAL_WL_C_NODE);
+            h = splitmix64(h + s);
+            hrow[t] = h;
+            if (t == T) break;
+            std::fill(so.begin(), so.end(), 0ull);
+            std::fill(si.begin(), si.end(), 0ull);
+            for (int64_t e = elo; e < ehi; ++e) {
+                if (!inside(e)) continue;
+                const int64_t u = edge_index[e], v = edge_index[E + e];
+                so[(size_t)(u - nlo)] += splitmix64(c[v] ^ CAL_WL_C_OUT);
+                si[(size_t)(v - nlo)] += splitmix64(c[u] ^ CAL_WL_C_IN);
+            }
+            for (int64_t v = nlo; v < nhi; ++v) col[(t + 1) * N + v] = wl_next(c[v], so[(size_t)(v - nlo)], si[(size_t)(v - nlo)]);
+        }
+    }
+    totals[0] = ignored;
+    return 0;
+}
+
+HOST_EXPORT int cal_wl_match(const int64_t* colors_a, int64_t stride_a, int64_t Na, const int64_t* ptr_a, int64_t A,
+                             const int64_t* colors_p, int64_t stride_p, int64_t Np, const int64_t* ptr_p, int64_t P, int64_t T,
+                             int64_t max_nodes_a, int64_t* K, int64_t* self_a, void*) {
+    HOST_REQUIRE(Na >= 0 && A >= 0 && Np >= 0 && P >= 0 && max_nodes_a >= 0, "Na, A, Np, P, max_nodes_a must be >= 0");
+    HOST_REQUIRE(T >= 0 && T <= 4096, "T must be in [0, 4096]");
+    HOST_REQUIRE(Np <= 4096, "the prototype batch has more than 4096 nodes");
+    HOST_REQUIRE(stride_a >= Na && stride_p >= Np, "a row stride is shorter than its row");
+    if (A == 0) return 0;
+    HOST_REQUIRE(ptr_a && self_a, "ptr_a / self_a are null");
+    HOST_REQUIRE(P == 0 || (ptr_p && K), "ptr_p / K are null");
+    HOST_REQUIRE((Na == 0 || colors_a) && (Np == 0 || colors_p), "colors_a / colors_p are null");
+    const uint64_t* ca = reinterpret_cast<const uint64_t*>(colors_a);
+    const uint64_t* cp = reinterpret_cast<const uint64_t*>(colors_p);
+#pragma omp parallel for schedule(dynamic, 16)
+    for (int64_t g = 0; g < A; ++g) {
+        int64_t lo, hi;
+        seg_clamp(ptr_a, g, Na, lo, hi);
+        const bool skip = hi - lo > max_nodes_a;
+        std::vector<uint64_t> srt;
+        for (int64_t t = 0; t <= T; ++t) {
+            int64_t own = 0;
+            if (!skip) {
+                srt.assign(ca + t * stride_a + lo, ca + t * stride_a + hi);
+                std::sort(srt.begin(), srt.end());
+                for (size_t p = 0; p < srt.size();) {
+                    size_t e = p + 1;
+                    while (e < srt.size() && srt[e] == srt[p]) ++e;
+                    own += (int64_t)((e - p) * (e - p));
+                    p = e;
+                }
+            }
+            self_a[g * (T + 1) + t] = own;
+            for (int64_t p = 0; p < P; ++p) {
+                int64_t plo, phi, cnt = 0;
+                seg_clamp(ptr_p, p, Np, plo, phi);
+                for (int64_t w = plo; w < phi && !skip; ++w) {
+                    const auto r = std::equal_range(srt.begin(), srt.end(), cp[t * stride_p + w]);
+                    cnt += (int64_t)(r.second - r.first);
+                }
+                K[(g * P + p) * (T + 1) + t] = cnt;
+            }
+        }
+    }
+    return 0;
+}

@@ -308,6 +308,11 @@ class _CausalBase(torch.nn.Module):
         from .noise import stability
         return stability(self, data, **kw)
 
+    def explanation_census(self, data, **kw):
+        """``cal_amd.wl.explanation_census(self, data, **kw)``: the WL shape of every graph's causal explanation."""
+        from .wl import explanation_census
+        return explanation_census(self, data, **kw)
+
     def explain(self, data, **kw):
         """``cal_amd.explain.explain(self, data, **kw)``: per-graph top-k causal subgraphs of ``data``."""
         from .explain import explain

@@ -120,6 +120,22 @@ def _motif_tables(dev) -> Tuple[torch.Tensor, torch.Tensor]:
     return t
 
 
+def motif_batch(device=None):
+    """The four motifs of ``CLASS_LIST`` as one ``Batch`` (graph c is the motif of class c): both directions of every edge,
+    grouped by source, no features -- the prototypes of ``cal_amd.wl.subgraph_census``."""
+    from .data import Batch
+    gs = []
+    for s in CLASS_LIST:
+        n, edges = _MOTIFS[s]
+        cols = sorted([(a, b) for a, b in edges] + [(b, a) for a, b in edges])
+        d = Data(edge_index=torch.tensor(cols, dtype=torch.long).t().contiguous())
+        d.num_nodes = n
+        gs.append(d)
+    b = Batch.from_data_list(gs)
+    b.y = torch.arange(len(CLASS_LIST), dtype=torch.long)
+    return b if device is None else b.to(device)
+
+
 def ground_truth(batch) -> Tuple[torch.Tensor, torch.Tensor]:
     """(node_gt [N], edge_gt [E]) bool tensors on the batch's device: the planted motif of every graph.
 

@@ -663,6 +663,52 @@ CAL_API int cal_noise_write(const int64_t* edge_index, int64_t E, int64_t N, con
  * launches on `stream`, no ws, no synchronisation. */
 CAL_API int cal_degree_onehot(const int64_t* edge_index, int64_t E, int64_t N, int64_t F, float* x_out, void* stream);
 
+/* ---- Weisfeiler-Lehman colour refinement of a batch, and the WL subtree kernel of two batches (cal_amd/wl.py wl_refine /
+ * wl_match; shape census of explanations) ----
+ * The batch is edge_index [2, E] int64, ptr / edge_ptr [B+1] int64 as in cal_noise_*: graph g owns the nodes [ptr[g], ptr[g+1])
+ * and the columns [edge_ptr[g], edge_ptr[g+1]).  A column COUNTS iff both endpoints lie inside g's node range; the others are
+ * ignored and counted in totals[0] (summed over the graphs, whatever max_nodes).  Self loops and duplicates count, with
+ * multiplicity.  All arithmetic is mod 2^64 and sm is the splitmix64 of the noise block above.  With init int64 [N] (null: 0
+ * everywhere) and depth T >= 0:
+ *   c_0[v] = sm(init[v] ^ CAL_WL_C_INIT)
+ *   for t = 1 .. T:  out[v] = sum over the counted columns (v, w) of sm(c_{t-1}[w] ^ CAL_WL_C_OUT)
+ *                    in[v]  = sum over the counted columns (w, v) of sm(c_{t-1}[w] ^ CAL_WL_C_IN)
+ *                    c_t[v] = sm(sm(sm(c_{t-1}[v] + CAL_WL_C_SELF) + out[v]) + in[v])
+ *   graph hash, cumulative over the depths: h = sm(n_g ^ CAL_WL_C_GRAPH); for t = 0 .. T:
+ *                    h = sm(h + sum over v in g of sm(c_t[v] ^ CAL_WL_C_NODE)), hash[g, t] = h.
+ * colors int64 [T+1, N] (row t = c_t), hash int64 [B, T+1], totals [1] int64 on the device; the int64s carry the uint64 bit
+ * patterns: compare them for equality only.  Equal hashes mean "1-WL-equivalent up to a 64-bit collision", not "isomorphic".
+ * A graph with more than max_nodes nodes gets hash 0 and colours 0.  Every output is uniquely determined: the sums are integer
+ * sums, so the order of the integer atomics that form them (into LDS, or into ws) cannot show; the host library and a plain
+ * restatement agree bit for bit.
+ *   cal_wl_refine: a memset of totals and ONE launch on `stream`, one workgroup per graph for all T rounds, no read-back, no
+ *   synchronisation.  Graphs within cal_explain_lds_cap() nodes keep both colour buffers and the two sum arrays in LDS and
+ *   stream their columns from global memory every round; larger graphs (max_nodes above the cap) run the same rounds through
+ *   the rows of colors and the two sum arrays in ws (8-byte aligned, cal_wl_ws(N, E, B) bytes; not read when max_nodes is
+ *   within the cap).  B = 0: nothing is launched.  N = 0 with B > 0: every graph gets the hash of the empty graph.  E = 0 is
+ *   legal.  0 <= T <= 4096.
+ *   cal_wl_match: the WL subtree kernel of every graph of a batch A against every graph of a prototype batch P, from the two
+ *   colors arrays (row strides stride_a / stride_p in elements, Na / Np nodes, ptr_a [A+1] / ptr_p [P+1]) of ONE refinement
+ *   depth T:   K[a, p, t] = sum over w in p of #{v in a : c_t[v] == c_t[w]}   int64 [A, P, T+1]
+ *              self_a[a, t] = sum over the colours of a at depth t of count^2  int64 [A, T+1].
+ *   ONE launch, one workgroup per graph of A, integers only, no atomics, no ws.  Per depth a graph within the cap has its
+ *   colours sorted in LDS (by counting); one wave per prototype looks its nodes up by binary search -- a colour's count is the
+ *   length of its run -- and sums.  Above the cap every pair is compared.  A graph of A with more than max_nodes_a nodes gets
+ *   zeros.  Np <= 4096, else an error.  A = 0 launches nothing; P = 0 writes self_a only. */
+#define CAL_WL_C_INIT 0xD6E8FEB86659FD93ULL
+#define CAL_WL_C_SELF 0xC2B2AE3D27D4EB4FULL
+#define CAL_WL_C_OUT 0x165667B19E3779F9ULL
+#define CAL_WL_C_IN 0x27D4EB2F165667C5ULL
+#define CAL_WL_C_NODE 0x85EBCA77C2B2AE63ULL
+#define CAL_WL_C_GRAPH 0xFF51AFD7ED558CCDULL
+CAL_API int64_t cal_wl_ws(int64_t N, int64_t E, int64_t B);
+CAL_API int cal_wl_refine(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                          int64_t B, const int64_t* init, int64_t T, int64_t max_nodes, int64_t* colors, int64_t* hash,
+                          int64_t* totals, void* ws, int64_t ws_bytes, void* stream);
+CAL_API int cal_wl_match(const int64_t* colors_a, int64_t stride_a, int64_t Na, const int64_t* ptr_a, int64_t A,
+                         const int64_t* colors_p, int64_t stride_p, int64_t Np, const int64_t* ptr_p, int64_t P, int64_t T,
+                         int64_t max_nodes_a, int64_t* K, int64_t* self_a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
