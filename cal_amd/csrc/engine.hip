@@ -236,6 +236,11 @@ struct Engine {
     unsigned long long* gat_ctr;
     int o_conv_att[MAX_LAYERS];
     float *gz, *gsc, *gws;      // per layer: z = BN(h) W [L][N,H]; a_dst, a_src, max, denominator [L][4][N,K]; backward scratch
+    // what the latest bwd_commit handed k_finish, kept for cal_engine_finish_layout (host bookkeeping only; tests read it):
+    // the flat-buffer interval of every slab task (kind 0), commit task (1) and update-only range (2), in task order, and the
+    // value of adam_in_finish the step ended with (0: no update in k_finish, 1: in k_finish, 2: fell back to k_adam)
+    struct FinishIv { int64_t begin, end; int kind; } fin_iv[MAX_SLABS + MAX_COMMITS + MAX_ADAM_RANGES];
+    int fin_n, fin_adam;
 };
 
 static size_t al(size_t n) { return (n + 63) / 64 * 64; }   // 256 B granules (in floats/ints)
@@ -2227,6 +2232,10 @@ int bwd_commit(Ctx& c, Bwd& b) {
             fa.adam.on = 0; fa.nar = 0; c.adam_in_finish = 2;     // 2: k_adam follows, counter already advanced
         }
     }
+    e->fin_n = 0; e->fin_adam = c.adam_in_finish;
+    for (int i = 0; i < fa.nst; ++i) e->fin_iv[e->fin_n++] = {fa.st[i].dst - e->G, (fa.st[i].dst - e->G) + fa.st[i].n, 0};
+    for (int i = 0; i < fa.nct; ++i) e->fin_iv[e->fin_n++] = {fa.ct[i].dst, (int64_t)fa.ct[i].dst + fa.ct[i].n, 1};
+    for (int i = 0; i < fa.nar; ++i) e->fin_iv[e->fin_n++] = {fa.ar[i].begin, fa.ar[i].end, 2};
     int nblk = 0;
     for (int i = 0; i < fa.nst; ++i) { fa.blk0[i] = nblk; nblk += std::max(1, cdiv(fa.st[i].n, 64)); }
     for (int i = 0; i < fa.nct; ++i) { fa.blk0[fa.nst + i] = nblk; nblk += std::max(1, cdiv(fa.ct[i].n, 16)); }
@@ -2323,7 +2332,10 @@ CAL_EXPORT int cal_engine_step(void* h, const float* x0, const int64_t* edge_ind
             if (rc) return rc;
         }
     }
-    if ((mode & 4) && c.adam_in_finish != 1) return launch_adam(e, c.st, 1);      // k_finish has already advanced the step counter (c.tick_in_finish)
+    if ((mode & 4) && c.adam_in_finish != 1) {          // k_finish has already advanced the step counter (c.tick_in_finish)
+        RC(launch_adam(e, c.st, 1));
+        if (g_stop_after == 0) g_stage_names.push_back(cal::g_last_launch);      // (named like a stage; never a stop point)
+    }
     return 0;
 }
 
@@ -2518,12 +2530,26 @@ CAL_EXPORT int64_t cal_engine_profile_read(double* out, int64_t cap) {
     return n;
 }
 
+// The layout of the latest step's k_finish launch (read-only; see Engine::fin_iv): writes up to cap / 3 triples
+// (begin, end, kind) into out -- kind 0 = slab task, 1 = commit task, 2 = update-only Adam range -- and the step's final
+// adam_in_finish (0 / 1 / 2 = k_adam followed behind an already advanced counter) into *adam_in_finish; returns the number
+// of intervals the step had (-1: bad arguments).
+CAL_EXPORT int64_t cal_engine_finish_layout(void* h, int64_t* out, int64_t cap, int64_t* adam_in_finish) {
+    Engine* e = (Engine*)h;
+    if (!e || (cap > 0 && !out)) return -1;
+    for (int i = 0; i < e->fin_n && 3 * (int64_t)(i + 1) <= cap; ++i) {
+        out[3 * i] = e->fin_iv[i].begin; out[3 * i + 1] = e->fin_iv[i].end; out[3 * i + 2] = e->fin_iv[i].kind;
+    }
+    if (adam_in_finish) *adam_in_finish = e->fin_adam;
+    return e->fin_n;
+}
+
 // Adam alone (after an external gradient all-reduce)
 CAL_EXPORT int cal_engine_adam(void* h, void* stream_) {
     Engine* e = (Engine*)h;
     hipStream_t st = (hipStream_t)stream_;
     RC(launch_adam(e, st, 0));
-    hipLaunchKernelGGL(k_adam_tick, dim3(1), dim3(1), 0, st, e->step);
+    hipLaunchKernelGGL(k_adam_tick, dim3(1), dim3(1), 0, st, e->step, (const int*)e->status);
     CAL_CHECK_LAUNCH("k_adam_tick");
     return 0;
 }

@@ -1343,7 +1343,11 @@ __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float
     const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
     p[i] -= (lr / bc1) * (mi / denom);
 }
-__global__ void k_adam_tick(float* step) { step[0] += 1.f; }
+// (a flagged step was not applied by the k_adam in front, so it is not counted either: the bias corrections must not drift)
+__global__ void k_adam_tick(float* step, const int* __restrict__ status) {
+    if (status && (status[0] | status[1]) != 0) return;
+    step[0] += 1.f;
+}
 
 // ------------------------------------------------------------------------------------------------------------------
 // One-shot gradient exchange over peer-mapped memory + Adam (the data-parallel exchange of the ~0.5 MB

@@ -313,6 +313,11 @@ CAL_API int64_t cal_engine_p2p_status(void* engine);
  * (train_causal.py:171-192 has no counterpart: the reference validates nothing; here a stale batch attribute must not train on
  * garbage silently) */
 CAL_API int64_t cal_engine_peek_status(void* engine);
+/* read-only view of the latest backward step's last launch (k_finish): up to cap / 3 triples (begin, end, kind) of the flat
+ * parameter buffer -- kind 0: finished by a slab task, 1: by a commit task, 2: an update-only Adam range -- and
+ * *adam_in_finish = 0 (the update is a launch of its own or absent), 1 (every element updated inside k_finish) or 2 (the
+ * ranges did not fit: k_adam followed behind the already advanced step counter).  Returns the number of intervals. */
+CAL_API int64_t cal_engine_finish_layout(void* engine, int64_t* out, int64_t cap, int64_t* adam_in_finish);
 CAL_API int cal_engine_p2p_adam(void* engine, void* stream);
 /* the 3-term loss of train_causal.py:176-183 on log-probabilities logp [3,B,C] (heads c, o, co) and labels y [B]:
  * out [4] = {loss, c_loss, o_loss, co_loss}; dlogp [3,B,C] (or null) = d loss / d logp, the input of cal_engine_backward_from.

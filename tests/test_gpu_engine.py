@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from oracle import cal_oracle as O
+from tests import adam_oracle as AO
 from tests.helpers import GOLDEN, ref_batch
 
 pytestmark = pytest.mark.gpu
@@ -611,14 +612,20 @@ def test_one_launch_readout_and_in_kernel_adam_equal_the_separate_launches():
                 else:
                     os.environ[k] = v
         out = []
-        for _ in range(2):
+        for it in range(2):
+            before = AO.snapshot(eng)
             stats = eng.train_step(bd, perm, adam=True).cpu().numpy().copy()
             out.append((stats, eng.buffer("logp", 3 * 96 * 4).cpu().numpy().copy()))
+            # each run obeys the Adam contract against ITS OWN read-back gradient and moments, on every element of the flat
+            # buffers (tests/adam_oracle.py) -- the two runs' parameters (p0, p1) cannot be compared with each other more
+            # closely than their gradients, which differ by the summation order of the whole step
+            AO.check_step(eng, before, it + 1, 0.9, 0.999, 1e-8, 0.0, 1.0, label=(sorted(env), it))
         runs.append((out, {k: p.detach().cpu().numpy().copy() for k, p in m.named_parameters()},
                      {k: p.grad.detach().cpu().numpy().copy() for k, p in m.named_parameters()},
                      (eng.exp_avg.cpu().numpy().copy(), eng.exp_avg_sq.cpu().numpy().copy(), float(eng.step_count.item()))))
         eng.check_status()
     (o0, p0, g0, m0), (o1, p1, g1, m1) = runs
+    assert all(np.isfinite(p0[k]).all() and np.isfinite(p1[k]).all() and p0[k].shape == p1[k].shape for k in p0)
     # step 1 differs by the summation order of the logits only; step 2 starts from parameters that went through Adam at
     # lr = 1e-2, where the sign of a ~1e-8 gradient is rounding noise (the golden-fixture test masks those the same way)
     for it, ((s0, l0), (s1, l1)) in enumerate(zip(o0, o1)):

@@ -21,7 +21,7 @@ def test_header_parses_and_library_exports_every_symbol():
     protos = _lib.parse_header()
     assert len(protos) >= 20
     for must in ("cal_plan_build", "cal_spmm_fwd", "cal_gcn_norm_bwd", "cal_edge_att_fwd",
-                 "cal_node_att_split_bwd", "cal_add_pool_fwd", "cal_gat_fwd", "cal_gat_bwd"):
+                 "cal_node_att_split_bwd", "cal_add_pool_fwd", "cal_gat_fwd", "cal_gat_bwd", "cal_engine_finish_layout"):
         assert must in protos
     h = _lib.lib()          # raises AttributeError if a declared symbol is not exported
     assert h.cal_version() >= 100
