@@ -9,6 +9,8 @@ __version__ = "0.1.0"
 _MASKOPT = ("LearnedMask", "MaskOptimizer", "learn_mask", "mask_agreement")
 _PGEXPLAIN = ("EdgeExplainer", "ExplainerTrainer", "ParametricMask", "fit_explainer", "explain_edges", "explainer_agreement",
               "eval_explainer")
+_MOTIF = ("MotifMatch", "MotifPatterns", "motif_match", "automorphisms", "contains", "isomorphic", "motif_census",
+          "explanation_motifs", "eval_explanation_motifs")
 
 
 def __getattr__(name):
@@ -20,4 +22,7 @@ def __getattr__(name):
     if name in _PGEXPLAIN:                                    # the parametric edge explainer (cal_amd/pgexplain.py), likewise
         from . import pgexplain
         return getattr(pgexplain, name)
+    if name in _MOTIF:                                        # exact motif matching (cal_amd/motif.py), likewise
+        from . import motif
+        return getattr(motif, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -1877,3 +1877,205 @@ HOST_EXPORT int cal_wl_match(const int64_t* colors_a, int64_t stride_a, int64_t 
     }
     return 0;
 }
+
+// ---- exact motif matching (cal_amd/csrc/motif.hip; cal_amd/motif.py): the same plan, roots, steps and key, graph by graph.
+namespace {
+constexpr int kMotifN = CAL_MOTIF_MAX_NODES, kMotifK = CAL_MOTIF_MAX_PATTERN;
+
+struct MotifPlan {
+    int k, pi[kMotifK], parent[kMotifK];
+    unsigned padj[kMotifK];     // by position: bit j set iff pi[d] and pi[j] are adjacent
+    int64_t lo, edges;
+};
+
+// A pattern's plan from its columns; false: no node, too many nodes or not connected.
+bool motif_plan(const int64_t* ei, int64_t PE, int64_t elo, int64_t ehi, int64_t nlo, int64_t k, MotifPlan& q) {
+    if (k < 1 || k > kMotifK) return false;
+    unsigned adj[kMotifK] = {};
+    for (int64_t e = elo; e < ehi; ++e) {
+        const int64_t u = ei[e] - nlo, v = ei[PE + e] - nlo;
+        if (u < 0 || u >= k || v < 0 || v >= k || u == v) continue;
+        adj[u] |= 1u << v;
+        adj[v] |= 1u << u;
+    }
+    unsigned placed = 0;
+    q.edges = 0;
+    for (int d = 0; d < k; ++d) {
+        int bestn = -1, bests = -1;
+        for (int i = 0; i < k; ++i) {
+            if (placed >> i & 1u) continue;
+            const int s = __builtin_popcount(d ? adj[i] & placed : adj[i]);
+            if (s > bests) {
+                bests = s;
+                bestn = i;
+            }
+        }
+        if (d && bests == 0) return false;                            // not connected
+        q.pi[d] = bestn;
+        placed |= 1u << bestn;
+        q.edges += __builtin_popcount(adj[d]);
+    }
+    for (int d = 0; d < k; ++d) {
+        q.padj[d] = 0;
+        q.parent[d] = -1;
+        for (int j = 0; j < k; ++j)
+            if (adj[q.pi[d]] >> q.pi[j] & 1u) {
+                q.padj[d] |= 1u << j;
+                if (q.parent[d] < 0 && j < d) q.parent[d] = j;
+            }
+    }
+    q.k = (int)k;
+    q.lo = nlo;
+    q.edges /= 2;
+    return true;
+}
+
+struct MotifGraph {
+    int n;
+    uint64_t adj[kMotifN][4];
+    const int64_t* lab;         // the graph's labels or null
+    bool has(int a, int b) const { return (adj[a][b >> 6] >> (b & 63)) & 1ull; }
+    int next(int a, int s) const {                                    // the lowest neighbour of a at or above s; 256: none
+        for (int w = s >> 6; w < 4; ++w) {
+            uint64_t m = adj[a][w];
+            if (w == (s >> 6)) m &= ~0ull << (s & 63);
+            if (m) return w * 64 + __builtin_ctzll(m);
+        }
+        return kMotifN;
+    }
+};
+
+inline uint64_t motif_key(const MotifPlan& q, const int* img) {
+    uint64_t key = q.k < kMotifK ? ~0ull >> (8 * q.k) : 0ull;
+    for (int d = 0; d < q.k; ++d) key |= (uint64_t)img[d] << (56 - 8 * q.pi[d]);
+    return key;
+}
+
+// one pattern in one graph -> count, truncated roots, the smallest key
+void motif_search(const MotifGraph& G, const MotifPlan& q, const int64_t* plab, int induced, uint64_t budget, uint64_t& cnt,
+                  uint64_t& trc, uint64_t& best) {
+    cnt = trc = 0;
+    best = ~0ull;
+    const int k = q.k, n = G.n;
+    auto label_ok = [&](int v, int d) { return !G.lab || G.lab[v] == plab[q.lo + q.pi[d]]; };
+    int img[kMotifK], cur[kMotifK];
+    if (k == 1) {
+        for (int v = 0; v < n; ++v)
+            if (label_ok(v, 0)) {
+                ++cnt;
+                img[0] = v;
+                best = std::min(best, motif_key(q, img));
+            }
+        return;
+    }
+    for (int u = 0; u < n; ++u)
+        for (int w = G.next(u, 0); w < kMotifN; w = G.next(u, w + 1)) {
+            if (!label_ok(u, 0) || !label_ok(w, 1)) continue;
+            img[0] = u;
+            img[1] = w;
+            if (k == 2) {
+                ++cnt;
+                best = std::min(best, motif_key(q, img));
+                continue;
+            }
+            uint64_t steps = 0;
+            int d = 2;
+            cur[2] = 0;
+            for (;;) {
+                const int v = G.next(img[q.parent[d]], cur[d]);
+                if (v >= kMotifN) {
+                    if (d == 2) break;
+                    --d;
+                    continue;
+                }
+                if (steps == budget) {
+                    ++trc;
+                    break;
+                }
+                ++steps;
+                cur[d] = v + 1;
+                bool ok = label_ok(v, d);
+                for (int j = 0; j < d && ok; ++j) {
+                    const bool a = G.has(v, img[j]);
+                    ok = img[j] != v && ((q.padj[d] >> j & 1u) ? a : !(induced && a));
+                }
+                if (!ok) continue;
+                img[d] = v;
+                if (d == k - 1) {
+                    ++cnt;
+                    best = std::min(best, motif_key(q, img));
+                } else {
+                    ++d;
+                    cur[d] = 0;
+                }
+            }
+        }
+}
+}  // namespace
+
+HOST_EXPORT int cal_motif_match(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                                int64_t B, const int64_t* labels, const int64_t* pat_edge_index, int64_t PE, int64_t PN,
+                                const int64_t* pat_ptr, const int64_t* pat_edge_ptr, int64_t P, const int64_t* pat_labels,
+                                int induced, int64_t budget, int64_t* count, int64_t* truncated, int32_t* first,
+                                int64_t* tgt_edges, int64_t* pat_edges, int64_t* totals, void*) {
+    HOST_REQUIRE(E >= 0 && N >= 0 && B >= 0 && PE >= 0 && PN >= 0 && P >= 0, "E, N, B, PE, PN, P must be >= 0");
+    HOST_REQUIRE(induced == 0 || induced == 1, "induced must be 0 or 1");
+    HOST_REQUIRE(budget >= 0, "budget must be >= 0");
+    HOST_REQUIRE(P <= CAL_MOTIF_MAX_PATTERNS, "more than CAL_MOTIF_MAX_PATTERNS patterns");
+    HOST_REQUIRE((labels == nullptr) == (pat_labels == nullptr) || N == 0 || PN == 0, "labels and pat_labels go together");
+    HOST_REQUIRE(totals, "totals is null");
+    HOST_REQUIRE(P == 0 || (pat_ptr && pat_edge_ptr), "pat_ptr / pat_edge_ptr are null");
+    HOST_REQUIRE(PE == 0 || pat_edge_index, "pat_edge_index is null");
+    std::vector<MotifPlan> plan((size_t)P);
+    for (int64_t p = 0; p < P; ++p) {
+        const int64_t nlo = pat_ptr[p], nhi = pat_ptr[p + 1], elo = pat_edge_ptr[p], ehi = pat_edge_ptr[p + 1];
+        HOST_REQUIRE(nlo >= 0 && nlo <= nhi && nhi <= PN && elo >= 0 && elo <= ehi && ehi <= PE, "pat_ptr / pat_edge_ptr are malformed");
+        HOST_REQUIRE(motif_plan(pat_edge_index, PE, elo, ehi, nlo, nhi - nlo, plan[(size_t)p]),
+                     "a pattern must be connected and have 1 to CAL_MOTIF_MAX_PATTERN nodes");
+    }
+    totals[0] = 0;
+    if (B == 0 || P == 0) return 0;
+    HOST_REQUIRE(ptr && edge_ptr, "ptr / edge_ptr are null");
+    HOST_REQUIRE(E == 0 || edge_index, "edge_index is null");
+    HOST_REQUIRE(count && truncated && first && tgt_edges && pat_edges, "an output is null");
+    const bool labelled = labels && pat_labels;
+    for (int64_t p = 0; p < P; ++p) pat_edges[p] = plan[(size_t)p].edges;
+    int64_t ignored = 0;
+#pragma omp parallel for schedule(dynamic, 1) reduction(+ : ignored)
+    for (int64_t g = 0; g < B; ++g) {
+        int64_t nlo, nhi, elo, ehi;
+        seg_clamp(ptr, g, N, nlo, nhi);
+        seg_clamp(edge_ptr, g, E, elo, ehi);
+        const int64_t n = nhi - nlo;
+        const bool skip = n > kMotifN;
+        std::vector<MotifGraph> box(1);
+        MotifGraph& G = box[0];
+        G.n = skip ? 0 : (int)n;
+        G.lab = labelled ? labels + nlo : nullptr;
+        memset(G.adj, 0, sizeof(G.adj));
+        for (int64_t e = elo; e < ehi; ++e) {
+            const int64_t u = edge_index[e] - nlo, v = edge_index[E + e] - nlo;
+            if (!(u >= 0 && u < n && v >= 0 && v < n)) {
+                ++ignored;
+            } else if (!skip && u != v) {
+                G.adj[u][v >> 6] |= 1ull << (v & 63);
+                G.adj[v][u >> 6] |= 1ull << (u & 63);
+            }
+        }
+        int64_t deg = 0;
+        for (int v = 0; v < G.n; ++v)
+            for (int w = 0; w < 4; ++w) deg += __builtin_popcountll(G.adj[v][w]);
+        tgt_edges[g] = skip ? -1 : deg / 2;
+        for (int64_t p = 0; p < P; ++p) {
+            const MotifPlan& q = plan[(size_t)p];
+            uint64_t cnt = 0, trc = 0, best = ~0ull;
+            if (!skip) motif_search(G, q, pat_labels, induced, (uint64_t)budget, cnt, trc, best);
+            count[g * P + p] = skip ? -1 : (int64_t)cnt;
+            truncated[g * P + p] = (int64_t)trc;
+            for (int i = 0; i < kMotifK; ++i)
+                first[(g * P + p) * kMotifK + i] = cnt && i < q.k ? (int32_t)((best >> (56 - 8 * i)) & 0xFF) : -1;
+        }
+    }
+    totals[0] = ignored;
+    return 0;
+}

@@ -313,6 +313,11 @@ class _CausalBase(torch.nn.Module):
         from .wl import explanation_census
         return explanation_census(self, data, **kw)
 
+    def explanation_motifs(self, data, **kw):
+        """``cal_amd.motif.explanation_motifs(self, data, **kw)``: the prototypes every graph's causal explanation contains or is."""
+        from .motif import explanation_motifs
+        return explanation_motifs(self, data, **kw)
+
     def explain(self, data, **kw):
         """``cal_amd.explain.explain(self, data, **kw)``: per-graph top-k causal subgraphs of ``data``."""
         from .explain import explain

@@ -714,6 +714,50 @@ CAL_API int cal_wl_match(const int64_t* colors_a, int64_t stride_a, int64_t Na, 
                          const int64_t* colors_p, int64_t stride_p, int64_t Np, const int64_t* ptr_p, int64_t P, int64_t T,
                          int64_t max_nodes_a, int64_t* K, int64_t* self_a, void* stream);
 
+/* ---- exact motif matching: the embeddings of small connected patterns in every graph of a batch (cal_amd/motif.py
+ * motif_match; what 1-WL cannot tell: does an explanation CONTAIN the motif, IS it the motif, WHERE does the motif sit) ----
+ * The target batch is edge_index [2, E] int64, ptr / edge_ptr [B+1] int64 as in cal_wl_refine, on the device (the host library:
+ * host memory), with optional labels int64 [N].  The pattern batch of P graphs has the same layout -- pat_edge_index [2, PE],
+ * pat_ptr / pat_edge_ptr [P+1] -- but lives in HOST memory in both libraries: the launcher reads it, works out every pattern's
+ * match order and passes the plans to the kernel by value, so the call neither copies nor synchronises.  pat_labels int64 [PN]
+ * lies where labels lies.  labels and pat_labels are both null (no labels) or both given.
+ *   Both sides are read as SIMPLE UNDIRECTED graphs: nodes u != w of a graph are adjacent iff a column (u, w) or (w, u) exists
+ *   with both endpoints inside the graph's node range.  Self loops and duplicate columns add nothing.  A target column with an
+ *   endpoint outside its graph is ignored and counted in totals[0] (summed over the graphs, larger ones included); such a
+ *   pattern column is ignored.
+ *   A pattern has 1 .. CAL_MOTIF_MAX_PATTERN nodes and is connected, and P <= CAL_MOTIF_MAX_PATTERNS (the plans travel as
+ *   kernel arguments): otherwise the call returns an error and launches nothing.  A target graph of more than
+ *   CAL_MOTIF_MAX_NODES nodes is skipped: count = -1, truncated = 0, first = -1, tgt_edges = -1.
+ *   count[g, p] = the number of injective maps f: V(p) -> V(g) such that labels[f(i)] == pat_labels[i] (with labels), adjacent
+ *   pattern nodes have adjacent images and, with induced = 1, non-adjacent pattern nodes have non-adjacent images.  So the count
+ *   of a pattern in itself with induced = 1 is |Aut(p)|, and count / |Aut(p)| the number of distinct occurrences.
+ *   Match order (positions 0 .. k-1): pi[0] is the pattern node of the largest degree, the lowest id on ties; every next node
+ *   is the unplaced node with the most placed neighbours, the lowest id on ties; the PARENT of position d >= 1 is the earliest
+ *   position whose node is adjacent to pi[d].
+ *   Roots: a root is an ordered pair (u, w) of adjacent target nodes, the images of pi[0] and pi[1]; both labels are checked at
+ *   the root.  A one-node pattern has no roots: its count is the number of label-compatible nodes.
+ *   Steps: below a root, position d = 2 .. k-1 tries the neighbours v of the parent's image in ascending id, depth first.
+ *   Every v tried costs one step, counted BEFORE any filter (v already used, its label, adjacency / non-adjacency to the images
+ *   of the positions before d).  A root that would take step budget + 1 stops; the embeddings it found before still count.
+ *   truncated[g, p] = the number of roots that stopped.  budget >= 0.
+ *   first[g, p, i] = the image of pattern node i in the lexicographically smallest embedding found (compared as
+ *   (f(0), f(1), ..)), a local id of graph g; -1 where there is none and for i >= k.  int32 [B, P, CAL_MOTIF_MAX_PATTERN].
+ *   tgt_edges int64 [B] / pat_edges int64 [P]: the numbers of adjacent unordered pairs.  count, truncated int64 [B, P];
+ *   totals int64 [1].  Every output is uniquely determined; the host library and a plain restatement agree bit for bit.
+ *   A memset of totals and ONE launch on `stream`, one workgroup per target graph: the adjacency as a 256 x 256 bit matrix in
+ *   LDS (built with integer OR-atomics, used for all P patterns), the roots dealt to the lanes, every lane's depth-first search
+ *   in registers, integer sums and an unsigned 64-bit minimum (the embedding as eight bytes, pattern node 0 on top) over the
+ *   workgroup.  No floating point, no read-back, no ws.  B = 0 or P = 0 launches nothing (pat_edges is then not written either:
+ *   workgroup 0 writes it).  N = 0 and E = 0 are legal. */
+#define CAL_MOTIF_MAX_PATTERN 8
+#define CAL_MOTIF_MAX_NODES 256
+#define CAL_MOTIF_MAX_PATTERNS 64
+CAL_API int cal_motif_match(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                            int64_t B, const int64_t* labels, const int64_t* pat_edge_index, int64_t PE, int64_t PN,
+                            const int64_t* pat_ptr, const int64_t* pat_edge_ptr, int64_t P, const int64_t* pat_labels,
+                            int induced, int64_t budget, int64_t* count, int64_t* truncated, int32_t* first,
+                            int64_t* tgt_edges, int64_t* pat_edges, int64_t* totals, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
