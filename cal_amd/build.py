@@ -62,12 +62,12 @@ def build_host(force: bool = False, verbose: bool = True) -> str:
     """libcalhost.so: the plain-C++ HOST implementation of the operator-level entry points (same symbols; g++, no HIP)."""
     os.makedirs(LIBDIR, exist_ok=True)
     hdr = os.path.join(os.path.dirname(HERE), "include", "cal_hip.h")
-    if force or _needs(HOST_SRC, HOST_LIB, [hdr]):
+    if force or _needs(HOST_SRC, HOST_LIB, [hdr, os.path.join(CSRC, "rules.hpp")]):
         cxx = shutil.which("g++") or shutil.which("c++")
         if not cxx:
             raise RuntimeError("g++ not found: libcalhost.so cannot be built")
         cmd = [cxx, "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fopenmp", "-Wall",
-               "-I", os.path.join(os.path.dirname(HERE), "include"), HOST_SRC, "-o", HOST_LIB]
+               "-I", os.path.join(os.path.dirname(HERE), "include"), "-I", CSRC, HOST_SRC, "-o", HOST_LIB]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("host build failed:\n%s\n%s" % (r.stdout, r.stderr))

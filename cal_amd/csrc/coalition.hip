@@ -48,42 +48,7 @@ struct CoArgs {
     int ticket, nblk;
 };
 
-// replica r: its graph's node range [nlo, nlo + nn) and column range [elo, elo + em) (all zero without a graph), its key row
-// (null: everything stays) and threshold.  In mode 1 a graph with more nodes than the map's row length has no replica either.
-struct Rep {
-    int64_t nlo, nn, elo, em, th;
-    const int32_t* row;
-};
-
-__device__ __forceinline__ Rep replica(const CoArgs& a, int64_t r) {
-    Rep q{0, 0, 0, 0, 0, nullptr};
-    const int64_t g = a.rg[r];
-    if (g < 0 || g >= a.B) return q;
-    seg_clamp(a.ptr, g, a.N, q.nlo, q.nn);
-    seg_clamp(a.eptr, g, a.E, q.elo, q.em);
-    if (a.mode == 1 && q.nn > a.mx) {
-        q.nlo = q.nn = q.elo = q.em = 0;
-        return q;
-    }
-    const int64_t k = a.rrow[r];
-    if (k >= 0 && k < a.K) q.row = a.key + k * a.M;
-    q.th = a.rth[r];
-    return q;
-}
-
-// element e (a column in mode 0, a node in mode 1; inside [0, M)) stays in the replica
-__device__ __forceinline__ bool elem_stays(const CoArgs& a, const Rep& q, int64_t e) {
-    if (!q.row) return true;
-    const int64_t k = q.row[e];
-    return a.invert ? k >= q.th : k < q.th;
-}
-
-// column e of the replica's graph stays
-__device__ __forceinline__ bool col_stays(const CoArgs& a, const Rep& q, int64_t e) {
-    const int64_t u = a.ei[e], v = a.ei[a.E + e];
-    if (!(u >= q.nlo && u < q.nlo + q.nn && v >= q.nlo && v < q.nlo + q.nn)) return false;
-    return a.mode == 0 ? elem_stays(a, q, e) : elem_stays(a, q, u) && elem_stays(a, q, v);
-}
+// (CoRep, co_replica, elem_stays, col_stays: rules.hpp)
 
 // grid R, NT threads
 template <int NT>
@@ -92,9 +57,9 @@ __global__ void __launch_bounds__(NT) k_coalition_count(CoArgs a) {
     __shared__ int wcnt[NT / 64];
     __shared__ int last;
     const int64_t r = blockIdx.x, R = a.R;
-    const Rep q = replica(a, r);
+    const CoRep q = co_replica(a, r);
     int64_t nodes = q.nn;
-    if (a.mode == 1) {                                            // the map row: q.nn <= a.mx (replica()), uniform over the workgroup
+    if (a.mode == 1) {                                            // the map row: q.nn <= a.mx (co_replica()), uniform over the workgroup
         int32_t* row = a.map + r * a.mx;
         nodes = 0;
         for (int64_t base = 0; base < q.nn; base += NT) {
@@ -124,7 +89,7 @@ __global__ void __launch_bounds__(256) k_coalition_write(CoArgs a, int node_bloc
         write_nodes(
             a.out, a.ptr_out, a.R, -1, src,
             [&](int64_t r, int64_t l) -> int64_t {
-                const Rep q = replica(a, r);
+                const CoRep q = co_replica(a, r);
                 if (a.mode == 1 && q.nn > 0) l = owner(a.map + r * a.mx, q.nn, l);
                 return l < q.nn ? q.nlo + l : -1;
             },
@@ -132,7 +97,7 @@ __global__ void __launch_bounds__(256) k_coalition_write(CoArgs a, int node_bloc
         return;
     }
     const int64_t r = (int64_t)((int)blockIdx.x - node_blocks);
-    const Rep q = replica(a, r);
+    const CoRep q = co_replica(a, r);
     const int32_t* row = a.mode == 1 ? a.map + r * a.mx : nullptr;
     write_cols(
         a.out, a.ptr_out, a.eptr_out, r, a.ei, a.E, q.elo, q.em, wcnt,

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rules.hpp"
+
 #define CAL_EXPORT extern "C" __attribute__((visibility("default")))
 
 namespace cal {
@@ -147,15 +149,9 @@ template <> struct Vec<1> {
 };
 
 // Random-intervention permutation (model.py:147-152, `random.shuffle(range(num))`) drawn on the device: graph b gets
-// the key splitmix64(seed, *counter, b), the permutation is the argsort of the keys (rank sort in LDS, one
+// the key splitmix64(seed, *counter, b) (rules.hpp), the permutation is the argsort of the keys (rank sort in LDS, one
 // workgroup of NT threads, B <= CAP); *counter is advanced, so a replayed hipGraph draws a fresh permutation every
 // step.  Shared by cal_randperm (collate.hip, stand-alone) and the step engine's first kernel.
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 template <int NT>
 __device__ __forceinline__ void randperm_block(int64_t* __restrict__ perm, int B, unsigned long long seed,
                                                unsigned long long* __restrict__ counter, unsigned long long* key, int* idx) {

@@ -21,27 +21,8 @@ namespace {
 
 constexpr int kMlpNT = 256;
 
-// what a player's z gives, all of it finite for any finite z (maskopt.hip's logit_terms): with e = exp(-|z|) in (0, 1]
-//   m = sigma(z),  dm = m (1 - m),  H(m) = softplus(z) - z m = log1p(e) + |z| e / (1 + e)
-struct Gate { float m, dm, ent; };
-__device__ __forceinline__ Gate gate_terms(float z) {
-    const float a = fabsf(z), e = expf(-a), r = 1.f / (1.f + e);
-    Gate o;
-    o.m = z >= 0.f ? r : e * r;
-    o.dm = e * r * r;
-    o.ent = log1pf(e) + a * (e * r);
-    return o;
-}
-
-// column e of a player: in range, with both end nodes in range
-__device__ __forceinline__ bool column_ok(int64_t e, const int32_t* __restrict__ row32, const int32_t* __restrict__ col32, int64_t E,
-                                          int64_t N, int& u, int& v) {
-    u = v = 0;
-    if (e < 0 || e >= E) return false;
-    u = row32[e];
-    v = col32[e];
-    return u >= 0 && u < N && v >= 0 && v < N;
-}
+// (what a player's z gives -- m = sigma(z), dm = m (1 - m), H(m) -- is logit_terms of rules.hpp, as in maskopt.hip;
+// column_ok, mlp_rows_per_block and mlp_sizes_ok are there too)
 
 // A group of G lanes serves one player, 256 / G players per pass of the workgroup over its graph.
 template <int VEC, int G>
@@ -98,7 +79,7 @@ __global__ void __launch_bounds__(kMlpNT) k_edge_mlp_fwd(const float* __restrict
                     noise = logf(u) - logf(1.f - u);
                 }
                 z = (noise + om) / tau;
-                const Gate q = gate_terms(z);
+                const Logit q = logit_terms(z);
                 mask[rep[p]] = q.m;
                 if (t_ok) mask[mate[p]] = q.m;
                 s_size += (double)q.m;
@@ -138,7 +119,7 @@ __global__ void __launch_bounds__(kMlpNT) k_edge_mlp_coef(const int32_t* __restr
         if (!column_ok(r, row32, col32, E, N, u, v)) continue;
         const bool t_ok = column_ok(t, row32, col32, E, N, u, v);
         const float zz = z[p];
-        const Gate q = gate_terms(zz);
+        const Logit q = logit_terms(zz);
         const float g = ((gmask[r] + (t_ok ? gmask[t] : 0.f) + (l_size - ent_w * zz)) * q.dm) / tau;
         if (t_ok) {
             c[r] = 0.5f * g;
@@ -261,16 +242,6 @@ __global__ void __launch_bounds__(256) k_edge_mlp_finish(const float* __restrict
     if ((threadIdx.x >> 4) != 0 || c > Hd) return;
     if (c < Hd) dw2[c] = s;
     else db2[0] = s;
-}
-
-inline int mlp_rows_per_block(int64_t N) {
-    const int64_t rpb = (N + 511) / 512;
-    return (int)(rpb < 16 ? 16 : rpb);
-}
-
-inline bool mlp_sizes_ok(int64_t N, int64_t E, int64_t Hd, int64_t B, int64_t P) {
-    return N >= 0 && E >= 0 && B >= 0 && P >= 0 && N < (1ll << 31) && E < (1ll << 31) && B < (1ll << 31) && P < (1ll << 31) &&
-           Hd >= 4 && Hd <= 256 && Hd % 4 == 0;
 }
 
 }  // namespace

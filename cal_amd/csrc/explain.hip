@@ -47,12 +47,6 @@ struct RankArgs {
     const int64_t* seg_len;   // or null: segment g is [seg_ptr[g], seg_ptr[g] + seg_len[g]) (compacted rows of the pair ranking)
 };
 
-__device__ __forceinline__ uint32_t score_key(float s) {
-    if (s != s) return 1u;                                     // NaN: below every number
-    const uint32_t u = s == 0.f ? 0u : __float_as_uint(s);     // -0 ranks as +0
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 __device__ __forceinline__ void seg_range(const RankArgs& a, int64_t g, int64_t& lo, int64_t& m) {
     seg_clamp(a.seg_ptr, g, a.M, lo, m);
     if (a.seg_len) {                                           // compacted rows: [lo, lo + seg_len[g]), clamped alike
@@ -61,20 +55,7 @@ __device__ __forceinline__ void seg_range(const RankArgs& a, int64_t g, int64_t&
     }
 }
 
-// k_g of a segment of m elements with P positives (k >= 0: top k; -1: ceil(ratio m); -2: P)
-__device__ __forceinline__ int64_t sel_count(int64_t m, int64_t P, double ratio, int64_t k) {
-    if (k >= 0) return k < m ? k : m;
-    if (k == -1) {
-        const double c = ceil(ratio * (double)m);
-        return c < (double)m ? (int64_t)c : m;
-    }
-    return P;
-}
-
-__device__ __forceinline__ double seg_auc(int64_t m, int64_t P, int64_t r2) {
-    if (P <= 0 || P >= m) return __builtin_nan("");
-    return ((double)r2 * 0.5 - (double)P * (double)(P + 1) * 0.5) / ((double)P * (double)(m - P));
-}
+// (score_key, sel_count -- the k_g of a segment -- and seg_auc: rules.hpp)
 
 __device__ __forceinline__ void put_metrics(double* row, int64_t kg, int64_t hits, int64_t P, double auc) {
     row[0] = (double)kg; row[1] = (double)hits; row[2] = (double)P; row[3] = auc;

@@ -25,7 +25,6 @@ __device__ __forceinline__ int xcd_block() {
     return (int)blockIdx.x < 8 * per ? (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
 }
 
-__device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : slope * v; }
 constexpr float GAT_LOG2E = 1.4426950408889634f;      // softmax weights as base-2 exponentials (v_exp_f32) of log2(e)-scaled logits
 
 // sum over the 16 lanes of a DPP row (every lane gets the total): four v_add_f32 with row_ror modifiers instead of four

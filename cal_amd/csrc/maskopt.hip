@@ -18,18 +18,7 @@ namespace {
 
 constexpr int kMaskNT = 256;
 
-// what one player's logit gives, all of it finite for any finite theta: with z = exp(-|theta|) in (0, 1]
-//   m = sigma(theta),  dm = m (1 - m) = z / (1 + z)^2,  H(m) = softplus(theta) - theta m = log1p(z) + |theta| z / (1 + z)
-// (no difference of large numbers, no logarithm of m)
-struct Logit { float m, dm, ent; };
-__device__ __forceinline__ Logit logit_terms(float th) {
-    const float a = fabsf(th), z = expf(-a), r = 1.f / (1.f + z);
-    Logit o;
-    o.m = th >= 0.f ? r : z * r;
-    o.dm = z * r * r;
-    o.ent = log1pf(z) + a * (z * r);
-    return o;
-}
+// (Logit, logit_terms -- what one player's logit gives: rules.hpp)
 
 // step_size = lr / (1 - beta1^step), rsq2 = 1 / sqrt(1 - beta2^step): taken once on the host, in double
 __global__ void __launch_bounds__(kMaskNT) k_mask_step(const int64_t* __restrict__ pptr, const int32_t* __restrict__ rep,

@@ -38,20 +38,8 @@ namespace {
 typedef unsigned long long u64;
 
 constexpr int kMotifNT = 256;                        // threads of a workgroup
-constexpr int kMotifN = CAL_MOTIF_MAX_NODES;         // nodes of a target graph, rows of the bit matrix
-constexpr int kMotifK = CAL_MOTIF_MAX_PATTERN;
 constexpr int kMotifP = CAL_MOTIF_MAX_PATTERNS;
-static_assert(kMotifN == 256 && kMotifK == 8, "a node id is one byte of the key, a row four 64-bit words");
-
-// one pattern, planned.  Positions are the places of the match order.
-struct MotifPlan {
-    u64 order;          // byte d: pi[d], the pattern node of position d
-    u64 padj;           // byte d: bit j set iff pi[d] and pi[j] are adjacent
-    uint32_t parent;    // bits [3d, 3d + 3): the parent position of position d >= 1
-    int32_t k;          // nodes
-    int64_t lo;         // first node of the pattern in pat_labels
-    int64_t edges;      // adjacent unordered pairs
-};
+// (kMotifN, kMotifK, MotifPlan -- one pattern, planned -- and motif_plan, the planner the launcher runs on the host: rules.hpp)
 
 struct MotifArgs {
     const int64_t* ei;         // [2, E]
@@ -336,52 +324,6 @@ __global__ void __launch_bounds__(kMotifNT) k_motif_match(MotifArgs a) {
         for (int i = 0; i < kMotifK; ++i)
             a.first[(g * P + p) * kMotifK + i] = c && i < plan[p].k ? (int32_t)((b >> (56 - 8 * i)) & 0xFF) : -1;
     }
-}
-
-// A pattern's plan from its columns; false: no node, too many nodes or not connected.
-bool motif_plan(const int64_t* ei, int64_t PE, int64_t elo, int64_t ehi, int64_t nlo, int64_t k, MotifPlan& q) {
-    if (k < 1 || k > kMotifK) return false;
-    unsigned adj[kMotifK] = {};
-    for (int64_t e = elo; e < ehi; ++e) {
-        const int64_t u = ei[e] - nlo, v = ei[PE + e] - nlo;
-        if (u < 0 || u >= k || v < 0 || v >= k || u == v) continue;
-        adj[u] |= 1u << v;
-        adj[v] |= 1u << u;
-    }
-    int pi[kMotifK], edges = 0;
-    unsigned placed = 0;
-    for (int d = 0; d < k; ++d) {
-        int bestn = -1, bests = -1;
-        for (int i = 0; i < k; ++i) {
-            if (placed >> i & 1u) continue;
-            const int s = __builtin_popcount(d ? adj[i] & placed : adj[i]);
-            if (s > bests) {
-                bests = s;
-                bestn = i;
-            }
-        }
-        if (d && bests == 0) return false;                            // not connected
-        pi[d] = bestn;
-        placed |= 1u << bestn;
-    }
-    q.order = 0;
-    q.padj = 0;
-    q.parent = 0;
-    for (int d = 0; d < k; ++d) {
-        q.order |= (u64)pi[d] << (8 * d);
-        int par = -1;
-        for (int j = 0; j < k; ++j)
-            if (adj[pi[d]] >> pi[j] & 1u) {
-                q.padj |= 1ull << (8 * d + j);
-                if (par < 0 && j < d) par = j;
-            }
-        if (d) q.parent |= (uint32_t)par << (3 * d);
-        edges += __builtin_popcount(adj[d]);
-    }
-    q.k = (int32_t)k;
-    q.lo = nlo;
-    q.edges = edges / 2;
-    return true;
 }
 
 }  // namespace

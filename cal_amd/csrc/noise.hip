@@ -33,7 +33,6 @@
 namespace cal {
 namespace {
 
-constexpr unsigned long long kNoiseDel = CAL_NOISE_C_DEL, kNoiseAdd = CAL_NOISE_C_ADD;
 constexpr int kNoiseSlots = 4096;          // hash set slots (64-bit keys, 32 KB of LDS)
 constexpr int kNoiseFill = 3072;           // keys it may hold: the load stays at or below 3 / 4
 constexpr int64_t kNoisePairs = (int64_t)1 << 31;   // accepted pairs ws is taken to hold, at the most
@@ -65,47 +64,7 @@ struct NoArgs {
     int ticket, nblk;
 };
 
-__device__ __forceinline__ unsigned long long noise_hash(unsigned long long s, unsigned long long i) {
-    return splitmix64(splitmix64(s) + i);
-}
-
-// replica r: its graph's node range [nlo, nlo + nn) and column range [elo, elo + em) (all zero without a graph), its seed,
-// deletion threshold and a = max(rep_add, 0)
-struct NoRep {
-    int64_t nlo, nn, elo, em, del, a;
-    unsigned long long seed;
-};
-
-__device__ __forceinline__ NoRep noise_replica(const NoArgs& a, int64_t r) {
-    NoRep q{0, 0, 0, 0, 0, 0, 0};
-    const int64_t add = a.radd[r];
-    q.a = add > 0 ? add : 0;
-    const int64_t g = a.rg[r];
-    if (g < 0 || g >= a.B) return q;
-    seg_clamp(a.ptr, g, a.N, q.nlo, q.nn);
-    seg_clamp(a.eptr, g, a.E, q.elo, q.em);
-    q.seed = (unsigned long long)a.rseed[r];
-    q.del = a.rdel[r];
-    return q;
-}
-
-// column e of the replica's graph stays: inside the node range, and a self loop or its player not deleted
-__device__ __forceinline__ bool noise_stays(const NoArgs& a, const NoRep& q, int64_t e) {
-    const int64_t u = a.ei[e], v = a.ei[a.E + e];
-    if (!(u >= q.nlo && u < q.nlo + q.nn && v >= q.nlo && v < q.nlo + q.nn)) return false;
-    if (u == v || q.del <= 0) return true;
-    int64_t rep = e;
-    if (a.twin) {                                                  // the lower column of a pair (a twin outside the segment: none)
-        const int64_t t = a.twin[e];
-        if (t >= q.elo && t < e) rep = t;
-    }
-    return !((int64_t)(noise_hash(q.seed ^ kNoiseDel, (unsigned long long)(rep - q.elo)) >> 1) < q.del);
-}
-
-// the key of the pair (u, v) of local ids of a graph of n nodes
-__device__ __forceinline__ uint64_t pair_key(bool undirected, uint64_t u, uint64_t v, uint64_t n) {
-    return undirected ? (u < v ? u * n + v : v * n + u) : u * n + v;
-}
+// (kNoiseDel, kNoiseAdd, noise_hash, NoRep, noise_replica, noise_stays, pair_key: rules.hpp)
 
 __device__ __forceinline__ unsigned slot_of(uint64_t k) { return (unsigned)(splitmix64(k) & (kNoiseSlots - 1)); }
 

@@ -44,35 +44,7 @@ struct OccArgs {
     int ticket, nblk;
 };
 
-// replica r: its graph's node range [nlo, nlo + nn) and column range [elo, elo + em) (all zero without a graph), the node
-// removed (rn) and the columns removed (c0, c1); -1 = none, which equals no id
-struct Rep {
-    int64_t nlo, nn, elo, em, rn, c0, c1;
-};
-
-__device__ __forceinline__ Rep replica(const OccArgs& a, int64_t r) {
-    Rep q{0, 0, 0, 0, -1, -1, -1};
-    const int64_t g = a.rg[r];
-    if (g < 0 || g >= a.B) return q;
-    seg_clamp(a.ptr, g, a.N, q.nlo, q.nn);
-    seg_clamp(a.eptr, g, a.E, q.elo, q.em);
-    const int64_t e = a.re[r];
-    if (a.mode == 0) {
-        if (e >= q.elo && e < q.elo + q.em) {
-            q.c0 = e;
-            if (a.twin) q.c1 = a.twin[e];                         // (a negative twin or one outside the graph meets no column)
-        }
-    } else if (e >= q.nlo && e < q.nlo + q.nn) {
-        q.rn = e;
-    }
-    return q;
-}
-
-// column e of the replica's graph stays
-__device__ __forceinline__ bool col_stays(const OccArgs& a, const Rep& q, int64_t e) {
-    const int64_t u = a.ei[e], v = a.ei[a.E + e];
-    return u >= q.nlo && u < q.nlo + q.nn && v >= q.nlo && v < q.nlo + q.nn && e != q.c0 && e != q.c1 && u != q.rn && v != q.rn;
-}
+// (OccRep, occ_replica, col_stays: rules.hpp)
 
 // grid R, NT threads
 template <int NT>
@@ -80,7 +52,7 @@ __global__ void __launch_bounds__(NT) k_occlude_count(OccArgs a) {
     __shared__ long long red[NT / 64];
     __shared__ int last;
     const int64_t r = blockIdx.x, R = a.R;
-    const Rep q = replica(a, r);
+    const OccRep q = occ_replica(a, r);
     long long c = 0;
     for (int64_t t = threadIdx.x; t < q.em; t += NT) c += col_stays(a, q, q.elo + t);
     const int64_t kept = wg_sum<NT>(c, red);
@@ -99,7 +71,7 @@ __global__ void __launch_bounds__(256) k_occlude_write(OccArgs a, int node_block
         write_nodes(
             a.out, a.ptr_out, a.R, -1, src,
             [&](int64_t r, int64_t l) -> int64_t {
-                const Rep q = replica(a, r);
+                const OccRep q = occ_replica(a, r);
                 int64_t c = q.nlo + l;
                 c += q.rn >= 0 && c >= q.rn;
                 return c < q.nlo + q.nn ? c : -1;
@@ -108,7 +80,7 @@ __global__ void __launch_bounds__(256) k_occlude_write(OccArgs a, int node_block
         return;
     }
     const int64_t r = (int64_t)((int)blockIdx.x - node_blocks);
-    const Rep q = replica(a, r);
+    const OccRep q = occ_replica(a, r);
     write_cols(
         a.out, a.ptr_out, a.eptr_out, r, a.ei, a.E, q.elo, q.em, wcnt,
         [&](int64_t e) { return col_stays(a, q, e); },
@@ -160,12 +132,6 @@ struct AgArgs {
     int64_t* part;             // ws [slots, kAgPart] (large launches)
     int large;
 };
-
-__device__ __forceinline__ int64_t ag_sel_count(int64_t n, double ratio, int64_t k) {
-    if (k >= 0) return k < n ? k : n;
-    const double c = ceil(ratio * (double)n);
-    return c < (double)n ? (int64_t)c : n;
-}
 
 // the (a, b) of element i of the batch, NaN twice when it does not take part
 __device__ __forceinline__ float2 ag_load(const AgArgs& a, int64_t i, bool& part) {

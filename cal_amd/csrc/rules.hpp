@@ -1,0 +1,354 @@
+// The rules libcalhip.so (the kernels of this directory) and libcalhost.so (csrc_host/calhost.cpp) share, each stated ONCE: the
+// hashes, keys, clamps, selection counts, plans and replica rules whose integer results the two libraries promise bit for bit.
+// A new rule of that kind goes here first; neither side keeps a copy.
+//
+// Plain C++: <math.h>, <stdint.h>, <string.h> and cal_hip.h, no HIP header.  CAL_RULE is the qualifier of every function:
+// host + device, always inlined under hipcc; `inline` under any other compiler.  The replica rules are templates over the
+// argument struct: the kernels' *Args and the host's *Src carry the same field names (ei, E, N, ptr, eptr, B, rg, ...).
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "cal_hip.h"
+
+#if defined(__HIPCC__)
+#define CAL_RULE __host__ __device__ __forceinline__
+#else
+#define CAL_RULE inline
+#endif
+
+namespace cal {
+
+// ---- hashes ----------------------------------------------------------------------------------------------------------------------
+// Random-intervention permutation (model.py:147-152, `random.shuffle(range(num))`) drawn on the device: graph b gets
+// the key splitmix64(seed, *counter, b), the permutation is the argsort of the keys (randperm_block, common.hpp).  Also the
+// hash of the noise replicas, the WL colours and the edge explainer's concrete samples.
+CAL_RULE unsigned long long splitmix64(unsigned long long x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+// 32-bit finaliser (two multiply-xorshift rounds).  Round 4: the 64-bit splitmix used before cost three 64-bit multiplies per
+// decision -- ~12 quarter-rate v_mul_lo/hi_u32, ~250 cycles per wave -- and every row needs (slots + 1) x heads of them: the
+// training-mode GAT kernels spent more VALU time hashing than on the softmax.  Keys are (slot id * K + head) < 2^32.
+CAL_RULE uint32_t mix32(uint32_t x) {
+    x ^= x >> 16; x *= 0x21F0AAADu;
+    x ^= x >> 15; x *= 0x735A2D97u;
+    x ^= x >> 15;
+    return x;
+}
+// Counter-based attention-dropout keep decision for (edge slot id, head): reproducible in the backward.
+CAL_RULE float keep_scale(uint64_t seed, int64_t id, int k, int K, float p, float inv_keep) {
+    if (p <= 0.f) return 1.f;
+    const uint32_t key = (uint32_t)(id * K + k);
+    const uint32_t r = mix32(mix32(key + (uint32_t)seed) ^ (uint32_t)(seed >> 32));
+    return ((float)r * (1.0f / 4294967296.0f)) >= p ? inv_keep : 0.f;
+}
+
+CAL_RULE float lrelu(float v, float slope) { return v > 0.f ? v : slope * v; }
+
+// what one player's logit gives, all of it finite for any finite theta: with z = exp(-|theta|) in (0, 1]
+//   m = sigma(theta),  dm = m (1 - m) = z / (1 + z)^2,  H(m) = softplus(theta) - theta m = log1p(z) + |theta| z / (1 + z)
+// (no difference of large numbers, no logarithm of m).  One text; each side compiles it under its own flags.
+struct Logit { float m, dm, ent; };
+CAL_RULE Logit logit_terms(float th) {
+    const float a = fabsf(th), z = expf(-a), r = 1.f / (1.f + z);
+    Logit o;
+    o.m = th >= 0.f ? r : z * r;
+    o.dm = z * r * r;
+    o.ent = log1pf(z) + a * (z * r);
+    return o;
+}
+
+// ---- segments and ranking --------------------------------------------------------------------------------------------------------
+// segment g of p clamped into [0, M]: [lo, lo + m); a malformed p reads nothing outside the arrays.  With hi = lo + m this is
+// lo = min(max(p[g], 0), M), hi = min(max(p[g + 1], lo), M) for every p, decreasing or out of range, and every M >= 0 (every
+// entry point requires that): lo <= M, so max(.., lo) followed by min(.., M) is the two-sided clamp below.
+CAL_RULE void seg_clamp(const int64_t* p, int64_t g, int64_t M, int64_t& lo, int64_t& m) {
+    int64_t l = p[g], h = p[g + 1];
+    l = l < 0 ? 0 : (l > M ? M : l);
+    h = h < l ? l : (h > M ? M : h);
+    lo = l;
+    m = h - l;
+}
+
+CAL_RULE uint32_t float_bits(float s) {
+    uint32_t u;
+    memcpy(&u, &s, 4);
+    return u;
+}
+// 32-bit keys that order like the scores
+CAL_RULE uint32_t score_key(float s) {
+    if (s != s) return 1u;                                     // NaN: below every number
+    const uint32_t u = s == 0.f ? 0u : float_bits(s);          // -0 ranks as +0
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// k_g of a segment of m elements with P positives (k >= 0: top k; -1: ceil(ratio m); -2: P)
+CAL_RULE int64_t sel_count(int64_t m, int64_t P, double ratio, int64_t k) {
+    if (k >= 0) return k < m ? k : m;
+    if (k == -1) {
+        const double c = ceil(ratio * (double)m);
+        return c < (double)m ? (int64_t)c : m;
+    }
+    return P;
+}
+// ... of the n elements of a segment that take part in a rank agreement (k >= 0: top k; else ceil(ratio n))
+CAL_RULE int64_t ag_sel_count(int64_t n, double ratio, int64_t k) {
+    if (k >= 0) return k < n ? k : n;
+    const double c = ceil(ratio * (double)n);
+    return c < (double)n ? (int64_t)c : n;
+}
+
+// ROC-AUC of a segment of m elements from r2 = 2 x the sum of the positives' 1-based ascending average ranks
+CAL_RULE double seg_auc(int64_t m, int64_t P, int64_t r2) {
+    if (P <= 0 || P >= m) return __builtin_nan("");
+    return ((double)r2 * 0.5 - (double)P * (double)(P + 1) * 0.5) / ((double)P * (double)(m - P));
+}
+
+// key of the column (u, v) of a graph of nn nodes, x = u - nlo, y = v - nlo its local ends: the undirected edge, then the
+// direction (rev: u > v)
+CAL_RULE uint64_t und_edge_key(uint64_t x, uint64_t y, uint64_t nn, bool rev) {
+    return (((x < y ? x : y) * nn + (x < y ? y : x)) << 1) | (uint64_t)rev;
+}
+
+// ---- the parametric edge explainer -----------------------------------------------------------------------------------------------
+// column e of a player: in range, with both end nodes in range
+CAL_RULE bool column_ok(int64_t e, const int32_t* __restrict__ row32, const int32_t* __restrict__ col32, int64_t E, int64_t N,
+                        int& u, int& v) {
+    u = v = 0;
+    if (e < 0 || e >= E) return false;
+    u = row32[e];
+    v = col32[e];
+    return u >= 0 && u < N && v >= 0 && v < N;
+}
+
+// nodes of one workgroup of the row kernel: 16 at the least, at most 512 workgroups
+CAL_RULE int mlp_rows_per_block(int64_t N) {
+    const int64_t rpb = (N + 511) / 512;
+    return (int)(rpb < 16 ? 16 : rpb);
+}
+
+CAL_RULE bool mlp_sizes_ok(int64_t N, int64_t E, int64_t Hd, int64_t B, int64_t P) {
+    return N >= 0 && E >= 0 && B >= 0 && P >= 0 && N < (1ll << 31) && E < (1ll << 31) && B < (1ll << 31) && P < (1ll << 31) &&
+           Hd >= 4 && Hd <= 256 && Hd % 4 == 0;
+}
+
+// ---- Weisfeiler-Lehman colours ---------------------------------------------------------------------------------------------------
+constexpr unsigned long long kWlInit = CAL_WL_C_INIT, kWlSelf = CAL_WL_C_SELF, kWlOut = CAL_WL_C_OUT, kWlIn = CAL_WL_C_IN,
+                             kWlNode = CAL_WL_C_NODE, kWlGraph = CAL_WL_C_GRAPH;
+
+// the next colour of a node
+CAL_RULE unsigned long long wl_next(unsigned long long c, unsigned long long so, unsigned long long si) {
+    return splitmix64(splitmix64(splitmix64(c + kWlSelf) + so) + si);
+}
+
+// ---- the batch builders: replica r -> node range [nlo, nlo + nn), column range [elo, elo + em) (all zero without a graph), and
+// which of the graph's columns / elements stay.  A: OccArgs / OccludeSrc, CoArgs / CoalitionSrc, NoArgs / NoiseSrc, Side / SpliceSide.
+
+// occlusion: the node removed (rn) and the columns removed (c0, c1); -1 = none, which equals no id
+struct OccRep {
+    int64_t nlo, nn, elo, em, rn, c0, c1;
+};
+
+template <class A>
+CAL_RULE OccRep occ_replica(const A& a, int64_t r) {
+    OccRep q{0, 0, 0, 0, -1, -1, -1};
+    const int64_t g = a.rg[r];
+    if (g < 0 || g >= a.B) return q;
+    seg_clamp(a.ptr, g, a.N, q.nlo, q.nn);
+    seg_clamp(a.eptr, g, a.E, q.elo, q.em);
+    const int64_t e = a.re[r];
+    if (a.mode == 0) {
+        if (e >= q.elo && e < q.elo + q.em) {
+            q.c0 = e;
+            if (a.twin) q.c1 = a.twin[e];                         // (a negative twin or one outside the graph meets no column)
+        }
+    } else if (e >= q.nlo && e < q.nlo + q.nn) {
+        q.rn = e;
+    }
+    return q;
+}
+
+// column e of the replica's graph stays
+template <class A>
+CAL_RULE bool col_stays(const A& a, const OccRep& q, int64_t e) {
+    const int64_t u = a.ei[e], v = a.ei[a.E + e];
+    return u >= q.nlo && u < q.nlo + q.nn && v >= q.nlo && v < q.nlo + q.nn && e != q.c0 && e != q.c1 && u != q.rn && v != q.rn;
+}
+
+// coalitions: the replica's key row (null: everything stays) and threshold.  In mode 1 a graph with more nodes than the map's row
+// length (mx) has no replica either.
+struct CoRep {
+    int64_t nlo, nn, elo, em, th;
+    const int32_t* row;
+};
+
+template <class A>
+CAL_RULE CoRep co_replica(const A& a, int64_t r) {
+    CoRep q{0, 0, 0, 0, 0, nullptr};
+    const int64_t g = a.rg[r];
+    if (g < 0 || g >= a.B) return q;
+    seg_clamp(a.ptr, g, a.N, q.nlo, q.nn);
+    seg_clamp(a.eptr, g, a.E, q.elo, q.em);
+    if (a.mode == 1 && q.nn > a.mx) {
+        q.nlo = q.nn = q.elo = q.em = 0;
+        return q;
+    }
+    const int64_t k = a.rrow[r];
+    if (k >= 0 && k < a.K) q.row = a.key + k * a.M;
+    q.th = a.rth[r];
+    return q;
+}
+
+// element e (a column in mode 0, a node in mode 1; inside [0, M)) stays in the replica
+template <class A>
+CAL_RULE bool elem_stays(const A& a, const CoRep& q, int64_t e) {
+    if (!q.row) return true;
+    const int64_t k = q.row[e];
+    return a.invert ? k >= q.th : k < q.th;
+}
+
+// column e of the replica's graph stays
+template <class A>
+CAL_RULE bool col_stays(const A& a, const CoRep& q, int64_t e) {
+    const int64_t u = a.ei[e], v = a.ei[a.E + e];
+    if (!(u >= q.nlo && u < q.nlo + q.nn && v >= q.nlo && v < q.nlo + q.nn)) return false;
+    return a.mode == 0 ? elem_stays(a, q, e) : elem_stays(a, q, u) && elem_stays(a, q, v);
+}
+
+// structural noise: H(s, i), the replica's seed, deletion threshold and a = max(rep_add, 0)
+constexpr unsigned long long kNoiseDel = CAL_NOISE_C_DEL, kNoiseAdd = CAL_NOISE_C_ADD;
+
+CAL_RULE unsigned long long noise_hash(unsigned long long s, unsigned long long i) { return splitmix64(splitmix64(s) + i); }
+
+struct NoRep {
+    int64_t nlo, nn, elo, em, del, a;
+    unsigned long long seed;
+};
+
+template <class A>
+CAL_RULE NoRep noise_replica(const A& a, int64_t r) {
+    NoRep q{0, 0, 0, 0, 0, 0, 0};
+    const int64_t add = a.radd[r];
+    q.a = add > 0 ? add : 0;
+    const int64_t g = a.rg[r];
+    if (g < 0 || g >= a.B) return q;
+    seg_clamp(a.ptr, g, a.N, q.nlo, q.nn);
+    seg_clamp(a.eptr, g, a.E, q.elo, q.em);
+    q.seed = (unsigned long long)a.rseed[r];
+    q.del = a.rdel[r];
+    return q;
+}
+
+// column e of the replica's graph stays: inside the node range, and a self loop or its player not deleted
+template <class A>
+CAL_RULE bool noise_stays(const A& a, const NoRep& q, int64_t e) {
+    const int64_t u = a.ei[e], v = a.ei[a.E + e];
+    if (!(u >= q.nlo && u < q.nlo + q.nn && v >= q.nlo && v < q.nlo + q.nn)) return false;
+    if (u == v || q.del <= 0) return true;
+    int64_t rep = e;
+    if (a.twin) {                                                  // the lower column of a pair (a twin outside the segment: none)
+        const int64_t t = a.twin[e];
+        if (t >= q.elo && t < e) rep = t;
+    }
+    return !((int64_t)(noise_hash(q.seed ^ kNoiseDel, (unsigned long long)(rep - q.elo)) >> 1) < q.del);
+}
+
+// the key of the pair (u, v) of local ids of a graph of n nodes
+CAL_RULE uint64_t pair_key(bool undirected, uint64_t u, uint64_t v, uint64_t n) {
+    return undirected ? (u < v ? u * n + v : v * n + u) : u * n + v;
+}
+
+// splice: the part of pair p on side s; all zero when absent
+template <class S>
+CAL_RULE void side_ranges(const S& s, int64_t p, int64_t& nlo, int64_t& nn, int64_t& elo, int64_t& em) {
+    const int64_t g = s.pick[p];
+    nlo = nn = elo = em = 0;
+    if (g < 0 || g >= s.B) return;
+    seg_clamp(s.ptr, g, s.N, nlo, nn);
+    seg_clamp(s.eptr, g, s.E, elo, em);
+}
+
+template <class S>
+CAL_RULE bool col_valid(const S& s, int64_t e, int64_t nlo, int64_t nn) {
+    const int64_t u = s.ei[e], v = s.ei[s.E + e];
+    return u >= nlo && u < nlo + nn && v >= nlo && v < nlo + nn;
+}
+
+// ---- exact motif matching --------------------------------------------------------------------------------------------------------
+constexpr int kMotifN = CAL_MOTIF_MAX_NODES;         // nodes of a target graph, rows of the bit matrix
+constexpr int kMotifK = CAL_MOTIF_MAX_PATTERN;
+static_assert(kMotifN == 256 && kMotifK == 8, "a node id is one byte of the key, a row four 64-bit words");
+
+// one pattern, planned.  Positions are the places of the match order.
+struct MotifPlan {
+    unsigned long long order;   // byte d: pi[d], the pattern node of position d
+    unsigned long long padj;    // byte d: bit j set iff pi[d] and pi[j] are adjacent
+    uint32_t parent;            // bits [3d, 3d + 3): the parent position of position d >= 1
+    int32_t k;                  // nodes
+    int64_t lo;                 // first node of the pattern in pat_labels
+    int64_t edges;              // adjacent unordered pairs
+};
+CAL_RULE int motif_node(const MotifPlan& q, int d) { return (int)((q.order >> (8 * d)) & 0xFF); }
+CAL_RULE unsigned motif_adj(const MotifPlan& q, int d) { return (unsigned)(q.padj >> (8 * d)) & 0xFFu; }
+CAL_RULE int motif_parent(const MotifPlan& q, int d) { return (int)(q.parent >> (3 * d)) & 7; }
+
+// A pattern's plan from its columns; false: no node, too many nodes or not connected.
+CAL_RULE bool motif_plan(const int64_t* ei, int64_t PE, int64_t elo, int64_t ehi, int64_t nlo, int64_t k, MotifPlan& q) {
+    if (k < 1 || k > kMotifK) return false;
+    unsigned adj[kMotifK] = {};
+    for (int64_t e = elo; e < ehi; ++e) {
+        const int64_t u = ei[e] - nlo, v = ei[PE + e] - nlo;
+        if (u < 0 || u >= k || v < 0 || v >= k || u == v) continue;
+        adj[u] |= 1u << v;
+        adj[v] |= 1u << u;
+    }
+    int pi[kMotifK], edges = 0;
+    unsigned placed = 0;
+    for (int d = 0; d < k; ++d) {
+        int bestn = -1, bests = -1;
+        for (int i = 0; i < k; ++i) {
+            if (placed >> i & 1u) continue;
+            const int s = __builtin_popcount(d ? adj[i] & placed : adj[i]);
+            if (s > bests) {
+                bests = s;
+                bestn = i;
+            }
+        }
+        if (d && bests == 0) return false;                            // not connected
+        pi[d] = bestn;
+        placed |= 1u << bestn;
+    }
+    q.order = 0;
+    q.padj = 0;
+    q.parent = 0;
+    for (int d = 0; d < k; ++d) {
+        q.order |= (unsigned long long)pi[d] << (8 * d);
+        int par = -1;
+        for (int j = 0; j < k; ++j)
+            if (adj[pi[d]] >> pi[j] & 1u) {
+                q.padj |= 1ull << (8 * d + j);
+                if (par < 0 && j < d) par = j;
+            }
+        if (d) q.parent |= (uint32_t)par << (3 * d);
+        edges += __builtin_popcount(adj[d]);
+    }
+    q.k = (int32_t)k;
+    q.lo = nlo;
+    q.edges = edges / 2;
+    return true;
+}
+
+// the key of an embedding: the images img[d] of the positions as bytes in pattern-node order, node 0 in the top byte, the bytes
+// of the nodes k .. 7 0xFF
+CAL_RULE unsigned long long motif_key(const MotifPlan& q, const int* img) {
+    unsigned long long key = q.k < kMotifK ? ~0ull >> (8 * q.k) : 0ull;
+    for (int d = 0; d < q.k; ++d) key |= (unsigned long long)img[d] << (56 - 8 * motif_node(q, d));
+    return key;
+}
+
+}  // namespace cal

@@ -9,14 +9,7 @@ namespace cal {
 constexpr int kSegCap = 2048;    // LDS capacity S: elements of one segment / chunk (cal_explain_lds_cap())
 constexpr int kSegWide = 1024;   // threads of the widest group and of the large-segment workgroups
 
-// segment g of p clamped into [0, M]: a malformed p reads nothing outside the arrays
-__device__ __forceinline__ void seg_clamp(const int64_t* p, int64_t g, int64_t M, int64_t& lo, int64_t& m) {
-    int64_t l = p[g], h = p[g + 1];
-    l = l < 0 ? 0 : (l > M ? M : l);
-    h = h < l ? l : (h > M ? M : h);
-    lo = l;
-    m = h - l;
-}
+// (seg_clamp, segment g of p clamped into [0, M]: rules.hpp)
 
 // sum over the nw consecutive waves from wave w0 on (this thread's group), every thread of the group gets it; all threads of
 // the workgroup call it (two barriers).  Fixed order: wave butterflies, then the group's wave partials in wave order.

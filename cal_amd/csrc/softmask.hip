@@ -12,7 +12,6 @@
 namespace cal {
 namespace {
 
-__device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : slope * v; }
 
 // butterfly sum / max over the lane offsets lo, 2 lo, ... < hi (powers of two): every lane of the span ends with the same bits
 __device__ __forceinline__ float span_sum(float v, int lo, int hi) {

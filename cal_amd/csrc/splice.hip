@@ -46,19 +46,7 @@ struct SpliceArgs {
     int ticket, nblk;
 };
 
-// the part of pair p on side s: node range [nlo, nlo + nn), column range [elo, elo + em); all zero when absent
-__device__ __forceinline__ void side_ranges(const Side& s, int64_t p, int64_t& nlo, int64_t& nn, int64_t& elo, int64_t& em) {
-    const int64_t g = s.pick[p];
-    nlo = nn = elo = em = 0;
-    if (g < 0 || g >= s.B) return;
-    seg_clamp(s.ptr, g, s.N, nlo, nn);
-    seg_clamp(s.eptr, g, s.E, elo, em);
-}
-
-__device__ __forceinline__ bool col_valid(const Side& s, int64_t e, int64_t nlo, int64_t nn) {
-    const int64_t u = s.ei[e], v = s.ei[s.E + e];
-    return u >= nlo && u < nlo + nn && v >= nlo && v < nlo + nn;
-}
+// (side_ranges, col_valid: rules.hpp)
 
 // valid columns of the part; when one is dropped, sel[elo + k] = local index of the k-th valid one.  All threads call it.
 template <int NT>

@@ -60,7 +60,7 @@ __device__ __forceinline__ uint64_t edge_key(const TwinArgs& a, int64_t e, int64
     if (u < nlo || u >= nlo + nn || v < nlo || v >= nlo + nn) return kPad;
     self = u == v;
     const uint64_t x = (uint64_t)(u - nlo), y = (uint64_t)(v - nlo);
-    return (((x < y ? x : y) * (uint64_t)nn + (x < y ? y : x)) << 1) | (uint64_t)(u > v);
+    return und_edge_key(x, y, (uint64_t)nn, u > v);
 }
 
 // grid (ceil(B / (NT / G)), chunks), NT threads; dynamic LDS: keys [NT/G][cap] u64, sorted [NT/G][cap] i32, [NT/64] i64.

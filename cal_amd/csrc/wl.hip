@@ -32,8 +32,6 @@
 namespace cal {
 namespace {
 
-constexpr unsigned long long kWlInit = CAL_WL_C_INIT, kWlSelf = CAL_WL_C_SELF, kWlOut = CAL_WL_C_OUT, kWlIn = CAL_WL_C_IN,
-                             kWlNode = CAL_WL_C_NODE, kWlGraph = CAL_WL_C_GRAPH;
 constexpr int64_t kWlMaxT = 4096;
 constexpr int64_t kWlMaxProtoNodes = 4096;
 constexpr int kWlSmall = 256;              // nodes (and threads) of the small instantiation
@@ -69,9 +67,6 @@ struct WlArgs {
     u64* wout;                 // ws [N]  (graphs above the cap)
     u64* win;                  // ws [N]
 };
-
-// the next colour of a node
-__device__ __forceinline__ u64 wl_next(u64 c, u64 so, u64 si) { return splitmix64(splitmix64(splitmix64(c + kWlSelf) + so) + si); }
 
 // grid B, NT threads
 template <int NT, int CAP>

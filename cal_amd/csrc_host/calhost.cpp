@@ -9,7 +9,8 @@
 //
 // Every function cites the reference call site it stands for, like its HIP twin (cal_amd/csrc/*.hip): the formulas,
 // the slot order of the plan (by edge id inside a row) and the summation order of every segment reduction are the
-// same, so host and device agree to fp32 rounding.
+// same, so host and device agree to fp32 rounding.  The rules whose results the two libraries promise bit for bit -- hashes, keys,
+// clamps, selection counts, plans, replica rules -- are not restated here: both sides read them from cal_amd/csrc/rules.hpp.
 #include <math.h>
 #include <stdarg.h>
 #include <stdint.h>
@@ -21,6 +22,9 @@
 #include <vector>
 
 #include "cal_hip.h"
+#include "rules.hpp"
+
+using namespace cal;
 
 #define HOST_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -34,22 +38,6 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 #define HOST_REQUIRE(cond, msg) do { if (!(cond)) { set_error("%s: %s", __func__, msg); return 2; } } while (0)
-
-inline float lrelu(float v, float slope) { return v > 0.f ? v : slope * v; }
-
-// counter-based attention-dropout keep decision: bit-identical to cal_amd/csrc/gat_common.hpp (32-bit finaliser, round 4)
-inline uint32_t mix32(uint32_t x) {
-    x ^= x >> 16; x *= 0x21F0AAADu;
-    x ^= x >> 15; x *= 0x735A2D97u;
-    x ^= x >> 15;
-    return x;
-}
-inline float keep_scale(uint64_t seed, int64_t id, int k, int K, float p, float inv_keep) {
-    if (p <= 0.f) return 1.f;
-    const uint32_t key = (uint32_t)(id * K + k);
-    const uint32_t r = mix32(mix32(key + (uint32_t)seed) ^ (uint32_t)(seed >> 32));
-    return ((float)r * (1.0f / 4294967296.0f)) >= p ? inv_keep : 0.f;
-}
 
 }  // namespace
 
@@ -622,15 +610,6 @@ HOST_EXPORT int cal_gat_mask_bwd(const int32_t* rowptr_dst, const int32_t* nbr_d
 // ---- learned masks (cal_amd/csrc/maskopt.hip; cal_amd/maskopt.py): the same formulas in fp32, the per-graph sums in double in the
 // kernel's order -- 256 strided lane partials, a butterfly per 64 of them, the four wave partials in order
 namespace {
-struct Logit { float m, dm, ent; };
-inline Logit logit_terms(float th) {
-    const float a = fabsf(th), z = expf(-a), r = 1.f / (1.f + z);
-    Logit o;
-    o.m = th >= 0.f ? r : z * r;
-    o.dm = z * r * r;
-    o.ent = log1pf(z) + a * (z * r);
-    return o;
-}
 inline double lanes_total(double* v) {                        // [256], destroyed
     for (int w = 0; w < 4; ++w)
         for (int o = 32; o > 0; o >>= 1)
@@ -653,10 +632,8 @@ HOST_EXPORT int cal_mask_step(const int64_t* pptr, const int32_t* rep, const int
         rsq2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, (double)step)));
     }
     for (int64_t g = 0; g < B; ++g) {
-        int64_t lo = pptr[g], hi = pptr[g + 1];
-        lo = lo < 0 ? 0 : (lo > P ? P : lo);
-        hi = hi < lo ? lo : (hi > P ? P : hi);
-        const int64_t n = hi - lo;
+        int64_t lo, n;
+        seg_clamp(pptr, g, P, lo, n);
         const float ent_w = n > 0 ? l_ent / (float)n : 0.f;
         double s_size[256] = {0.0}, s_ent[256] = {0.0};
         for (int64_t i = 0; i < n; ++i) {
@@ -693,31 +670,10 @@ HOST_EXPORT int cal_mask_step(const int64_t* pptr, const int32_t* rep, const int
 // product over the hidden units in order, a node's row sums in slot order, dw2 / db2 through the kernel's per-block, per-wave
 // partials -- the per-graph sums in double
 namespace {
-inline uint64_t splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-inline bool column_ok(int64_t e, const int32_t* row32, const int32_t* col32, int64_t E, int64_t N, int64_t& u, int64_t& v) {
-    u = v = 0;
-    if (e < 0 || e >= E) return false;
-    u = row32[e];
-    v = col32[e];
-    return u >= 0 && u < N && v >= 0 && v < N;
-}
 inline float column_omega(const float* pq, const float* w2, float b2, int64_t u, int64_t v, int64_t Hd) {
     float a = 0.f;
     for (int64_t k = 0; k < Hd; ++k) a = fmaf(fmaxf(pq[u * 2 * Hd + k] + pq[v * 2 * Hd + Hd + k], 0.f), w2[k], a);
     return b2 + a;
-}
-inline bool mlp_sizes_ok(int64_t N, int64_t E, int64_t Hd, int64_t B, int64_t P) {
-    return N >= 0 && E >= 0 && B >= 0 && P >= 0 && N < (1ll << 31) && E < (1ll << 31) && B < (1ll << 31) && P < (1ll << 31) &&
-           Hd >= 4 && Hd <= 256 && Hd % 4 == 0;
-}
-inline int mlp_rows_per_block(int64_t N) {
-    const int64_t rpb = (N + 511) / 512;
-    return (int)(rpb < 16 ? 16 : rpb);
 }
 }  // namespace
 
@@ -730,12 +686,11 @@ HOST_EXPORT int cal_edge_mlp_fwd(const float* pq, const float* w2, const float* 
     if (B == 0 || P == 0) return 0;
     HOST_REQUIRE(pq && w2 && b2 && row32 && col32 && pptr && rep && mate && omega && z && mask, "null operand");
     for (int64_t g = 0; g < B; ++g) {
-        int64_t lo = pptr[g], hi = pptr[g + 1];
-        lo = lo < 0 ? 0 : (lo > P ? P : lo);
-        hi = hi < lo ? lo : (hi > P ? P : hi);
+        int64_t lo, n;
+        seg_clamp(pptr, g, P, lo, n);
         double s_size = 0.0, s_ent = 0.0;
-        for (int64_t p = lo; p < hi; ++p) {
-            int64_t ur, vr, ut, vt;
+        for (int64_t p = lo; p < lo + n; ++p) {
+            int ur, vr, ut, vt;
             float om = 0.f, zz = 0.f;
             if (column_ok(rep[p], row32, col32, E, N, ur, vr)) {
                 const bool t_ok = column_ok(mate[p], row32, col32, E, N, ut, vt);
@@ -777,12 +732,11 @@ HOST_EXPORT int cal_edge_mlp_bwd(const float* pq, const float* w2, const int32_t
                      dpq && dw2 && db2, "null operand");
     std::vector<float> c((size_t)(E > 0 ? E : 1), 0.f);
     for (int64_t g = 0; g < B; ++g) {
-        int64_t lo = pptr[g], hi = pptr[g + 1];
-        lo = lo < 0 ? 0 : (lo > P ? P : lo);
-        hi = hi < lo ? lo : (hi > P ? P : hi);
-        const float ent_w = hi > lo ? l_ent / (float)(hi - lo) : 0.f;
-        for (int64_t p = lo; p < hi; ++p) {
-            int64_t u, v;
+        int64_t lo, n;
+        seg_clamp(pptr, g, P, lo, n);
+        const float ent_w = n > 0 ? l_ent / (float)n : 0.f;
+        for (int64_t p = lo; p < lo + n; ++p) {
+            int u, v;
             const int64_t r = rep[p], t = mate[p];
             if (!column_ok(r, row32, col32, E, N, u, v)) continue;
             const bool t_ok = column_ok(t, row32, col32, E, N, u, v);
@@ -878,19 +832,6 @@ HOST_EXPORT int cal_collate_host(const float* X, const int64_t* EI, int64_t Etot
 // order, k_g rule and integer rank sums as cal_amd/csrc/explain.hip, so masks, ranks and metrics agree bit for bit.
 namespace {
 constexpr int64_t kExplainLdsCap = 2048;
-
-inline uint32_t score_key(float s) {
-    if (s != s) return 1u;                                    // NaN: below every number
-    uint32_t u = 0u;
-    if (s != 0.f) memcpy(&u, &s, 4);                          // -0 ranks as +0
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// segment g of p clamped into [0, M] (seg_clamp of cal_amd/csrc/segment.hpp): [lo, hi)
-inline void seg_clamp(const int64_t* p, int64_t g, int64_t M, int64_t& lo, int64_t& hi) {
-    lo = std::min(std::max(p[g], (int64_t)0), M);
-    hi = std::min(std::max(p[g + 1], lo), M);
-}
 }  // namespace
 
 HOST_EXPORT int64_t cal_explain_ws(int64_t M, int64_t) { return 8 * (M > 0 ? M : 0) + 256; }
@@ -908,9 +849,8 @@ HOST_EXPORT int cal_explain_rank(const float* score, int64_t stride, const int64
     HOST_REQUIRE(max_seg < ((int64_t)1 << 30), "segments of 2^30 elements or more are not supported");
 #pragma omp parallel for schedule(dynamic, 16)
     for (int64_t g = 0; g < B; ++g) {
-        int64_t lo, hi;
-        seg_clamp(seg_ptr, g, M, lo, hi);
-        const int64_t m = hi - lo;
+        int64_t lo, m;
+        seg_clamp(seg_ptr, g, M, lo, m);
         double* row = metrics ? metrics + 4 * g : nullptr;
         if (m > max_seg) {                                    // not ranked (max_seg must bound every segment)
             for (int64_t q = 0; q < m; ++q) { rank[lo + q] = -1; mask[lo + q] = 0; }
@@ -926,9 +866,7 @@ HOST_EXPORT int cal_explain_rank(const float* score, int64_t stride, const int64
             if (gt) P += gt[lo + q] != 0;
         }
         std::sort(ord.begin(), ord.end(), [&](int64_t a, int64_t b) { return key[a] != key[b] ? key[a] > key[b] : a < b; });
-        int64_t kg = P;
-        if (k >= 0) kg = std::min(k, m);
-        else if (k == -1) { const double c = ceil(ratio * (double)m); kg = c < (double)m ? (int64_t)c : m; }
+        const int64_t kg = sel_count(m, P, ratio, k);
         int64_t hits = 0, r2 = 0;
         for (int64_t s = 0; s < m;) {                         // runs of equal keys: [s, e)
             int64_t e = s + 1;
@@ -944,8 +882,7 @@ HOST_EXPORT int cal_explain_rank(const float* score, int64_t stride, const int64
         }
         if (row) {
             row[0] = (double)kg; row[1] = (double)hits; row[2] = (double)P;
-            row[3] = (P <= 0 || P >= m) ? NAN
-                     : ((double)r2 * 0.5 - (double)P * (double)(P + 1) * 0.5) / ((double)P * (double)(m - P));
+            row[3] = seg_auc(m, P, r2);
         }
     }
     return 0;
@@ -978,9 +915,10 @@ HOST_EXPORT int cal_subgraph_extract(const int64_t* edge_index, int64_t E, int64
     dst.reserve(E);
     int64_t nt = 0, et = 0, mn = 0, me = 0;
     for (int64_t g = 0; g < B; ++g) {
-        int64_t nlo, nhi, elo, ehi;
-        seg_clamp(ptr, g, N, nlo, nhi);
-        seg_clamp(edge_ptr, g, E, elo, ehi);
+        int64_t nlo, nn, elo, em;
+        seg_clamp(ptr, g, N, nlo, nn);
+        seg_clamp(edge_ptr, g, E, elo, em);
+        const int64_t nhi = nlo + nn, ehi = elo + em;
         if (node_keep)
             for (int64_t i = nlo; i < nhi; ++i) nflag[i] = (node_keep[i] != 0) != comp;
         else if (from_edges)
@@ -1048,11 +986,12 @@ HOST_EXPORT int cal_edge_twin(const int64_t* edge_index, int64_t E, const int64_
     std::vector<std::pair<uint64_t, int64_t>> keys;
     for (int64_t g = 0; g < B; ++g) {
         const int64_t nlo = ptr[g], nn = std::max(ptr[g + 1] - nlo, (int64_t)0);
-        int64_t elo, ehi;
-        seg_clamp(edge_ptr, g, E, elo, ehi);
-        if (ehi - elo > max_edges) {
+        int64_t elo, em;
+        seg_clamp(edge_ptr, g, E, elo, em);
+        const int64_t ehi = elo + em;
+        if (em > max_edges) {
             for (int64_t e = elo; e < ehi; ++e) twin[e] = -1;
-            unp += ehi - elo;
+            unp += em;
             continue;
         }
         keys.clear();
@@ -1061,8 +1000,7 @@ HOST_EXPORT int cal_edge_twin(const int64_t* edge_index, int64_t E, const int64_
             twin[e] = -1;
             if (u < nlo || u >= nlo + nn || v < nlo || v >= nlo + nn) continue;
             if (u == v) { twin[e] = (int32_t)e; ++nself; continue; }
-            const uint64_t x = (uint64_t)(std::min(u, v) - nlo), y = (uint64_t)(std::max(u, v) - nlo);
-            keys.emplace_back(((x * (uint64_t)nn + y) << 1) | (uint64_t)(u > v), e);
+            keys.emplace_back(und_edge_key((uint64_t)(u - nlo), (uint64_t)(v - nlo), (uint64_t)nn, u > v), e);
         }
         std::sort(keys.begin(), keys.end());                  // by key, then column index
         for (size_t s = 0; s < keys.size();) {                 // one undirected edge: its (u < v) columns, then its (u > v) columns
@@ -1108,9 +1046,10 @@ HOST_EXPORT int cal_explain_rank_pairs(const float* score, int64_t stride, const
     std::vector<int64_t> cptr(B + 1, 0), rep(M, -1), lens(B, 0);
     int64_t longest = 0;
     for (int64_t g = 0; g < B; ++g) {
-        int64_t lo, hi;
-        seg_clamp(seg_ptr, g, M, lo, hi);
-        const bool bad = hi - lo > max_seg;
+        int64_t lo, m;
+        seg_clamp(seg_ptr, g, M, lo, m);
+        const int64_t hi = lo + m;
+        const bool bad = m > max_seg;
         for (int64_t e = lo; e < hi; ++e) {
             int64_t t = twin[e];
             if (!(t >= lo && t < hi && t != e && twin[t] == e)) t = -1;
@@ -1131,7 +1070,7 @@ HOST_EXPORT int cal_explain_rank_pairs(const float* score, int64_t stride, const
             cgt.push_back(pos);
         }
         // a segment that is not ranked keeps its length, so the ranking below marks it (NaN metrics)
-        if (bad) { cs.resize(cs.size() + (hi - lo), 0.f); cgt.resize(cgt.size() + (hi - lo), 0); }
+        if (bad) { cs.resize(cs.size() + m, 0.f); cgt.resize(cgt.size() + m, 0); }
         cptr[g + 1] = (int64_t)cs.size();
         lens[g] = cptr[g + 1] - cptr[g];
         if (!bad) longest = std::max(longest, lens[g]);
@@ -1143,9 +1082,10 @@ HOST_EXPORT int cal_explain_rank_pairs(const float* score, int64_t stride, const
                                     gt ? cgt.data() : nullptr, cmask.data(), crank.data(), metrics, nullptr, 0, nullptr);
     if (rc != 0) return rc;
     for (int64_t g = 0; g < B; ++g) {
-        int64_t lo, hi;
-        seg_clamp(seg_ptr, g, M, lo, hi);
-        const bool bad = hi - lo > max_seg;
+        int64_t lo, m;
+        seg_clamp(seg_ptr, g, M, lo, m);
+        const int64_t hi = lo + m;
+        const bool bad = m > max_seg;
         int64_t p = cptr[g];
         for (int64_t e = lo; e < hi; ++e) {                    // (a representative comes before its partner)
             if (bad) { rank[e] = -1; mask[e] = 0; continue; }
@@ -1214,25 +1154,14 @@ struct OutWriter {
 // ---- batch splice (cal_amd/csrc/splice.hip): the same order of nodes and columns, the same dropped columns and bridge rules, so
 // every integer output agrees bit for bit.  The count leaves each pair's valid-column counts in ws, as the device does.
 namespace {
-struct SpliceSide {
+struct SpliceSide {            // (the fields side_ranges and col_valid of rules.hpp read, named as splice.hip's Side)
     const int64_t* ei; int64_t E, N; const int64_t* ptr; const int64_t* eptr; int64_t B; const int64_t* pick; const int64_t* bridge;
-    void ranges(int64_t p, int64_t& nlo, int64_t& nhi, int64_t& elo, int64_t& ehi) const {
-        const int64_t g = pick[p];
-        nlo = nhi = elo = ehi = 0;
-        if (g < 0 || g >= B) return;
-        seg_clamp(ptr, g, N, nlo, nhi);
-        seg_clamp(eptr, g, E, elo, ehi);
-    }
-    bool valid(int64_t e, int64_t nlo, int64_t nhi) const {
-        const int64_t u = ei[e], v = ei[E + e];
-        return u >= nlo && u < nhi && v >= nlo && v < nhi;
-    }
 };
-inline bool splice_bridge(const SpliceSide& a, const SpliceSide& b, int64_t p, int64_t alo, int64_t ahi, int64_t blo, int64_t bhi,
+inline bool splice_bridge(const SpliceSide& a, const SpliceSide& b, int64_t p, int64_t alo, int64_t an, int64_t blo, int64_t bn,
                           bool& asked) {
     const int64_t ba = a.bridge ? a.bridge[p] : -1, bb = b.bridge ? b.bridge[p] : -1;
     asked = ba >= 0 || bb >= 0;
-    return ba >= 0 && bb >= 0 && ba >= alo && ba < ahi && bb >= blo && bb < bhi;
+    return ba >= 0 && bb >= 0 && ba >= alo && ba < alo + an && bb >= blo && bb < blo + bn;
 }
 }  // namespace
 
@@ -1260,16 +1189,16 @@ HOST_EXPORT int cal_graph_splice_count(const int64_t* eia, int64_t Ea, int64_t N
     BatchScan scan{ptr_out, edge_ptr_out, totals};
     int64_t unput = 0;
     for (int64_t p = 0; p < P; ++p) {
-        int64_t alo, ahi, aelo, aehi, blo, bhi, belo, behi, ea = 0, eb = 0;
-        A.ranges(p, alo, ahi, aelo, aehi);
-        B.ranges(p, blo, bhi, belo, behi);
-        for (int64_t e = aelo; e < aehi; ++e) ea += A.valid(e, alo, ahi);
-        for (int64_t e = belo; e < behi; ++e) eb += B.valid(e, blo, bhi);
+        int64_t alo, an, aelo, aem, blo, bn, belo, bem, ea = 0, eb = 0;
+        side_ranges(A, p, alo, an, aelo, aem);
+        side_ranges(B, p, blo, bn, belo, bem);
+        for (int64_t e = aelo; e < aelo + aem; ++e) ea += col_valid(A, e, alo, an);
+        for (int64_t e = belo; e < belo + bem; ++e) eb += col_valid(B, e, blo, bn);
         bool asked;
-        const bool put = splice_bridge(A, B, p, alo, ahi, blo, bhi, asked);
+        const bool put = splice_bridge(A, B, p, alo, an, blo, bn, asked);
         cnt[p] = ea;
         cnt[P + p] = eb;
-        scan.add(p, (ahi - alo) + (bhi - blo), ea + eb + (put ? 2 : 0));
+        scan.add(p, an + bn, ea + eb + (put ? 2 : 0));
         unput += asked && !put;
     }
     scan.finish(P);
@@ -1288,19 +1217,19 @@ HOST_EXPORT int cal_graph_splice_write(const int64_t* eia, int64_t Ea, int64_t N
     HOST_REQUIRE_WRITE(P, !x_out || (F > 0 && (Na == 0 || xa) && (Nb == 0 || xb)), "x_out needs F > 0, xa and xb");
     const SpliceSide A{eia, Ea, Na, ptr_a, eptr_a, Ba, ga, bridge_a}, B{eib, Eb, Nb, ptr_b, eptr_b, Bb, gb, bridge_b};
     for (int64_t p = 0; p < P; ++p) {
-        int64_t alo, ahi, aelo, aehi, blo, bhi, belo, behi;
-        A.ranges(p, alo, ahi, aelo, aehi);
-        B.ranges(p, blo, bhi, belo, behi);
+        int64_t alo, an, aelo, aem, blo, bn, belo, bem;
+        side_ranges(A, p, alo, an, aelo, aem);
+        side_ranges(B, p, blo, bn, belo, bem);
         W.begin(p);
-        const int64_t n0 = W.n0, an = ahi - alo;
-        for (int64_t s = alo; s < ahi; ++s) W.node(s, xa, s);
-        for (int64_t s = blo; s < bhi; ++s) W.node(-1 - s, xb, s);
-        for (int64_t e = aelo; e < aehi; ++e)
-            if (A.valid(e, alo, ahi)) W.col(n0 + (eia[e] - alo), n0 + (eia[Ea + e] - alo), e);
-        for (int64_t e = belo; e < behi; ++e)
-            if (B.valid(e, blo, bhi)) W.col(n0 + an + (eib[e] - blo), n0 + an + (eib[Eb + e] - blo), -1 - e);
+        const int64_t n0 = W.n0;
+        for (int64_t s = alo; s < alo + an; ++s) W.node(s, xa, s);
+        for (int64_t s = blo; s < blo + bn; ++s) W.node(-1 - s, xb, s);
+        for (int64_t e = aelo; e < aelo + aem; ++e)
+            if (col_valid(A, e, alo, an)) W.col(n0 + (eia[e] - alo), n0 + (eia[Ea + e] - alo), e);
+        for (int64_t e = belo; e < belo + bem; ++e)
+            if (col_valid(B, e, blo, bn)) W.col(n0 + an + (eib[e] - blo), n0 + an + (eib[Eb + e] - blo), -1 - e);
         bool asked;
-        if (splice_bridge(A, B, p, alo, ahi, blo, bhi, asked)) {
+        if (splice_bridge(A, B, p, alo, an, blo, bn, asked)) {
             const int64_t u = n0 + (bridge_a[p] - alo), v = n0 + an + (bridge_b[p] - blo);
             W.col(u, v, CAL_SPLICE_BRIDGE);
             W.col(v, u, CAL_SPLICE_BRIDGE);
@@ -1313,27 +1242,9 @@ HOST_EXPORT int cal_graph_splice_write(const int64_t* eia, int64_t Ea, int64_t N
 // ---- occlusion replicas (cal_amd/csrc/occlude.hip; cal_amd/occlude.py occlude_batch): the same nodes and columns in the same
 // order, so every integer output agrees bit for bit.
 namespace {
-struct OccludeSrc {
+struct OccludeSrc {            // (the fields occ_replica and col_stays of rules.hpp read, named as occlude.hip's OccArgs)
     const int64_t* ei; int64_t E, N; const int64_t* ptr; const int64_t* eptr; int64_t B; const int64_t* rg; const int64_t* re;
     int mode; const int32_t* twin;
-    // replica r: node range, column range, the node removed, the two columns removed (-1: none)
-    void ranges(int64_t r, int64_t& nlo, int64_t& nhi, int64_t& elo, int64_t& ehi, int64_t& rn, int64_t& c0, int64_t& c1) const {
-        const int64_t g = rg[r], e = re[r];
-        nlo = nhi = elo = ehi = 0;
-        rn = c0 = c1 = -1;
-        if (g < 0 || g >= B) return;
-        seg_clamp(ptr, g, N, nlo, nhi);
-        seg_clamp(eptr, g, E, elo, ehi);
-        if (mode == 0) {
-            if (e >= elo && e < ehi) { c0 = e; if (twin) c1 = twin[e]; }
-        } else if (e >= nlo && e < nhi) {
-            rn = e;
-        }
-    }
-    bool stays(int64_t e, int64_t nlo, int64_t nhi, int64_t rn, int64_t c0, int64_t c1) const {
-        const int64_t u = ei[e], v = ei[E + e];
-        return u >= nlo && u < nhi && v >= nlo && v < nhi && e != c0 && e != c1 && u != rn && v != rn;
-    }
 };
 }  // namespace
 
@@ -1355,10 +1266,10 @@ HOST_EXPORT int cal_occlude_count(const int64_t* edge_index, int64_t E, int64_t 
     const OccludeSrc S{edge_index, E, N, ptr, edge_ptr, B, rep_graph, rep_elem, mode, mode == 0 ? twin : nullptr};
     BatchScan scan{ptr_out, edge_ptr_out, totals};
     for (int64_t r = 0; r < R; ++r) {
-        int64_t nlo, nhi, elo, ehi, rn, c0, c1, m = 0;
-        S.ranges(r, nlo, nhi, elo, ehi, rn, c0, c1);
-        for (int64_t e = elo; e < ehi; ++e) m += S.stays(e, nlo, nhi, rn, c0, c1);
-        scan.add(r, (nhi - nlo) - (rn >= 0 ? 1 : 0), m);
+        const OccRep q = occ_replica(S, r);
+        int64_t m = 0;
+        for (int64_t e = q.elo; e < q.elo + q.em; ++e) m += col_stays(S, q, e);
+        scan.add(r, q.nn - (q.rn >= 0 ? 1 : 0), m);
     }
     scan.finish(R);
     return 0;
@@ -1373,15 +1284,14 @@ HOST_EXPORT int cal_occlude_write(const int64_t* edge_index, int64_t E, int64_t 
     HOST_REQUIRE_WRITE(R, !x_out || (F > 0 && (N == 0 || x)), "x_out needs F > 0 and x");
     const OccludeSrc S{edge_index, E, N, ptr, edge_ptr, B, rep_graph, rep_elem, mode, mode == 0 ? twin : nullptr};
     for (int64_t r = 0; r < R; ++r) {
-        int64_t nlo, nhi, elo, ehi, rn, c0, c1;
-        S.ranges(r, nlo, nhi, elo, ehi, rn, c0, c1);
+        const OccRep q = occ_replica(S, r);
         W.begin(r);
-        for (int64_t s = nlo; s < nhi; ++s)
-            if (s != rn) W.node(s, x, s);
-        for (int64_t e = elo; e < ehi; ++e) {
-            if (!S.stays(e, nlo, nhi, rn, c0, c1)) continue;
+        for (int64_t s = q.nlo; s < q.nlo + q.nn; ++s)
+            if (s != q.rn) W.node(s, x, s);
+        for (int64_t e = q.elo; e < q.elo + q.em; ++e) {
+            if (!col_stays(S, q, e)) continue;
             const int64_t u = edge_index[e], v = edge_index[E + e];
-            W.col(W.n0 + (u - nlo) - (rn >= 0 && u > rn ? 1 : 0), W.n0 + (v - nlo) - (rn >= 0 && v > rn ? 1 : 0), e);
+            W.col(W.n0 + (u - q.nlo) - (q.rn >= 0 && u > q.rn ? 1 : 0), W.n0 + (v - q.nlo) - (q.rn >= 0 && v > q.rn ? 1 : 0), e);
         }
     }
     return 0;
@@ -1391,28 +1301,9 @@ HOST_EXPORT int cal_occlude_write(const int64_t* edge_index, int64_t E, int64_t 
 // ---- coalition replicas (cal_amd/csrc/coalition.hip; cal_amd/coalition.py coalition_batch): the same nodes and columns in the
 // same order, so every integer output agrees bit for bit.
 namespace {
-struct CoalitionSrc {
+struct CoalitionSrc {          // (the fields co_replica, elem_stays and col_stays of rules.hpp read, named as coalition.hip's CoArgs)
     const int64_t* ei; int64_t E, N; const int64_t* ptr; const int64_t* eptr; int64_t B; const int32_t* key; int64_t K, M;
     const int64_t* rg; const int64_t* rrow; const int64_t* rth; int mode, invert; int64_t mx;
-    // replica r: node range, column range, its key row (null: everything stays) and threshold
-    void ranges(int64_t r, int64_t& nlo, int64_t& nhi, int64_t& elo, int64_t& ehi, const int32_t*& row, int64_t& th) const {
-        const int64_t g = rg[r];
-        nlo = nhi = elo = ehi = th = 0;
-        row = nullptr;
-        if (g < 0 || g >= B) return;
-        seg_clamp(ptr, g, N, nlo, nhi);
-        seg_clamp(eptr, g, E, elo, ehi);
-        if (mode == 1 && nhi - nlo > mx) { nlo = nhi = elo = ehi = 0; return; }
-        const int64_t k = rrow[r];
-        if (k >= 0 && k < K) row = key + k * M;
-        th = rth[r];
-    }
-    bool elem(const int32_t* row, int64_t th, int64_t e) const { return !row || (invert ? row[e] >= th : row[e] < th); }
-    bool stays(int64_t e, int64_t nlo, int64_t nhi, const int32_t* row, int64_t th) const {
-        const int64_t u = ei[e], v = ei[E + e];
-        if (!(u >= nlo && u < nhi && v >= nlo && v < nhi)) return false;
-        return mode == 0 ? elem(row, th, e) : elem(row, th, u) && elem(row, th, v);
-    }
 };
 }  // namespace
 
@@ -1442,12 +1333,11 @@ HOST_EXPORT int cal_coalition_count(const int64_t* edge_index, int64_t E, int64_
     HOST_REQUIRE(totals && ptr_out && edge_ptr_out, "totals / ptr_out / edge_ptr_out are null");
     BatchScan scan{ptr_out, edge_ptr_out, totals};
     for (int64_t r = 0; r < R; ++r) {
-        int64_t nlo, nhi, elo, ehi, th, n = 0, m = 0;
-        const int32_t* row;
-        S.ranges(r, nlo, nhi, elo, ehi, row, th);
-        if (mode == 0) n = nhi - nlo;
-        else for (int64_t s = nlo; s < nhi; ++s) n += S.elem(row, th, s);
-        for (int64_t e = elo; e < ehi; ++e) m += S.stays(e, nlo, nhi, row, th);
+        const CoRep q = co_replica(S, r);
+        int64_t n = 0, m = 0;
+        if (mode == 0) n = q.nn;
+        else for (int64_t s = q.nlo; s < q.nlo + q.nn; ++s) n += elem_stays(S, q, s);
+        for (int64_t e = q.elo; e < q.elo + q.em; ++e) m += col_stays(S, q, e);
         scan.add(r, n, m);
     }
     scan.finish(R);
@@ -1464,69 +1354,46 @@ HOST_EXPORT int cal_coalition_write(const int64_t* edge_index, int64_t E, int64_
     HOST_REQUIRE_WRITE(R, !x_out || (F > 0 && (N == 0 || x)), "x_out needs F > 0 and x");
     std::vector<int64_t> local;                            // (mode 1) new local id of every node of the replica's graph
     for (int64_t r = 0; r < R; ++r) {
-        int64_t nlo, nhi, elo, ehi, th;
-        const int32_t* row;
-        S.ranges(r, nlo, nhi, elo, ehi, row, th);
+        const CoRep q = co_replica(S, r);
         W.begin(r);
-        local.assign((size_t)(nhi - nlo), 0);
-        for (int64_t s = nlo; s < nhi; ++s) {
-            local[(size_t)(s - nlo)] = W.i - W.n0;
-            if (mode == 0 || S.elem(row, th, s)) W.node(s, x, s);
+        local.assign((size_t)q.nn, 0);
+        for (int64_t s = q.nlo; s < q.nlo + q.nn; ++s) {
+            local[(size_t)(s - q.nlo)] = W.i - W.n0;
+            if (mode == 0 || elem_stays(S, q, s)) W.node(s, x, s);
         }
-        for (int64_t e = elo; e < ehi; ++e)
-            if (S.stays(e, nlo, nhi, row, th))
-                W.col(W.n0 + local[(size_t)(edge_index[e] - nlo)], W.n0 + local[(size_t)(edge_index[E + e] - nlo)], e);
+        for (int64_t e = q.elo; e < q.elo + q.em; ++e)
+            if (col_stays(S, q, e))
+                W.col(W.n0 + local[(size_t)(edge_index[e] - q.nlo)], W.n0 + local[(size_t)(edge_index[E + e] - q.nlo)], e);
     }
     return 0;
 }
 #undef COALITION_REQUIRE_INPUTS
 
-// ---- structural-noise replicas (cal_amd/csrc/noise.hip; cal_amd/noise.py noise_batch): the same hash, the same deletions and the
-// same accepted candidates in the same order, so every integer output agrees bit for bit.  Nothing is kept between the two
-// calls: the write decides the insertions again.
+// ---- structural-noise replicas (cal_amd/csrc/noise.hip; cal_amd/noise.py noise_batch): the hash, the deletions and the pair key of
+// rules.hpp and the same accepted candidates in the same order, so every integer output agrees bit for bit.  Nothing is kept
+// between the two calls: the write decides the insertions again.
 namespace {
-// (splitmix64: above, with the edge explainer's twins)
-inline uint64_t noise_hash(uint64_t s, uint64_t i) { return splitmix64(splitmix64(s) + i); }
-
-struct NoiseSrc {
+struct NoiseSrc {              // (the fields noise_replica and noise_stays of rules.hpp read, named as noise.hip's NoArgs)
     const int64_t* ei; int64_t E, N; const int64_t* ptr; const int64_t* eptr; int64_t B; const int32_t* twin;
     const int64_t* rg; const int64_t* rseed; const int64_t* rdel; const int64_t* radd; int64_t tries;
-    void ranges(int64_t r, int64_t& nlo, int64_t& nhi, int64_t& elo, int64_t& ehi) const {
-        const int64_t g = rg[r];
-        nlo = nhi = elo = ehi = 0;
-        if (g < 0 || g >= B) return;
-        seg_clamp(ptr, g, N, nlo, nhi);
-        seg_clamp(eptr, g, E, elo, ehi);
-    }
-    bool inside(int64_t e, int64_t nlo, int64_t nhi) const {
-        const int64_t u = ei[e], v = ei[E + e];
-        return u >= nlo && u < nhi && v >= nlo && v < nhi;
-    }
-    bool stays(int64_t r, int64_t e, int64_t nlo, int64_t nhi, int64_t elo) const {
-        if (!inside(e, nlo, nhi)) return false;
-        if (ei[e] == ei[E + e] || rdel[r] <= 0) return true;
-        int64_t rep = e;
-        if (twin && twin[e] >= elo && twin[e] < e) rep = twin[e];
-        return !((int64_t)(noise_hash((uint64_t)rseed[r] ^ CAL_NOISE_C_DEL, (uint64_t)(rep - elo)) >> 1) < rdel[r]);
-    }
-    uint64_t key(uint64_t u, uint64_t v, uint64_t n) const { return twin ? (u < v ? u * n + v : v * n + u) : u * n + v; }
-    // the accepted pairs of replica r, in candidate order
-    void insertions(int64_t r, int64_t nlo, int64_t nhi, int64_t elo, int64_t ehi, std::vector<std::pair<int64_t, int64_t>>& out) const {
+    // the accepted pairs of replica q, in candidate order
+    void insertions(const NoRep& q, std::vector<std::pair<int64_t, int64_t>>& out) const {
         out.clear();
-        const int64_t a = radd[r] > 0 ? radd[r] : 0;
-        const uint64_t n = (uint64_t)(nhi - nlo);
+        const int64_t a = q.a;
+        const uint64_t n = (uint64_t)q.nn;
         if (a == 0 || n <= 1) return;
         std::vector<uint64_t> taken;                           // the source pairs, sorted; then the accepted ones, unsorted
-        for (int64_t e = elo; e < ehi; ++e)
-            if (inside(e, nlo, nhi) && ei[e] != ei[E + e]) taken.push_back(key((uint64_t)(ei[e] - nlo), (uint64_t)(ei[E + e] - nlo), n));
+        for (int64_t e = q.elo; e < q.elo + q.em; ++e)
+            if (col_valid(*this, e, q.nlo, q.nn) && ei[e] != ei[E + e])
+                taken.push_back(pair_key(twin != nullptr, (uint64_t)(ei[e] - q.nlo), (uint64_t)(ei[E + e] - q.nlo), n));
         std::sort(taken.begin(), taken.end());
         const size_t ns = taken.size();
         const uint64_t total = (uint64_t)tries * (uint64_t)a;
         for (uint64_t c = 0; c < total && (int64_t)out.size() < a; ++c) {
-            const uint64_t h = noise_hash((uint64_t)rseed[r] ^ CAL_NOISE_C_ADD, c);
+            const uint64_t h = noise_hash(q.seed ^ kNoiseAdd, c);
             const uint64_t u = (h >> 32) % n, v = (h & 0xffffffffull) % n;
             if (u == v) continue;
-            const uint64_t k = key(u, v, n);
+            const uint64_t k = pair_key(twin != nullptr, u, v, n);
             if (std::binary_search(taken.begin(), taken.begin() + (long)ns, k)) continue;
             if (std::find(taken.begin() + (long)ns, taken.end(), k) != taken.end()) continue;
             taken.push_back(k);
@@ -1556,14 +1423,14 @@ HOST_EXPORT int cal_noise_count(const int64_t* edge_index, int64_t E, int64_t N,
     std::vector<std::pair<int64_t, int64_t>> ins;
     int64_t sum = 0, fell = 0;
     for (int64_t r = 0; r < R; ++r) {
-        int64_t nlo, nhi, elo, ehi, m = 0;
-        S.ranges(r, nlo, nhi, elo, ehi);
-        for (int64_t e = elo; e < ehi; ++e) m += S.stays(r, e, nlo, nhi, elo);
-        S.insertions(r, nlo, nhi, elo, ehi, ins);
+        const NoRep q = noise_replica(S, r);
+        int64_t m = 0;
+        for (int64_t e = q.elo; e < q.elo + q.em; ++e) m += noise_stays(S, q, e);
+        S.insertions(q, ins);
         added[r] = (int64_t)ins.size();
         sum += added[r];
-        fell += added[r] < (rep_add[r] > 0 ? rep_add[r] : 0);
-        scan.add(r, nhi - nlo, m + added[r] * (S.twin ? 2 : 1));
+        fell += added[r] < q.a;
+        scan.add(r, q.nn, m + added[r] * (S.twin ? 2 : 1));
     }
     scan.finish(R);
     totals[5] = sum;
@@ -1581,13 +1448,12 @@ HOST_EXPORT int cal_noise_write(const int64_t* edge_index, int64_t E, int64_t N,
     HOST_REQUIRE_WRITE(R, !x_out || (F > 0 && (N == 0 || x)), "x_out needs F > 0 and x");
     std::vector<std::pair<int64_t, int64_t>> ins;
     for (int64_t r = 0; r < R; ++r) {
-        int64_t nlo, nhi, elo, ehi;
-        S.ranges(r, nlo, nhi, elo, ehi);
+        const NoRep q = noise_replica(S, r);
         W.begin(r);
-        for (int64_t s = nlo; s < nhi; ++s) W.node(s, x, s);
-        for (int64_t e = elo; e < ehi; ++e)
-            if (S.stays(r, e, nlo, nhi, elo)) W.col(W.n0 + edge_index[e] - nlo, W.n0 + edge_index[E + e] - nlo, e);
-        S.insertions(r, nlo, nhi, elo, ehi, ins);
+        for (int64_t s = q.nlo; s < q.nlo + q.nn; ++s) W.node(s, x, s);
+        for (int64_t e = q.elo; e < q.elo + q.em; ++e)
+            if (noise_stays(S, q, e)) W.col(W.n0 + edge_index[e] - q.nlo, W.n0 + edge_index[E + e] - q.nlo, e);
+        S.insertions(q, ins);
         for (const auto& p : ins) {
             W.col(W.n0 + p.first, W.n0 + p.second, -1);
             if (S.twin) W.col(W.n0 + p.second, W.n0 + p.first, -1);
@@ -1628,17 +1494,16 @@ HOST_EXPORT int cal_rank_agreement(const float* a, const float* b, int64_t M, co
     HOST_REQUIRE(M == 0 || (a && b), "a / b are null");
 #pragma omp parallel for schedule(dynamic, 16)
     for (int64_t g = 0; g < B; ++g) {
-        int64_t lo, hi;
-        seg_clamp(seg_ptr, g, M, lo, hi);
+        int64_t lo, m;
+        seg_clamp(seg_ptr, g, M, lo, m);
         int64_t* row = counts + 10 * g;
         for (int t = 0; t < 10; ++t) row[t] = 0;
-        if (hi - lo > max_seg) { row[0] = -1; continue; }
+        if (m > max_seg) { row[0] = -1; continue; }
         std::vector<int64_t> id;                               // the elements taking part, ascending
-        for (int64_t i = lo; i < hi; ++i)
+        for (int64_t i = lo; i < lo + m; ++i)
             if ((!sel || sel[i]) && a[i] == a[i] && b[i] == b[i]) id.push_back(i);
         const int64_t n = (int64_t)id.size();
-        int64_t kg = k_code >= 0 ? std::min(k_code, n) : 0;
-        if (k_code == -1) { const double c = ceil(k_val * (double)n); kg = c < (double)n ? (int64_t)c : n; }
+        const int64_t kg = ag_sel_count(n, k_val, k_code);
         // doubled mid-ranks and top-k membership of one vector: positions in the order value descending, then index
         std::vector<int64_t> r2[2];
         std::vector<uint8_t> top[2];
@@ -1764,13 +1629,8 @@ HOST_EXPORT int cal_intervene_pairs(const float* xo, int64_t B, const float* xc,
     return 0;
 }
 
-// ---- Weisfeiler-Lehman refinement and the WL subtree kernel (cal_amd/csrc/wl.hip; cal_amd/wl.py): the same integer formulas,
-// graph by graph; the match counts colours through a sorted copy, as the device does.
-namespace {
-inline uint64_t wl_next(uint64_t c, uint64_t so, uint64_t si) {
-    return splitmix64(splitmix64(splitmix64(c + CAL_WL_C_SELF) + so) + si);
-}
-}  // namespace
+// ---- Weisfeiler-Lehman refinement and the WL subtree kernel (cal_amd/csrc/wl.hip; cal_amd/wl.py): the same integer formulas
+// (wl_next and the constants: rules.hpp), graph by graph; the match counts colours through a sorted copy, as the device does.
 
 HOST_EXPORT int64_t cal_wl_ws(int64_t, int64_t, int64_t) { return 0; }
 
@@ -1790,10 +1650,10 @@ HOST_EXPORT int cal_wl_refine(const int64_t* edge_index, int64_t E, int64_t N, c
     int64_t ignored = 0;
 #pragma omp parallel for schedule(dynamic, 16) reduction(+ : ignored)
     for (int64_t g = 0; g < B; ++g) {
-        int64_t nlo, nhi, elo, ehi;
-        seg_clamp(ptr, g, N, nlo, nhi);
-        seg_clamp(edge_ptr, g, E, elo, ehi);
-        const int64_t n = nhi - nlo;
+        int64_t nlo, n, elo, em;
+        seg_clamp(ptr, g, N, nlo, n);
+        seg_clamp(edge_ptr, g, E, elo, em);
+        const int64_t nhi = nlo + n, ehi = elo + em;
         auto inside = [&](int64_t e) {
             const int64_t u = edge_index[e], v = edge_index[E + e];
             return u >= nlo && u < nhi && v >= nlo && v < nhi;
@@ -1807,13 +1667,13 @@ HOST_EXPORT int cal_wl_refine(const int64_t* edge_index, int64_t E, int64_t N, c
             }
             continue;
         }
-        for (int64_t v = nlo; v < nhi; ++v) col[v] = splitmix64((init ? (uint64_t)init[v] : 0ull) ^ CAL_WL_C_INIT);
+        for (int64_t v = nlo; v < nhi; ++v) col[v] = splitmix64((init ? (uint64_t)init[v] : 0ull) ^ kWlInit);
         std::vector<uint64_t> so((size_t)n), si((size_t)n);
-        uint64_t h = splitmix64((uint64_t)n ^ CAL_WL_C_GRAPH);
+        uint64_t h = splitmix64((uint64_t)n ^ kWlGraph);
         for (int64_t t = 0;; ++t) {
             const uint64_t* c = col + t * N;
             uint64_t s = 0;
-            for (int64_t v = nlo; v < nhi; ++v) s += splitmix64(c[v] ^ CAL_WL_C_NODE);
+            for (int64_t v = nlo; v < nhi; ++v) s += splitmix64(c[v] ^ kWlNode);
             h = splitmix64(h + s);
             hrow[t] = h;
             if (t == T) break;
@@ -1822,8 +1682,8 @@ HOST_EXPORT int cal_wl_refine(const int64_t* edge_index, int64_t E, int64_t N, c
             for (int64_t e = elo; e < ehi; ++e) {
                 if (!inside(e)) continue;
                 const int64_t u = edge_index[e], v = edge_index[E + e];
-                so[(size_t)(u - nlo)] += splitmix64(c[v] ^ CAL_WL_C_OUT);
-                si[(size_t)(v - nlo)] += splitmix64(c[u] ^ CAL_WL_C_IN);
+                so[(size_t)(u - nlo)] += splitmix64(c[v] ^ kWlOut);
+                si[(size_t)(v - nlo)] += splitmix64(c[u] ^ kWlIn);
             }
             for (int64_t v = nlo; v < nhi; ++v) col[(t + 1) * N + v] = wl_next(c[v], so[(size_t)(v - nlo)], si[(size_t)(v - nlo)]);
         }
@@ -1847,9 +1707,10 @@ HOST_EXPORT int cal_wl_match(const int64_t* colors_a, int64_t stride_a, int64_t 
     const uint64_t* cp = reinterpret_cast<const uint64_t*>(colors_p);
 #pragma omp parallel for schedule(dynamic, 16)
     for (int64_t g = 0; g < A; ++g) {
-        int64_t lo, hi;
-        seg_clamp(ptr_a, g, Na, lo, hi);
-        const bool skip = hi - lo > max_nodes_a;
+        int64_t lo, na;
+        seg_clamp(ptr_a, g, Na, lo, na);
+        const int64_t hi = lo + na;
+        const bool skip = na > max_nodes_a;
         std::vector<uint64_t> srt;
         for (int64_t t = 0; t <= T; ++t) {
             int64_t own = 0;
@@ -1865,9 +1726,9 @@ HOST_EXPORT int cal_wl_match(const int64_t* colors_a, int64_t stride_a, int64_t 
             }
             self_a[g * (T + 1) + t] = own;
             for (int64_t p = 0; p < P; ++p) {
-                int64_t plo, phi, cnt = 0;
-                seg_clamp(ptr_p, p, Np, plo, phi);
-                for (int64_t w = plo; w < phi && !skip; ++w) {
+                int64_t plo, np, cnt = 0;
+                seg_clamp(ptr_p, p, Np, plo, np);
+                for (int64_t w = plo; w < plo + np && !skip; ++w) {
                     const auto r = std::equal_range(srt.begin(), srt.end(), cp[t * stride_p + w]);
                     cnt += (int64_t)(r.second - r.first);
                 }
@@ -1878,58 +1739,9 @@ HOST_EXPORT int cal_wl_match(const int64_t* colors_a, int64_t stride_a, int64_t 
     return 0;
 }
 
-// ---- exact motif matching (cal_amd/csrc/motif.hip; cal_amd/motif.py): the same plan, roots, steps and key, graph by graph.
+// ---- exact motif matching (cal_amd/csrc/motif.hip; cal_amd/motif.py): the plan and the key of rules.hpp, the same roots and steps,
+// graph by graph.
 namespace {
-constexpr int kMotifN = CAL_MOTIF_MAX_NODES, kMotifK = CAL_MOTIF_MAX_PATTERN;
-
-struct MotifPlan {
-    int k, pi[kMotifK], parent[kMotifK];
-    unsigned padj[kMotifK];     // by position: bit j set iff pi[d] and pi[j] are adjacent
-    int64_t lo, edges;
-};
-
-// A pattern's plan from its columns; false: no node, too many nodes or not connected.
-bool motif_plan(const int64_t* ei, int64_t PE, int64_t elo, int64_t ehi, int64_t nlo, int64_t k, MotifPlan& q) {
-    if (k < 1 || k > kMotifK) return false;
-    unsigned adj[kMotifK] = {};
-    for (int64_t e = elo; e < ehi; ++e) {
-        const int64_t u = ei[e] - nlo, v = ei[PE + e] - nlo;
-        if (u < 0 || u >= k || v < 0 || v >= k || u == v) continue;
-        adj[u] |= 1u << v;
-        adj[v] |= 1u << u;
-    }
-    unsigned placed = 0;
-    q.edges = 0;
-    for (int d = 0; d < k; ++d) {
-        int bestn = -1, bests = -1;
-        for (int i = 0; i < k; ++i) {
-            if (placed >> i & 1u) continue;
-            const int s = __builtin_popcount(d ? adj[i] & placed : adj[i]);
-            if (s > bests) {
-                bests = s;
-                bestn = i;
-            }
-        }
-        if (d && bests == 0) return false;                            // not connected
-        q.pi[d] = bestn;
-        placed |= 1u << bestn;
-        q.edges += __builtin_popcount(adj[d]);
-    }
-    for (int d = 0; d < k; ++d) {
-        q.padj[d] = 0;
-        q.parent[d] = -1;
-        for (int j = 0; j < k; ++j)
-            if (adj[q.pi[d]] >> q.pi[j] & 1u) {
-                q.padj[d] |= 1u << j;
-                if (q.parent[d] < 0 && j < d) q.parent[d] = j;
-            }
-    }
-    q.k = (int)k;
-    q.lo = nlo;
-    q.edges /= 2;
-    return true;
-}
-
 struct MotifGraph {
     int n;
     uint64_t adj[kMotifN][4];
@@ -1945,26 +1757,20 @@ struct MotifGraph {
     }
 };
 
-inline uint64_t motif_key(const MotifPlan& q, const int* img) {
-    uint64_t key = q.k < kMotifK ? ~0ull >> (8 * q.k) : 0ull;
-    for (int d = 0; d < q.k; ++d) key |= (uint64_t)img[d] << (56 - 8 * q.pi[d]);
-    return key;
-}
-
 // one pattern in one graph -> count, truncated roots, the smallest key
 void motif_search(const MotifGraph& G, const MotifPlan& q, const int64_t* plab, int induced, uint64_t budget, uint64_t& cnt,
                   uint64_t& trc, uint64_t& best) {
     cnt = trc = 0;
     best = ~0ull;
     const int k = q.k, n = G.n;
-    auto label_ok = [&](int v, int d) { return !G.lab || G.lab[v] == plab[q.lo + q.pi[d]]; };
+    auto label_ok = [&](int v, int d) { return !G.lab || G.lab[v] == plab[q.lo + motif_node(q, d)]; };
     int img[kMotifK], cur[kMotifK];
     if (k == 1) {
         for (int v = 0; v < n; ++v)
             if (label_ok(v, 0)) {
                 ++cnt;
                 img[0] = v;
-                best = std::min(best, motif_key(q, img));
+                best = std::min<uint64_t>(best, motif_key(q, img));
             }
         return;
     }
@@ -1975,14 +1781,14 @@ void motif_search(const MotifGraph& G, const MotifPlan& q, const int64_t* plab, 
             img[1] = w;
             if (k == 2) {
                 ++cnt;
-                best = std::min(best, motif_key(q, img));
+                best = std::min<uint64_t>(best, motif_key(q, img));
                 continue;
             }
             uint64_t steps = 0;
             int d = 2;
             cur[2] = 0;
             for (;;) {
-                const int v = G.next(img[q.parent[d]], cur[d]);
+                const int v = G.next(img[motif_parent(q, d)], cur[d]);
                 if (v >= kMotifN) {
                     if (d == 2) break;
                     --d;
@@ -1997,13 +1803,13 @@ void motif_search(const MotifGraph& G, const MotifPlan& q, const int64_t* plab, 
                 bool ok = label_ok(v, d);
                 for (int j = 0; j < d && ok; ++j) {
                     const bool a = G.has(v, img[j]);
-                    ok = img[j] != v && ((q.padj[d] >> j & 1u) ? a : !(induced && a));
+                    ok = img[j] != v && ((motif_adj(q, d) >> j & 1u) ? a : !(induced && a));
                 }
                 if (!ok) continue;
                 img[d] = v;
                 if (d == k - 1) {
                     ++cnt;
-                    best = std::min(best, motif_key(q, img));
+                    best = std::min<uint64_t>(best, motif_key(q, img));
                 } else {
                     ++d;
                     cur[d] = 0;
@@ -2043,17 +1849,16 @@ HOST_EXPORT int cal_motif_match(const int64_t* edge_index, int64_t E, int64_t N,
     int64_t ignored = 0;
 #pragma omp parallel for schedule(dynamic, 1) reduction(+ : ignored)
     for (int64_t g = 0; g < B; ++g) {
-        int64_t nlo, nhi, elo, ehi;
-        seg_clamp(ptr, g, N, nlo, nhi);
-        seg_clamp(edge_ptr, g, E, elo, ehi);
-        const int64_t n = nhi - nlo;
+        int64_t nlo, n, elo, em;
+        seg_clamp(ptr, g, N, nlo, n);
+        seg_clamp(edge_ptr, g, E, elo, em);
         const bool skip = n > kMotifN;
         std::vector<MotifGraph> box(1);
         MotifGraph& G = box[0];
         G.n = skip ? 0 : (int)n;
         G.lab = labelled ? labels + nlo : nullptr;
         memset(G.adj, 0, sizeof(G.adj));
-        for (int64_t e = elo; e < ehi; ++e) {
+        for (int64_t e = elo; e < elo + em; ++e) {
             const int64_t u = edge_index[e] - nlo, v = edge_index[E + e] - nlo;
             if (!(u >= 0 && u < n && v >= 0 && v < n)) {
                 ++ignored;
