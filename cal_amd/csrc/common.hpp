@@ -210,6 +210,15 @@ __device__ __forceinline__ void randperm_slice(int64_t* __restrict__ perm, int B
     r += __shfl_xor(r, 2, 64);
     if (q == 0 && i < B) perm[r] = i;
 }
+// The same draw keyed by *counter + ahead: for a workgroup that runs beside the kernel that advances the counter (the plan part of
+// k_finish_plan draws the NEXT step's permutation while the commit part writes the advanced counter to another word)
+template <int NT>
+__device__ __forceinline__ void randperm_slice(int64_t* __restrict__ perm, int B, unsigned long long seed,
+                                               const unsigned long long* __restrict__ counter, unsigned long long ahead,
+                                               unsigned long long* key, int part) {
+    const unsigned long long cnt = *counter + ahead;
+    randperm_slice<NT>(perm, B, seed, &cnt, key, part);
+}
 
 // Touch every 64 B line of the kernel-argument segment in ONE round of scalar loads at the top of a kernel: hipcc sinks
 // argument loads into the blocks that use them, and each first touch of another line is a scalar-cache miss (a few

@@ -36,39 +36,12 @@
 #include "engine_feat.hpp"
 #include "engine_gwide.hpp"
 #include "engine_attwide.hpp"
+#include "engine_finish.hpp"        // FinishArgs; ChainPlan / ChainCtl (the kernel that takes them is in finish_plan.hip)
 #include "engine_attfwd_fold.hpp"     // AttFwdFoldArgs (the kernel that takes them is in gconv_fwd_att.hip)
 #include "engine_unit.hpp"            // the entries of the side units (gconv_fwd_att.hip, gconv_bwd_att.hip, gconv_bwd_seq.hip)
 
 namespace cal {
 
-constexpr int MAX_LAYERS = 6;
-constexpr int MAX_SLABS = 24;
-constexpr int MAX_COMMITS = 64;
-
-struct FinishArgs {
-    SlabTask st[MAX_SLABS];
-    CommitTask ct[MAX_COMMITS];
-    int nst, nct;
-    float* stats;            // fused readout: stats[0] = wc*stats[1] + wo*stats[2] + wco*stats[3]
-    float wc, wo, wco;
-    float* tick;             // Adam step counter to advance (the update follows in the same step) or null
-    float* ticked;           // Adam step counter the step's FIRST kernel has already advanced (k_zero_f64), or null: taken back here when the
-                             // step is flagged -- whether the update rides in this kernel (adam.on) or follows as k_adam (range overflow)
-    unsigned long long* perm_ctr;   // counter of the in-step permutation draw to advance (k_zero_f64's rank-sort workgroups only read it), or null
-    // Adam inside this kernel (single-process steps, mode bit 4 without bit 8): every gradient element is updated by the
-    // thread that finishes it, the ranges no task writes (gradients other kernels stored directly) by `nar` extra tasks
-    // of 256 elements per block; the step counter was advanced by the step's FIRST kernel (a ticket of 2700 blocks on one
-    // address, each behind a device-scope fence, cost 47 us)
-    AdamArgs adam;
-    AdamRange ar[MAX_ADAM_RANGES];
-    int nar;
-    double* bn0z; int bn0z_n;   // bn_feat's statistics range of the fp64 arena: zeroed HERE for the next step (engine_plan.hpp: PlanFold)
-    int* dirty;              // the device word of that invariant, cleared here
-    int* host_status;        // host-mapped mirror of status[0] | status[1], written by this kernel (cal_engine_peek_status), or null
-    const int* status;       // the engine's status words: while any bit is up (this step's or a sticky earlier one) the gradients are
-                             // not trusted and NO parameter / moment is updated (check_status raises and clears them)
-    int blk0[MAX_SLABS + MAX_COMMITS + MAX_ADAM_RANGES + 1];   // first block of every task in the flattened 1-D grid (filled at launch)
-};
 // grid: 1-D, task t owns blocks [blk0[t], blk0[t+1]): n/64 per slab task, ceil(n/16) per commit task (a
 // (64, tasks) grid spent most of its ~12k blocks on nothing once the slab tasks wanted 256 blocks each)
 __global__ void __launch_bounds__(256) k_finish(const FinishArgs fa, float* __restrict__ grad) {
@@ -95,74 +68,7 @@ __global__ void __launch_bounds__(256) k_finish(const FinishArgs fa, float* __re
     }
     if (fa.host_status && fa.status && blockIdx.x == 0 && threadIdx.x == 0)
         __hip_atomic_store(fa.host_status, fa.status[0] | fa.status[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    // Both task kinds are pure reductions over S slabs / P partial rows: the loops keep 8 loads in flight
-    // per lane (unconditional on a clamped index, pinned, masked when added) -- as dependent loops with
-    // two loads in flight the 58-slab weight-gradient sums made this kernel 11 us.
-    if (task < fa.nst) {
-        // 64 elements per block pass, the S slabs split over the block's 4 waves (S = #graphs = 128 with the
-        // per-graph fused backward): 4x shorter load chains, combined through LDS in a fixed order
-        const SlabTask t = fa.st[task];
-        __shared__ float sred[256];
-        const int el = threadIdx.x & 63, grp = threadIdx.x >> 6;
-        const int per = (t.S + 3) / 4, z_lo = grp * per, z_hi = min(t.S, z_lo + per);
-        for (int i0 = bx * 64; i0 < t.n; i0 += nbx * 64) {
-            const int i = min(i0 + el, t.n - 1);
-            float s0 = 0.f, s1 = 0.f;
-            for (int z0 = z_lo; z0 < z_hi; z0 += 8) {
-                float v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = t.slabs[(size_t)max(min(z0 + u, z_hi - 1), 0) * t.n + i];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) asm volatile("" : "+v"(v[u]));
-#pragma unroll
-                for (int u = 0; u < 8; u += 2) {
-                    s0 += z0 + u < z_hi ? v[u] : 0.f;
-                    s1 += z0 + u + 1 < z_hi ? v[u + 1] : 0.f;
-                }
-            }
-            sred[threadIdx.x] = s0 + s1;
-            __syncthreads();
-            if (grp == 0 && i0 + el < t.n) {
-                const float gsum = (sred[el] + sred[64 + el]) + (sred[128 + el] + sred[192 + el]);
-                t.dst[i] = gsum;
-                if (A.on) adam_update(A, (t.dst - grad) + i, gsum, adam_t, adam_lr);
-            }
-            __syncthreads();
-        }
-    } else if (task - fa.nst < fa.nct) {
-        const CommitTask t = fa.ct[task - fa.nst];
-        // 16 part-lanes x 16 columns per block pass
-        __shared__ double red[256];
-        const int pl = threadIdx.x >> 4, cl = threadIdx.x & 15;
-        for (int c0 = bx * 16; c0 < t.n; c0 += nbx * 16) {
-            const int c = c0 + cl, cc = min(c, t.n - 1);
-            double sacc = 0.0;
-            for (int q0 = pl; q0 < t.P; q0 += 16 * 8) {
-                double v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = t.src[(size_t)max(min(q0 + 16 * u, t.P - 1), 0) * t.stride + cc];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) asm volatile("" : "+v"(v[u]));
-#pragma unroll
-                for (int u = 0; u < 8; ++u) sacc += q0 + 16 * u < t.P ? v[u] : 0.0;
-            }
-            red[threadIdx.x] = sacc;
-            __syncthreads();
-            if (pl == 0 && c < t.n) {
-                double tot = 0.0;
-#pragma unroll
-                for (int k = 0; k < 16; ++k) tot += red[k * 16 + cl];
-                const float gv = t.scale * (float)tot;
-                grad[t.dst + c] = gv;
-                if (A.on) adam_update(A, t.dst + c, gv, adam_t, adam_lr);
-            }
-            __syncthreads();
-        }
-    } else if (A.on) {
-        const AdamRange r = fa.ar[task - fa.nst - fa.nct];
-        const int64_t i = r.begin + (int64_t)bx * 256 + threadIdx.x;
-        if (i < r.end) adam_update(A, i, grad[i], adam_t, adam_lr);
-    }
+#include "engine_finish_body.hpp"
 }
 
 struct BNSlot { int gamma, beta; int width; float* rm; float* rv; int64_t* nbt; int arena; };
@@ -241,6 +147,18 @@ struct Engine {
     // value of adam_in_finish the step ended with (0: no update in k_finish, 1: in k_finish, 2: fell back to k_adam)
     struct FinishIv { int64_t begin, end; int kind; } fin_iv[MAX_SLABS + MAX_COMMITS + MAX_ADAM_RANGES];
     int fin_n, fin_adam;
+    // chained steps (finish_plan.hip; DESIGN.md section 7, "Chained steps"): a step whose successor is known (cal_engine_set_next) ends
+    // with k_finish_plan, which also plans the successor; that step then skips fwd_plan and runs on the other fp64 arena
+    int chain;               // 1: on; CAL_AMD_CHAIN=0 / cal_engine_set_chain(h, 0): every step ends with k_finish and starts with its own plan
+    int chain_ok;            // 0 after cal_engine_chain_reset dropped a planned step: arena 1 is no longer known to be clean (until the next workspace)
+    double* arena2[2];       // the two arenas; `arena` is the current step's: arena2[0] for a stand-alone step, alternating inside a chain
+    // a batch as a step call describes it; `next`: announced by cal_engine_set_next for the coming call only; `planned`: what the
+    // latest k_finish_plan planned for -- the next cal_engine_step must be for exactly this (valid: 1 while a planned step is owed)
+    struct BatchDesc {
+        const float* x0; const int64_t* ei; const int64_t* batch; int64_t N, E, B;
+        const int64_t *node_ptr, *edge_ptr, *tile_gptr; int ntiles, max_nodes, max_edges;
+        int mode, parity, valid; const char* ws;
+    } next, planned;
 };
 
 static size_t al(size_t n) { return (n + 63) / 64 * 64; }   // 256 B granules (in floats/ints)
@@ -286,6 +204,7 @@ CAL_EXPORT void* cal_engine_create(int64_t F, int64_t H, int64_t C, int64_t L) {
     e->gwide = env_on("CAL_AMD_GWIDE"); e->fold_zero = env_on("CAL_AMD_FOLD_ZERO"); e->att_fold = env_on("CAL_AMD_ATT_FOLD");
     e->att_fwd_fold = env_on("CAL_AMD_ATT_FWD_FOLD");
     e->adam_fused = env_on("CAL_AMD_ADAM_FUSED");
+    e->chain = env_on("CAL_AMD_CHAIN");
     e->bn0_dirty_host = 1;
     {
         // k_ro_step's 3 * H / 16 workgroups (133 KB of LDS each: one per CU) meet at spin barriers: they must all be
@@ -418,7 +337,7 @@ static size_t engine_layout(Engine* e, int64_t N, int64_t E, int64_t B, bool ass
     {
         float* tmp = nullptr;
         F32(tmp, 2 * (size_t)e->arena_n);
-        if (assign) e->arena = (double*)tmp;
+        if (assign) e->arena = e->arena2[0] = (double*)tmp;
         // partial rows of the cross-row sums: <= 1024 producer blocks x (2..6)H columns per set,
         // ~(3L + 16) sets alive per step
         size_t pcap = std::max<size_t>((N + 15) / 16 + 1, (std::min<int64_t>(N, 16384) + 7) / 8 + 1);
@@ -445,6 +364,14 @@ static size_t engine_layout(Engine* e, int64_t N, int64_t E, int64_t B, bool ass
         F32(e->gws, (size_t)cal_gat_bwd_ws(N, E, K, H / K));
     }
     F32(e->att_xch, (size_t)std::min<size_t>(B, AFF_MAXT) * 2 * AFF_XCH);
+    {
+        // the second arena of chained steps ("arena1"), behind everything else so that every other buffer keeps its offset: whoever
+        // sets the workspace zeroes it once (StepEngine.reserve) -- a chain's first k_finish_plan adds bn_feat's sums of the next batch
+        // into it, and only a commit that ran on it cleans that range
+        float* tmp = nullptr;
+        F32(tmp, 2 * (size_t)e->arena_n);
+        if (assign) e->arena2[1] = (double*)tmp;
+    }
     return off * 4;
 }
 
@@ -477,6 +404,7 @@ CAL_EXPORT int cal_engine_set_workspace(void* h, void* ws, int64_t bytes, int64_
     CAL_REQUIRE((int64_t)need <= bytes, "workspace too small");
     e->ws_bytes = bytes;
     e->bn0_dirty_host = 1;          // nothing is known about the new arena: the next step zeroes all of it (k_zero_f64)
+    e->planned.valid = 0; e->next.valid = 0; e->chain_ok = 1;
     return 0;
 }
 
@@ -489,7 +417,7 @@ CAL_EXPORT int64_t cal_engine_buffer_offset(void* h, const char* name) {
         {"zl", e->zl}, {"logp", e->logp}, {"stats", e->stats}, {"dzl", e->dzl}, {"dyh1", e->dyh1}, {"dy1", e->dy1},
         {"dxh", e->dxh}, {"dpool", e->dpool}, {"dZco", e->dZco}, {"gn", e->gn}, {"gself", e->gself}, {"ddeg", e->ddeg},
         {"dl", e->dl}, {"dzco", e->dzco}, {"dXhco", e->dXhco}, {"dZ", e->dZ}, {"dzi", e->dzi}, {"dXh", e->dXh},
-        {"arena", e->arena}, {"gptr", e->gptr}, {"status", e->status}, {"eptr", e->eptr},
+        {"arena", e->arena2[0]}, {"arena1", e->arena2[1]}, {"gptr", e->gptr}, {"status", e->status}, {"eptr", e->eptr},
         {"gt1", e->gin ? e->gt1 : nullptr}, {"gy", e->gin ? e->gy : nullptr},
         {"rowptr_dst", e->rowptr_dst}, {"nbr_dst", e->nbr_dst}, {"eid_dst", e->eid_dst},
         {"rowptr_src", e->rowptr_src}, {"nbr_src", e->nbr_src}, {"eid_src", e->eid_src}, {"perm", e->perm_dev}, {"ones", e->ones},
@@ -569,6 +497,11 @@ struct Ctx {
     int draw_perm;      // the step draws its own intervention permutation (first kernel) into Engine::perm_dev
     int tick_in_finish; // the step ends with the Adam update: k_finish advances the step counter
     int adam_in_finish; // k_finish applies Adam to every gradient it completes (no k_adam launch)
+    int chained_in;     // the previous step's k_finish_plan has planned this batch: no fwd_plan, arena and counter words of `parity`
+    int chain_out;      // the step ends with k_finish_plan, which plans Engine::next (decided before the forward; bwd_commit may still
+                        // fall back when Adam does not fit the commit launch)
+    int parity;         // position in the chain, mod 2 (0: a stand-alone step or a chain's first)
+    int mode;
     size_t parts_off;   // bump allocator over Engine::parts
     FinalArgs fin;      // pending k_stats_final tasks
     Route r;
@@ -589,6 +522,8 @@ struct Bwd {
     float* slabs_at(Ctx& c, size_t at, int S, int n, float* dst);
     double* defer(Ctx& c, Deferred& d, int P, int cols);
 };
+
+void next_ctx(Ctx& cn, Engine* e, hipStream_t st, const Engine::BatchDesc& d, int mode);
 
 BNRef bnref(const Ctx& c, int k, int rows, int update) {
     const Engine* e = c.e;
@@ -1111,6 +1046,10 @@ int fwd_plan(Ctx& c, const float* x0, const int64_t* edge_index) {
     const int N = c.N, B = c.B, T = c.T, F = e->F;
     const int64_t E = c.E;
     hipStream_t st = c.st;
+    if (c.chained_in) {                             // planned by the previous step's last launch (k_finish_plan), PlanFold duties included
+        if (c.training) e->bn0_dirty_host = 1;
+        return 0;
+    }
     const bool graph_plan = r.plan == Plan::Graph256 || r.plan == Plan::Graph1024;
     const bool fold = e->fold_zero && graph_plan && c.training && c.want_grad && !e->bn0_dirty_host && g_stop_after == 0;
     if (c.training) e->bn0_dirty_host = 1;          // (cleared where k_finish is enqueued)
@@ -2160,6 +2099,59 @@ int bwd_feat(Ctx& c, Bwd& b, const float* x0) {
     return 0;
 }
 
+// The commit as k_finish_plan (finish_plan.hip): beside it the plan of Engine::next (plan_next), or alone as the finish-only launch
+// that ends a chain.  The words a stand-alone pair of launches shares go through in / out addresses here (engine_finish.hpp,
+// ChainCtl): position j of a chain reads the words of parity j & 1 and writes those of the other parity; the chain's first step
+// reads, and its last step writes, the tensors the optimizer and the permutation stream are bound to.
+int commit_chained(Ctx& c, FinishArgs& fa, int nblk, bool plan_next) {
+    Engine* e = c.e;
+    const int p = c.parity, q = p ^ 1;
+    float* step_w = (float*)(e->status + ST_STEP);
+    unsigned long long* ctr_w = (unsigned long long*)(e->status + ST_CTR);
+    ChainPlan pn; ChainCtl ctl;
+    memset(&pn, 0, sizeof(pn)); memset(&ctl, 0, sizeof(ctl));
+    ctl.step_in = c.chained_in ? step_w + p : e->step;
+    ctl.step_out = plan_next ? step_w + q : e->step;
+    if (c.draw_perm) {
+        ctl.ctr_in = c.chained_in ? ctr_w + p : e->perm_ctr;
+        ctl.ctr_out = plan_next ? ctr_w + q : e->perm_ctr;
+    }
+    ctl.pend_cur = c.chained_in ? e->status + ST_PEND + p : nullptr;
+    if (ctl.step_in == ctl.step_out || (c.draw_perm && ctl.ctr_in == ctl.ctr_out)) { set_error("engine: a chained commit would read the word it writes"); return 2; }
+    fa.tick = nullptr; fa.ticked = nullptr; fa.perm_ctr = nullptr;      // (ChainCtl's words instead)
+    fa.adam.step = const_cast<float*>(ctl.step_in);
+    if (plan_next) {
+        const Engine::BatchDesc& d = e->next;
+        Ctx cn;
+        next_ctx(cn, e, c.st, d, c.mode);
+        const int wp0 = (e->bn[0].width + 3) / 4 * 4;
+        double* an = e->arena2[q];
+        pn.ei = d.ei; pn.E = d.E; pn.N = (int)d.N; pn.B = cn.T;
+        pn.node_ptr = d.node_ptr; pn.edge_ptr = d.edge_ptr; pn.batch = d.batch; pn.tile_gptr = d.ntiles > 0 ? d.tile_gptr : nullptr;
+        pn.Bgraphs = (int)d.B; pn.loop_w = e->loop_w;
+        pn.ptr_dst = e->rowptr_dst; pn.nbr_dst = e->nbr_dst; pn.eid_dst = e->eid_dst;
+        pn.ptr_src = e->rowptr_src; pn.nbr_src = e->nbr_src; pn.eid_src = e->eid_src;
+        pn.row32 = e->row32; pn.col32 = e->col32; pn.gptr = e->gptr; pn.eptr = e->eptr; pn.dis_unit = e->dis_unit;
+        pn.pending = e->status + ST_PEND + q;
+        pn.x0 = cn.r.plan_stats ? d.x0 : nullptr; pn.F = e->F;
+        pn.st_sum = an + e->bn[0].arena; pn.st_sq = an + e->bn[0].arena + wp0;
+        pn.coef_dst = cn.r.plan_coef ? e->coef : nullptr; pn.coef_src = cn.r.plan_coef ? e->coef_src : nullptr;
+        pn.arena = an; pn.n = e->arena_n; pn.skip_lo = e->bn[0].arena; pn.skip_hi = e->bn[0].arena + 2 * wp0;
+        pn.gat_tick = e->K > 0 ? e->gat_ctr : nullptr;
+        pn.perm = c.draw_perm ? e->perm_dev : nullptr; pn.permB = (int)d.B; pn.seed = e->perm_seed;
+        ctl.nplan = cn.T + (c.draw_perm ? cdiv((int)d.B, 256 / 4) : 0);
+    }
+    const calunit::LaunchSite at{dim3(ctl.nplan + nblk), c.st, nullptr, nullptr};
+    const int rc = cal_launch_finish_plan(at, &fa, sizeof(fa), e->G, &pn, sizeof(pn), &ctl, sizeof(ctl));
+    if (rc) { set_error("engine: finish_plan.hip was built with other structures than engine.hip (code %d)", rc); return 2; }
+    CAL_CHECK_LAUNCH(plan_next ? "k_finish_plan" : "k_finish_plan(finish)"); STAGE();
+    e->bn0_dirty_host = 0;          // bn_feat's statistics range of this step's arena is clean again behind this launch (PlanFold)
+    if (plan_next) {
+        e->planned = e->next; e->planned.valid = 1; e->planned.parity = q; e->planned.mode = c.mode; e->planned.ws = e->ws;
+    }
+    return 0;
+}
+
 // commits: fp64 arena / partial rows -> fp32 gradients, the slab sums and (single-process steps) Adam in one k_finish
 int bwd_commit(Ctx& c, Bwd& b) {
     Engine* e = c.e;
@@ -2241,6 +2233,8 @@ int bwd_commit(Ctx& c, Bwd& b) {
     for (int i = 0; i < fa.nct; ++i) { fa.blk0[fa.nst + i] = nblk; nblk += std::max(1, cdiv(fa.ct[i].n, 16)); }
     for (int i = 0; i < fa.nar; ++i) { fa.blk0[fa.nst + fa.nct + i] = nblk; nblk += (int)cdiv(fa.ar[i].end - fa.ar[i].begin, 256); }
     fa.blk0[fa.nst + fa.nct + fa.nar] = nblk;
+    const bool plan_next = c.chain_out && c.adam_in_finish == 1;
+    if (plan_next || c.chained_in) return commit_chained(c, fa, nblk, plan_next);
     hipLaunchKernelGGL(k_finish, dim3(nblk), dim3(256), 0, c.st, fa, e->G);
     CAL_CHECK_LAUNCH("k_finish"); STAGE();
     e->bn0_dirty_host = 0;          // bn_feat's statistics range is clean again behind this launch (PlanFold)
@@ -2280,6 +2274,30 @@ void ctx_init(Ctx& c, Engine* e, void* stream, int64_t N, int64_t E, int64_t B, 
     c.r = make_route(c, c.want_grad);
 }
 
+// The Ctx (and so the route) of the batch `d` in a `mode` step: the engine's description of the coming batch is swapped for d's
+// while the route is made
+void next_ctx(Ctx& cn, Engine* e, hipStream_t st, const Engine::BatchDesc& d, int mode) {
+    const Engine::BatchDesc cur{nullptr, nullptr, nullptr, 0, 0, 0, e->node_ptr, e->edge_ptr, e->tile_gptr, e->ntiles, e->max_nodes, e->max_edges, 0, 0, 0, nullptr};
+    e->node_ptr = d.node_ptr; e->edge_ptr = d.edge_ptr; e->tile_gptr = d.tile_gptr; e->ntiles = d.ntiles;
+    e->max_nodes = d.max_nodes; e->max_edges = d.max_edges;
+    ctx_init(cn, e, st, d.N, d.E, d.B, d.batch, mode);
+    e->node_ptr = cur.node_ptr; e->edge_ptr = cur.edge_ptr; e->tile_gptr = cur.tile_gptr; e->ntiles = cur.ntiles;
+    e->max_nodes = cur.max_nodes; e->max_edges = cur.max_edges;
+}
+// May a `mode` step of context c end with k_finish_plan for Engine::next?  (Adam inside the commit, the successor on the 256-thread
+// per-graph plan with the PlanFold, both batches inside the workspace; otherwise the step ends and the next one starts as ever)
+bool can_chain(const Ctx& c, Engine* e, int mode) {
+    const Engine::BatchDesc& d = e->next;
+    if (!e->chain || !e->chain_ok || !d.valid || g_stop_after != 0 || g_prof_on) return false;
+    if (c.adam_in_finish != 1 || (mode & 8) || !c.training || !c.want_grad || !e->fold_zero) return false;
+    if (d.N <= 0 || d.B <= 0 || d.N > e->capN || d.E > e->capE || d.B > e->capB || d.ntiles > d.B) return false;
+    if (c.draw_perm && d.B > ZP_CAP) return false;
+    if (!d.node_ptr || !d.edge_ptr) return false;
+    Ctx cn;
+    next_ctx(cn, e, c.st, d, mode);
+    return cn.r.plan == Plan::Graph256;
+}
+
 // Adam as one kernel over the flat parameter buffer; ticked: the step counter has already been advanced (by the step's k_finish)
 int launch_adam(Engine* e, hipStream_t st, int ticked) {
     hipLaunchKernelGGL(k_adam, dim3(cdiv(e->nparam, 256)), dim3(256), 0, st, e->P, e->G, e->M1, e->M2, e->step, e->lr, e->beta1,
@@ -2314,12 +2332,31 @@ CAL_EXPORT int cal_engine_step(void* h, const float* x0, const int64_t* edge_ind
     CAL_REQUIRE(!(mode & 8) || want_grad, "mode bit 8 (Adam follows a gradient exchange) needs the backward pass");
     CAL_REQUIRE(!want_grad || (mode & 1), "backward needs a training-mode forward");
     CAL_REQUIRE(!(mode & 4) || want_grad, "the Adam update needs the backward pass in the same step");
+    if (e->planned.valid) {
+        // the previous step's last launch has planned a batch: this call must be for it (nothing is enqueued otherwise, and nothing re-planned)
+        const Engine::BatchDesc& d = e->planned;
+        const bool same = d.x0 == x0 && d.ei == edge_index && d.batch == batch && d.N == N && d.E == E && d.B == B && d.mode == mode &&
+                          d.node_ptr == e->node_ptr && d.edge_ptr == e->edge_ptr && d.ntiles == e->ntiles &&
+                          (d.ntiles == 0 || d.tile_gptr == e->tile_gptr) && d.max_nodes == e->max_nodes && d.max_edges == e->max_edges && d.ws == e->ws;
+        if (!same) {
+            e->next.valid = 0;
+            set_error("cal_engine_step: the previous step planned another batch (cal_engine_set_next): this call is not the step it announced "
+                      "(run that step, or cal_engine_chain_reset)");
+            return 2;
+        }
+    }
     Ctx c;
     ctx_init(c, e, stream_, N, E, B, batch, mode);
+    c.mode = mode;
+    c.chained_in = e->planned.valid; c.parity = c.chained_in ? e->planned.parity : 0;
+    e->planned.valid = 0;
+    e->arena = e->arena2[c.parity];
     c.adam_in_finish = ((mode & 4) && e->adam_fused) ? 1 : 0;
     c.draw_perm = (mode & 16) ? 1 : 0;
     c.y = y; c.perm = c.draw_perm ? e->perm_dev : perm; c.wc = wc; c.wo = wo; c.wco = wco;
     c.tick_in_finish = (mode & (4 | 8)) ? 1 : 0;
+    c.chain_out = can_chain(c, e, mode) ? 1 : 0;
+    struct NextOnce { Engine* e; ~NextOnce() { e->next.valid = 0; } } next_once{e};      // an announcement holds for one call
     g_stage = 0;
     g_stage_names.clear();
     {
@@ -2349,6 +2386,7 @@ CAL_EXPORT int cal_engine_backward_from(void* h, const float* x0, const int64_t*
     CAL_REQUIRE(e && e->ws, "engine has no workspace");
     CAL_REQUIRE(N <= e->capN && E <= e->capE && B <= e->capB && N > 0 && B > 0, "bad batch sizes");
     CAL_REQUIRE(e->ntiles <= B, "more tiles than graphs (cal_engine_set_tiles belongs to another batch)");
+    CAL_REQUIRE(!e->planned.valid, "a planned step is owed (cal_engine_set_next): run it first");
     Ctx c;
     ctx_init(c, e, stream_, N, E, B, batch, 1);      // the route of the mode-1 forward it follows
     c.want_grad = 1;
@@ -2421,6 +2459,43 @@ CAL_EXPORT int cal_engine_set_att_fwd_fold(void* h, int on) {
     e->att_fwd_fold = on ? 1 : 0;
     return 0;
 }
+// on = 0: no step ends with k_finish_plan (what CAL_AMD_CHAIN=0 selects process-wide).  Call before a sequence is captured.
+CAL_EXPORT int cal_engine_set_chain(void* h, int on) {
+    Engine* e = (Engine*)h;
+    CAL_REQUIRE(e != nullptr, "bad arguments");
+    e->chain = on ? 1 : 0;
+    return 0;
+}
+// Announce the batch of the step AFTER the coming cal_engine_step (same mode): that step may then end with ONE launch that commits it
+// and plans this batch (k_finish_plan), and the step after it must be called for exactly this batch -- same pointers, sizes, layout
+// (node_ptr / edge_ptr or the tiles' offsets + tile_gptr, the per-graph bounds) and workspace -- or it is refused.  Holds for one
+// call; N = 0 withdraws it.  Whether the engine chains is its own decision (cal_engine_stage_name shows it).
+CAL_EXPORT int cal_engine_set_next(void* h, const float* x0, const int64_t* edge_index, const int64_t* batch, int64_t N, int64_t E, int64_t B,
+                                   const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* tile_gptr, int64_t ntiles,
+                                   int64_t max_nodes, int64_t max_edges) {
+    Engine* e = (Engine*)h;
+    CAL_REQUIRE(e != nullptr && N >= 0 && E >= 0 && B >= 0 && ntiles >= 0 && max_nodes >= 0 && max_edges >= 0, "bad arguments");
+    memset(&e->next, 0, sizeof(e->next));
+    if (N == 0 || !x0 || !edge_index || !batch) return 0;
+    e->next.x0 = x0; e->next.ei = edge_index; e->next.batch = batch; e->next.N = N; e->next.E = E; e->next.B = B;
+    e->next.node_ptr = node_ptr; e->next.edge_ptr = edge_ptr; e->next.tile_gptr = ntiles > 0 ? tile_gptr : nullptr; e->next.ntiles = (int)ntiles;
+    e->next.max_nodes = (int)std::min<int64_t>(max_nodes, 1 << 30); e->next.max_edges = (int)std::min<int64_t>(max_edges, 1 << 30);
+    e->next.valid = 1;
+    return 0;
+}
+// 1 while the latest step has planned its successor and that step is owed
+CAL_EXPORT int64_t cal_engine_chain_pending(void* h) { Engine* e = (Engine*)h; return e && e->planned.valid ? 1 : 0; }
+// Drop a planned step that will not be run (an error path).  The chain's counters never reached the bound tensors and the second
+// arena is no longer clean: the next step zeroes its arena itself and nothing is chained until the workspace is set again.
+CAL_EXPORT int cal_engine_chain_reset(void* h) {
+    Engine* e = (Engine*)h;
+    CAL_REQUIRE(e != nullptr, "bad arguments");
+    if (e->planned.valid) { e->planned.valid = 0; e->chain_ok = 0; e->bn0_dirty_host = 1; }
+    e->next.valid = 0;
+    return 0;
+}
+// doubles of one fp64 arena (buffers "arena", "arena1")
+CAL_EXPORT int64_t cal_engine_arena_doubles(void* h) { Engine* e = (Engine*)h; return e ? e->arena_n : 0; }
 CAL_EXPORT int cal_engine_debug_stop(int k) { g_stop_after = k; return 0; }
 // name of launch site k (1-based, as counted by cal_engine_debug_stop) in the latest untruncated step; "" past the end
 CAL_EXPORT const char* cal_engine_stage_name(int k) {

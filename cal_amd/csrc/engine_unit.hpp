@@ -45,6 +45,10 @@ int cal_launch_gconv_bwd_att(const calunit::LaunchSite& at, const void* csr, siz
 // sel: 1 = two branches (POOL), 2 = packed tiles (POOL only), 4 = dOut given (MODE 0; otherwise UP), 8 = LEAN
 int cal_launch_gconv_bwd_seq(const calunit::LaunchSite& at, int sel, const void* csr, size_t csr_bytes, const int* gptr, const int* eptr,
                              const void* branches, size_t branches_bytes, float loop_w, int N, int H, int K, int* status);
+// finish_plan.hip: k_finish_plan, the step's final commit (FinishArgs) beside the graph plan of the next batch (ChainPlan; B = 0: none) with
+// the counters' in / out words (ChainCtl); 1-D grid of ChainCtl::nplan plan blocks + the commit's blocks, 256 threads
+int cal_launch_finish_plan(const calunit::LaunchSite& at, const void* finish, size_t finish_bytes, float* grad, const void* plan, size_t plan_bytes,
+                           const void* ctl, size_t ctl_bytes);
 }
 
 // A unit's accessor of ITS copies of the clock buffers (engine_kernels.hpp): marks 0 .. 3 to out, 4 .. 7 to outx, 8192 values each

@@ -201,6 +201,8 @@ class StepEngine:
         self.tiles = {"0": False, "force": "force"}.get(os.environ.get("CAL_AMD_TILES", "1"), True)
         self.tile_min_units = 256
         self._tiles = (0, 0)
+        #: a list: every engine call appends the names of the launch sites it passed (tests read which kernels a step ran)
+        self.launch_log = None
         self._identity = {}             # identity permutations by batch size (eval passes, models that do not shuffle)
         self._ws: Optional[torch.Tensor] = None
         self.ws_generation = 0          # bumped whenever the workspace is re-allocated (captured graphs check it)
@@ -216,6 +218,15 @@ class StepEngine:
         layer's forward launch (k_gconv_fwd_att, ``Route::att_fwd_fold``); the environment variable CAL_AMD_ATT_FWD_FOLD=0
         selects the same process-wide.  Call before a step is captured."""
         _lib.call("cal_engine_set_att_fwd_fold", self._h, int(bool(on)))
+
+    def set_chain(self, on: bool):
+        """False: no train step ends with the launch that also plans its successor (k_finish_plan); the environment variable
+        CAL_AMD_CHAIN=0 selects the same process-wide.  Call before a sequence is captured."""
+        _lib.call("cal_engine_set_chain", self._h, int(bool(on)))
+
+    def chain_reset(self):
+        """Drop a step the engine has planned but that will not be run (an error between two chained steps)."""
+        _lib.call("cal_engine_chain_reset", self._h)
 
     def set_adam(self, beta1: float, beta2: float, eps: float, weight_decay: float):
         """Adam hyper-parameters of an attached optimizer object (cal_amd/optim.py); the learning rate is ``self.lr``."""
@@ -266,7 +277,10 @@ class StepEngine:
         assert self._ws.data_ptr() % 256 == 0
         _lib.call("cal_engine_set_workspace", self._h, _p(self._ws), nbytes, N, E, B)
         self._cap = (N, E, B)
-        self.buffer("status", 4, torch.int32).zero_()       # [0] = latest step, [1] = sticky OR of the earlier steps
+        # [0] = latest step, [1] = sticky OR of the earlier steps, [4:6] = what a chained step's plan found, until that step commits
+        self.buffer("status", 12, torch.int32).zero_()
+        # the second fp64 arena of chained steps: clean once, kept clean by the commits that run on it
+        self.buffer("arena1", _lib.query("cal_engine_arena_doubles", self._h), torch.float64).zero_()
         if sticky:
             self.buffer("status", 4, torch.int32)[1] = sticky
         if self.gin:
@@ -298,10 +312,12 @@ class StepEngine:
         silently.  Called where the loops already synchronise (per-epoch statistics read-back, evaluation)."""
         if self._ws is None:
             return
-        st = self.buffer("status", 4, torch.int32)
-        word = int((st[0] | st[1]).item())
+        st = self.buffer("status", 6, torch.int32)
+        word = int((st[0] | st[1]).item())      # (a pending word [4:6] belongs to a step that has not committed: not reported yet)
         if reset:
             st[:2].zero_()
+            if not _lib.query("cal_engine_chain_pending", self._h):
+                st[4:6].zero_()
         if word:
             for cb in list(getattr(self, "_on_flag", ())):
                 cb()                           # (optim.Binding: the flagged steps were not applied -- re-read the device step counter)
@@ -335,7 +351,7 @@ class StepEngine:
         """The permutation the latest ``draw_perm`` step drew (device int64 [B], a view into the workspace)."""
         return self.buffer("perm", B, torch.int64)
 
-    def _run(self, batch, perm, mode: int):
+    def _run(self, batch, perm, mode: int, next_batch=None):
         x = batch.x if getattr(batch, "x", None) is not None else batch.feat
         ei, bvec, y = batch.edge_index, batch.batch, batch.y
         if not (x.is_cuda and ei.is_cuda):
@@ -352,6 +368,61 @@ class StepEngine:
             self._sync_gat()
         self.reserve(N, E, B)
         self._last_B = B
+        ptrs, bounds, tiles = self._describe(batch, B)
+        if tiles != self._tiles:
+            _lib.call("cal_engine_set_tiles", self._h, tiles[0] or None, tiles[1])
+            self._tiles = tiles
+        if ptrs != self._ptrs:
+            _lib.call("cal_engine_set_graph_ptrs", self._h, ptrs[0] or None, ptrs[1] or None)
+            self._ptrs = ptrs
+        if bounds != self._bounds:
+            _lib.call("cal_engine_set_graph_bounds", self._h, bounds[0], bounds[1])
+            self._bounds = bounds
+        if mode & 16:
+            perm = None                                   # drawn by the step's first kernel
+        elif perm is None:
+            perm = self._identity.get(B)
+            if perm is None:
+                perm = self._identity[B] = torch.arange(B, device=self.device)
+        if y is None:
+            y = torch.zeros(B, dtype=torch.long, device=self.device)
+        if next_batch is not None:
+            self._announce(next_batch)
+        try:
+            _lib.call("cal_engine_step", self._h, _p(x.contiguous()), _p(ei.contiguous()), _p(bvec.contiguous()),
+                      _p(y.view(-1).contiguous()), _p(perm.contiguous()) if perm is not None else None, N, E, B,
+                      self.wc, self.wo, self.wco, mode, _stream())
+        finally:
+            if self.launch_log is not None:
+                names, k = [], 1
+                while True:
+                    nm = _lib.lib().cal_engine_stage_name(k)
+                    if not nm:
+                        break
+                    names.append(nm.decode())
+                    k += 1
+                self.launch_log.append(names)
+        return B
+
+    def _announce(self, nxt):
+        """Tell the engine which batch the step AFTER the coming one is for (``cal_engine_set_next``): the coming step may then
+        commit and plan ``nxt`` in one launch.  Nothing is announced for a batch that would not go through ``_run`` unchanged
+        (another device or dtype, a shape BatchNorm refuses) or that does not fit the workspace as it is."""
+        x = nxt.x if getattr(nxt, "x", None) is not None else nxt.feat
+        ei, bvec = nxt.edge_index, nxt.batch
+        N, E, B = x.size(0), ei.size(1), int(nxt.num_graphs)
+        cn, ce, cb = self._cap
+        if not (x.is_cuda and ei.is_cuda and x.dtype == torch.float32 and x.size(1) == self.F and x.is_contiguous()
+                and ei.is_contiguous() and bvec.is_contiguous() and B > 1 and N > 1 and N <= cn and E <= ce and B <= cb):
+            return
+        ptrs, bounds, tiles = self._describe(nxt, B)
+        if not ptrs[0]:
+            return
+        _lib.call("cal_engine_set_next", self._h, _p(x), _p(ei), _p(bvec), N, E, B, ptrs[0], ptrs[1], tiles[0] or None, tiles[1],
+                  bounds[0], bounds[1])
+
+    def _describe(self, batch, B: int):
+        """(node / edge offsets, per-graph bounds, tiles) of ``batch`` as the engine is told them: device addresses and sizes."""
         # layout facts of a collated batch -> one-kernel per-graph CSR build (the tensors stay referenced by the batch)
         lay = _layout_of(batch, B) if self.fused else dict(ptr=None, edge_ptr=None, no_self_loops=False, max_nodes=0, max_edges=0)
         nptr, eptr = lay["ptr"], lay["edge_ptr"]
@@ -373,27 +444,7 @@ class StepEngine:
             tiles = (tp.data_ptr(), int(tp.numel()) - 1)
             ptrs = (batch.tile_node_ptr.data_ptr(), batch.tile_edge_ptr.data_ptr())
             bounds = (int(batch.tile_max_nodes), int(batch.tile_max_edges))
-        if tiles != self._tiles:
-            _lib.call("cal_engine_set_tiles", self._h, tiles[0] or None, tiles[1])
-            self._tiles = tiles
-        if ptrs != self._ptrs:
-            _lib.call("cal_engine_set_graph_ptrs", self._h, ptrs[0] or None, ptrs[1] or None)
-            self._ptrs = ptrs
-        if bounds != self._bounds:
-            _lib.call("cal_engine_set_graph_bounds", self._h, bounds[0], bounds[1])
-            self._bounds = bounds
-        if mode & 16:
-            perm = None                                   # drawn by the step's first kernel
-        elif perm is None:
-            perm = self._identity.get(B)
-            if perm is None:
-                perm = self._identity[B] = torch.arange(B, device=self.device)
-        if y is None:
-            y = torch.zeros(B, dtype=torch.long, device=self.device)
-        _lib.call("cal_engine_step", self._h, _p(x.contiguous()), _p(ei.contiguous()), _p(bvec.contiguous()),
-                  _p(y.view(-1).contiguous()), _p(perm.contiguous()) if perm is not None else None, N, E, B,
-                  self.wc, self.wo, self.wco, mode, _stream())
-        return B
+        return ptrs, bounds, tiles
 
     def forward(self, batch, perm=None, training: bool = False):
         B = self._run(batch, perm, 1 if training else 0)
@@ -436,12 +487,16 @@ class StepEngine:
         lp = self.buffer("logp", 3 * B * self.C).clone().view(3, B, self.C)
         return lp[0], lp[1], lp[2]
 
-    def train_step(self, batch, perm=None, adam: bool = True, tick: bool = False, draw_perm: bool = False):
+    def train_step(self, batch, perm=None, adam: bool = True, tick: bool = False, draw_perm: bool = False, next_batch=None):
         """forward + loss + backward (+ Adam); returns the device stats tensor
         [loss, c_loss, o_loss, co_loss, correct_o] (a view into the workspace).  ``tick`` (with ``adam=False``):
         the update follows a gradient exchange as ``adam_ticked()``; the step advances the Adam step counter.
-        ``draw_perm``: the step draws the random-intervention permutation itself (``set_perm_rng``), in its first kernel."""
-        self._run(batch, perm, 3 | (4 if adam else (8 if tick else 0)) | (16 if draw_perm else 0))
+        ``draw_perm``: the step draws the random-intervention permutation itself (``set_perm_rng``), in its first kernel.
+        ``next_batch``: the batch of the train step that FOLLOWS, with the same arguments (a sequence whose steps are known when they
+        are enqueued, ``CausalTrainer.step_sequence``): the engine may end this step with one launch that also plans that batch
+        (k_finish_plan), and then refuses any other call until that step has run."""
+        self._run(batch, perm, 3 | (4 if adam else (8 if tick else 0)) | (16 if draw_perm else 0),
+                  next_batch=next_batch if adam else None)
         return self.buffer("stats", 5)
 
     def adam(self):

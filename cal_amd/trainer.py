@@ -229,7 +229,7 @@ class CausalTrainer:
         """The engine draws the permutation in its own first kernel (up to 1024 graphs; beyond that cal_randperm)."""
         return self.engine is not None and num <= 1024 and self._shuffles()
 
-    def _fwd_bwd(self, batch, perm, stats, draw: bool = False):
+    def _fwd_bwd(self, batch, perm, stats, draw: bool = False, next_batch=None):
         """One forward + backward (+ fused Adam); returns the device stats tensor.  On the engine path that is a
         view of the engine's own stats buffer (no copy node in the graph): it holds the LATEST step's values.
         ``draw``: the intervention permutation is drawn on the device for this step (inside the engine's first kernel
@@ -239,7 +239,7 @@ class CausalTrainer:
             draw = False
         if self.engine is not None:
             if not self.exchange:
-                return self.engine.train_step(batch, perm, adam=True, draw_perm=draw)
+                return self.engine.train_step(batch, perm, adam=True, draw_perm=draw, next_batch=next_batch)
             stats = self.engine.train_step(batch, perm, adam=False, tick=True, draw_perm=draw)  # k_finish advances the Adam step
             if self.p2p is not None:                  # publish / wait / sum / Adam: one kernel
                 self.p2p.adam()
@@ -447,9 +447,15 @@ class CausalTrainer:
                 self._pinned = set()
             snap = self._snapshot()
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=self._pool):
-                for b, cap in zip(batches, caps):
-                    stats = self._fwd_bwd(b, cap.perm, cap.stats, draw=self._shuffles())
+            try:
+                with torch.cuda.graph(g, pool=self._pool):
+                    # every step but the last knows its successor: the engine may commit it and plan the next batch in one launch
+                    for i, (b, cap) in enumerate(zip(batches, caps)):
+                        nxt = batches[i + 1] if i + 1 < len(batches) else None
+                        stats = self._fwd_bwd(b, cap.perm, cap.stats, draw=self._shuffles(), next_batch=nxt)
+            except Exception:
+                self.engine.chain_reset()          # a step that was planned but never enqueued must not be owed
+                raise
             self._restore(snap)
             seq = self._seqs[key] = (g, stats, list(batches), self.engine.ws_generation)
         seq[0].replay()

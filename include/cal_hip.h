@@ -342,6 +342,22 @@ CAL_API int cal_engine_set_deterministic(void* engine, int on);
 /* on = 0: the per-graph attention forward stays a launch of its own instead of the tail of the last GCN layer's forward launch
  * (k_gconv_fwd_att; the environment variable CAL_AMD_ATT_FWD_FOLD=0 selects the same process-wide).  No reference counterpart. */
 CAL_API int cal_engine_set_att_fwd_fold(void* engine, int on);
+/* Chained steps (k_finish_plan; no reference counterpart).  cal_engine_set_next announces the batch of the step AFTER the coming
+ * cal_engine_step (same mode): that step may then end with ONE launch that commits it and builds the graph plan of this batch, and
+ * the step after it must be called for exactly this batch (same pointers, sizes, layout and workspace) or it is refused with an
+ * error and nothing is enqueued.  node_ptr / edge_ptr, tile_gptr / ntiles and the bounds are what cal_engine_set_graph_ptrs,
+ * cal_engine_set_tiles and cal_engine_set_graph_bounds will be given for it.  The announcement holds for one call; N = 0 withdraws
+ * it.  The engine chains only single-process Adam steps (mode bit 4) whose successor takes the 256-thread per-graph plan; otherwise
+ * the steps run as ever.  cal_engine_set_chain(on = 0) / the environment variable CAL_AMD_CHAIN=0: never.  cal_engine_chain_pending:
+ * 1 while a planned step is owed; cal_engine_chain_reset drops it (error paths: the chain's counters are lost with it).
+ * cal_engine_arena_doubles: size of the fp64 arenas (buffers "arena", "arena1"; whoever sets the workspace zeroes "arena1"). */
+CAL_API int cal_engine_set_chain(void* engine, int on);
+CAL_API int cal_engine_set_next(void* engine, const float* x0, const int64_t* edge_index, const int64_t* batch, int64_t N, int64_t E,
+                                int64_t B, const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* tile_gptr, int64_t ntiles,
+                                int64_t max_nodes, int64_t max_edges);
+CAL_API int64_t cal_engine_chain_pending(void* engine);
+CAL_API int cal_engine_chain_reset(void* engine);
+CAL_API int64_t cal_engine_arena_doubles(void* engine);
 /* test aid: where BatchNorm k's batch sums live in the engine's fp64 arena (buffer "arena"), in doubles: out[0] offset of the column
  * sums (plane 0 of the four accumulator planes), out[1] padded width (the sums of squares follow that far behind), out[2] distance
  * of the planes.  BatchNorms in the order 0 bn_feat, 1..L bns_conv, L+1 bnc, L+2 bno, then the readout's. */
