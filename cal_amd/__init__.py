@@ -11,6 +11,8 @@ _PGEXPLAIN = ("EdgeExplainer", "ExplainerTrainer", "ParametricMask", "fit_explai
               "eval_explainer")
 _MOTIF = ("MotifMatch", "MotifPatterns", "motif_match", "automorphisms", "contains", "isomorphic", "motif_census",
           "explanation_motifs", "eval_explanation_motifs")
+_CENTRALITY = ("Centrality", "hop_distance", "structural_scores", "structural_baseline", "eval_structural_baseline",
+               "explanation_locality", "eval_explanation_locality")
 
 
 def __getattr__(name):
@@ -25,4 +27,8 @@ def __getattr__(name):
     if name in _MOTIF:                                        # exact motif matching (cal_amd/motif.py), likewise
         from . import motif
         return getattr(motif, name)
+    if name in _CENTRALITY:                                   # graph centralities and the structural baselines, likewise
+        # (``cal_amd.centrality`` is the module; its function of that name is ``cal_amd.centrality.centrality``)
+        from . import centrality
+        return getattr(centrality, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

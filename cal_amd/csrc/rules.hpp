@@ -351,4 +351,44 @@ CAL_RULE unsigned long long motif_key(const MotifPlan& q, const int* img) {
     return key;
 }
 
+// ---- graph centralities (cal_centrality) -----------------------------------------------------------------------------------------
+// Sources are dealt to kCentW "waves" statically: source s belongs to wave s mod kCentW, a wave takes its sources in ascending
+// s and keeps ONE partial sum per output element; the partials are added in wave order, ((p0 + p1) + p2) + p3.  On the host a
+// wave is a loop index.
+constexpr int kCentW = 4;
+static_assert(kCentW == 4, "cent_join adds four partials");
+constexpr int kCentUnreached = -1;                   // hop distance of a node the search did not reach (also what `hop` reports)
+constexpr int kCentHopSeed = 0;                      // `hop` of a marked node
+constexpr int64_t kCentSkipInt = -1;                 // every integer output of a skipped graph; the fp64 outputs are NaN
+constexpr int kCentSlots = 256;                      // slots of cent_tree_sum
+
+CAL_RULE int cent_wave(int64_t s) { return (int)(s % kCentW); }
+CAL_RULE double cent_skip_f64() { return __builtin_nan(""); }
+CAL_RULE double cent_join(double p0, double p1, double p2, double p3) { return ((p0 + p1) + p2) + p3; }
+
+// what a node v one level above u pulls from u, in ascending u: sigma(v) * q(u) with q(u) = (1 + delta(u)) / sigma(u); the same
+// product is the term of the edge {v, u}
+CAL_RULE double cent_q(double delta, double sigma) { return (1.0 + delta) / sigma; }
+
+// The sum of v[0 .. n) PageRank uses (dangling mass, L1 change): slot i & 255 takes v[i] in ascending i, then the 256 slots are
+// halved, s[i] += s[i + h] for h = 128, 64, .. 1.  s: kCentSlots doubles, destroyed.  (On the device the halvings of h <= 32 are
+// the xor butterfly of a wave, which gives every lane the bits of s[0].)
+CAL_RULE double cent_tree_sum(double* s) {
+    for (int h = kCentSlots / 2; h > 0; h >>= 1)
+        for (int i = 0; i < h; ++i) s[i] += s[i + h];
+    return s[0];
+}
+
+// one PageRank step of a node: pull = the sum of x[u] / deg[u] over its neighbours u in ascending id, dangling = the tree sum of
+// x over the nodes without a neighbour, n the graph's nodes
+// One operation per statement: the device build contracts a * b + c inside a statement, and pr_iters is promised bit for bit.
+CAL_RULE double cent_pr_step(double alpha, double pull, double dangling, double n) {
+    const double t = pull + dangling / n;
+    const double a = alpha * t;
+    const double b = (1.0 - alpha) / n;
+    return a + b;
+}
+// the stopping test: err = the tree sum of |x_new - x_old|.  The step that meets it is counted in pr_iters.
+CAL_RULE bool cent_pr_done(double err, double tol) { return err < tol; }
+
 }  // namespace cal

@@ -1884,3 +1884,164 @@ HOST_EXPORT int cal_motif_match(const int64_t* edge_index, int64_t E, int64_t N,
     totals[0] = ignored;
     return 0;
 }
+
+// ---- graph centralities (cal_amd/csrc/centrality.hip; cal_amd/centrality.py): the same searches and the same order of every sum
+// (rules.hpp), graph by graph, over a CSR of the distinct neighbours in ascending id.  No limit on a graph's nodes.
+HOST_EXPORT int64_t cal_centrality_ws(int64_t) { return 0; }
+
+HOST_EXPORT int cal_centrality(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                               int64_t B, const uint8_t* sources, double alpha, double tol, int64_t max_iter, int64_t* far,
+                               int64_t* reach, int64_t* ecc, int64_t* deg, double* bc, double* ebc, double* pr, int32_t* pr_iters,
+                               int32_t* hop, int64_t* skipped, int64_t* totals, void*, int64_t, void*) {
+    HOST_REQUIRE(E >= 0 && N >= 0 && B >= 0, "E, N, B must be >= 0");
+    HOST_REQUIRE(alpha >= 0.0 && alpha < 1.0, "alpha must be in [0, 1)");
+    HOST_REQUIRE(tol >= 0.0 && max_iter >= 0 && max_iter <= 0x7FFFFFFF, "tol must be >= 0 and max_iter in [0, 2^31)");
+    HOST_REQUIRE(totals, "totals is null");
+    HOST_REQUIRE(!hop || sources || N == 0, "hop needs sources");
+    totals[0] = 0;
+    if (B == 0) return 0;
+    const bool cent = pr_iters != nullptr;
+    HOST_REQUIRE(!cent || ((N == 0 || (far && reach && ecc && deg && bc && pr)) && (E == 0 || ebc)),
+                 "pr_iters is given: far, reach, ecc, deg, bc, ebc and pr must be");
+    HOST_REQUIRE(cent || hop || N == 0, "nothing is asked for");
+    HOST_REQUIRE(ptr && edge_ptr && skipped, "ptr / edge_ptr / skipped are null");
+    HOST_REQUIRE(E == 0 || edge_index, "edge_index is null");
+    int64_t ignored = 0;
+#pragma omp parallel for schedule(dynamic, 1) reduction(+ : ignored)
+    for (int64_t g = 0; g < B; ++g) {
+        int64_t nlo, n, elo, em;
+        seg_clamp(ptr, g, N, nlo, n);
+        seg_clamp(edge_ptr, g, E, elo, em);
+        skipped[g] = 0;
+        // the distinct neighbours of every node, ascending
+        std::vector<int64_t> rp((size_t)n + 1, 0);
+        std::vector<int32_t> nb;
+        {
+            std::vector<std::pair<int32_t, int32_t>> pairs;
+            pairs.reserve((size_t)em * 2);
+            for (int64_t e = elo; e < elo + em; ++e) {
+                const int64_t u = edge_index[e] - nlo, v = edge_index[E + e] - nlo;
+                if (!(u >= 0 && u < n && v >= 0 && v < n)) {
+                    ++ignored;
+                } else if (u != v) {
+                    pairs.emplace_back((int32_t)u, (int32_t)v);
+                    pairs.emplace_back((int32_t)v, (int32_t)u);
+                }
+            }
+            std::sort(pairs.begin(), pairs.end());
+            pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+            nb.resize(pairs.size());
+            for (size_t i = 0; i < pairs.size(); ++i) {
+                nb[i] = pairs[i].second;
+                rp[(size_t)pairs[i].first + 1]++;
+            }
+            for (int64_t v = 0; v < n; ++v) rp[(size_t)v + 1] += rp[(size_t)v];
+        }
+        std::vector<int32_t> dist((size_t)n), order;
+        order.reserve((size_t)n);
+        if (hop) {                                                    // levels from the marked nodes
+            std::fill(dist.begin(), dist.end(), kCentUnreached);
+            for (int64_t v = 0; v < n; ++v)
+                if (sources && sources[nlo + v]) {
+                    dist[(size_t)v] = kCentHopSeed;
+                    order.push_back((int32_t)v);
+                }
+            for (size_t h = 0; h < order.size(); ++h) {
+                const int32_t v = order[h];
+                for (int64_t i = rp[(size_t)v]; i < rp[(size_t)v + 1]; ++i)
+                    if (dist[(size_t)nb[(size_t)i]] == kCentUnreached) {
+                        dist[(size_t)nb[(size_t)i]] = dist[(size_t)v] + 1;
+                        order.push_back(nb[(size_t)i]);
+                    }
+            }
+            for (int64_t v = 0; v < n; ++v) hop[nlo + v] = dist[(size_t)v];
+        }
+        if (!cent) continue;
+        std::vector<double> sig((size_t)n), q((size_t)n), delta((size_t)n);
+        std::vector<double> bcp((size_t)n * kCentW, 0.0), ep((size_t)em * kCentW, 0.0);
+        for (int64_t v = 0; v < n; ++v) {
+            far[nlo + v] = reach[nlo + v] = ecc[nlo + v] = 0;
+            deg[nlo + v] = rp[(size_t)v + 1] - rp[(size_t)v];
+        }
+        for (int64_t s = 0; s < n; ++s) {
+            const int w = cent_wave(s);
+            std::fill(dist.begin(), dist.end(), kCentUnreached);
+            order.clear();
+            dist[(size_t)s] = 0;
+            sig[(size_t)s] = 1.0;
+            order.push_back((int32_t)s);
+            for (size_t h = 0; h < order.size(); ++h) {               // levels; sigma pulls from the level above, ascending
+                const int32_t v = order[h];
+                if (h) {
+                    double sum = 0.0;
+                    for (int64_t i = rp[(size_t)v]; i < rp[(size_t)v + 1]; ++i)
+                        if (dist[(size_t)nb[(size_t)i]] == dist[(size_t)v] - 1) sum += sig[(size_t)nb[(size_t)i]];
+                    sig[(size_t)v] = sum;
+                }
+                for (int64_t i = rp[(size_t)v]; i < rp[(size_t)v + 1]; ++i)
+                    if (dist[(size_t)nb[(size_t)i]] == kCentUnreached) {
+                        dist[(size_t)nb[(size_t)i]] = dist[(size_t)v] + 1;
+                        order.push_back(nb[(size_t)i]);
+                    }
+            }
+            for (size_t h = order.size(); h-- > 1;) {                 // the deepest level first; the source is left out
+                const int32_t v = order[h];
+                double acc = 0.0;
+                for (int64_t i = rp[(size_t)v]; i < rp[(size_t)v + 1]; ++i)
+                    if (dist[(size_t)nb[(size_t)i]] == dist[(size_t)v] + 1) acc += sig[(size_t)v] * q[(size_t)nb[(size_t)i]];
+                delta[(size_t)v] = acc;
+                q[(size_t)v] = cent_q(acc, sig[(size_t)v]);
+                bcp[(size_t)v * kCentW + w] += acc;
+            }
+            for (size_t h = 0; h < order.size(); ++h) {               // (d(s, v) = d(v, s))
+                const int32_t v = order[h];
+                far[nlo + v] += dist[(size_t)v];
+                reach[nlo + v] += 1;
+                ecc[nlo + v] = std::max<int64_t>(ecc[nlo + v], dist[(size_t)v]);
+            }
+            for (int64_t e = 0; e < em; ++e) {
+                const int64_t x = edge_index[elo + e] - nlo, y = edge_index[E + elo + e] - nlo;
+                if (!(x >= 0 && x < n && y >= 0 && y < n)) continue;
+                const int dx = dist[(size_t)x], dy = dist[(size_t)y];
+                if (dx >= 0 && dy == dx + 1) ep[(size_t)e * kCentW + w] += sig[(size_t)x] * q[(size_t)y];
+                else if (dy >= 0 && dx == dy + 1) ep[(size_t)e * kCentW + w] += sig[(size_t)y] * q[(size_t)x];
+            }
+        }
+        for (int64_t v = 0; v < n; ++v) {
+            const double* p = &bcp[(size_t)v * kCentW];
+            bc[nlo + v] = cent_join(p[0], p[1], p[2], p[3]);
+        }
+        for (int64_t e = 0; e < em; ++e) {
+            const double* p = &ep[(size_t)e * kCentW];
+            ebc[elo + e] = cent_join(p[0], p[1], p[2], p[3]);
+        }
+        // PageRank
+        std::vector<double> x((size_t)n, n ? 1.0 / (double)n : 0.0), xd((size_t)n), xn((size_t)n);
+        double slots[kCentSlots];
+        auto tree = [&](auto term) {
+            std::fill(slots, slots + kCentSlots, 0.0);
+            for (int64_t v = 0; v < n; ++v) slots[v & (kCentSlots - 1)] += term(v);
+            return cent_tree_sum(slots);
+        };
+        auto degree = [&](int64_t v) { return rp[(size_t)v + 1] - rp[(size_t)v]; };
+        double dsum = tree([&](int64_t v) { return degree(v) ? 0.0 : x[(size_t)v]; });
+        int32_t it = 0;
+        while (it < max_iter && n > 0) {
+            for (int64_t v = 0; v < n; ++v) xd[(size_t)v] = degree(v) ? x[(size_t)v] / (double)degree(v) : 0.0;
+            for (int64_t v = 0; v < n; ++v) {
+                double pull = 0.0;
+                for (int64_t i = rp[(size_t)v]; i < rp[(size_t)v + 1]; ++i) pull += xd[(size_t)nb[(size_t)i]];
+                xn[(size_t)v] = cent_pr_step(alpha, pull, dsum, (double)n);
+            }
+            const double err = tree([&](int64_t v) { return fabs(xn[(size_t)v] - x[(size_t)v]); });
+            x.swap(xn);
+            dsum = tree([&](int64_t v) { return degree(v) ? 0.0 : x[(size_t)v]; });
+            ++it;
+            if (cent_pr_done(err, tol)) break;
+        }
+        for (int64_t v = 0; v < n; ++v) pr[nlo + v] = x[(size_t)v];
+        pr_iters[g] = it;
+    }
+    totals[0] = ignored;
+    return 0;
+}

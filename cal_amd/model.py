@@ -318,6 +318,16 @@ class _CausalBase(torch.nn.Module):
         from .motif import explanation_motifs
         return explanation_motifs(self, data, **kw)
 
+    def structural_baseline(self, data, **kw):
+        """``cal_amd.centrality.structural_baseline(self, data, **kw)``: the causal attention against structure-only rankings."""
+        from .centrality import structural_baseline
+        return structural_baseline(self, data, **kw)
+
+    def explanation_locality(self, data, **kw):
+        """``cal_amd.centrality.explanation_locality(self, data, **kw)``: how far from the motif the explanation's edges lie."""
+        from .centrality import explanation_locality
+        return explanation_locality(self, data, **kw)
+
     def explain(self, data, **kw):
         """``cal_amd.explain.explain(self, data, **kw)``: per-graph top-k causal subgraphs of ``data``."""
         from .explain import explain

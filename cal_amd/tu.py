@@ -5,11 +5,13 @@
   ``<name>_node_attributes.txt``) as PyG's ``read_tu_data`` reads it for ``tu_dataset.py:72``: node labels shifted to
   start at 0 and one-hot encoded per column, node attributes in front of them, self loops removed, edges sorted and
   de-duplicated, graph labels mapped onto 0..C-1 in sorted order.
-* ``expand_features`` -- the ``deg+odegN`` part of the reference's ``FeatureExpander`` (``feature_expansion.py:41-62,
-  96-113``, selected by ``datasets.py:16-18``): a degree column and a one-hot degree capped at N, appended to the node
-  features (a column of ones when the dataset has none).  The other switches of the feature string (``ak``, ``cent``,
-  ``re*``, ``rand*``, ``groupd``) are off in every configuration the reference's ``opts.py`` produces for the CAL
-  models and raise ``NotImplementedError`` here.
+* ``expand_features`` -- the ``deg+odegN`` and ``cent`` parts of the reference's ``FeatureExpander``
+  (``feature_expansion.py:41-62, 96-127``, selected by ``datasets.py:16-18``): a degree column, a one-hot degree capped at N
+  and, with ``cent``, closeness, betweenness and PageRank per node (``cal_amd.centrality``; the reference asks networkx),
+  appended to the node features (a column of ones when the dataset has none).  The other switches of the feature string
+  (``ak``, ``re*``, ``rand*``, ``groupd``) are off in every configuration the reference's ``opts.py`` produces for the CAL
+  models and raise ``NotImplementedError`` (``parse_feat_options``; ``parse_feat_str`` is the older parser, which also
+  refuses ``cent``).
 * ``TUDataset`` -- list-like (index by int / index tensor, ``num_features``, ``num_classes``, ``y``), what
   ``train_causal_real`` (``train_causal.py:63-76``) needs from ``TUDatasetExt``.
 * ``k_fold`` -- ``utils.py:18-36``: stratified folds (sklearn ``StratifiedKFold(folds, shuffle=True,
@@ -98,8 +100,29 @@ def parse_feat_str(feat_str: str):
     return degree, onehot_maxdeg
 
 
-def expand_features(data: Data, degree: bool = True, onehot_maxdeg: Optional[int] = None) -> Data:
-    """feature_expansion.py:41-62 with AK = 0, no centrality: x <- [x | deg | onehot(min(deg, maxdeg))]."""
+def parse_feat_options(feat_str: str) -> dict:
+    """datasets.py:16-33 -> ``{"degree": bool, "onehot_maxdeg": int | None, "cent": bool}``, the keywords of ``expand_features``;
+    ``NotImplementedError`` for what is still unsupported (``ak``, ``groupd``, ``re*``, ``randa``, ``randd``)."""
+    cent = feat_str.find("cent") >= 0
+    degree, onehot_maxdeg = parse_feat_str(feat_str.replace("cent", ""))
+    return {"degree": degree, "onehot_maxdeg": onehot_maxdeg, "cent": cent}
+
+
+def _centrality_features(data: Data) -> torch.Tensor:
+    """feature_expansion.py:115-127: [closeness, betweenness, pagerank] float32 [n, 3] with networkx's defaults (Wasserman-Faust
+    closeness, normalised betweenness, alpha = 0.85; the reference's ``pagerank_numpy`` is the exact stationary vector, which
+    the iteration meets far below float32).  One ``cal_centrality`` call on the graph's own device."""
+    from types import SimpleNamespace
+    from .centrality import centrality
+    n = int(data.num_nodes)
+    ei = data.edge_index
+    one = SimpleNamespace(edge_index=ei, batch=torch.zeros(n, dtype=torch.long, device=ei.device), num_graphs=1)
+    c = centrality(one)
+    return torch.stack([c.closeness(), c.betweenness(), c.pr], 1).float().cpu()
+
+
+def expand_features(data: Data, degree: bool = True, onehot_maxdeg: Optional[int] = None, cent: bool = False) -> Data:
+    """feature_expansion.py:41-62 with AK = 0: x <- [x | deg | onehot(min(deg, maxdeg)) | closeness, betweenness, pagerank]."""
     n = data.num_nodes
     x = data.x if data.x is not None else torch.ones(n, 1)
     row = data.edge_index[0]
@@ -110,6 +133,8 @@ def expand_features(data: Data, degree: bool = True, onehot_maxdeg: Optional[int
     if onehot_maxdeg is not None and onehot_maxdeg > 0:
         capped = torch.clamp(deg, max=float(onehot_maxdeg)).long()
         parts.append(torch.nn.functional.one_hot(capped, onehot_maxdeg + 1).float())
+    if cent:
+        parts.append(_centrality_features(data))
     out = Data(x=torch.cat(parts, -1), edge_index=data.edge_index, y=data.y)
     out.num_nodes = n
     return out
@@ -157,8 +182,8 @@ def get_dataset(name: str, feat_str: str = "deg+odeg100", root: Optional[str] = 
     if not os.path.exists(os.path.join(raw, "%s_A.txt" % name)):
         raise FileNotFoundError("TU files for %r not found under %s (no download in this build: supply the raw text files)"
                                 % (name, raw))
-    degree, maxdeg = parse_feat_str(feat_str)
-    graphs = [expand_features(g, degree, maxdeg) for g in read_tu_data(raw, name)]
+    opts = parse_feat_options(feat_str)
+    graphs = [expand_features(g, **opts) for g in read_tu_data(raw, name)]
     return TUDataset(graphs, name)
 
 

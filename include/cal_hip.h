@@ -774,6 +774,57 @@ CAL_API int cal_motif_match(const int64_t* edge_index, int64_t E, int64_t N, con
                             int induced, int64_t budget, int64_t* count, int64_t* truncated, int32_t* first,
                             int64_t* tgt_edges, int64_t* pat_edges, int64_t* totals, void* stream);
 
+/* ---- graph centralities: hop distances, Brandes' node and edge betweenness and PageRank of every graph of a batch
+ * (cal_amd/centrality.py; the structure-only baselines of the explanations, the reference's `cent` features) ----
+ * The batch is edge_index [2, E] int64, ptr / edge_ptr [B+1] int64 as in cal_motif_match, and the graph semantics are
+ * cal_motif_match's: SIMPLE UNDIRECTED graphs -- nodes u != w of a graph are adjacent iff a column (u, w) or (w, u) exists with
+ * both endpoints inside the graph's node range [ptr[g], ptr[g+1]); self loops and duplicate columns add nothing; a column with
+ * an endpoint outside its graph is ignored and counted in totals[0] (over all graphs, skipped ones included); segments are
+ * clamped as everywhere (seg_clamp).  n = the graph's nodes, d(u, v) the hop distance, R(v) the nodes v reaches (v included).
+ *   far[v]   int64 [N]  sum of d(v, u) over u in R(v)
+ *   reach[v] int64 [N]  |R(v)|
+ *   ecc[v]   int64 [N]  max of d(v, u) over u in R(v)
+ *   deg[v]   int64 [N]  the neighbours of v (distinct, v itself never)
+ *   bc[v]    fp64  [N]  sum over the sources s != v of Brandes' dependency delta_s(v): RAW, twice networkx's unnormalised value
+ *   ebc[e]   fp64  [E]  per COLUMN, in the caller's order: for the column (a, b) the sum over s of sigma_s(a) q_s(b) where b is
+ *                       one level below a (d(s, b) = d(s, a) + 1), of sigma_s(b) q_s(a) where a is below b, with
+ *                       q_s(u) = (1 + delta_s(u)) / sigma_s(u): RAW, twice networkx's unnormalised value.  A column, its reverse
+ *                       and its duplicates carry the same value (the same sums of the same terms); a self loop and an ignored
+ *                       column 0.
+ *   pr[v]    fp64  [N]  PageRank: x_0 = 1/n; x_{t+1}[v] = alpha (sum over the neighbours u of x_t[u] / deg(u) + D_t / n) +
+ *                       (1 - alpha) / n with D_t the sum of x_t over the nodes without a neighbour (dangling mass spread
+ *                       uniformly, uniform teleport, uniform start: nx.pagerank of an undirected graph); iterate until
+ *                       err_t = sum_v |x_{t+1}[v] - x_t[v]| < tol (NOT n tol) or max_iter steps are done.
+ *   pr_iters int32 [B]  the steps taken, the one that met the test included; 0 for a graph without nodes or max_iter = 0
+ *   hop[v]   int32 [N]  optional (null: not wanted): the distance to the nearest node u of the same graph with sources[u] != 0
+ *                       (sources: bytes [N]); 0 on such a node, -1 where there is none within reach
+ *   skipped  int64 [B]  1 for a graph of more than CAL_MOTIF_MAX_NODES nodes, else 0.  The device library skips such a graph:
+ *                       its far, reach, ecc, deg, hop and pr_iters are -1, its bc, ebc (every column of its segment) and pr NaN.
+ *                       The HOST library has no such limit (plain Brandes over a CSR, OpenMP over the graphs): skipped is 0.
+ *   totals   int64 [1]  the ignored columns
+ * pr_iters null: only hop is wanted, far .. pr are not touched; else all of them are given.  Nodes and columns outside every graph's segment are not
+ * written.  alpha in [0, 1), tol >= 0, max_iter >= 0.
+ *   Integers are exact, the same bits in both libraries.  Floating point is DETERMINISTIC: no floating-point atomic; every sum
+ *   has one order, the same in both libraries (rules.hpp):
+ *   - sigma_s(v) = the sum of sigma_s(u) over the neighbours u of v one level above, in ascending u; sigma_s(s) = 1;
+ *   - delta_s(v) = the sum of sigma_s(v) * q_s(u) over the neighbours u one level below, in ascending u (one product per term);
+ *   - source s belongs to wave s mod 4; a wave adds its sources' delta_s(v) (its columns' terms) in ascending s into one partial
+ *     per node (per column); the value is ((p0 + p1) + p2) + p3;
+ *   - pr: the neighbours' sum in ascending u; D_t and err_t are the tree sum cent_tree_sum of rules.hpp (slot i mod 256, halved).
+ *   The two libraries are NOT promised to agree bit for bit in fp64 (the device build contracts a * b + c within a statement);
+ *   both are within gamma_k of the exact value, k = 2 n (n + 3): every output is a sum of non-negative terms.
+ *   One memset of totals and ONE launch on `stream`, one workgroup of 4 waves per graph: the bit matrix in LDS, the sources dealt
+ *   to the waves, sigma / q / distances per wave in LDS, the nodes lane + 64 j of a lane in registers, frontiers and level masks
+ *   by ballot.  The per-wave partials of ebc sit in LDS for a graph of at most CAL_CENTRALITY_LDS_COLS columns; a graph with
+ *   more uses ws, [4, E] fp64: cal_centrality_ws(E) bytes, 0 for E <= CAL_CENTRALITY_LDS_COLS (no graph can have more).  No
+ *   read-back.  B = 0 launches nothing.  N = 0 and E = 0 are legal. */
+#define CAL_CENTRALITY_LDS_COLS 768
+CAL_API int64_t cal_centrality_ws(int64_t E);
+CAL_API int cal_centrality(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                           int64_t B, const uint8_t* sources, double alpha, double tol, int64_t max_iter, int64_t* far,
+                           int64_t* reach, int64_t* ecc, int64_t* deg, double* bc, double* ebc, double* pr, int32_t* pr_iters,
+                           int32_t* hop, int64_t* skipped, int64_t* totals, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
