@@ -13,6 +13,8 @@ _MOTIF = ("MotifMatch", "MotifPatterns", "motif_match", "automorphisms", "contai
           "explanation_motifs", "eval_explanation_motifs")
 _CENTRALITY = ("Centrality", "hop_distance", "structural_scores", "structural_baseline", "eval_structural_baseline",
                "explanation_locality", "eval_explanation_locality")
+_COUNTERFACTUAL = ("Counterfactual", "subset_batch", "pack_bits", "unpack_bits", "beam_step", "ranking_flip", "counterfactual_report",
+                   "eval_counterfactual")
 
 
 def __getattr__(name):
@@ -31,4 +33,8 @@ def __getattr__(name):
         # (``cal_amd.centrality`` is the module; its function of that name is ``cal_amd.centrality.centrality``)
         from . import centrality
         return getattr(centrality, name)
+    if name in _COUNTERFACTUAL:                               # counterfactual explanations, likewise
+        # (``cal_amd.counterfactual`` is the module; its function of that name is ``cal_amd.counterfactual.counterfactual``)
+        from . import counterfactual
+        return getattr(counterfactual, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -28,8 +28,8 @@ from .explain import _eval_mode, _Layout, _scores
 from .occlude import rank_agreement
 from .plan import _p
 from .replica import (_agree_report, _agree_sums, _built_batch, _caller_columns, _causal_in_order, _check_driver_args, _check_topk,
-                      _check_use, _feature_width, _grouped, _members, _p_at, _pairs, _Players, _rebatch, _replica_log_probs,
-                      _Source, _symmetrised, _whole)
+                      _check_use, _feature_width, _grouped, _members, _node_map_rows, _p_at, _pairs, _Players, _rebatch,
+                      _replica_log_probs, _Source, _symmetrised, _whole)
 
 __all__ = ["Shapley", "coalition_batch", "shapley", "perturbation_curve", "eval_perturbation_curve", "shapley_agreement"]
 
@@ -57,7 +57,6 @@ def coalition_batch(data, rep_graph, rep_thresh, key, *, rep_row=None, use: str 
     between them; CPU tensors: libcalhost.  Inputs other than ``Batch`` objects get their layout derived as in ``occlude_batch``;
     edge columns that are not grouped by graph are put in stable graph order first, ``key`` is taken in the caller's column
     numbering and ``edge_src`` is mapped back to it."""
-    from .data import Batch
     _check_use(use)
     mode = 0 if use == "edges" else 1
     S = _Source(data)
@@ -86,11 +85,7 @@ def coalition_batch(data, rep_graph, rep_thresh, key, *, rep_row=None, use: str 
     if S.order is not None and mode == 0 and S.E:          # the caller's column numbering -> graph order
         key = key[:, S.order]
     key = key.contiguous()
-    mx = 0
-    if mode == 1 and S.N and S.B:                          # the row length of the node maps
-        mx = int(getattr(data, "max_nodes", 0) or 0) if isinstance(data, Batch) else 0
-        if mx <= 0:
-            mx = int((S.ptr[1:] - S.ptr[:-1]).max())
+    mx = _node_map_rows(S, data) if mode == 1 else 0
     inputs = S.args() + [_p(key) if K and M else None, K, _p(rg) if R else None, _p(rrow) if R else None, _p(rth) if R else None, R,
                          mode, int(bool(invert)), mx]
     built = _rebatch("cal_coalition", (S.E, R, mx, mode), inputs, R, 5, (S,), F, lambda: (rg < 0) | (rg >= S.B))

@@ -147,7 +147,8 @@ CAL_RULE unsigned long long wl_next(unsigned long long c, unsigned long long so,
 }
 
 // ---- the batch builders: replica r -> node range [nlo, nlo + nn), column range [elo, elo + em) (all zero without a graph), and
-// which of the graph's columns / elements stay.  A: OccArgs / OccludeSrc, CoArgs / CoalitionSrc, NoArgs / NoiseSrc, Side / SpliceSide.
+// which of the graph's columns / elements stay.  A: OccArgs / OccludeSrc, CoArgs / CoalitionSrc, SubArgs / SubsetSrc, NoArgs / NoiseSrc,
+// Side / SpliceSide.
 
 // occlusion: the node removed (rn) and the columns removed (c0, c1); -1 = none, which equals no id
 struct OccRep {
@@ -218,6 +219,116 @@ CAL_RULE bool col_stays(const A& a, const CoRep& q, int64_t e) {
     const int64_t u = a.ei[e], v = a.ei[a.E + e];
     if (!(u >= q.nlo && u < q.nlo + q.nn && v >= q.nlo && v < q.nlo + q.nn)) return false;
     return a.mode == 0 ? elem_stays(a, q, e) : elem_stays(a, q, u) && elem_stays(a, q, v);
+}
+
+// subsets: the replica's bitset row over its own graph's elements (all: no row, everything present) and the LOCAL indices its
+// flip toggles (f0 the flip, f1 its twin column; -1: none).  The elements are the graph's columns in mode 0, its nodes in mode 1.
+// A: SubArgs / SubsetSrc (bits, K, W, rrow, rflip, twin, mode, mx besides the batch).
+struct SubRep {
+    int64_t nlo, nn, elo, em, f0, f1;
+    const uint32_t* row;
+    bool all;
+};
+
+// bit j of a row of W words: a local index >= 32 W is absent
+CAL_RULE bool bit_at(const uint32_t* row, int64_t W, int64_t j) {
+    if (j < 0 || j >= 32 * W) return false;
+    return (row[j >> 5] >> (j & 31)) & 1u;
+}
+
+// the local indices a flip toggles in a segment of m elements that starts at global element lo: f itself when inside [0, m), and
+// (twin given, a column segment) the twin column when it lies inside the segment and is another column than f
+CAL_RULE void flip_pair(int64_t f, int64_t lo, int64_t m, const int32_t* twin, int64_t& f0, int64_t& f1) {
+    f0 = f1 = -1;
+    if (f < 0 || f >= m) return;
+    f0 = f;
+    if (twin) {
+        const int64_t t = (int64_t)twin[lo + f] - lo;
+        if (t >= 0 && t < m && t != f) f1 = t;
+    }
+}
+
+template <class A>
+CAL_RULE SubRep sub_replica(const A& a, int64_t r) {
+    SubRep q{0, 0, 0, 0, -1, -1, nullptr, true};
+    const int64_t g = a.rg[r];
+    if (g < 0 || g >= a.B) return q;
+    seg_clamp(a.ptr, g, a.N, q.nlo, q.nn);
+    seg_clamp(a.eptr, g, a.E, q.elo, q.em);
+    if (a.mode == 1 && q.nn > a.mx) {
+        q.nlo = q.nn = q.elo = q.em = 0;
+        return q;
+    }
+    const int64_t k = a.rrow[r];
+    if (k >= 0 && k < a.K) {
+        q.row = a.bits + k * a.W;
+        q.all = false;
+    }
+    if (a.mode == 0) flip_pair(a.rflip[r], q.elo, q.em, a.twin, q.f0, q.f1);
+    else flip_pair(a.rflip[r], q.nlo, q.nn, nullptr, q.f0, q.f1);
+    return q;
+}
+
+// LOCAL element j (a column of the graph in mode 0, a node in mode 1) stays in the replica: its bit after the toggle
+template <class A>
+CAL_RULE bool elem_stays(const A& a, const SubRep& q, int64_t j) {
+    return (q.all || bit_at(q.row, a.W, j)) != (j == q.f0 || j == q.f1);
+}
+
+// column e of the replica's graph stays
+template <class A>
+CAL_RULE bool col_stays(const A& a, const SubRep& q, int64_t e) {
+    const int64_t u = a.ei[e], v = a.ei[a.E + e];
+    if (!(u >= q.nlo && u < q.nlo + q.nn && v >= q.nlo && v < q.nlo + q.nn)) return false;
+    return a.mode == 0 ? elem_stays(a, q, e - q.elo) : elem_stays(a, q, u - q.nlo) && elem_stays(a, q, v - q.nlo);
+}
+
+// ---- the beam step (cal_beam_step): all integer.  Graph g's states are the rows [g beam, g beam + n_state[g]) of bits; a
+// candidate c is (rep_row[c], rep_flip[c]) with its replica's p[c] and flipped[c].  A: BeamArgs / BeamSrc (beam, nst, rrow, rflip, p,
+// flipped).
+constexpr int kBeamMax = 16;                         // states of a graph
+constexpr int kBeamWords = 64;                       // words of a state: 2048 local elements
+
+// the parent of candidate c of graph g: its slot in [0, beam) among g's live states, or `beam`: the full set (a row that is none
+// of them)
+template <class A>
+CAL_RULE int beam_parent(const A& a, int64_t g, int64_t c) {
+    const int64_t s = a.rrow[c] - g * (int64_t)a.beam;
+    int64_t n = a.nst[g];
+    n = n < 0 ? 0 : (n > a.beam ? a.beam : n);
+    return s >= 0 && s < n ? (int)s : a.beam;
+}
+
+// word w of the full set of a segment of m elements in W words
+CAL_RULE uint32_t full_word(int64_t m, int64_t W, int64_t w) {
+    const int64_t n = m < 32 * W ? m : 32 * W, lo = 32 * w;
+    if (n <= lo) return 0u;
+    return n - lo >= 32 ? 0xFFFFFFFFu : (1u << (n - lo)) - 1u;
+}
+
+// what the flips f0, f1 (local, -1: none; an index >= 32 W toggles nothing) toggle in word w
+CAL_RULE uint32_t flip_word(int64_t f0, int64_t f1, int64_t w) {
+    uint32_t x = 0u;
+    if (f0 >= 0 && (f0 >> 5) == w) x ^= 1u << (f0 & 31);
+    if (f1 >= 0 && (f1 >> 5) == w) x ^= 1u << (f1 & 31);
+    return x;
+}
+
+// the 64-bit head of a candidate's place in the order: flipped first, then score_key(p) ascending (smaller sorts first)
+CAL_RULE uint64_t beam_head(uint8_t flipped, float p) { return ((uint64_t)(flipped ? 0u : 1u) << 32) | (uint64_t)score_key(p); }
+
+// candidate i comes before candidate j: (flipped first, score_key(p) ascending, rep_row ascending, rep_flip ascending), and two
+// candidates that agree in all four in index order.  h: beam_head, r: rep_row, f: rep_flip.
+CAL_RULE bool beam_before(uint64_t hi, int64_t ri, int64_t fi, int64_t i, uint64_t hj, int64_t rj, int64_t fj, int64_t j) {
+    if (hi != hj) return hi < hj;
+    if (ri != rj) return ri < rj;
+    if (fi != fj) return fi < fj;
+    return i < j;
+}
+template <class A>
+CAL_RULE bool beam_before(const A& a, int64_t i, int64_t j) {
+    return beam_before(beam_head(a.flipped[i], a.p[i]), a.rrow[i], a.rflip[i], i, beam_head(a.flipped[j], a.p[j]), a.rrow[j],
+                       a.rflip[j], j);
 }
 
 // structural noise: H(s, i), the replica's seed, deletion threshold and a = max(rep_add, 0)

@@ -1096,8 +1096,8 @@ HOST_EXPORT int cal_explain_rank_pairs(const float* score, int64_t stride, const
     return 0;
 }
 
-// ---- the batch builders (cal_amd/csrc/rebatch.hpp: splice, occlusion replicas, coalition replicas): what their count and write
-// entry points share.
+// ---- the batch builders (cal_amd/csrc/rebatch.hpp: splice, occlusion, coalition, noise and subset replicas): what their count and
+// write entry points share.
 namespace {
 // the count side: result graph r has n nodes and m columns; finish(R) after the last one
 struct BatchScan {
@@ -1368,6 +1368,159 @@ HOST_EXPORT int cal_coalition_write(const int64_t* edge_index, int64_t E, int64_
     return 0;
 }
 #undef COALITION_REQUIRE_INPUTS
+
+// ---- subset replicas (cal_amd/csrc/subset.hip; cal_amd/counterfactual.py subset_batch): the same nodes and columns in the same
+// order, so every integer output agrees bit for bit.
+namespace {
+struct SubsetSrc {             // (the fields sub_replica, elem_stays and col_stays of rules.hpp read, named as subset.hip's SubArgs)
+    const int64_t* ei; int64_t E, N; const int64_t* ptr; const int64_t* eptr; int64_t B; const uint32_t* bits; int64_t K, W;
+    const int64_t* rg; const int64_t* rrow; const int64_t* rflip; const int32_t* twin; int mode; int64_t mx;
+};
+}  // namespace
+
+HOST_EXPORT int64_t cal_subset_ws(int64_t, int64_t R, int64_t max_nodes, int mode) {
+    R = R > 0 ? R : 0;
+    return 16 * R + (mode == 1 ? 4 * R * (max_nodes > 0 ? max_nodes : 0) : 0) + 256;
+}
+
+#define SUBSET_REQUIRE_INPUTS()                                                                                                  \
+    HOST_REQUIRE(E >= 0 && N >= 0 && B >= 0 && R >= 0 && K >= 0 && NW >= 0, "sizes must be >= 0");                               \
+    HOST_REQUIRE(NW <= (1 << 26), "W must be <= 2^26");                                                                          \
+    HOST_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (edges) or 1 (nodes)");                                                 \
+    HOST_REQUIRE(max_nodes >= 0 && max_nodes <= 0x7FFFFFFF, "max_nodes must be in [0, 2^31)");                                   \
+    HOST_REQUIRE(R == 0 || (rep_graph && rep_row && rep_flip), "rep_graph / rep_row / rep_flip are null");                       \
+    HOST_REQUIRE(K == 0 || NW == 0 || bits, "bits is null");                                                                     \
+    HOST_REQUIRE(B == 0 || (ptr && edge_ptr), "ptr / edge_ptr are null");                                                        \
+    HOST_REQUIRE(E == 0 || edge_index, "edge_index is null");                                                                    \
+    const SubsetSrc S{edge_index, E, N, ptr, edge_ptr, B, bits, K, NW, rep_graph, rep_row, rep_flip,                  \
+                      mode == 0 ? twin : nullptr, mode, max_nodes}
+
+HOST_EXPORT int cal_subset_count(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                                 int64_t B, const uint32_t* bits, int64_t K, int64_t NW, const int64_t* rep_graph,
+                                 const int64_t* rep_row, const int64_t* rep_flip, int64_t R, const int32_t* twin, int mode,
+                                 int64_t max_nodes, int64_t* ptr_out, int64_t* edge_ptr_out, int64_t* totals, void*, int64_t,
+                                 void*) {
+    SUBSET_REQUIRE_INPUTS();
+    HOST_REQUIRE(totals && ptr_out && edge_ptr_out, "totals / ptr_out / edge_ptr_out are null");
+    std::vector<int64_t> cn((size_t)R), cm((size_t)R);
+#pragma omp parallel for schedule(dynamic, 16)
+    for (int64_t r = 0; r < R; ++r) {
+        const SubRep q = sub_replica(S, r);
+        int64_t n = 0, m = 0;
+        if (mode == 0) n = q.nn;
+        else for (int64_t l = 0; l < q.nn; ++l) n += elem_stays(S, q, l);
+        for (int64_t e = q.elo; e < q.elo + q.em; ++e) m += col_stays(S, q, e);
+        cn[(size_t)r] = n;
+        cm[(size_t)r] = m;
+    }
+    BatchScan scan{ptr_out, edge_ptr_out, totals};
+    for (int64_t r = 0; r < R; ++r) scan.add(r, cn[(size_t)r], cm[(size_t)r]);
+    scan.finish(R);
+    return 0;
+}
+
+HOST_EXPORT int cal_subset_write(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                                 int64_t B, const uint32_t* bits, int64_t K, int64_t NW, const int64_t* rep_graph,
+                                 const int64_t* rep_row, const int64_t* rep_flip, int64_t R, const int32_t* twin, int mode,
+                                 int64_t max_nodes, const float* x, int64_t F, const int64_t* ptr_out,
+                                 const int64_t* edge_ptr_out, int64_t Nout, int64_t Eout, int64_t* batch_out, float* x_out,
+                                 int64_t* edge_index_out, int64_t* node_src, int64_t* edge_src, void*, int64_t, void*) {
+    SUBSET_REQUIRE_INPUTS();
+    HOST_REQUIRE_WRITE(R, !x_out || (F > 0 && (N == 0 || x)), "x_out needs F > 0 and x");
+#pragma omp parallel for schedule(dynamic, 16) firstprivate(W)
+    for (int64_t r = 0; r < R; ++r) {                          // (every replica writes its own run of the outputs)
+        std::vector<int64_t> local;                            // (mode 1) new local id of every node of the replica's graph
+        const SubRep q = sub_replica(S, r);
+        W.begin(r);
+        local.assign((size_t)q.nn, 0);
+        for (int64_t l = 0; l < q.nn; ++l) {
+            local[(size_t)l] = W.i - W.n0;
+            if (mode == 0 || elem_stays(S, q, l)) W.node(q.nlo + l, x, q.nlo + l);
+        }
+        for (int64_t e = q.elo; e < q.elo + q.em; ++e)
+            if (col_stays(S, q, e))
+                W.col(W.n0 + local[(size_t)(edge_index[e] - q.nlo)], W.n0 + local[(size_t)(edge_index[E + e] - q.nlo)], e);
+    }
+    return 0;
+}
+#undef SUBSET_REQUIRE_INPUTS
+
+// ---- the beam step (cal_amd/csrc/beam.hip; cal_amd/counterfactual.py): the order, the children and the duplicates of rules.hpp,
+// graph by graph.
+namespace {
+struct BeamSrc {               // (the fields beam_parent and beam_before of rules.hpp read, named as beam.hip's BeamArgs)
+    const uint32_t* bits; int beam; int64_t W; const int64_t* nst; const int64_t* rrow; const int64_t* rflip; const float* p;
+    const uint8_t* flipped;
+};
+}  // namespace
+
+HOST_EXPORT int cal_beam_step(const uint32_t* bits, int64_t B, int beam, int64_t W, const int64_t* n_state,
+                              const int64_t* cand_ptr, const int64_t* rep_row, const int64_t* rep_flip, const float* p,
+                              const uint8_t* flipped, int64_t R, const int64_t* seg_ptr, int64_t M, const int32_t* twin, int mode,
+                              int64_t max_cand, uint8_t* done, uint32_t* bits_out, float* p_state_out, int64_t* n_state_out,
+                              uint32_t* cf_bits, float* cf_p, int64_t* cf_cand, int32_t* status, void*) {
+    HOST_REQUIRE(B >= 0 && R >= 0 && M >= 0 && B <= 0x7FFFFFFF, "sizes must be >= 0, B < 2^31");
+    HOST_REQUIRE(beam >= 1 && beam <= kBeamMax, "beam must be in [1, 16]");
+    HOST_REQUIRE(W >= 0 && W <= kBeamWords, "W must be in [0, 64]");
+    HOST_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (edges) or 1 (nodes)");
+    HOST_REQUIRE(max_cand >= 0 && max_cand <= cal_explain_lds_cap(), "max_cand must be <= cal_explain_lds_cap()");
+    if (B == 0) return 0;
+    HOST_REQUIRE(n_state && cand_ptr && seg_ptr && done && n_state_out && status,
+                 "n_state / cand_ptr / seg_ptr / done / n_state_out / status are null");
+    HOST_REQUIRE(W == 0 || (bits && bits_out && cf_bits), "bits / bits_out / cf_bits are null");
+    HOST_REQUIRE(p_state_out && cf_p && cf_cand, "p_state_out / cf_p / cf_cand are null");
+    HOST_REQUIRE(R == 0 || (rep_row && rep_flip && p && flipped), "rep_row / rep_flip / p / flipped are null");
+    const BeamSrc S{bits, beam, W, n_state, rep_row, rep_flip, p, flipped};
+    if (mode != 0) twin = nullptr;
+#pragma omp parallel for schedule(dynamic, 4)
+    for (int64_t g = 0; g < B; ++g) {
+        n_state_out[g] = 0;
+        int64_t clo, cn, lo, m;
+        seg_clamp(cand_ptr, g, R, clo, cn);
+        if (done[g] || cn == 0) continue;
+        if (cn > max_cand) {
+            status[g] = 2;
+            continue;
+        }
+        status[g] = 0;
+        seg_clamp(seg_ptr, g, M, lo, m);
+        std::vector<int64_t> ord((size_t)cn);
+        for (int64_t c = 0; c < cn; ++c) ord[(size_t)c] = clo + c;
+        std::sort(ord.begin(), ord.end(), [&](int64_t i, int64_t j) { return beam_before(S, i, j); });
+        std::vector<uint32_t> child((size_t)W), kept;            // kept: the children picked so far, W words each
+        auto make = [&](int64_t i) {
+            const int s = beam_parent(S, g, i);
+            int64_t f0, f1;
+            flip_pair(rep_flip[i], lo, m, twin, f0, f1);
+            if (f0 >= 32 * W) f0 = -1;                             // (an index >= 32 W toggles nothing)
+            if (f1 >= 32 * W) f1 = -1;
+            for (int64_t w = 0; w < W; ++w)
+                child[(size_t)w] = (s < beam ? bits[(g * beam + s) * W + w] : full_word(m, W, w)) ^ flip_word(f0, f1, w);
+        };
+        if (flipped[ord[0]]) {
+            make(ord[0]);
+            for (int64_t w = 0; w < W; ++w) cf_bits[g * W + w] = child[(size_t)w];
+            done[g] = 1;
+            cf_p[g] = p[ord[0]];
+            cf_cand[g] = ord[0];
+            continue;
+        }
+        int64_t picked = 0;
+        for (int64_t c = 0; c < cn && picked < beam; ++c) {
+            make(ord[(size_t)c]);
+            bool dup = false;
+            for (int64_t k = 0; k < picked && !dup; ++k)
+                dup = std::equal(child.begin(), child.end(), kept.begin() + (size_t)(k * W));
+            if (dup) continue;
+            kept.insert(kept.end(), child.begin(), child.end());
+            for (int64_t w = 0; w < W; ++w) bits_out[(g * beam + picked) * W + w] = child[(size_t)w];
+            p_state_out[g * beam + picked] = p[ord[(size_t)c]];
+            ++picked;
+        }
+        n_state_out[g] = picked;
+    }
+    return 0;
+}
 
 // ---- structural-noise replicas (cal_amd/csrc/noise.hip; cal_amd/noise.py noise_batch): the hash, the deletions and the pair key of
 // rules.hpp and the same accepted candidates in the same order, so every integer output agrees bit for bit.  Nothing is kept

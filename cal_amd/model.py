@@ -298,6 +298,16 @@ class _CausalBase(torch.nn.Module):
         from .coalition import perturbation_curve
         return perturbation_curve(self, data, **kw)
 
+    def counterfactual(self, data, **kw):
+        """``cal_amd.counterfactual.counterfactual(self, data, **kw)``: a small set of edges or nodes whose removal flips the prediction."""
+        from .counterfactual import counterfactual
+        return counterfactual(self, data, **kw)
+
+    def ranking_flip(self, data, order=None, **kw):
+        """``cal_amd.counterfactual.ranking_flip(self, data, order, **kw)``: the smallest flipping prefix of a ranking."""
+        from .counterfactual import ranking_flip
+        return ranking_flip(self, data, order, **kw)
+
     def noise_curve(self, data, **kw):
         """``cal_amd.noise.noise_curve(self, data, **kw)``: the prediction under growing random edge insertion / deletion."""
         from .noise import noise_curve

@@ -1,5 +1,5 @@
-"""What the replica builders (``splice_batches``, ``occlude_batch``, ``coalition_batch``, ``noise_batch``) and the drivers on top of
-them share: the builders' plumbing (``_Source`` ... ``_built_batch``), the whole batch on the replicas' route (``_grouped``,
+"""What the replica builders (``splice_batches``, ``occlude_batch``, ``coalition_batch``, ``noise_batch``, ``subset_batch``) and the drivers on top of
+them share: the builders' plumbing (``_Source`` ... ``_built_batch``, ``_twin_in_order``, ``_node_map_rows``), the whole batch on the replicas' route (``_grouped``,
 ``_whole``), one replica forward (``_replica_log_probs``), the players of a batch (``_Players``, ``_representatives``, ``_members``),
 the causal score in graph order and the rho / tau / jaccard report.  It imports from ``explain`` and ``plan`` only; a new
 replica-based attribution method starts from these pieces instead of copying a sibling driver.
@@ -117,6 +117,32 @@ def _caller_columns(S, esrc, n_cols: int):
     if S.order is None or not n_cols:
         return esrc
     return torch.where(esrc >= 0, S.order[esrc.clamp(min=0)], esrc)
+
+
+def _twin_in_order(S, twin):
+    """``twin`` (int32 [E] as ``edge_twins`` gives it for the caller's columns, or ``None``) as the builders of ``S`` take it: int32,
+    contiguous, and for columns that were reordered (``S.order``) a map between positions in graph order."""
+    if twin is None:
+        return None
+    if not torch.is_tensor(twin) or twin.dim() != 1 or int(twin.numel()) != S.E:
+        raise ValueError("twin must be a 1-D tensor with one entry per edge column")
+    tw = twin.to(device=S.dev, dtype=torch.int32).contiguous()
+    if S.order is not None and S.E:
+        inv = torch.empty_like(S.order)
+        inv[S.order] = torch.arange(S.E, device=S.dev)
+        tw = tw[S.order]
+        tw = torch.where(tw >= 0, inv[tw.clamp(min=0).long()].to(torch.int32), tw).contiguous()
+    return tw
+
+
+def _node_map_rows(S, data) -> int:
+    """The row length of a node-mode builder's per-replica node map: a bound on every graph's node count (a ``Batch``'s own
+    ``max_nodes`` when it knows it, else one read-back)."""
+    from .data import Batch
+    if not (S.N and S.B):
+        return 0
+    mx = int(getattr(data, "max_nodes", 0) or 0) if isinstance(data, Batch) else 0
+    return mx if mx > 0 else int((S.ptr[1:] - S.ptr[:-1]).max())
 
 
 # ---- argument checks ----------------------------------------------------------------------------------------------------------

@@ -627,6 +627,70 @@ CAL_API int cal_coalition_write(const int64_t* edge_index, int64_t E, int64_t N,
                                 int64_t* batch_out, float* x_out, int64_t* edge_index_out, int64_t* node_src,
                                 int64_t* edge_src, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- subset replicas: R copies of graphs of one batch, each restricted to an arbitrary subset of its elements given as a bitset
+ * over the replica's OWN graph (cal_amd/counterfactual.py subset_batch; the counterfactual search) ----
+ * The batch is x [N, F] fp32 (or null, F = 0), edge_index [2, E] int64, ptr / edge_ptr [B+1] int64 as in cal_coalition_*.  bits is
+ * uint32 [K, W], row-major: bit j of a row (word j >> 5, bit j & 31) is LOCAL element j of the replica's graph g -- column
+ * edge_ptr[g] + j in mode 0, node ptr[g] + j in mode 1.  Replica r (of R) is graph g = rep_graph[r]; an id outside [0, B) gives
+ * a replica with no node and no column.  Its base set is row rep_row[r]; a row id outside [0, K) means EVERY element is present
+ * (the control replica, and the only base with K = 0; bits may be null when K = 0 or W = 0).  A local index >= 32 W is absent.
+ * Then rep_flip[r], a local index, is toggled (XOR): a cleared bit is set, a set bit cleared, an absent index >= 32 W becomes
+ * present.  In mode 0, when twin (int32 [E], as cal_edge_twin writes it; or null) is given and twin[edge_ptr[g] + rep_flip[r]]
+ * lies inside g's segment, that twin column is toggled too; a self loop is its own twin (toggled once).  A flip outside
+ * [0, m), m the graph's element count, toggles nothing.  mode 0 (edges): all nodes of g stay in order, the columns whose bit is set after the toggle stay in
+ * order.  mode 1 (nodes): the nodes that stay are renumbered densely in their order and their rows copied; a column stays iff
+ * both endpoints stay, and its endpoints are rewritten.  In both modes a source column with an endpoint outside its graph's node
+ * range is dropped, as everywhere.  max_nodes (< 2^31) must bound every graph's node count: in mode 1 it is the row length of the
+ * per-replica node map in ws, and a graph with more nodes gives a replica with nothing in it.  Every integer output is uniquely
+ * determined.
+ *   cal_subset_count: ONE launch.  ptr_out / edge_ptr_out [R+1] and totals [5] int64 on the device: N', E', max_nodes',
+ *     max_edges', replicas with no node.  The per-replica counts and (mode 1) the node maps stay in ws.  The caller reads totals
+ *     back once.
+ *   cal_subset_write: ONE launch with the same inputs, the same ws and Nout = totals[0], Eout = totals[1]: node workgroups, then
+ *     one column workgroup per replica.  batch_out [N'], x_out [N', F] (row copies; null with F = 0), edge_index_out (a
+ *     contiguous [2, E']), node_src [N'] / edge_src [E'] (the source node / column of every new one).  The rows are copied 16
+ *     bytes per lane when F % 4 == 0 and x, x_out are 16-byte aligned, else element by element (0 <= F < 2^22).
+ * ws: 8-byte aligned, cal_subset_ws bytes (16 R + 256, and 4 R max_nodes more in mode 1).  Everything on `stream`, no
+ * synchronisation inside; no value that reaches an output is accumulated atomically (the completion ticket and the ordered scan
+ * of cal_occlude_count).  R = 0: nothing is launched (the count zeroes totals and the two offsets with memsets). */
+CAL_API int64_t cal_subset_ws(int64_t E, int64_t R, int64_t max_nodes, int mode);
+CAL_API int cal_subset_count(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                             int64_t B, const uint32_t* bits, int64_t K, int64_t W, const int64_t* rep_graph,
+                             const int64_t* rep_row, const int64_t* rep_flip, int64_t R, const int32_t* twin, int mode,
+                             int64_t max_nodes, int64_t* ptr_out, int64_t* edge_ptr_out, int64_t* totals, void* ws,
+                             int64_t ws_bytes, void* stream);
+CAL_API int cal_subset_write(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
+                             int64_t B, const uint32_t* bits, int64_t K, int64_t W, const int64_t* rep_graph,
+                             const int64_t* rep_row, const int64_t* rep_flip, int64_t R, const int32_t* twin, int mode,
+                             int64_t max_nodes, const float* x, int64_t F, const int64_t* ptr_out,
+                             const int64_t* edge_ptr_out, int64_t Nout, int64_t Eout, int64_t* batch_out, float* x_out,
+                             int64_t* edge_index_out, int64_t* node_src, int64_t* edge_src, void* ws, int64_t ws_bytes,
+                             void* stream);
+
+/* ---- the beam step of the counterfactual search (cal_amd/counterfactual.py counterfactual) ----
+ * Graph g's current states are the rows [g beam, g beam + n_state[g]) of bits (uint32 [B beam, W], bitsets as in cal_subset_*
+ * over the segments seg_ptr [B+1] of M elements: edge_ptr / E in mode 0, ptr / N in mode 1), 1 <= beam <= 16, W <= 64.  Its
+ * candidates are [cand_ptr[g], cand_ptr[g+1]) of R: candidate c is the state row rep_row[c] with the local index rep_flip[c]
+ * toggled -- and, in mode 0 with twin (int32 [M] or null), the twin column, exactly as in cal_subset_* -- whose replica gave
+ * p[c] = p(y^) and flipped[c] (uint8: its argmax is no longer y^).  A rep_row[c] that is none of g's live rows stands for the
+ * FULL set: the bits [0, min(m, 32 W)) of g's m elements.  A flip outside [0, min(m, 32 W)) toggles nothing.  All integer:
+ *   - done[g] != 0 or no candidate: n_state_out[g] = 0 and nothing else of g is written.
+ *   - more than max_cand candidates (max_cand <= cal_explain_lds_cap()): status[g] = 2, n_state_out[g] = 0, nothing else.
+ *   - else status[g] = 0.  The candidates are totally ordered by (flipped first, score_key(p) ascending -- the 32-bit key that
+ *     orders like the floats with NaN below every number and -0 as +0 --, rep_row ascending, rep_flip ascending, then index).
+ *     A candidate's child is its parent row with the flip applied.  Candidates with equal children (all W words) are ONE child,
+ *     the earliest in the order stands.  If the first candidate is flipped: done[g] = 1, cf_bits[g] (uint32 [B, W]) its child,
+ *     cf_p[g] its p, cf_cand[g] its index in [0, R), n_state_out[g] = 0.  Otherwise the first `beam` distinct children become the
+ *     rows g beam, g beam + 1, .. of bits_out in that order, p_state_out [B beam] their p and n_state_out[g] their count.
+ * No floating-point arithmetic: p is compared through its key and copied.  ONE launch, one workgroup per graph, the candidates'
+ * keys and the parent rows in LDS; no atomics, no synchronisation, no read-back.  bits_out must not alias bits.  B = 0: nothing is
+ * launched. */
+CAL_API int cal_beam_step(const uint32_t* bits, int64_t B, int beam, int64_t W, const int64_t* n_state,
+                          const int64_t* cand_ptr, const int64_t* rep_row, const int64_t* rep_flip, const float* p,
+                          const uint8_t* flipped, int64_t R, const int64_t* seg_ptr, int64_t M, const int32_t* twin, int mode,
+                          int64_t max_cand, uint8_t* done, uint32_t* bits_out, float* p_state_out, int64_t* n_state_out,
+                          uint32_t* cf_bits, float* cf_p, int64_t* cf_cand, int32_t* status, void* stream);
+
 /* ---- structural-noise replicas: R copies of graphs of one batch, each with random edges deleted and random edges inserted
  * (cal_amd/noise.py noise_batch; noise curves, explanation stability) ----
  * The batch is x [N, F] fp32 (or null, F = 0), edge_index [2, E] int64, ptr / edge_ptr [B+1] int64 as in cal_coalition_*.  Replica
