@@ -6,9 +6,11 @@
 // nodes move down by one, every column incident to it goes, the remaining endpoints are rewritten).  An element that is not one
 // of g's removes nothing (the control replica); a graph id outside the batch gives a replica with nothing in it.  A source
 // column with an endpoint outside its graph's node range is dropped.  Every integer output is uniquely determined (the host
-// twin and a plain-torch restatement agree bit for bit); the feature rows are copies.  The two launches follow the protocol of
-// rebatch.hpp; a replica drops a different set of columns each, so one column workgroup per replica walks the source graph's
-// columns (the replicas of an occlusion run are small graphs, one chunk each).
+// twin and a plain-torch restatement agree bit for bit); the feature rows are copies.  The rule is OccSrc of rules.hpp (occ_src,
+// replica, node_stays, col_stays), which the host twin compiles too; the kernels and the launches are the restriction pair of
+// restrict.hpp in its closed form (no node map: ws holds the counts alone).  A replica drops a different set of columns each,
+// so one column workgroup per replica walks the source graph's columns (the replicas of an occlusion run are small graphs, one
+// chunk each).  Here: the two entry points' checks.
 //
 // (2) cal_rank_agreement: per segment the ten integer counts two score vectors' rank correlations are made of (Spearman's rho
 // from the doubled mid-ranks, Kendall's tau-b from the concordant / discordant / tied pairs, the top-k overlap).  Each lane owns
@@ -16,107 +18,13 @@
 // within kSegCap: one launch (the geometry of segment.hpp: G = 64 .. 1024 threads per segment).  Longer ones: workgroup
 // (g, c) owns the rows [c S, (c + 1) S) of segment g and stages the segment tile by tile; its partial sums go to ws and
 // k_agree_finish adds them per segment in chunk order.  Integers only: the same bits in any order.
-#include "rebatch.hpp"
+#include "restrict.hpp"
 
 namespace cal {
 namespace {
 
 constexpr int kAgIt = kSegCap / kSegWide;  // elements per lane at the widest group
 constexpr int kAgPart = 9;                 // a row chunk's partial: the eight sums (pair counts doubled) and n
-
-struct OccArgs {
-    const int64_t* ei;         // [2, E]
-    int64_t E, N;
-    const int64_t* ptr;        // [B + 1]
-    const int64_t* eptr;       // [B + 1]
-    int64_t B;
-    const int64_t* rg;         // [R] graph of every replica (outside [0, B): none)
-    const int64_t* re;         // [R] the element removed (global column / node id; not one of the graph's: nothing)
-    int64_t R;
-    int mode;                  // 0 edges, 1 nodes
-    const int32_t* twin;       // [E] or null (mode 0)
-    int64_t* ptr_out;          // [R + 1]
-    int64_t* eptr_out;         // [R + 1]
-    int64_t* totals;           // [5]
-    int64_t* cnt;              // ws [2 R]: nodes, columns of every replica
-    const float* x;            // (write) [N, F] or null
-    WriteOut out;              // (write)
-    int ticket, nblk;
-};
-
-// (OccRep, occ_replica, col_stays: rules.hpp)
-
-// grid R, NT threads
-template <int NT>
-__global__ void __launch_bounds__(NT) k_occlude_count(OccArgs a) {
-    __shared__ long long red[NT / 64];
-    __shared__ int last;
-    const int64_t r = blockIdx.x, R = a.R;
-    const OccRep q = occ_replica(a, r);
-    long long c = 0;
-    for (int64_t t = threadIdx.x; t < q.em; t += NT) c += col_stays(a, q, q.elo + t);
-    const int64_t kept = wg_sum<NT>(c, red);
-    if (threadIdx.x == 0) {
-        a.cnt[r] = q.nn - (q.rn >= 0 ? 1 : 0);
-        a.cnt[R + r] = kept;
-    }
-    if (last_workgroup(a.ticket, a.nblk, &last)) scan_counts<NT>(a.cnt, a.cnt + R, R, a.ptr_out, a.eptr_out, a.totals, red);
-}
-
-// grid ceil(Nout / kNodeChunk) node workgroups, then R column workgroups; 256 threads
-__global__ void __launch_bounds__(256) k_occlude_write(OccArgs a, int node_blocks) {
-    __shared__ int64_t src[kNodeChunk];
-    __shared__ int wcnt[4];
-    if ((int)blockIdx.x < node_blocks) {
-        write_nodes(
-            a.out, a.ptr_out, a.R, -1, src,
-            [&](int64_t r, int64_t l) -> int64_t {
-                const OccRep q = occ_replica(a, r);
-                int64_t c = q.nlo + l;
-                c += q.rn >= 0 && c >= q.rn;
-                return c < q.nlo + q.nn ? c : -1;
-            },
-            [&](int64_t s) { return a.x + s * a.out.F; });
-        return;
-    }
-    const int64_t r = (int64_t)((int)blockIdx.x - node_blocks);
-    const OccRep q = occ_replica(a, r);
-    write_cols(
-        a.out, a.ptr_out, a.eptr_out, r, a.ei, a.E, q.elo, q.em, wcnt,
-        [&](int64_t e) { return col_stays(a, q, e); },
-        [&](int64_t u) { return (u - q.nlo) - (q.rn >= 0 && u > q.rn); });
-}
-
-int64_t occ_ws_need(int64_t R) { return 16 * (R > 0 ? R : 0) + 256; }
-
-// the checks both entry points share (CAL_REQUIRE names the entry point)
-#define OCCLUDE_REQUIRE_INPUTS()                                                                                                 \
-    CAL_REQUIRE(E >= 0 && N >= 0 && B >= 0 && R >= 0, "sizes must be >= 0");                                                     \
-    CAL_REQUIRE(R <= 0x7FFFFFFF, "too many replicas");                                                             \
-    CAL_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (edges) or 1 (nodes)");                                                  \
-    CAL_REQUIRE(R == 0 || (rep_graph && rep_elem), "rep_graph / rep_elem are null");                                             \
-    CAL_REQUIRE(B == 0 || (ptr && edge_ptr), "ptr / edge_ptr are null");                                                         \
-    CAL_REQUIRE(E == 0 || edge_index, "edge_index is null");                                                                     \
-    CAL_REQUIRE(R == 0 || (ws && ws_bytes >= occ_ws_need(R) && (reinterpret_cast<uintptr_t>(ws) & 7) == 0),                      \
-                "ws must be 8-byte aligned and hold cal_occlude_ws(E, R) bytes")
-
-OccArgs occ_args(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr, int64_t B,
-                 const int64_t* rep_graph, const int64_t* rep_elem, int64_t R, int mode, const int32_t* twin, void* ws) {
-    OccArgs a{};
-    a.ei = edge_index;
-    a.E = E;
-    a.N = N;
-    a.ptr = ptr;
-    a.eptr = edge_ptr;
-    a.B = B;
-    a.rg = rep_graph;
-    a.re = rep_elem;
-    a.R = R;
-    a.mode = mode;
-    a.twin = mode == 0 ? twin : nullptr;
-    a.cnt = (int64_t*)ws;
-    return a;
-}
 
 // ---- rank agreement ------------------------------------------------------------------------------------------------------------
 struct AgArgs {
@@ -290,25 +198,22 @@ int64_t ag_ws_need(int64_t M, int64_t B, int64_t max_seg) {
 
 using namespace cal;
 
-CAL_EXPORT int64_t cal_occlude_ws(int64_t, int64_t R) { return occ_ws_need(R); }
+// the checks both occlusion entry points share (CAL_REQUIRE names the entry point)
+#define OCCLUDE_REQUIRE_INPUTS()                                                                                                 \
+    CAL_RESTRICT_REQUIRE_HEAD(E >= 0 && N >= 0 && B >= 0 && R >= 0);                                                             \
+    CAL_REQUIRE(R == 0 || (rep_graph && rep_elem), "rep_graph / rep_elem are null");                                             \
+    CAL_RESTRICT_REQUIRE_TAIL(0, "ws must be 8-byte aligned and hold cal_occlude_ws(E, R) bytes");                               \
+    const OccSrc src = occ_src({edge_index, E, N, ptr, edge_ptr, B, rep_graph, mode}, rep_elem, twin)
+
+CAL_EXPORT int64_t cal_occlude_ws(int64_t, int64_t R) { return restrict_ws_need(R, 0, 0); }
 
 CAL_EXPORT int cal_occlude_count(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
                                  int64_t B, const int64_t* rep_graph, const int64_t* rep_elem, int64_t R, int mode,
                                  const int32_t* twin, int64_t* ptr_out, int64_t* edge_ptr_out, int64_t* totals, void* ws,
-                                 int64_t ws_bytes, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+                                 int64_t ws_bytes, void* stream) {
     OCCLUDE_REQUIRE_INPUTS();
     CAL_REQUIRE(totals && ptr_out && edge_ptr_out, "totals / ptr_out / edge_ptr_out are null");
-    if (R == 0) return zero_counts(__func__, totals, 5, ptr_out, edge_ptr_out, stream);
-    OccArgs a = occ_args(edge_index, E, N, ptr, edge_ptr, B, rep_graph, rep_elem, R, mode, twin, ws);
-    a.ptr_out = ptr_out;
-    a.eptr_out = edge_ptr_out;
-    a.totals = totals;
-    a.ticket = next_ticket();
-    a.nblk = (int)R;
-    CAL_REBATCH_COUNT(k_occlude_count, E / (B > 0 ? B : 1), R, stream, a);
-    CAL_CHECK_LAUNCH("k_occlude_count");
-    return 0;
+    return restrict_count(__func__, src, R, ptr_out, edge_ptr_out, totals, ws, (hipStream_t)stream);
 }
 
 CAL_EXPORT int cal_occlude_write(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
@@ -316,19 +221,12 @@ CAL_EXPORT int cal_occlude_write(const int64_t* edge_index, int64_t E, int64_t N
                                  const int32_t* twin, const float* x, int64_t F, const int64_t* ptr_out,
                                  const int64_t* edge_ptr_out, int64_t Nout, int64_t Eout, int64_t* batch_out, float* x_out,
                                  int64_t* edge_index_out, int64_t* node_src, int64_t* edge_src, void* ws, int64_t ws_bytes,
-                                 void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+                                 void* stream) {
     OCCLUDE_REQUIRE_INPUTS();
     CAL_REBATCH_REQUIRE_WRITE(R, !x_out || (F > 0 && (N == 0 || x)), "x_out needs F > 0 and x", Eout > 0 ? R : 0);
-    if (R == 0 || nb + eb == 0) return 0;
-    OccArgs a = occ_args(edge_index, E, N, ptr, edge_ptr, B, rep_graph, rep_elem, R, mode, twin, ws);
-    a.x = x;
-    a.ptr_out = const_cast<int64_t*>(ptr_out);
-    a.eptr_out = const_cast<int64_t*>(edge_ptr_out);
-    a.out = write_out(Nout, Eout, batch_out, x_out, edge_index_out, node_src, edge_src, F, x);
-    hipLaunchKernelGGL(k_occlude_write, dim3((unsigned)(nb + eb)), dim3(256), 0, stream, a, (int)nb);
-    CAL_CHECK_LAUNCH("k_occlude_write");
-    return 0;
+    return restrict_write(src, R, x, ptr_out, edge_ptr_out,
+                          write_out(Nout, Eout, batch_out, x_out, edge_index_out, node_src, edge_src, F, x), nb, eb, ws,
+                          (hipStream_t)stream);
 }
 
 CAL_EXPORT int64_t cal_rank_agreement_ws(int64_t M, int64_t B, int64_t max_seg) { return ag_ws_need(M, B, max_seg); }

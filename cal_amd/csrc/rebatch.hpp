@@ -1,6 +1,7 @@
 // The count / scan / write toolkit of the batch builders (splice.hip, occlude.hip, coalition.hip, noise.hip, subset.hip): operators
 // that make a new batch of R result graphs out of the graphs of an old one.  Device helpers are __device__ __forceinline__, host
-// helpers plain inline or macros: no kernel and no translation unit of their own.
+// helpers plain inline or macros: no kernel and no translation unit of their own.  (Occlusion, coalitions and subsets share their
+// two kernels as well: restrict.hpp, on top of this.)
 //
 // The protocol, two launches with the caller's one read-back of totals between them:
 //  * the count launch, one workgroup per result graph, leaves every result graph's node and column count in ws.  The workgroup

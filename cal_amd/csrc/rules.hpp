@@ -3,8 +3,9 @@
 // A new rule of that kind goes here first; neither side keeps a copy.
 //
 // Plain C++: <math.h>, <stdint.h>, <string.h> and cal_hip.h, no HIP header.  CAL_RULE is the qualifier of every function:
-// host + device, always inlined under hipcc; `inline` under any other compiler.  The replica rules are templates over the
-// argument struct: the kernels' *Args and the host's *Src carry the same field names (ei, E, N, ptr, eptr, B, rg, ...).
+// host + device, always inlined under hipcc; `inline` under any other compiler.  The restriction builders' rules read the
+// sources declared here; the other replica rules are templates over the argument struct: the kernels' *Args and the host's *Src
+// carry the same field names (ei, E, N, ptr, eptr, B, rg, ...).
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -147,16 +148,45 @@ CAL_RULE unsigned long long wl_next(unsigned long long c, unsigned long long so,
 }
 
 // ---- the batch builders: replica r -> node range [nlo, nlo + nn), column range [elo, elo + em) (all zero without a graph), and
-// which of the graph's columns / elements stay.  A: OccArgs / OccludeSrc, CoArgs / CoalitionSrc, SubArgs / SubsetSrc, NoArgs / NoiseSrc,
-// Side / SpliceSide.
+// which of the graph's columns / elements stay.  A: the sources below for the restriction builders, NoArgs / NoiseSrc, Side /
+// SpliceSide.
+
+// The restriction builders (occlusion, coalitions, subsets): replica r is graph rg[r] of the batch with some of its elements
+// left out.  Mode 0: every node stays; mode 1: the nodes that stay are renumbered densely and a column stays iff both ends stay.
+// A column that leaves its graph is dropped.  Each rule is a source -- the batch and what the rule reads, made by its maker,
+// which both libraries call -- and three overloads on it: replica(s, r), node_stays(s, q, l) for LOCAL node l of the replica's
+// graph, col_stays(s, q, e) for column e of it.  A new rule is a source, a maker and these three.
+struct BatchSrc {
+    const int64_t* ei;         // [2, E]
+    int64_t E, N;
+    const int64_t* ptr;        // [B + 1]
+    const int64_t* eptr;       // [B + 1]
+    int64_t B;
+    const int64_t* rg;         // [R] graph of every replica (outside [0, B): none)
+    int mode;                  // 0 edges, 1 nodes
+};
+
+// bytes of ws of R replicas: two counts each, and in mode 1 a map row of max_nodes ids each (occlusion has no map: max_nodes = 0)
+CAL_RULE int64_t restrict_ws_need(int64_t R, int64_t max_nodes, int mode) {
+    R = R > 0 ? R : 0;
+    return 16 * R + (mode == 1 ? 4 * R * (max_nodes > 0 ? max_nodes : 0) : 0) + 256;
+}
 
 // occlusion: the node removed (rn) and the columns removed (c0, c1); -1 = none, which equals no id
+struct OccSrc : BatchSrc {
+    const int64_t* re;         // [R] the element removed (global column / node id; not one of the graph's: nothing)
+    const int32_t* twin;       // [E] or null
+};
 struct OccRep {
     int64_t nlo, nn, elo, em, rn, c0, c1;
 };
 
-template <class A>
-CAL_RULE OccRep occ_replica(const A& a, int64_t r) {
+// (a twin map pairs columns: it counts in mode 0 only)
+CAL_RULE OccSrc occ_src(const BatchSrc& b, const int64_t* rep_elem, const int32_t* twin) {
+    return OccSrc{b, rep_elem, b.mode == 0 ? twin : nullptr};
+}
+
+CAL_RULE OccRep replica(const OccSrc& a, int64_t r) {
     OccRep q{0, 0, 0, 0, -1, -1, -1};
     const int64_t g = a.rg[r];
     if (g < 0 || g >= a.B) return q;
@@ -174,22 +204,38 @@ CAL_RULE OccRep occ_replica(const A& a, int64_t r) {
     return q;
 }
 
+// LOCAL node l of the replica's graph stays
+CAL_RULE bool node_stays(const OccSrc&, const OccRep& q, int64_t l) { return q.nlo + l != q.rn; }
+
 // column e of the replica's graph stays
-template <class A>
-CAL_RULE bool col_stays(const A& a, const OccRep& q, int64_t e) {
+CAL_RULE bool col_stays(const OccSrc& a, const OccRep& q, int64_t e) {
     const int64_t u = a.ei[e], v = a.ei[a.E + e];
     return u >= q.nlo && u < q.nlo + q.nn && v >= q.nlo && v < q.nlo + q.nn && e != q.c0 && e != q.c1 && u != q.rn && v != q.rn;
 }
 
 // coalitions: the replica's key row (null: everything stays) and threshold.  In mode 1 a graph with more nodes than the map's row
 // length (mx) has no replica either.
+struct CoSrc : BatchSrc {
+    const int32_t* key;        // [K, M], M = E (mode 0) or N (mode 1)
+    int64_t K, M;
+    const int64_t* rrow;       // [R] key row of every replica (outside [0, K): everything stays)
+    const int64_t* rth;        // [R] threshold
+    int invert;                // 0: key < threshold stays, 1: key >= threshold stays
+    int64_t mx;                // (mode 1) the map's row length: bounds every graph's node count
+};
 struct CoRep {
     int64_t nlo, nn, elo, em, th;
     const int32_t* row;
 };
 
-template <class A>
-CAL_RULE CoRep co_replica(const A& a, int64_t r) {
+// (no key entry: K = 0, every replica keeps everything there is)
+CAL_RULE CoSrc co_src(const BatchSrc& b, const int32_t* key, int64_t K, const int64_t* rep_row, const int64_t* rep_thresh, int invert,
+                      int64_t max_nodes) {
+    const int64_t M = b.mode == 0 ? b.E : b.N;
+    return CoSrc{b, key, key && M > 0 ? K : 0, M, rep_row, rep_thresh, invert, max_nodes};
+}
+
+CAL_RULE CoRep replica(const CoSrc& a, int64_t r) {
     CoRep q{0, 0, 0, 0, 0, nullptr};
     const int64_t g = a.rg[r];
     if (g < 0 || g >= a.B) return q;
@@ -206,16 +252,17 @@ CAL_RULE CoRep co_replica(const A& a, int64_t r) {
 }
 
 // element e (a column in mode 0, a node in mode 1; inside [0, M)) stays in the replica
-template <class A>
-CAL_RULE bool elem_stays(const A& a, const CoRep& q, int64_t e) {
+CAL_RULE bool elem_stays(const CoSrc& a, const CoRep& q, int64_t e) {
     if (!q.row) return true;
     const int64_t k = q.row[e];
     return a.invert ? k >= q.th : k < q.th;
 }
 
+// LOCAL node l of the replica's graph stays
+CAL_RULE bool node_stays(const CoSrc& a, const CoRep& q, int64_t l) { return a.mode == 0 || elem_stays(a, q, q.nlo + l); }
+
 // column e of the replica's graph stays
-template <class A>
-CAL_RULE bool col_stays(const A& a, const CoRep& q, int64_t e) {
+CAL_RULE bool col_stays(const CoSrc& a, const CoRep& q, int64_t e) {
     const int64_t u = a.ei[e], v = a.ei[a.E + e];
     if (!(u >= q.nlo && u < q.nlo + q.nn && v >= q.nlo && v < q.nlo + q.nn)) return false;
     return a.mode == 0 ? elem_stays(a, q, e) : elem_stays(a, q, u) && elem_stays(a, q, v);
@@ -223,12 +270,25 @@ CAL_RULE bool col_stays(const A& a, const CoRep& q, int64_t e) {
 
 // subsets: the replica's bitset row over its own graph's elements (all: no row, everything present) and the LOCAL indices its
 // flip toggles (f0 the flip, f1 its twin column; -1: none).  The elements are the graph's columns in mode 0, its nodes in mode 1.
-// A: SubArgs / SubsetSrc (bits, K, W, rrow, rflip, twin, mode, mx besides the batch).
+struct SubSrc : BatchSrc {
+    const uint32_t* bits;      // [K, W]
+    int64_t K, W;
+    const int64_t* rrow;       // [R] bitset row of every replica (outside [0, K): everything present)
+    const int64_t* rflip;      // [R] local index toggled (outside the graph's elements: none)
+    const int32_t* twin;       // [E] or null
+    int64_t mx;                // (mode 1) the map's row length: bounds every graph's node count
+};
 struct SubRep {
     int64_t nlo, nn, elo, em, f0, f1;
     const uint32_t* row;
     bool all;
 };
+
+// (a twin map pairs columns: it counts in mode 0 only)
+CAL_RULE SubSrc sub_src(const BatchSrc& b, const uint32_t* bits, int64_t K, int64_t W, const int64_t* rep_row,
+                        const int64_t* rep_flip, const int32_t* twin, int64_t max_nodes) {
+    return SubSrc{b, bits, K, W, rep_row, rep_flip, b.mode == 0 ? twin : nullptr, max_nodes};
+}
 
 // bit j of a row of W words: a local index >= 32 W is absent
 CAL_RULE bool bit_at(const uint32_t* row, int64_t W, int64_t j) {
@@ -248,8 +308,7 @@ CAL_RULE void flip_pair(int64_t f, int64_t lo, int64_t m, const int32_t* twin, i
     }
 }
 
-template <class A>
-CAL_RULE SubRep sub_replica(const A& a, int64_t r) {
+CAL_RULE SubRep replica(const SubSrc& a, int64_t r) {
     SubRep q{0, 0, 0, 0, -1, -1, nullptr, true};
     const int64_t g = a.rg[r];
     if (g < 0 || g >= a.B) return q;
@@ -270,14 +329,15 @@ CAL_RULE SubRep sub_replica(const A& a, int64_t r) {
 }
 
 // LOCAL element j (a column of the graph in mode 0, a node in mode 1) stays in the replica: its bit after the toggle
-template <class A>
-CAL_RULE bool elem_stays(const A& a, const SubRep& q, int64_t j) {
+CAL_RULE bool elem_stays(const SubSrc& a, const SubRep& q, int64_t j) {
     return (q.all || bit_at(q.row, a.W, j)) != (j == q.f0 || j == q.f1);
 }
 
+// LOCAL node l of the replica's graph stays
+CAL_RULE bool node_stays(const SubSrc& a, const SubRep& q, int64_t l) { return a.mode == 0 || elem_stays(a, q, l); }
+
 // column e of the replica's graph stays
-template <class A>
-CAL_RULE bool col_stays(const A& a, const SubRep& q, int64_t e) {
+CAL_RULE bool col_stays(const SubSrc& a, const SubRep& q, int64_t e) {
     const int64_t u = a.ei[e], v = a.ei[a.E + e];
     if (!(u >= q.nlo && u < q.nlo + q.nn && v >= q.nlo && v < q.nlo + q.nn)) return false;
     return a.mode == 0 ? elem_stays(a, q, e - q.elo) : elem_stays(a, q, u - q.nlo) && elem_stays(a, q, v - q.nlo);

@@ -1239,23 +1239,64 @@ HOST_EXPORT int cal_graph_splice_write(const int64_t* eia, int64_t Ea, int64_t N
 }
 #undef SPLICE_REQUIRE_INPUTS
 
-// ---- occlusion replicas (cal_amd/csrc/occlude.hip; cal_amd/occlude.py occlude_batch): the same nodes and columns in the same
-// order, so every integer output agrees bit for bit.
+// ---- the restriction builders: occlusion, coalition and subset replicas (cal_amd/csrc/restrict.hpp with occlude.hip, coalition.hip,
+// subset.hip; occlude_batch, coalition_batch, subset_batch).  One count loop and one write loop over the sources and the
+// replica / node_stays / col_stays overloads of rules.hpp: the same nodes and columns in the same order as the kernels, so every
+// integer output agrees bit for bit.  An entry point is its checks, its source and one call.
 namespace {
-struct OccludeSrc {            // (the fields occ_replica and col_stays of rules.hpp read, named as occlude.hip's OccArgs)
-    const int64_t* ei; int64_t E, N; const int64_t* ptr; const int64_t* eptr; int64_t B; const int64_t* rg; const int64_t* re;
-    int mode; const int32_t* twin;
-};
+template <class S>
+int restrict_count(const S& s, int64_t R, int64_t* ptr_out, int64_t* edge_ptr_out, int64_t* totals) {
+    std::vector<int64_t> cn((size_t)R), cm((size_t)R);
+#pragma omp parallel for schedule(dynamic, 16)
+    for (int64_t r = 0; r < R; ++r) {
+        const auto q = replica(s, r);
+        int64_t n = 0, m = 0;
+        for (int64_t l = 0; l < q.nn; ++l) n += node_stays(s, q, l);
+        for (int64_t e = q.elo; e < q.elo + q.em; ++e) m += col_stays(s, q, e);
+        cn[(size_t)r] = n;
+        cm[(size_t)r] = m;
+    }
+    BatchScan scan{ptr_out, edge_ptr_out, totals};
+    for (int64_t r = 0; r < R; ++r) scan.add(r, cn[(size_t)r], cm[(size_t)r]);
+    scan.finish(R);
+    return 0;
+}
+
+template <class S>
+int restrict_write(const S& s, int64_t R, const float* x, OutWriter W) {
+#pragma omp parallel for schedule(dynamic, 16) firstprivate(W)
+    for (int64_t r = 0; r < R; ++r) {                          // (every replica writes its own run of the outputs)
+        std::vector<int64_t> local;                            // new local id of every node of the replica's graph
+        const auto q = replica(s, r);
+        W.begin(r);
+        local.assign((size_t)q.nn, 0);
+        for (int64_t l = 0; l < q.nn; ++l) {
+            local[(size_t)l] = W.i - W.n0;
+            if (node_stays(s, q, l)) W.node(q.nlo + l, x, q.nlo + l);
+        }
+        for (int64_t e = q.elo; e < q.elo + q.em; ++e)
+            if (col_stays(s, q, e)) W.col(W.n0 + local[(size_t)(s.ei[e] - q.nlo)], W.n0 + local[(size_t)(s.ei[s.E + e] - q.nlo)], e);
+    }
+    return 0;
+}
 }  // namespace
 
-HOST_EXPORT int64_t cal_occlude_ws(int64_t, int64_t R) { return 16 * (R > 0 ? R : 0) + 256; }
+// the checks the six entry points share (HOST_REQUIRE names the entry point): HEAD, then the builder's own, then TAIL
+#define RESTRICT_REQUIRE_HEAD(sizes_ok)                                                                                          \
+    HOST_REQUIRE(sizes_ok, "sizes must be >= 0");                                                                                \
+    HOST_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (edges) or 1 (nodes)")
+#define RESTRICT_REQUIRE_TAIL()                                                                                                  \
+    HOST_REQUIRE(B == 0 || (ptr && edge_ptr), "ptr / edge_ptr are null");                                                        \
+    HOST_REQUIRE(E == 0 || edge_index, "edge_index is null");                                                                    \
+    const BatchSrc batch{edge_index, E, N, ptr, edge_ptr, B, rep_graph, mode}
+
+HOST_EXPORT int64_t cal_occlude_ws(int64_t, int64_t R) { return restrict_ws_need(R, 0, 0); }
 
 #define OCCLUDE_REQUIRE_INPUTS()                                                                                                 \
-    HOST_REQUIRE(E >= 0 && N >= 0 && B >= 0 && R >= 0, "sizes must be >= 0");                                                    \
-    HOST_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (edges) or 1 (nodes)");                                                 \
+    RESTRICT_REQUIRE_HEAD(E >= 0 && N >= 0 && B >= 0 && R >= 0);                                                                 \
     HOST_REQUIRE(R == 0 || (rep_graph && rep_elem), "rep_graph / rep_elem are null");                                            \
-    HOST_REQUIRE(B == 0 || (ptr && edge_ptr), "ptr / edge_ptr are null");                                                        \
-    HOST_REQUIRE(E == 0 || edge_index, "edge_index is null")
+    RESTRICT_REQUIRE_TAIL();                                                                                                     \
+    const OccSrc S = occ_src(batch, rep_elem, twin)
 
 HOST_EXPORT int cal_occlude_count(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
                                   int64_t B, const int64_t* rep_graph, const int64_t* rep_elem, int64_t R, int mode,
@@ -1263,16 +1304,7 @@ HOST_EXPORT int cal_occlude_count(const int64_t* edge_index, int64_t E, int64_t 
                                   void*) {
     OCCLUDE_REQUIRE_INPUTS();
     HOST_REQUIRE(totals && ptr_out && edge_ptr_out, "totals / ptr_out / edge_ptr_out are null");
-    const OccludeSrc S{edge_index, E, N, ptr, edge_ptr, B, rep_graph, rep_elem, mode, mode == 0 ? twin : nullptr};
-    BatchScan scan{ptr_out, edge_ptr_out, totals};
-    for (int64_t r = 0; r < R; ++r) {
-        const OccRep q = occ_replica(S, r);
-        int64_t m = 0;
-        for (int64_t e = q.elo; e < q.elo + q.em; ++e) m += col_stays(S, q, e);
-        scan.add(r, q.nn - (q.rn >= 0 ? 1 : 0), m);
-    }
-    scan.finish(R);
-    return 0;
+    return restrict_count(S, R, ptr_out, edge_ptr_out, totals);
 }
 
 HOST_EXPORT int cal_occlude_write(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
@@ -1282,48 +1314,20 @@ HOST_EXPORT int cal_occlude_write(const int64_t* edge_index, int64_t E, int64_t 
                                   int64_t* edge_index_out, int64_t* node_src, int64_t* edge_src, void*, int64_t, void*) {
     OCCLUDE_REQUIRE_INPUTS();
     HOST_REQUIRE_WRITE(R, !x_out || (F > 0 && (N == 0 || x)), "x_out needs F > 0 and x");
-    const OccludeSrc S{edge_index, E, N, ptr, edge_ptr, B, rep_graph, rep_elem, mode, mode == 0 ? twin : nullptr};
-    for (int64_t r = 0; r < R; ++r) {
-        const OccRep q = occ_replica(S, r);
-        W.begin(r);
-        for (int64_t s = q.nlo; s < q.nlo + q.nn; ++s)
-            if (s != q.rn) W.node(s, x, s);
-        for (int64_t e = q.elo; e < q.elo + q.em; ++e) {
-            if (!col_stays(S, q, e)) continue;
-            const int64_t u = edge_index[e], v = edge_index[E + e];
-            W.col(W.n0 + (u - q.nlo) - (q.rn >= 0 && u > q.rn ? 1 : 0), W.n0 + (v - q.nlo) - (q.rn >= 0 && v > q.rn ? 1 : 0), e);
-        }
-    }
-    return 0;
+    return restrict_write(S, R, x, W);
 }
 #undef OCCLUDE_REQUIRE_INPUTS
 
-// ---- coalition replicas (cal_amd/csrc/coalition.hip; cal_amd/coalition.py coalition_batch): the same nodes and columns in the
-// same order, so every integer output agrees bit for bit.
-namespace {
-struct CoalitionSrc {          // (the fields co_replica, elem_stays and col_stays of rules.hpp read, named as coalition.hip's CoArgs)
-    const int64_t* ei; int64_t E, N; const int64_t* ptr; const int64_t* eptr; int64_t B; const int32_t* key; int64_t K, M;
-    const int64_t* rg; const int64_t* rrow; const int64_t* rth; int mode, invert; int64_t mx;
-};
-}  // namespace
-
-HOST_EXPORT int64_t cal_coalition_ws(int64_t, int64_t R, int64_t max_nodes, int mode) {
-    R = R > 0 ? R : 0;
-    return 16 * R + (mode == 1 ? 4 * R * (max_nodes > 0 ? max_nodes : 0) : 0) + 256;
-}
+HOST_EXPORT int64_t cal_coalition_ws(int64_t, int64_t R, int64_t max_nodes, int mode) { return restrict_ws_need(R, max_nodes, mode); }
 
 #define COALITION_REQUIRE_INPUTS()                                                                                               \
-    HOST_REQUIRE(E >= 0 && N >= 0 && B >= 0 && R >= 0 && K >= 0, "sizes must be >= 0");                                          \
-    HOST_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (edges) or 1 (nodes)");                                                 \
+    RESTRICT_REQUIRE_HEAD(E >= 0 && N >= 0 && B >= 0 && R >= 0 && K >= 0);                                                       \
     HOST_REQUIRE(invert == 0 || invert == 1, "invert must be 0 or 1");                                                           \
     HOST_REQUIRE(max_nodes >= 0 && max_nodes <= 0x7FFFFFFF, "max_nodes must be in [0, 2^31)");                                   \
     HOST_REQUIRE(R == 0 || (rep_graph && rep_row && rep_thresh), "rep_graph / rep_row / rep_thresh are null");                   \
     HOST_REQUIRE(K == 0 || (mode == 0 ? E : N) == 0 || key, "key is null");                                                      \
-    HOST_REQUIRE(B == 0 || (ptr && edge_ptr), "ptr / edge_ptr are null");                                                        \
-    HOST_REQUIRE(E == 0 || edge_index, "edge_index is null");                                                                    \
-    const int64_t M = mode == 0 ? E : N;                                                                                         \
-    const CoalitionSrc S{edge_index, E, N, ptr, edge_ptr, B, key, key && M > 0 ? K : 0, M, rep_graph, rep_row, rep_thresh, mode, \
-                         invert, max_nodes}
+    RESTRICT_REQUIRE_TAIL();                                                                                                     \
+    const CoSrc S = co_src(batch, key, K, rep_row, rep_thresh, invert, max_nodes)
 
 HOST_EXPORT int cal_coalition_count(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
                                     int64_t B, const int32_t* key, int64_t K, const int64_t* rep_graph, const int64_t* rep_row,
@@ -1331,17 +1335,7 @@ HOST_EXPORT int cal_coalition_count(const int64_t* edge_index, int64_t E, int64_
                                     int64_t* ptr_out, int64_t* edge_ptr_out, int64_t* totals, void*, int64_t, void*) {
     COALITION_REQUIRE_INPUTS();
     HOST_REQUIRE(totals && ptr_out && edge_ptr_out, "totals / ptr_out / edge_ptr_out are null");
-    BatchScan scan{ptr_out, edge_ptr_out, totals};
-    for (int64_t r = 0; r < R; ++r) {
-        const CoRep q = co_replica(S, r);
-        int64_t n = 0, m = 0;
-        if (mode == 0) n = q.nn;
-        else for (int64_t s = q.nlo; s < q.nlo + q.nn; ++s) n += elem_stays(S, q, s);
-        for (int64_t e = q.elo; e < q.elo + q.em; ++e) m += col_stays(S, q, e);
-        scan.add(r, n, m);
-    }
-    scan.finish(R);
-    return 0;
+    return restrict_count(S, R, ptr_out, edge_ptr_out, totals);
 }
 
 HOST_EXPORT int cal_coalition_write(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
@@ -1352,48 +1346,20 @@ HOST_EXPORT int cal_coalition_write(const int64_t* edge_index, int64_t E, int64_
                                     int64_t* edge_src, void*, int64_t, void*) {
     COALITION_REQUIRE_INPUTS();
     HOST_REQUIRE_WRITE(R, !x_out || (F > 0 && (N == 0 || x)), "x_out needs F > 0 and x");
-    std::vector<int64_t> local;                            // (mode 1) new local id of every node of the replica's graph
-    for (int64_t r = 0; r < R; ++r) {
-        const CoRep q = co_replica(S, r);
-        W.begin(r);
-        local.assign((size_t)q.nn, 0);
-        for (int64_t s = q.nlo; s < q.nlo + q.nn; ++s) {
-            local[(size_t)(s - q.nlo)] = W.i - W.n0;
-            if (mode == 0 || elem_stays(S, q, s)) W.node(s, x, s);
-        }
-        for (int64_t e = q.elo; e < q.elo + q.em; ++e)
-            if (col_stays(S, q, e))
-                W.col(W.n0 + local[(size_t)(edge_index[e] - q.nlo)], W.n0 + local[(size_t)(edge_index[E + e] - q.nlo)], e);
-    }
-    return 0;
+    return restrict_write(S, R, x, W);
 }
 #undef COALITION_REQUIRE_INPUTS
 
-// ---- subset replicas (cal_amd/csrc/subset.hip; cal_amd/counterfactual.py subset_batch): the same nodes and columns in the same
-// order, so every integer output agrees bit for bit.
-namespace {
-struct SubsetSrc {             // (the fields sub_replica, elem_stays and col_stays of rules.hpp read, named as subset.hip's SubArgs)
-    const int64_t* ei; int64_t E, N; const int64_t* ptr; const int64_t* eptr; int64_t B; const uint32_t* bits; int64_t K, W;
-    const int64_t* rg; const int64_t* rrow; const int64_t* rflip; const int32_t* twin; int mode; int64_t mx;
-};
-}  // namespace
-
-HOST_EXPORT int64_t cal_subset_ws(int64_t, int64_t R, int64_t max_nodes, int mode) {
-    R = R > 0 ? R : 0;
-    return 16 * R + (mode == 1 ? 4 * R * (max_nodes > 0 ? max_nodes : 0) : 0) + 256;
-}
+HOST_EXPORT int64_t cal_subset_ws(int64_t, int64_t R, int64_t max_nodes, int mode) { return restrict_ws_need(R, max_nodes, mode); }
 
 #define SUBSET_REQUIRE_INPUTS()                                                                                                  \
-    HOST_REQUIRE(E >= 0 && N >= 0 && B >= 0 && R >= 0 && K >= 0 && NW >= 0, "sizes must be >= 0");                               \
+    RESTRICT_REQUIRE_HEAD(E >= 0 && N >= 0 && B >= 0 && R >= 0 && K >= 0 && NW >= 0);                                            \
     HOST_REQUIRE(NW <= (1 << 26), "W must be <= 2^26");                                                                          \
-    HOST_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (edges) or 1 (nodes)");                                                 \
     HOST_REQUIRE(max_nodes >= 0 && max_nodes <= 0x7FFFFFFF, "max_nodes must be in [0, 2^31)");                                   \
     HOST_REQUIRE(R == 0 || (rep_graph && rep_row && rep_flip), "rep_graph / rep_row / rep_flip are null");                       \
     HOST_REQUIRE(K == 0 || NW == 0 || bits, "bits is null");                                                                     \
-    HOST_REQUIRE(B == 0 || (ptr && edge_ptr), "ptr / edge_ptr are null");                                                        \
-    HOST_REQUIRE(E == 0 || edge_index, "edge_index is null");                                                                    \
-    const SubsetSrc S{edge_index, E, N, ptr, edge_ptr, B, bits, K, NW, rep_graph, rep_row, rep_flip,                  \
-                      mode == 0 ? twin : nullptr, mode, max_nodes}
+    RESTRICT_REQUIRE_TAIL();                                                                                                     \
+    const SubSrc S = sub_src(batch, bits, K, NW, rep_row, rep_flip, twin, max_nodes)
 
 HOST_EXPORT int cal_subset_count(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
                                  int64_t B, const uint32_t* bits, int64_t K, int64_t NW, const int64_t* rep_graph,
@@ -1402,21 +1368,7 @@ HOST_EXPORT int cal_subset_count(const int64_t* edge_index, int64_t E, int64_t N
                                  void*) {
     SUBSET_REQUIRE_INPUTS();
     HOST_REQUIRE(totals && ptr_out && edge_ptr_out, "totals / ptr_out / edge_ptr_out are null");
-    std::vector<int64_t> cn((size_t)R), cm((size_t)R);
-#pragma omp parallel for schedule(dynamic, 16)
-    for (int64_t r = 0; r < R; ++r) {
-        const SubRep q = sub_replica(S, r);
-        int64_t n = 0, m = 0;
-        if (mode == 0) n = q.nn;
-        else for (int64_t l = 0; l < q.nn; ++l) n += elem_stays(S, q, l);
-        for (int64_t e = q.elo; e < q.elo + q.em; ++e) m += col_stays(S, q, e);
-        cn[(size_t)r] = n;
-        cm[(size_t)r] = m;
-    }
-    BatchScan scan{ptr_out, edge_ptr_out, totals};
-    for (int64_t r = 0; r < R; ++r) scan.add(r, cn[(size_t)r], cm[(size_t)r]);
-    scan.finish(R);
-    return 0;
+    return restrict_count(S, R, ptr_out, edge_ptr_out, totals);
 }
 
 HOST_EXPORT int cal_subset_write(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* ptr, const int64_t* edge_ptr,
@@ -1427,23 +1379,11 @@ HOST_EXPORT int cal_subset_write(const int64_t* edge_index, int64_t E, int64_t N
                                  int64_t* edge_index_out, int64_t* node_src, int64_t* edge_src, void*, int64_t, void*) {
     SUBSET_REQUIRE_INPUTS();
     HOST_REQUIRE_WRITE(R, !x_out || (F > 0 && (N == 0 || x)), "x_out needs F > 0 and x");
-#pragma omp parallel for schedule(dynamic, 16) firstprivate(W)
-    for (int64_t r = 0; r < R; ++r) {                          // (every replica writes its own run of the outputs)
-        std::vector<int64_t> local;                            // (mode 1) new local id of every node of the replica's graph
-        const SubRep q = sub_replica(S, r);
-        W.begin(r);
-        local.assign((size_t)q.nn, 0);
-        for (int64_t l = 0; l < q.nn; ++l) {
-            local[(size_t)l] = W.i - W.n0;
-            if (mode == 0 || elem_stays(S, q, l)) W.node(q.nlo + l, x, q.nlo + l);
-        }
-        for (int64_t e = q.elo; e < q.elo + q.em; ++e)
-            if (col_stays(S, q, e))
-                W.col(W.n0 + local[(size_t)(edge_index[e] - q.nlo)], W.n0 + local[(size_t)(edge_index[E + e] - q.nlo)], e);
-    }
-    return 0;
+    return restrict_write(S, R, x, W);
 }
 #undef SUBSET_REQUIRE_INPUTS
+#undef RESTRICT_REQUIRE_HEAD
+#undef RESTRICT_REQUIRE_TAIL
 
 // ---- the beam step (cal_amd/csrc/beam.hip; cal_amd/counterfactual.py): the order, the children and the duplicates of rules.hpp,
 // graph by graph.

@@ -27,7 +27,7 @@ from .explain import _eval_mode, _keep8, _Layout, rank_segment_pairs, rank_segme
 from .plan import _p, _stream
 from .replica import (_agree_report, _agree_sums, _built_batch, _caller_columns, _causal_in_order, _check_driver_args, _check_topk,
                       _check_use, _feature_width, _grouped, _members, _p_at, _pairs, _Players, _rebatch, _replica_log_probs,
-                      _Source, _whole)
+                      _Source, _twin_in_order, _whole)
 
 __all__ = ["Occlusion", "occlude_batch", "occlusion", "rank_agreement", "faithfulness", "eval_faithfulness"]
 
@@ -61,18 +61,11 @@ def occlude_batch(data, rep_graph, rep_elem, *, use: str = "edges", twin=None):
     R = int(rg.numel())
     if int(re.numel()) != R:
         raise ValueError("rep_graph and rep_elem must have one entry per replica each (got %d and %d)" % (R, re.numel()))
-    tw = None
-    if twin is not None and mode == 0:
-        if not torch.is_tensor(twin) or twin.dim() != 1 or int(twin.numel()) != S.E:
-            raise ValueError("twin must be a 1-D tensor with one entry per edge column")
-        tw = twin.to(device=dev, dtype=torch.int32).contiguous()
+    tw = _twin_in_order(S, twin) if mode == 0 else None
     if S.order is not None and mode == 0 and S.E:          # the caller's column ids -> positions in graph order
         inv = torch.empty_like(S.order)
         inv[S.order] = torch.arange(S.E, device=dev)
         re = torch.where((re >= 0) & (re < S.E), inv[re.clamp(0, S.E - 1)], torch.full_like(re, -1))
-        if tw is not None:
-            tw = tw[S.order]
-            tw = torch.where(tw >= 0, inv[tw.clamp(min=0).long()].to(torch.int32), tw).contiguous()
     inputs = S.args() + [_p(rg) if R else None, _p(re) if R else None, R, mode, _p(tw) if S.E else None]
     built = _rebatch("cal_occlude", (S.E, R), inputs, R, 5, (S,), F, lambda: (rg < 0) | (rg >= S.B))
     return _built_batch(S, built, rg, S.no_self_loops, _caller_columns(S, built.edge_src, built.tot[1]))

@@ -1,6 +1,6 @@
 """Coalition replicas, Shapley values and perturbation curves on the MI355X: the HIP replica builder (cal_coalition_count /
-cal_coalition_write) against the plain-torch restatement and the host twin bit for bit (the CPU case list, a scan beyond one run
-per thread, a 5000-node graph next to 3-node ones, the scalar row copy next to the vector one), against occlude_batch and the
+cal_coalition_write) against the plain-torch restatement and the host twin bit for bit (the CPU case list; the sizes beyond
+it: tests/test_gpu_restrict.py), against occlude_batch and the
 composition of splice_batches and extract_subgraph, the replica batch on the engine's per-graph route against the fp64 oracle,
 shapley() and perturbation_curve() against the fp64 oracle, the exact properties of the estimate on a deterministic engine,
 the curves against fidelity(), and the engine's state left untouched."""
@@ -10,9 +10,9 @@ import random
 import pytest
 import torch
 
-from cal_amd import _lib, spmotif, synth
+from cal_amd import _lib, spmotif
 from cal_amd.coalition import (coalition_batch, eval_perturbation_curve, perturbation_curve, shapley, shapley_agreement)
-from cal_amd.data import Batch, Data, DataLoader
+from cal_amd.data import Batch, DataLoader
 from cal_amd.explain import _Layout, _log_probs, _untiled, edge_twins, explain, extract_subgraph, fidelity
 from cal_amd.occlude import occlude_batch
 from cal_amd.splice import splice_batches
@@ -78,79 +78,6 @@ def test_hip_ungrouped_columns():
     for k in ("edge_index", "ptr", "edge_ptr", "batch", "node_src"):
         assert torch.equal(getattr(res, k).cpu(), r[k]), k
     assert torch.equal(res.feat.cpu(), r["x"]) and torch.equal(res.edge_src.cpu(), order[r["edge_src"]])
-
-
-# ---- 2. the builder, sizes ----------------------------------------------------------------------------------------------------
-def _tiny(n, feat, g, hi=7):
-    ds = []
-    for _ in range(n):
-        k = int(torch.randint(3, hi, (1,), generator=g))
-        src = torch.arange(k)
-        ei = torch.stack([torch.cat([src, (src + 1) % k]), torch.cat([(src + 1) % k, src])])      # a ring, both directions
-        ds.append(Data(x=torch.randn(k, feat, generator=g), edge_index=ei, y=torch.randint(0, 4, (1,), generator=g)))
-    return ds
-
-
-@pytest.mark.parametrize("use", ["edges", "nodes"])
-def test_hip_scan_beyond_one_run_per_thread(use):
-    """3000 replicas of 3-6-node ring graphs, a third with graph id -1 (many short and many empty replicas): every thread of
-    the scanning workgroup owns a run of replicas."""
-    g = torch.Generator().manual_seed(4)
-    b = Batch.from_data_list(_tiny(500, 4, g))
-    M = int(b.edge_index.size(1)) if use == "edges" else int(b.batch.numel())
-    rg = torch.randint(-250, 500, (3000,), generator=g).clamp(min=-1)
-    key = torch.randint(-1, 7, (3, M), generator=g, dtype=torch.int32)
-    rrow = torch.randint(-1, 4, (3000,), generator=g)
-    rth = torch.randint(0, 8, (3000,), generator=g)
-    res = coalition_batch(_dev(b), rg.to(DEV), rth.to(DEV), key.to(DEV), rep_row=rrow.to(DEV), use=use)
-    r = check_coalition(res, b, rg, rrow, rth, key, use, False)
-    assert r["totals"][4] > 800
-
-
-@pytest.mark.parametrize("use", ["edges", "nodes"])
-def test_hip_large_graph_next_to_small_ones(use):
-    """Replicas of a 5000-node graph between replicas of 3-node graphs: element loops of thousands of columns in the count and
-    in the write, and in node mode a map row far beyond anything that would fit LDS.  The large graph also has columns that
-    leave its node range."""
-    g = torch.Generator().manual_seed(5)
-    big = synth.ba_graphs(1, n=5000, seed=1)
-    F = int(big[0].x.size(1)) if big[0].x is not None else int(big[0].feat.size(1))
-    small = _tiny(4, F, g, hi=4)
-    for d in small:
-        d.x, d.feat = (d.x, None) if big[0].x is not None else (None, d.x)
-    b = Batch.from_data_list(small[:2] + [big[0]] + small[2:])
-    b.edge_index = b.edge_index.clone()
-    lo = int(b.edge_ptr[2])
-    b.edge_index[0, lo + 1500] = 0
-    b.edge_index[1, lo + 7777] = int(b.ptr[3])
-    M = int(b.edge_index.size(1)) if use == "edges" else int(b.batch.numel())
-    key = torch.randint(0, 8, (2, M), generator=g, dtype=torch.int32)
-    bd = _dev(b)
-    for invert in (False, True):
-        rg = torch.tensor([0, 1, 2, 3, 4, 2, 2, 2])                        # the large graph in the middle, then thrice more
-        rrow = torch.tensor([0, 1, 0, 1, 0, 1, -1, 0])
-        rth = torch.tensor([4, 4, 5, 1, 9, 2, 0, 0])                       # ..., the control replica, nothing / everything
-        res = coalition_batch(bd, rg.to(DEV), rth.to(DEV), key.to(DEV), rep_row=rrow.to(DEV), use=use, invert=invert)
-        check_coalition(res, b, rg, rrow, rth, key, use, invert)
-        assert res.max_nodes == 5000 and res.max_edges > 7000
-
-
-@pytest.mark.parametrize("F", [5, 4])
-def test_hip_rows_at_odd_offsets(F):
-    """A feature matrix that starts one float into its storage: F = 5 takes the scalar copy as always, F = 4 takes it because the
-    rows are not 16-byte aligned (next to the aligned call, which takes the vector copy)."""
-    b0, rg, rrow, rth, key, use, invert = CASES["spmotif_nodes"]
-    b = Batch()
-    b.__dict__.update(b0.__dict__)
-    b.x, b.feat = torch.randn(b0.batch.numel(), F, generator=torch.Generator().manual_seed(31)), None
-    bd = _dev(b)
-    flat = torch.empty(b.x.numel() + 1, device=DEV)
-    flat[1:] = b.x.to(DEV).view(-1)
-    bd.x = flat[1:].view(-1, F)
-    assert bd.x.data_ptr() % 16 == 4 and bd.x.is_contiguous()
-    args = (rg.to(DEV), rth.to(DEV), key.to(DEV))
-    check_coalition(coalition_batch(bd, *args, rep_row=rrow.to(DEV), use=use), b, rg, rrow, rth, key, use, False)
-    check_coalition(coalition_batch(_dev(b), *args, rep_row=rrow.to(DEV), use=use), b, rg, rrow, rth, key, use, False)
 
 
 # ---- 3. the builder against the other builders ----------------------------------------------------------------------------------

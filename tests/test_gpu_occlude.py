@@ -1,6 +1,5 @@
 """Occlusion attributions on the MI355X: the HIP replica builder (cal_occlude_count / cal_occlude_write) against the plain-torch
-restatement and the host twin bit for bit (the CPU case list, a scan beyond one run per thread, a 5000-node graph next to 3-node
-ones, the scalar row copy next to the vector one), against the composition of splice_batches and extract_subgraph, the HIP
+restatement and the host twin bit for bit (the CPU case list; the sizes beyond it: tests/test_gpu_restrict.py), against the composition of splice_batches and extract_subgraph, the HIP
 rank-agreement kernel against the numpy counts and the host twin, the replica batch on the engine's per-graph route, occlusion()
 against the fp64 oracle, the exact zeros of control replicas on a deterministic engine, and faithfulness() /
 eval_faithfulness() recomputed from the engine's own scores, leaving the engine's state untouched."""
@@ -10,8 +9,8 @@ import random
 import pytest
 import torch
 
-from cal_amd import _lib, spmotif, synth
-from cal_amd.data import Batch, Data, DataLoader
+from cal_amd import _lib, spmotif
+from cal_amd.data import Batch, DataLoader
 from cal_amd.explain import _Layout, _log_probs, _untiled, edge_twins, explain, extract_subgraph
 from cal_amd.occlude import eval_faithfulness, faithfulness, occlude_batch, occlusion, rank_agreement
 from cal_amd.splice import splice_batches
@@ -53,82 +52,6 @@ def test_hip_equals_restatement_and_host_twin(name):
     assert res.edge_index.is_cuda and res.ptr.is_cuda and res.node_src.is_cuda
     check_occlude(res, b, rg, re, use, twin)
     _same(res, occlude_batch(b, rg, re, use=use, twin=twin))
-
-
-def _tiny(n, feat, g, hi=7):
-    ds = []
-    for _ in range(n):
-        k = int(torch.randint(3, hi, (1,), generator=g))
-        src = torch.arange(k)
-        ei = torch.stack([torch.cat([src, (src + 1) % k]), torch.cat([(src + 1) % k, src])])      # a ring, both directions
-        ds.append(Data(x=torch.randn(k, feat, generator=g), edge_index=ei, y=torch.randint(0, 4, (1,), generator=g)))
-    return ds
-
-
-@pytest.mark.parametrize("use", ["edges", "nodes"])
-def test_hip_scan_beyond_one_run_per_thread(use):
-    """3000 replicas of 3-6-node ring graphs, a third with graph id -1 (many short and many empty replicas): every thread of
-    the scanning workgroup owns a run of replicas."""
-    g = torch.Generator().manual_seed(4)
-    b = Batch.from_data_list(_tiny(500, 4, g))
-    rg = torch.randint(-250, 500, (3000,), generator=g).clamp(min=-1)
-    off = b.edge_ptr if use == "edges" else b.ptr
-    gc = rg.clamp(min=0)
-    re = off[gc] + torch.randint(0, 1 << 20, (3000,), generator=g) % (off[gc + 1] - off[gc])
-    twin = edge_twins(b)[0] if use == "edges" else None
-    res = occlude_batch(_dev(b), rg.to(DEV), re.to(DEV), use=use, twin=_m(twin))
-    r = check_occlude(res, b, rg, re, use, twin)
-    assert r["totals"][4] > 800
-
-
-@pytest.mark.parametrize("use", ["edges", "nodes"])
-def test_hip_large_graph_next_to_small_ones(use):
-    """One replica of a 5000-node graph between replicas of 3-node graphs: element loops of thousands of columns in the count
-    and in the write.  The large graph also has a column that leaves its node range."""
-    g = torch.Generator().manual_seed(5)
-    big = synth.ba_graphs(1, n=5000, seed=1)
-    F = int(big[0].x.size(1)) if big[0].x is not None else int(big[0].feat.size(1))
-    small = _tiny(4, F, g, hi=4)
-    for d in small:
-        d.x, d.feat = (d.x, None) if big[0].x is not None else (None, d.x)
-    b = Batch.from_data_list(small[:2] + [big[0]] + small[2:])
-    b.edge_index = b.edge_index.clone()
-    lo = int(b.edge_ptr[2])
-    b.edge_index[0, lo + 1500] = 0
-    b.edge_index[1, lo + 7777] = int(b.ptr[3])
-    twin = edge_twins(b)[0] if use == "edges" else None
-    bd = _dev(b)
-    rg = torch.arange(5)                                                  # one replica of the large graph in the middle
-    if use == "edges":
-        re = torch.tensor([int(b.edge_ptr[0]) + 1, int(b.edge_ptr[1]), lo + 4321, int(b.edge_ptr[3]), int(b.edge_ptr[5]) - 1])
-    else:
-        re = torch.tensor([int(b.ptr[0]), int(b.ptr[1]) + 1, int(b.ptr[2]) + 17, int(b.ptr[3]), int(b.ptr[5]) - 1])
-    res = occlude_batch(bd, rg.to(DEV), re.to(DEV), use=use, twin=_m(twin))
-    check_occlude(res, b, rg, re, use, twin)
-    assert res.max_nodes == 5000 - (use == "nodes") and res.max_edges > 7000
-    # the large graph's column that leaves its range / its last node as the element, and its control replica
-    rg = torch.tensor([2, 0, 2])
-    re = torch.tensor([lo + 1500 if use == "edges" else int(b.ptr[3]) - 1, -1, -1])
-    res = occlude_batch(bd, rg.to(DEV), re.to(DEV), use=use, twin=_m(twin))
-    check_occlude(res, b, rg, re, use, twin)
-    assert res.max_nodes == 5000
-
-
-@pytest.mark.parametrize("F", [5, 4])
-def test_hip_rows_at_odd_offsets(F):
-    """A feature matrix that starts one float into its storage: F = 5 takes the scalar copy as always, F = 4 takes it because the
-    rows are not 16-byte aligned (next to the aligned call, which takes the vector copy)."""
-    b0, rg, re, use, twin = CASES["repeated_edges"]
-    b = Batch()
-    b.__dict__.update(b0.__dict__)
-    b.x = torch.randn(b0.batch.numel(), F, generator=torch.Generator().manual_seed(31))
-    bd = _dev(b)
-    flat = torch.empty(b.x.numel() + 1, device=DEV)
-    flat[1:] = b.x.to(DEV).view(-1)
-    bd.x = flat[1:].view(-1, F)
-    assert bd.x.data_ptr() % 16 == 4 and bd.x.is_contiguous()
-    check_occlude(occlude_batch(bd, rg.to(DEV), re.to(DEV), use=use, twin=twin.to(DEV)), b, rg, re, use, twin)
-    check_occlude(occlude_batch(_dev(b), rg.to(DEV), re.to(DEV), use=use, twin=twin.to(DEV)), b, rg, re, use, twin)
 
 
 @pytest.mark.parametrize("name", ["spmotif_edges", "spmotif_nodes"])
