@@ -15,6 +15,8 @@ _CENTRALITY = ("Centrality", "hop_distance", "structural_scores", "structural_ba
                "explanation_locality", "eval_explanation_locality")
 _COUNTERFACTUAL = ("Counterfactual", "subset_batch", "pack_bits", "unpack_bits", "beam_step", "ranking_flip", "counterfactual_report",
                    "eval_counterfactual")
+_NEIGHBORS = ("KnnResult", "EmbeddingBank", "NearestExamples", "knn", "embedding_bank", "nearest_examples", "knn_probe",
+              "eval_disentanglement")
 
 
 def __getattr__(name):
@@ -37,4 +39,7 @@ def __getattr__(name):
         # (``cal_amd.counterfactual`` is the module; its function of that name is ``cal_amd.counterfactual.counterfactual``)
         from . import counterfactual
         return getattr(counterfactual, name)
+    if name in _NEIGHBORS:                                    # nearest neighbours in embedding space, likewise
+        from . import neighbors
+        return getattr(neighbors, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

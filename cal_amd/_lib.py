@@ -43,7 +43,8 @@ HOST_SYMBOLS = ("cal_last_error", "cal_version", "cal_plan_build", "cal_graph_pt
                 "cal_wl_ws", "cal_wl_refine", "cal_wl_match",
                 "cal_motif_match",
                 "cal_centrality_ws", "cal_centrality",
-                "cal_subset_ws", "cal_subset_count", "cal_subset_write", "cal_beam_step")
+                "cal_subset_ws", "cal_subset_count", "cal_subset_write", "cal_beam_step",
+                "cal_knn_ws", "cal_knn")
 
 _SCALARS = {
     "int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,

@@ -562,4 +562,65 @@ CAL_RULE double cent_pr_step(double alpha, double pull, double dangling, double 
 // the stopping test: err = the tree sum of |x_new - x_old|.  The step that meets it is counted in pr_iters.
 CAL_RULE bool cent_pr_done(double err, double tol) { return err < tol; }
 
+// ---- nearest neighbours in embedding space (cal_knn) -----------------------------------------------------------------------------
+constexpr int kKnnMaxK = 64, kKnnMaxH = 256, kKnnMaxC = 64;     // limits of the device library
+constexpr int kKnnQB = 32;                                      // queries of a workgroup
+constexpr int kKnnCUs = 256;                                    // compute units the chunk plan spreads over
+constexpr uint64_t kKnnNone = ~0ull;                            // no neighbour: above every key (an index is below 2^31)
+
+// the distance of a pair from the two squared norms and the dot product (T: float on the device, double on the host).
+// metric 0: squared Euclidean; 1: cosine distance, 1 where either row has norm zero.  The clamp is part of the key.
+CAL_RULE float knn_sqrt(float v) { return sqrtf(v); }
+CAL_RULE double knn_sqrt(double v) { return sqrt(v); }
+template <class T>
+CAL_RULE T knn_dist(int metric, T qn, T xn, T dot) {
+    if (metric == 0) return (qn + xn) - (T)2 * dot;
+    if (qn == (T)0 || xn == (T)0) return (T)1;
+    return (T)1 - dot / (knn_sqrt(qn) * knn_sqrt(xn));
+}
+
+// the distance as it is ordered and reported: a non-finite one is +inf (last), anything else not above zero (-0, a negative
+// rounding residue) is +0.  A distance is then >= +0, and its bits order like its value.
+CAL_RULE float knn_clamp(float d) {
+    if (d != d || d == __builtin_inff() || d == -__builtin_inff()) return __builtin_inff();
+    return d > 0.f ? d : 0.f;
+}
+// the total order of a query's candidates: distance first, the lower bank row on equal distances
+CAL_RULE uint64_t knn_key(float d, uint32_t idx) { return ((uint64_t)float_bits(knn_clamp(d)) << 32) | (uint64_t)idx; }
+CAL_RULE float knn_key_dist(uint64_t key) {
+    const uint32_t u = (uint32_t)(key >> 32);
+    float d;
+    memcpy(&d, &u, 4);
+    return d;
+}
+CAL_RULE int32_t knn_key_idx(uint64_t key) { return (int32_t)(uint32_t)key; }
+
+// bank row j may be returned for a query whose skipped row is skip (a skip outside [0, M) meets no row)
+CAL_RULE bool knn_eligible(int64_t j, int64_t skip) { return j != skip; }
+// k' of a query: the neighbours it gets
+CAL_RULE int64_t knn_count(int64_t k, int64_t M, int64_t skip) {
+    const int64_t n = M - ((skip >= 0 && skip < M) ? 1 : 0);
+    return k < n ? k : n;
+}
+// a neighbour's label counts for class `label` iff it lies in [0, C)
+CAL_RULE bool knn_votes_for(int64_t label, int64_t C) { return label >= 0 && label < C; }
+// the majority of a vote row: the lowest class among the most voted (0 for C = 0)
+CAL_RULE int knn_majority(const int32_t* votes, int C) {
+    int best = 0;
+    for (int c = 1; c < C; ++c)
+        if (votes[c] > votes[best]) best = c;
+    return best;
+}
+
+// the chunk plan: rows of a bank chunk, a multiple of 32.  A positive multiple of 32 given by the caller is taken as it is;
+// otherwise enough chunks that query blocks x chunks cover the compute units, as far as the bank has 32-row pieces.
+CAL_RULE int64_t knn_chunk_rows(int64_t nq, int64_t M, int64_t chunk_rows) {
+    if (chunk_rows > 0 && chunk_rows % 32 == 0) return chunk_rows;
+    const int64_t qb = (nq + kKnnQB - 1) / kKnnQB, pieces = (M + 31) / 32;
+    int64_t want = qb > 0 ? (kKnnCUs + qb - 1) / qb : 1;
+    want = want < 1 ? 1 : (want > pieces ? pieces : want);
+    return ((pieces + want - 1) / want) * 32;
+}
+CAL_RULE int64_t knn_chunks(int64_t M, int64_t rows) { return (M + rows - 1) / rows; }
+
 }  // namespace cal

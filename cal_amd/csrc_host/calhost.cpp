@@ -2138,3 +2138,52 @@ HOST_EXPORT int cal_centrality(const int64_t* edge_index, int64_t E, int64_t N, 
     totals[0] = ignored;
     return 0;
 }
+
+// ---- nearest neighbours in embedding space (cal_amd/csrc/knn.hip): norms and dot products in fp64, rounded once to the fp32 the key
+// holds; the same keys (knn_key), eligibility, k' and vote rule.  The chunking does not change the result: chunk_rows is only checked.
+HOST_EXPORT int64_t cal_knn_ws(int64_t, int64_t, int64_t, int64_t) { return 0; }
+
+HOST_EXPORT int cal_knn(const float* Q, int64_t nq, const float* X, int64_t M, int64_t H, int metric, int64_t k, const int64_t* skip,
+                        const int64_t* labels, int64_t C, int32_t* idx, float* dist, int32_t* votes, int64_t chunk_rows, void*,
+                        int64_t, void*) {
+    HOST_REQUIRE(nq >= 0, "nq must be >= 0");
+    HOST_REQUIRE(M >= 1 && M < (1ll << 31), "M must be in [1, 2^31)");
+    HOST_REQUIRE(H >= 1 && k >= 1 && C >= 0, "H and k must be >= 1, C >= 0");
+    HOST_REQUIRE(metric == 0 || metric == 1, "metric must be 0 (squared Euclidean) or 1 (cosine)");
+    HOST_REQUIRE(chunk_rows >= 0 && chunk_rows % 32 == 0, "chunk_rows must be 0 or a positive multiple of 32");
+    if (nq == 0) return 0;
+    HOST_REQUIRE(Q && X && idx && dist, "Q / X / idx / dist is null");
+    HOST_REQUIRE(!votes || (labels && C >= 1), "votes needs labels and C >= 1");
+    auto norm2 = [H](const float* r) {
+        double s = 0.0;
+        for (int64_t i = 0; i < H; ++i) s += (double)r[i] * (double)r[i];
+        return s;
+    };
+    std::vector<double> xn((size_t)M);
+#pragma omp parallel for schedule(static)
+    for (int64_t j = 0; j < M; ++j) xn[(size_t)j] = norm2(X + j * H);
+#pragma omp parallel for schedule(static)
+    for (int64_t q = 0; q < nq; ++q) {
+        const float* qr = Q + q * H;
+        const double qn = norm2(qr);
+        const int64_t sk = skip ? skip[q] : -1, kk = knn_count(k, M, sk);
+        std::vector<uint64_t> keys;
+        keys.reserve((size_t)M);
+        for (int64_t j = 0; j < M; ++j) {
+            if (!knn_eligible(j, sk)) continue;
+            const float* xr = X + j * H;
+            double dot = 0.0;
+            for (int64_t i = 0; i < H; ++i) dot += (double)qr[i] * (double)xr[i];
+            keys.push_back(knn_key((float)knn_dist<double>(metric, qn, xn[(size_t)j], dot), (uint32_t)j));
+        }
+        std::partial_sort(keys.begin(), keys.begin() + kk, keys.end());
+        for (int64_t c = 0; votes && c < C; ++c) votes[q * C + c] = 0;
+        for (int64_t p = 0; p < k; ++p) {
+            const uint64_t key = p < kk ? keys[(size_t)p] : kKnnNone;
+            idx[q * k + p] = p < kk ? knn_key_idx(key) : -1;
+            dist[q * k + p] = p < kk ? knn_key_dist(key) : INFINITY;
+            if (votes && p < kk && knn_votes_for(labels[knn_key_idx(key)], C)) ++votes[q * C + labels[knn_key_idx(key)]];
+        }
+    }
+    return 0;
+}

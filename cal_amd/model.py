@@ -272,6 +272,18 @@ class _CausalBase(torch.nn.Module):
         from .intervene import intervene
         return intervene(self, data, **kw)
 
+    def nearest_examples(self, data, bank, **kw):
+        """``cal_amd.neighbors.nearest_examples(self, data, bank, **kw)``: the bank graphs nearest to every graph of the batch in
+        the objects or the trivial space."""
+        from .neighbors import nearest_examples
+        return nearest_examples(self, data, bank, **kw)
+
+    def knn_probe(self, bank, **kw):
+        """``cal_amd.neighbors.knn_probe(bank, **kw)``: kNN accuracy of the label and the base type from ``xo`` and from ``xc``
+        of an ``EmbeddingBank`` of this model."""
+        from .neighbors import knn_probe
+        return knn_probe(bank, **kw)
+
     def structure_intervention(self, data, **kw):
         """``cal_amd.splice.structure_intervention(self, data, **kw)``: the model on causal parts spliced with other graphs'
         trivial parts."""

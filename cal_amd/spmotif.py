@@ -143,7 +143,12 @@ def ground_truth(batch) -> Tuple[torch.Tensor, torch.Tensor]:
     truth iff its local id is at least ``n_g - n_s``; an edge iff its local endpoint pair, less that base, is an edge of
     the motif in either direction.  The plug-in edge and noise edges between motif nodes are not ground truth.  Graphs of
     the reference generator (tests/golden/spmotif_ref_graphs.npz) place the motif nodes differently and are not covered."""
-    ei, bvec, y = batch.edge_index, batch.batch, batch.y.view(-1)
+    return _ground_truth(batch, batch.y.view(-1))
+
+
+def _ground_truth(batch, y):
+    """``ground_truth`` with the classes ``y`` [B] (inside ``CLASS_LIST``) in place of the batch's labels."""
+    ei, bvec = batch.edge_index, batch.batch
     dev = ei.device
     B = int(batch.num_graphs)
     sizes, adj = _motif_tables(dev)
@@ -161,6 +166,36 @@ def ground_truth(batch) -> Tuple[torch.Tensor, torch.Tensor]:
     b = (col - motif_base[g]).clamp(0, 5)
     edge_gt = node_gt[row] & node_gt[col] & (bvec[col] == g) & adj[yv[g], a, b]
     return node_gt, edge_gt
+
+
+def context_of(batch) -> torch.Tensor:
+    """int64 [B] on the batch's device: the base graph of every graph made by ``make_graph`` -- 0 tree, 1 ba, -1 anything else.
+
+    Read from the base size ``n_g - n_s(y_g)``: a BA base has ``node_num ** 2`` nodes, a tree ``1 + r + r ** 2``, which is never
+    a perfect square (it lies strictly between ``r ** 2`` and ``(r + 1) ** 2``).  A graph whose label is no class of
+    ``CLASS_LIST``, or whose last ``n_s`` nodes do not carry every edge of the motif (``ground_truth``), is -1: a batch of
+    another dataset is not told apart by node counts alone.  Nothing is added to ``Data``."""
+    y = batch.y.view(-1)
+    dev = batch.edge_index.device
+    B = int(batch.num_graphs)
+    sizes, adj = _motif_tables(dev)
+    known = (y >= 0) & (y < len(CLASS_LIST))
+    yc = y.to(dev).clamp(0, len(CLASS_LIST) - 1)
+    n = torch.bincount(batch.batch, minlength=B)[:B]
+    base = n - sizes[yc]
+    _, edge_gt = _ground_truth(batch, yc)
+    found = torch.zeros(B, dtype=torch.long, device=dev).index_add_(0, batch.batch[batch.edge_index[0]], edge_gt.long())
+    made = known.to(dev) & (base >= 1) & (found == adj[yc].sum((1, 2)))
+    r = base.clamp(min=0).double().sqrt().floor().long()
+    square = ((r * r == base) | ((r + 1) * (r + 1) == base))
+    tree = torch.zeros_like(square)
+    for d in (-1, 0, 1):                                  # r ~ sqrt(base): the root of 1 + r + r^2 = base is r or r - 1
+        c = (r + d).clamp(min=1)
+        tree |= 1 + c + c * c == base
+    out = torch.full((B,), -1, dtype=torch.long, device=dev)
+    out[made & tree & ~square] = 0
+    out[made & square] = 1
+    return out
 
 
 def generate_dataset(data_num: int, node_num: int = 7, noise: float = 0.1,

@@ -889,6 +889,31 @@ CAL_API int cal_centrality(const int64_t* edge_index, int64_t E, int64_t N, cons
                            int64_t* reach, int64_t* ecc, int64_t* deg, double* bc, double* ebc, double* pr, int32_t* pr_iters,
                            int32_t* hop, int64_t* skipped, int64_t* totals, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- nearest neighbours in embedding space: the pooled rows of pooled_representations (cal_amd/intervene.py) as queries and as
+ * a bank; what torch.cdist + torch.topk spell, without the [nq, M] matrix and with a total order (cal_amd/neighbors.py: knn) ----
+ *   Q        fp32  [nq, H]  the query rows
+ *   X        fp32  [M, H]   the bank
+ *   metric   0: squared Euclidean, max(0, |q|^2 + |x|^2 - 2 q.x); 1: cosine distance, 1 - q.x / (|q| |x|), 1 where either row
+ *            has norm zero.  A non-finite distance counts as +inf, anything else not above zero as +0 (knn_clamp of rules.hpp).
+ *   k        neighbours per query
+ *   skip     int64 [nq] or null: the bank row that is not returned for query q (the query's own row when the bank holds it); a
+ *            value outside [0, M) skips nothing
+ *   labels   int64 [M] or null, C: the classes of votes; a label outside [0, C) is not counted
+ *   idx      int32 [nq, k], dist fp32 [nq, k]: the k' = min(k, eligible rows) nearest rows of q in ascending order of the key
+ *            (bits of dist as uint32) << 32 | idx -- the lower row first on equal distances; positions k' .. k - 1: -1 and +inf
+ *   votes    int32 [nq, C] or null (needs labels): how many of the k' neighbours carry label c
+ *   chunk_rows  0: the bank is cut by the plan knn_chunk_rows of rules.hpp (enough chunks that 32-query blocks x chunks cover
+ *            the compute units); a positive multiple of 32: rows of a chunk.  The result does not depend on it.
+ *   ws       16-byte aligned, cal_knn_ws bytes: nq x chunks x k keys of 8 bytes (+ 256), never of the order of nq x M
+ * GPU: 1 <= H <= 256, 1 <= k <= 64, 1 <= M < 2^31, C <= 64, nq <= 65535 x 32.  TWO launches (distances on the matrix cores with the
+ * selection of a chunk's k nearest behind them; the merge of a query's chunk lists with idx, dist and votes), no floating-point
+ * atomic, no synchronisation, no read-back: the same bits on every call and under every chunking; safe to capture.  nq = 0:
+ * nothing is launched.  The host library takes any sizes, forms the distances in fp64 and needs no ws (cal_knn_ws is 0). */
+CAL_API int64_t cal_knn_ws(int64_t nq, int64_t M, int64_t k, int64_t chunk_rows);
+CAL_API int cal_knn(const float* Q, int64_t nq, const float* X, int64_t M, int64_t H, int metric, int64_t k, const int64_t* skip,
+                    const int64_t* labels, int64_t C, int32_t* idx, float* dist, int32_t* votes, int64_t chunk_rows, void* ws,
+                    int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
