@@ -17,6 +17,8 @@ _COUNTERFACTUAL = ("Counterfactual", "subset_batch", "pack_bits", "unpack_bits",
                    "eval_counterfactual")
 _NEIGHBORS = ("KnnResult", "EmbeddingBank", "NearestExamples", "knn", "embedding_bank", "nearest_examples", "knn_probe",
               "eval_disentanglement")
+_CONCEPTS = ("KMeansResult", "NodeBank", "Concepts", "kmeans", "node_bank", "discover_concepts", "assign_concepts",
+             "concept_report", "eval_concepts")
 
 
 def __getattr__(name):
@@ -42,4 +44,8 @@ def __getattr__(name):
     if name in _NEIGHBORS:                                    # nearest neighbours in embedding space, likewise
         from . import neighbors
         return getattr(neighbors, name)
+    if name in _CONCEPTS:                                     # concept discovery (k-means on node embeddings), likewise
+        # (``assign`` stays ``cal_amd.concepts.assign``: the name is too plain for the package)
+        from . import concepts
+        return getattr(concepts, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

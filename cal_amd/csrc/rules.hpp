@@ -623,4 +623,49 @@ CAL_RULE int64_t knn_chunk_rows(int64_t nq, int64_t M, int64_t chunk_rows) {
 }
 CAL_RULE int64_t knn_chunks(int64_t M, int64_t rows) { return (M + rows - 1) / rows; }
 
+// ---- k-means on embedding rows (cal_kmeans, cal_kmeans_assign) -------------------------------------------------------------------
+constexpr int kKmMaxK = 64, kKmMaxH = 256;                      // limits of the device library
+constexpr int kKmTile = 128;                                    // a superblock is a multiple of this many rows
+// superblocks of the default plan.  A superblock's partial is K x H floats (+ K counts, an fp64 inertia, a moved count): at the
+// device limits (K = 64, H = 256) 512 x 64 KB = 32 MB of partial sums (+ 136 KB for the rest), whatever N is.
+constexpr int64_t kKmMaxSpans = 512;
+
+// the distance of a row to a centroid: knn_dist(0, xn, cn, dot) through knn_clamp, the norms ONE ascending fmaf chain each (the
+// device) or fp64 sums (the host, rounded once).  The key orders a row's centroids: distance first, the LOWER centroid on ties.
+CAL_RULE uint64_t kmeans_key(float d, uint32_t c) { return knn_key(d, c); }
+// a row whose nearest key carries +inf (every distance non-finite) is assigned -1: no sum, no count, no inertia
+CAL_RULE bool kmeans_assignable(uint64_t best_key) { return knn_key_dist(best_key) != __builtin_inff(); }
+CAL_RULE int32_t kmeans_cluster(uint64_t best_key) { return kmeans_assignable(best_key) ? knn_key_idx(best_key) : -1; }
+
+// rows of a superblock: the caller's positive multiple of 128 as it is; for 0 the smallest multiple of 128 that leaves at most
+// kKmMaxSpans superblocks.  The order of sums below is by superblock, so the BITS of the centroids depend on this value.
+CAL_RULE int64_t kmeans_span(int64_t N, int64_t span_rows) {
+    if (span_rows > 0 && span_rows % kKmTile == 0) return span_rows;
+    const int64_t pieces = (N + kKmTile - 1) / kKmTile;
+    const int64_t per = (pieces + kKmMaxSpans - 1) / kKmMaxSpans;
+    return (per < 1 ? 1 : per) * kKmTile;
+}
+CAL_RULE int64_t kmeans_spans(int64_t N, int64_t span) { return (N + span - 1) / span; }
+
+// Order of sums.  The partial of superblock s for (c, h) is ONE chain of plain fp32 additions over the rows of s assigned to c,
+// in ascending row order, from +0; a cluster's sum is the partials added in ascending s (from the partial of s = 0); counts are
+// integers.  The inertia is fp64: a superblock's chain over its assigned rows' fp32 distances in ascending row order from 0,
+// then the superblocks in ascending s.
+CAL_RULE float kmeans_add(float acc, float v) { return acc + v; }
+// the new centroid coordinate: the mean, correctly rounded division; an empty cluster keeps its centroid's bits
+CAL_RULE float kmeans_mean(float sum, int64_t count, float old) { return count ? sum / (float)count : old; }
+
+// the K distinct initial rows of a seed: a splitmix64 walk x <- splitmix64(x) from x = seed, row x mod N, repeats rejected.
+// Needs 1 <= K <= N.  All integer.
+CAL_RULE void kmeans_seed_rows(int64_t N, int64_t K, uint64_t seed, int64_t* out) {
+    unsigned long long x = seed;
+    for (int64_t i = 0; i < K;) {
+        x = splitmix64(x);
+        const int64_t r = (int64_t)(x % (unsigned long long)N);
+        bool seen = false;
+        for (int64_t j = 0; j < i; ++j) seen = seen || out[j] == r;
+        if (!seen) out[i++] = r;
+    }
+}
+
 }  // namespace cal

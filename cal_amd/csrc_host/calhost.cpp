@@ -2187,3 +2187,106 @@ HOST_EXPORT int cal_knn(const float* Q, int64_t nq, const float* X, int64_t M, i
     }
     return 0;
 }
+
+// ---- k-means on embedding rows (cal_amd/csrc/kmeans.hip): norms and dot products in fp64, the distance rounded once to the fp32 the
+// key holds; the same key (kmeans_key), the same -1 rule, and the order of sums of rules.hpp in fp32: a superblock's chain in
+// ascending row order, the superblocks in ascending order, kmeans_mean.
+HOST_EXPORT int64_t cal_kmeans_ws(int64_t, int64_t, int64_t, int64_t) { return 0; }
+
+namespace {
+// assign[j], dist[j] of the rows [j0, j1) against the K centroids C (cn: their fp64 norms)
+void km_assign_rows(const float* X, int64_t j0, int64_t j1, int64_t H, const float* C, const std::vector<double>& cn, int64_t K,
+                    int32_t* assign, float* dist) {
+#pragma omp parallel for schedule(static)
+    for (int64_t j = j0; j < j1; ++j) {
+        const float* xr = X + j * H;
+        double xn = 0.0;
+        for (int64_t i = 0; i < H; ++i) xn += (double)xr[i] * (double)xr[i];
+        uint64_t best = kKnnNone;
+        for (int64_t c = 0; c < K; ++c) {
+            const float* cr = C + c * H;
+            double dot = 0.0;
+            for (int64_t i = 0; i < H; ++i) dot += (double)xr[i] * (double)cr[i];
+            const uint64_t key = kmeans_key((float)knn_dist<double>(0, xn, cn[(size_t)c], dot), (uint32_t)c);
+            best = key < best ? key : best;
+        }
+        assign[j] = kmeans_cluster(best);
+        dist[j] = knn_key_dist(best);
+    }
+}
+std::vector<double> km_norms(const float* C, int64_t K, int64_t H) {
+    std::vector<double> cn((size_t)K);
+    for (int64_t c = 0; c < K; ++c) {
+        double s = 0.0;
+        for (int64_t i = 0; i < H; ++i) s += (double)C[c * H + i] * (double)C[c * H + i];
+        cn[(size_t)c] = s;
+    }
+    return cn;
+}
+}  // namespace
+
+HOST_EXPORT int cal_kmeans_assign(const float* X, int64_t N, int64_t H, const float* Cn, int64_t K, int32_t* assign, float* dist,
+                                  void*) {
+    HOST_REQUIRE(N >= 0 && N < (1ll << 31), "N must be in [0, 2^31)");
+    HOST_REQUIRE(H >= 1 && K >= 1, "H and K must be >= 1");
+    if (N == 0) return 0;
+    HOST_REQUIRE(X && Cn && assign && dist, "X / Cn / assign / dist is null");
+    km_assign_rows(X, 0, N, H, Cn, km_norms(Cn, K, H), K, assign, dist);
+    return 0;
+}
+
+HOST_EXPORT int cal_kmeans(const float* X, int64_t N, int64_t H, const float* C_in, int64_t K, int64_t iters, int64_t span_rows,
+                           float* C_out, int32_t* assign, int64_t* counts, double* inertia, int64_t* moved, int32_t* iters_run,
+                           void*, int64_t, void*) {
+    HOST_REQUIRE(N >= 0 && N < (1ll << 31), "N must be in [0, 2^31)");
+    HOST_REQUIRE(H >= 1 && K >= 1, "H and K must be >= 1");
+    HOST_REQUIRE(iters >= 1 && iters < INT32_MAX, "iters must be >= 1");
+    HOST_REQUIRE(span_rows >= 0 && span_rows % kKmTile == 0, "span_rows must be 0 or a positive multiple of 128");
+    if (N == 0) return 0;
+    HOST_REQUIRE(X && C_in && C_out && assign && counts && inertia && moved && iters_run, "a tensor is null");
+    const int64_t span = kmeans_span(N, span_rows), spans = kmeans_spans(N, span);
+    std::vector<int32_t> now((size_t)N);
+    std::vector<float> dist((size_t)N), sum((size_t)(K * H)), part((size_t)(K * H));
+    std::vector<int64_t> cnt((size_t)K);
+    for (int64_t it = 0; it < iters; ++it) {
+        const float* C = it == 0 ? C_in : C_out;
+        km_assign_rows(X, 0, N, H, C, km_norms(C, K, H), K, now.data(), dist.data());
+        int64_t mv = 0;
+        for (int64_t j = 0; j < N; ++j) {
+            mv += now[(size_t)j] != (it == 0 ? -1 : assign[j]);
+            assign[j] = now[(size_t)j];
+        }
+        std::fill(cnt.begin(), cnt.end(), 0);
+        double in = 0.0;
+        for (int64_t s = 0; s < spans; ++s) {
+            std::fill(part.begin(), part.end(), 0.f);
+            double pin = 0.0;
+            const int64_t j1 = std::min(N, (s + 1) * span);
+            for (int64_t j = s * span; j < j1; ++j) {
+                const int32_t c = assign[j];
+                if (c < 0) continue;
+                ++cnt[(size_t)c];
+                pin += (double)dist[(size_t)j];
+                float* p = part.data() + (int64_t)c * H;
+                const float* xr = X + j * H;
+                for (int64_t h = 0; h < H; ++h) p[h] = kmeans_add(p[h], xr[h]);
+            }
+            if (s == 0) {
+                sum = part;
+                in = pin;
+            } else {
+                for (int64_t i = 0; i < K * H; ++i) sum[(size_t)i] = kmeans_add(sum[(size_t)i], part[(size_t)i]);
+                in += pin;
+            }
+        }
+        for (int64_t c = 0; c < K; ++c) {
+            counts[c] = cnt[(size_t)c];
+            for (int64_t h = 0; h < H; ++h) C_out[c * H + h] = kmeans_mean(sum[(size_t)(c * H + h)], cnt[(size_t)c], C[c * H + h]);
+        }
+        inertia[it] = in;
+        moved[it] = mv;
+        *iters_run = (int32_t)(it + 1);
+        if (mv == 0) break;
+    }
+    return 0;
+}

@@ -284,6 +284,21 @@ class _CausalBase(torch.nn.Module):
         from .neighbors import knn_probe
         return knn_probe(bank, **kw)
 
+    def discover_concepts(self, loader, device, **kw):
+        """``cal_amd.concepts.discover_concepts(self, loader, device, **kw)``: k-means on the node embeddings of a loader."""
+        from .concepts import discover_concepts
+        return discover_concepts(self, loader, device, **kw)
+
+    def assign_concepts(self, data, concepts):
+        """``cal_amd.concepts.assign_concepts(self, data, concepts)``: the concept of every node of a new batch."""
+        from .concepts import assign_concepts
+        return assign_concepts(self, data, concepts)
+
+    def concept_report(self, concepts, **kw):
+        """``cal_amd.concepts.concept_report(concepts, **kw)``: purity, motif share, attention and completeness per concept."""
+        from .concepts import concept_report
+        return concept_report(concepts, **kw)
+
     def structure_intervention(self, data, **kw):
         """``cal_amd.splice.structure_intervention(self, data, **kw)``: the model on causal parts spliced with other graphs'
         trivial parts."""

@@ -914,6 +914,39 @@ CAL_API int cal_knn(const float* Q, int64_t nq, const float* X, int64_t M, int64
                     const int64_t* labels, int64_t C, int32_t* idx, float* dist, int32_t* votes, int64_t chunk_rows, void* ws,
                     int64_t ws_bytes, void* stream);
 
+/* ---- k-means on embedding rows: Lloyd's iterations over the [N, H] node rows of a dataset (cal_amd/concepts.py: kmeans, assign);
+ * what torch.cdist(X, C).argmin(1) + index_add_ + bincount spell, with one read of the rows per iteration, no [N, K] matrix, a
+ * total order and fixed summation orders (the kmeans block of rules.hpp) ----
+ *   X        fp32  [N, H]   the rows
+ *   C_in     fp32  [K, H]   the initial centroids (Cn of cal_kmeans_assign: the centroids of a concept table)
+ *   iters    Lloyd iterations, >= 1
+ *   span_rows  0: superblocks of kmeans_span(N, 0) rows (at most 512 of them); a positive multiple of 128: rows of a superblock
+ *   C_out    fp32  [K, H]   the centroids after iters_run iterations; a cluster without rows keeps its centroid's bits
+ *   assign   int32 [N]      the centroid of every row under the centroids the LAST iteration run started from: the smallest key
+ *            (bits of the squared distance) << 32 | centroid -- the lower centroid on equal distances; -1 for a row whose
+ *            distance to every centroid is non-finite (it enters no sum, no count, no inertia)
+ *   dist     fp32  [N]      (cal_kmeans_assign) the squared distance to that centroid, +inf with -1
+ *   counts   int64 [K]      rows of every cluster under assign
+ *   inertia  fp64  [iters], moved int64 [iters]: per iteration the sum of the assigned rows' distances and the number of rows
+ *            whose assignment changed (iteration 0: against -1 everywhere, i.e. the assigned rows).  Entries at and behind
+ *            iters_run are not written.
+ *   iters_run int32 [1]     iterations run: the first with moved == 0 is the last
+ *   ws       16-byte aligned, cal_kmeans_ws bytes: per superblock K x H partial sums, K counts, an inertia, a moved count (+ 256)
+ * Order of sums: a superblock's partial for (c, h) is one chain of fp32 additions in ascending row order, a cluster's sum the
+ * partials in ascending superblock order, the mean one correctly rounded division.  Two calls give the same bits.  The bits of
+ * C_out DO depend on span_rows (the order is part of the rule); the assignment of a single step does not.
+ * GPU: 1 <= H <= 256, 1 <= K <= 64, 1 <= N < 2^31.  cal_kmeans launches exactly 2 x iters kernels (per iteration the step kernel,
+ * one workgroup per superblock, and the update kernel, one thread per (c, h)); after the iteration with moved == 0 the remaining
+ * launches read a flag in ws and return at once.  cal_kmeans_assign is ONE launch.  No floating-point atomic, no ticket, no
+ * synchronisation, no read-back: safe to capture.  N = 0: nothing is launched.  The host library takes any sizes, forms the
+ * distances in fp64, follows the same order of sums in fp32 and needs no ws (cal_kmeans_ws is 0). */
+CAL_API int64_t cal_kmeans_ws(int64_t N, int64_t K, int64_t H, int64_t span_rows);
+CAL_API int cal_kmeans_assign(const float* X, int64_t N, int64_t H, const float* Cn, int64_t K, int32_t* assign, float* dist,
+                              void* stream);
+CAL_API int cal_kmeans(const float* X, int64_t N, int64_t H, const float* C_in, int64_t K, int64_t iters, int64_t span_rows,
+                       float* C_out, int32_t* assign, int64_t* counts, double* inertia, int64_t* moved, int32_t* iters_run,
+                       void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
