@@ -19,6 +19,7 @@ _NEIGHBORS = ("KnnResult", "EmbeddingBank", "NearestExamples", "knn", "embedding
               "eval_disentanglement")
 _CONCEPTS = ("KMeansResult", "NodeBank", "Concepts", "kmeans", "node_bank", "discover_concepts", "assign_concepts",
              "concept_report", "eval_concepts")
+_SURROGATE = ("Surrogate", "surrogate_fit", "kernel_shap", "local_surrogate", "surrogate_agreement", "eval_surrogate")
 
 
 def __getattr__(name):
@@ -48,4 +49,7 @@ def __getattr__(name):
         # (``assign`` stays ``cal_amd.concepts.assign``: the name is too plain for the package)
         from . import concepts
         return getattr(concepts, name)
+    if name in _SURROGATE:                                    # surrogate attributions (KernelSHAP, a local linear fit), likewise
+        from . import surrogate
+        return getattr(surrogate, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -45,7 +45,8 @@ HOST_SYMBOLS = ("cal_last_error", "cal_version", "cal_plan_build", "cal_graph_pt
                 "cal_centrality_ws", "cal_centrality",
                 "cal_subset_ws", "cal_subset_count", "cal_subset_write", "cal_beam_step",
                 "cal_knn_ws", "cal_knn",
-                "cal_kmeans_ws", "cal_kmeans_assign", "cal_kmeans")
+                "cal_kmeans_ws", "cal_kmeans_assign", "cal_kmeans",
+                "cal_surrogate_fit")
 
 _SCALARS = {
     "int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,

@@ -668,4 +668,72 @@ CAL_RULE void kmeans_seed_rows(int64_t N, int64_t K, uint64_t seed, int64_t* out
     }
 }
 
+// ---- surrogate attributions: one weighted least-squares fit per graph (cal_surrogate_fit) ----------------------------------------
+// Graph g has the players pl_elem[pl_ptr[g] .. pl_ptr[g + 1]) (n of them, seg_clamp into [0, P]) and the samples rep_ptr[g] ..
+// rep_ptr[g + 1] (S of them, seg_clamp into [0, R]).  Mode 0 ("shap"): d = n unknowns, y_s = v_s - v_empty[g], the solution of
+// A x = b corrected onto sum(phi) = Delta = v_full[g] - v_empty[g].  Mode 1 ("lime"): d = n + 1, the intercept the LAST unknown
+// (its z is 1 in every sample), y_s = v_s, ridge on the first n diagonal entries only.
+//
+// Every floating-point operation is one of the functions below, so both libraries perform the same operations in the same order:
+// a multiply-add is __builtin_fma (never an a * b + c expression, which one compiler contracts and the other does not), a sum of
+// weights a plain add.  Terms whose z is 0 are SKIPPED, not added as zeros.
+//   Gram          A_ij = the chain of sur_gram_add(., w_s) over ascending s with z_si and z_sj, from +0; then sur_ridge on A_ii
+//   right side    b_i  = the chain of sur_rhs_add(., w_s, y_s) over ascending s with z_si, from +0
+//   Cholesky      left-looking.  d_j = the chain of sur_sub(., L_jk, L_jk) over ascending k < j from A_jj; column j is good iff
+//                 sur_pivot_ok(d_j, A_jj) (A_jj with its ridge); L_jj = sur_sqrt(d_j);
+//                 L_ij = sur_div(the chain of sur_sub(., L_ik, L_jk) over ascending k < j from A_ij, L_jj)
+//   forward       y_i = sur_div(the chain of sur_sub(., L_ik, y_k) over ASCENDING k < i from b_i, L_ii), i ascending
+//   back          x_i = sur_div(the chain of sur_sub(., L_ki, x_k) over DESCENDING k > i from y_i, L_ii), i descending
+//   u             the same two substitutions from the right side of ones (mode 0)
+//   sums          sum(x), sum(u): plain adds over ascending i from +0
+//   phi           mode 0: sur_correct(x_i, u_i, sum(x), sum(u), Delta), phi0 = v_empty[g];  mode 1: x_i, phi0 = x_n
+//   weighted R^2  sw = the chain of sur_gram_add(., w_s), swv = the chain of sur_rhs_add(., w_s, v_s), mean = sur_div(swv, sw);
+//                 fit_s = the chain of plain adds of phi_p over ascending p with z_sp, from phi0; SSR = the chain of
+//                 sur_sq_add(., w_s, v_s - fit_s), SST = the chain of sur_sq_add(., w_s, v_s - mean), all over ascending s from +0;
+//                 r2 = sur_r2(SSR, SST)
+constexpr int kSurrogateMaxDim = 128;                           // the largest matrix dimension d of the device library
+constexpr int kSurrogateMaxPlayers = 127;                       // the largest player count n of the device library
+
+// z(s, p) of sample s for the player whose representative is element elem (inside [0, M)): a key row outside [0, K) is the
+// control sample of coalition_batch, every player present whatever invert says
+CAL_RULE bool sur_member(const int32_t* key, int64_t K, int64_t M, int64_t row, int64_t elem, int64_t thresh, bool invert) {
+    if (row < 0 || row >= K) return true;
+    return ((int64_t)key[row * M + elem] < thresh) != invert;
+}
+CAL_RULE bool sur_finite(double v) { return __builtin_fabs(v) <= 1.7976931348623157e308; }
+// a sample the fit can use: a finite value, a finite weight >= 0
+CAL_RULE bool sur_sample_ok(double v, double w) { return sur_finite(v) && sur_finite(w) && w >= 0.0; }
+// a player the fit can use: its representative names an element
+CAL_RULE bool sur_player_ok(int64_t elem, int64_t M) { return elem >= 0 && elem < M; }
+CAL_RULE int64_t sur_dim(int64_t n, int mode) { return mode == 1 ? n + 1 : n; }
+// the status of a graph, by precedence: 2 too many players (device library only), 3 a sample or player that cannot be used (or,
+// mode 0, a non-finite v_empty / v_full), 1 rank-deficient by the pivot rule, 0 fitted.  Non-zero: phi, phi0 and r2 are NaN.
+CAL_RULE int sur_status(bool too_many, bool bad, bool deficient) { return too_many ? 2 : (bad ? 3 : (deficient ? 1 : 0)); }
+// mode 0 with ONE player is defined, not solved: phi = Delta (status 0 unless 3)
+CAL_RULE bool sur_one_player(int64_t n, int mode) { return mode == 0 && n == 1; }
+
+CAL_RULE double sur_y(double v, double v_empty, int mode) { return mode == 0 ? v - v_empty : v; }
+CAL_RULE double sur_gram_add(double acc, double w) { return acc + w; }
+CAL_RULE double sur_rhs_add(double acc, double w, double y) { return __builtin_fma(w, y, acc); }
+CAL_RULE double sur_ridge(double a, double ridge, int64_t i, int64_t n) { return i < n ? a + ridge : a; }
+CAL_RULE double sur_sub(double acc, double a, double b) { return __builtin_fma(-a, b, acc); }
+// column j is good iff its pivot is above 2^-30 of the diagonal entry it came from (NaN is not)
+CAL_RULE bool sur_pivot_ok(double dj, double ajj) { return dj > ajj * 0x1p-30; }
+CAL_RULE double sur_sqrt(double v) { return __builtin_sqrt(v); }
+CAL_RULE double sur_div(double a, double b) { return a / b; }
+// the Lagrange form of sum(phi) = Delta
+CAL_RULE double sur_correct(double x, double u, double sx, double su, double delta) {
+    const double c = (sx - delta) / su;
+    return __builtin_fma(-u, c, x);
+}
+CAL_RULE double sur_sq_add(double acc, double w, double r) {
+    const double e = w * r;
+    return __builtin_fma(e, r, acc);
+}
+CAL_RULE double sur_r2(double ssr, double sst) {
+    if (sst == 0.0) return __builtin_nan("");
+    const double q = ssr / sst;
+    return 1.0 - q;
+}
+
 }  // namespace cal

@@ -2290,3 +2290,152 @@ HOST_EXPORT int cal_kmeans(const float* X, int64_t N, int64_t H, const float* C_
     }
     return 0;
 }
+
+// ---- surrogate attributions (cal_amd/csrc/surrogate.hip): the same fit, every operation a function of the surrogate block of
+// rules.hpp in the order stated there, so the results are the device library's bit for bit.  No player limit: a dense lower
+// triangle per graph, OpenMP over the graphs.
+namespace {
+struct SurArgs {
+    const int32_t* key; int64_t K, M;
+    const int64_t *rptr, *rrow, *rth, *rinv;
+    const double *val, *wt; int64_t R;
+    const int64_t *pptr, *pel; int64_t P;
+    const double *ve, *vf; int mode; double ridge;
+    double *phi, *phi0, *r2; int32_t* status;
+};
+
+void sur_fit_graph(const SurArgs& a, int64_t g) {
+    const double nan = __builtin_nan("");
+    int64_t plo, n, rlo, S;
+    seg_clamp(a.pptr, g, a.P, plo, n);
+    seg_clamp(a.rptr, g, a.R, rlo, S);
+    const int mode = a.mode;
+    const int64_t d = sur_dim(n, mode);
+    const double ve = mode == 0 ? a.ve[g] : 0.0, vf = mode == 0 ? a.vf[g] : 0.0, delta = vf - ve;
+    bool bad = mode == 0 && !(sur_finite(ve) && sur_finite(vf));
+    for (int64_t p = 0; p < n; ++p) bad = bad || !sur_player_ok(a.pel[plo + p], a.M);
+    std::vector<double> w((size_t)S), v((size_t)S);
+    for (int64_t s = 0; s < S; ++s) {
+        v[(size_t)s] = a.val[rlo + s];
+        w[(size_t)s] = a.wt ? a.wt[rlo + s] : 1.0;
+        bad = bad || !sur_sample_ok(v[(size_t)s], w[(size_t)s]);
+    }
+    auto fail = [&](int st) {
+        for (int64_t p = 0; p < n; ++p) a.phi[plo + p] = nan;
+        a.phi0[g] = a.r2[g] = nan;
+        a.status[g] = st;
+    };
+    if (bad) return fail(sur_status(false, true, false));
+    std::vector<uint8_t> z((size_t)(S * d));
+    for (int64_t s = 0; s < S; ++s) {
+        const int64_t i = rlo + s;
+        for (int64_t p = 0; p < n; ++p)
+            z[(size_t)(s * d + p)] = sur_member(a.key, a.K, a.M, a.rrow[i], a.pel[plo + p], a.rth[i], a.rinv && a.rinv[i] != 0);
+        if (mode == 1) z[(size_t)(s * d + n)] = 1;
+    }
+    std::vector<double> phi((size_t)n);
+    double phi0 = ve;
+    bool deficient = false;
+    if (sur_one_player(n, mode)) {
+        phi[0] = delta;
+    } else if (d > 0) {
+        std::vector<double> L((size_t)(d * (d + 1) / 2)), x((size_t)d), u((size_t)d);
+        auto at = [&](int64_t i, int64_t j) -> double& { return L[(size_t)(i * (i + 1) / 2 + j)]; };
+        for (int64_t i = 0; i < d; ++i) {
+            for (int64_t j = 0; j <= i; ++j) {
+                double acc = 0.0;
+                for (int64_t s = 0; s < S; ++s)
+                    if (z[(size_t)(s * d + i)] && z[(size_t)(s * d + j)]) acc = sur_gram_add(acc, w[(size_t)s]);
+                at(i, j) = i == j ? sur_ridge(acc, a.ridge, i, n) : acc;
+            }
+            double acc = 0.0;
+            for (int64_t s = 0; s < S; ++s)
+                if (z[(size_t)(s * d + i)]) acc = sur_rhs_add(acc, w[(size_t)s], sur_y(v[(size_t)s], ve, mode));
+            x[(size_t)i] = acc;
+            u[(size_t)i] = 1.0;
+        }
+        for (int64_t j = 0; j < d && !deficient; ++j) {
+            const double ajj = at(j, j);
+            double dj = ajj;
+            for (int64_t k = 0; k < j; ++k) dj = sur_sub(dj, at(j, k), at(j, k));
+            if (!sur_pivot_ok(dj, ajj)) {
+                deficient = true;
+                break;
+            }
+            const double ljj = sur_sqrt(dj);
+            at(j, j) = ljj;
+            for (int64_t i = j + 1; i < d; ++i) {
+                double acc = at(i, j);
+                for (int64_t k = 0; k < j; ++k) acc = sur_sub(acc, at(i, k), at(j, k));
+                at(i, j) = sur_div(acc, ljj);
+            }
+        }
+        if (!deficient) {
+            for (std::vector<double>* r : {&x, &u}) {
+                std::vector<double>& t = *r;
+                for (int64_t i = 0; i < d; ++i) {
+                    double acc = t[(size_t)i];
+                    for (int64_t k = 0; k < i; ++k) acc = sur_sub(acc, at(i, k), t[(size_t)k]);
+                    t[(size_t)i] = sur_div(acc, at(i, i));
+                }
+                for (int64_t i = d - 1; i >= 0; --i) {
+                    double acc = t[(size_t)i];
+                    for (int64_t k = d - 1; k > i; --k) acc = sur_sub(acc, at(k, i), t[(size_t)k]);
+                    t[(size_t)i] = sur_div(acc, at(i, i));
+                }
+            }
+            if (mode == 0) {
+                double sx = 0.0, su = 0.0;
+                for (int64_t i = 0; i < d; ++i) {
+                    sx = sx + x[(size_t)i];
+                    su = su + u[(size_t)i];
+                }
+                for (int64_t i = 0; i < n; ++i) phi[(size_t)i] = sur_correct(x[(size_t)i], u[(size_t)i], sx, su, delta);
+            } else {
+                for (int64_t i = 0; i < n; ++i) phi[(size_t)i] = x[(size_t)i];
+                phi0 = x[(size_t)n];
+            }
+        }
+    }
+    if (deficient && n > 0) return fail(sur_status(false, false, true));
+    if (deficient) phi0 = nan;                                     // (mode 1 without a player and without weight)
+    double sw = 0.0, swv = 0.0;
+    for (int64_t s = 0; s < S; ++s) {
+        sw = sur_gram_add(sw, w[(size_t)s]);
+        swv = sur_rhs_add(swv, w[(size_t)s], v[(size_t)s]);
+    }
+    const double mean = sur_div(swv, sw);
+    double ssr = 0.0, sst = 0.0;
+    for (int64_t s = 0; s < S; ++s) {
+        double fit = phi0;
+        for (int64_t p = 0; p < n; ++p)
+            if (z[(size_t)(s * d + p)]) fit = fit + phi[(size_t)p];
+        ssr = sur_sq_add(ssr, w[(size_t)s], v[(size_t)s] - fit);
+        sst = sur_sq_add(sst, w[(size_t)s], v[(size_t)s] - mean);
+    }
+    for (int64_t p = 0; p < n; ++p) a.phi[plo + p] = phi[(size_t)p];
+    a.phi0[g] = phi0;
+    a.r2[g] = sur_r2(ssr, sst);
+    a.status[g] = 0;
+}
+}  // namespace
+
+HOST_EXPORT int cal_surrogate_fit(const int32_t* key, int64_t K, int64_t M, const int64_t* rep_ptr, const int64_t* rep_row,
+                                  const int64_t* rep_thresh, const int64_t* rep_invert, const double* value, const double* weight,
+                                  int64_t R, const int64_t* pl_ptr, const int64_t* pl_elem, int64_t P, int64_t B,
+                                  const double* v_empty, const double* v_full, int mode, double ridge, double* phi, double* phi0,
+                                  double* r2, int32_t* status, void*) {
+    HOST_REQUIRE(K >= 0 && M >= 0 && R >= 0 && P >= 0 && B >= 0, "sizes must be >= 0");
+    HOST_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (shap) or 1 (lime)");
+    HOST_REQUIRE(ridge >= 0.0 && sur_finite(ridge), "ridge must be finite and >= 0");
+    if (B == 0) return 0;
+    HOST_REQUIRE(rep_ptr && pl_ptr && phi0 && r2 && status, "rep_ptr / pl_ptr / phi0 / r2 / status is null");
+    HOST_REQUIRE(R == 0 || (rep_row && rep_thresh && value), "rep_row / rep_thresh / value is null");
+    HOST_REQUIRE(P == 0 || (pl_elem && phi), "pl_elem / phi is null");
+    HOST_REQUIRE(mode == 1 || (v_empty && v_full), "mode 0 needs v_empty and v_full");
+    const SurArgs a{key, key && M > 0 ? K : 0, M, rep_ptr, rep_row, rep_thresh, rep_invert, value, weight, R, pl_ptr, pl_elem, P,
+                    v_empty, v_full, mode, ridge, phi, phi0, r2, status};
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int64_t g = 0; g < B; ++g) sur_fit_graph(a, g);
+    return 0;
+}

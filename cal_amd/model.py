@@ -320,6 +320,16 @@ class _CausalBase(torch.nn.Module):
         from .coalition import shapley
         return shapley(self, data, **kw)
 
+    def kernel_shap(self, data, **kw):
+        """``cal_amd.surrogate.kernel_shap(self, data, **kw)``: Shapley values from a fixed budget of sampled coalitions."""
+        from .surrogate import kernel_shap
+        return kernel_shap(self, data, **kw)
+
+    def local_surrogate(self, data, **kw):
+        """``cal_amd.surrogate.local_surrogate(self, data, **kw)``: a local linear fit and its weighted R^2."""
+        from .surrogate import local_surrogate
+        return local_surrogate(self, data, **kw)
+
     def perturbation_curve(self, data, **kw):
         """``cal_amd.coalition.perturbation_curve(self, data, **kw)``: insertion and deletion curves under a ranking."""
         from .coalition import perturbation_curve

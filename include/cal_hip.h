@@ -947,6 +947,33 @@ CAL_API int cal_kmeans(const float* X, int64_t N, int64_t H, const float* C_in, 
                        float* C_out, int32_t* assign, int64_t* counts, double* inertia, int64_t* moved, int32_t* iters_run,
                        void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- surrogate attributions: per graph ONE weighted least-squares fit of the replicas' values on the players' membership bits
+ * (cal_amd/surrogate.py: surrogate_fit, kernel_shap, local_surrogate); what a padded [R, n_max] design matrix, a batched Gram
+ * product and cholesky_solve spell, in fp64 with one order for every sum (the surrogate block of rules.hpp) ----
+ *   key        int32 [K, M]  the key rows coalition_batch took
+ *   rep_ptr    int64 [B + 1] the samples (replicas) of graph g: rep_ptr[g] .. rep_ptr[g + 1], clamped into [0, R]
+ *   rep_row, rep_thresh int64 [R], rep_invert int64 [R] or null (zeros): sample s holds player p iff
+ *              (key[rep_row[s], pl_elem[p]] < rep_thresh[s]) != (rep_invert[s] != 0); a row outside [0, K): every player
+ *   value      fp64 [R]      v_s, the model's answer on the replica;  weight fp64 [R] or null (ones)
+ *   pl_ptr     int64 [B + 1], pl_elem int64 [P]: the element of every player's representative, grouped by graph
+ *   v_empty, v_full fp64 [B] (mode 0 only; mode 1 does not read them and takes null)
+ *   mode       0 "shap": d = n unknowns, y = v - v_empty, the solution corrected onto sum(phi) = v_full - v_empty, phi0 = v_empty;
+ *              n = 1 is defined as phi = v_full - v_empty.  1 "lime": d = n + 1, a free intercept as the last unknown (phi0),
+ *              y = v, ridge on the n player entries of the diagonal only
+ *   phi        fp64 [P], phi0 fp64 [B], r2 fp64 [B] (1 - SSR / SST, weighted; NaN when SST = 0)
+ *   status     int32 [B]     0 fitted; 1 rank-deficient (a Cholesky pivot d_j <= 2^-30 A_jj); 2 more than 127 players (device
+ *              library only); 3 a non-finite value, a negative or non-finite weight, a player outside [0, M) or (mode 0) a
+ *              non-finite v_empty / v_full.  Precedence 2, 3, 1.  Non-zero: the graph's phi, phi0 and r2 are NaN.  A graph without
+ *              a player is never 1: phi0 is v_empty (mode 0) or the weighted mean (mode 1, NaN without weight).
+ * ONE launch, one workgroup of 256 threads per graph, the packed lower triangle (66 KB at d = 128) and a tile of 512 samples'
+ * membership bits in LDS; no workspace, no read-back, no floating-point atomic: the same bits on every call, in any batch, and the
+ * same bits as the host library (which has no player limit).  B = 0 launches nothing. */
+CAL_API int cal_surrogate_fit(const int32_t* key, int64_t K, int64_t M, const int64_t* rep_ptr, const int64_t* rep_row,
+                              const int64_t* rep_thresh, const int64_t* rep_invert, const double* value, const double* weight,
+                              int64_t R, const int64_t* pl_ptr, const int64_t* pl_elem, int64_t P, int64_t B,
+                              const double* v_empty, const double* v_full, int mode, double ridge, double* phi, double* phi0,
+                              double* r2, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
